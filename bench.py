@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- dense gen.phi throughput on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg4]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg4] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run plans, warms up, times the K steps, writes the last step's result under --dump-outputs and prints
+the line.  --full adds what takes runs of its own: the hipGraph replay of the same sweep, the device-to-host
+copy of the result, the CPU baseline, one-shot gen.phi call walls and (cfg4) the other BASELINE.json
+configurations.
 
 A "step" is one full pass of the hot path: all level steps of gen.phi (Psi = 1/2 I ... the
 N x N proband matrix, delivered in proband order) for the synthetic pedigree of the named
@@ -283,6 +288,30 @@ def quick_workload(name, device, steps=5):
     return rec
 
 
+DUMP_ROW_BYTES = 48 << 20          # --dump-outputs: bytes of whole rows written (the dump stays below 64 MB with the diagonal)
+
+
+def dump_outputs(pl, out_dir, f64):
+    """--dump-outputs DIR: the N x N proband matrix the last timed step left in HBM -- what gen.phi hands its caller, in
+    proband order -- so that two builds can be compared output for output.  DIR/phi_rows.npy: the whole matrix when it takes at
+    most DUMP_ROW_BYTES, otherwise as many whole rows as fit, drawn by numpy default_rng(0) and sorted (the same rows for the same
+    N); DIR/phi_diag.npy: the diagonal.  float32 (float64 with --storage f64), read by point lookups on the device
+    (genphi_result_entries), so the matrix is never copied whole."""
+    n = pl.n_probands
+    dt = np.float64 if f64 else np.float32
+    k = min(n, DUMP_ROW_BYTES // max(n * np.dtype(dt).itemsize, 1))
+    rows = np.arange(n, dtype=np.int64) if k == n else np.sort(np.random.default_rng(0).choice(n, size=k, replace=False))
+    cols = np.arange(n, dtype=np.int64)
+    sample = np.empty((k, n), dtype=dt)
+    per_call = max(1, (4 << 20) // max(n, 1))             # rows per lookup call: ~4 M entries
+    for a in range(0, k, per_call):
+        rr = rows[a:a + per_call]
+        sample[a:a + len(rr)] = pl.result_entries(np.repeat(rr, n), np.tile(cols, len(rr))).reshape(len(rr), n)   # (Float32 values read as Float64: exact)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "phi_rows.npy"), sample)
+    np.save(os.path.join(out_dir, "phi_diag.npy"), pl.result_entries(cols, cols).astype(dt))
+
+
 def shard_rows(n, rank, world):
     """Final-level row shard [r0, r1) of `rank`: contiguous, disjoint, covering [0, n)."""
     return (n * rank) // world, (n * (rank + 1)) // world
@@ -451,13 +480,18 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default="cfg4", choices=sorted(WORKLOADS) + ["sparse140", "sparse2k"])
     ap.add_argument("--kernel", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: hipGraph replay, device-to-host copy, CPU baseline, one-shot "
+                         "call walls, the other BASELINE.json configurations (the --no-* switches below leave parts of it out)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed to DIR/*.npy (single-GPU dense sweep; see dump_outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--storage", default="f32", choices=["f32", "f64"],
                     help="f64: the secondary Float64 level sweep (GENPHI_FLAG_STORAGE_F64: what gen.f and pairwise phi(i, j) run); "
                          "N = 1 only, no D2H block, algorithmic bytes count 8 per entry")
     ap.add_argument("--no-d2h", action="store_true", help="skip the device-to-host copy of the end_to_end block")
     ap.add_argument("--no-others", action="store_true",
-                    help="default run (cfg4, 1 GPU): do not measure the other BASELINE.json configurations (cfg2, cfg3, cfg3s, cfg5) for `other_workloads`")
+                    help="--full run (cfg4, 1 GPU): do not measure the other BASELINE.json configurations (cfg2, cfg3, cfg3s, cfg5) for `other_workloads`")
     ap.add_argument("--no-call-wall", action="store_true", help="do not time one-shot gen.phi calls (profiling runs: only the sweeps of ONE plan in the process)")
     ap.add_argument("--no-sparse", action="store_true", help="A/B: every level as a dense matrix (GENPHI_FLAG_NO_SPARSE)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
@@ -477,6 +511,8 @@ def main():
     ap.add_argument("--dry-run", action="store_true",
                     help="CPU rehearsal of the N > 1 plumbing: plan + shard + barrier + max-reduce, no compute")
     args = ap.parse_args()
+    if args.dump_outputs and (args.gpus > 1 or args.exchange or args.dry_run or args.workload.startswith("sparse")):
+        raise SystemExit("--dump-outputs: single-GPU dense sweep only (not with --gpus N > 1, --exchange, --dry-run or a sparse workload)")
 
     import torch
     rank = int(os.environ.get("RANK", "0"))
@@ -573,11 +609,13 @@ def main():
         tt = torch.tensor([wall], dtype=torch.float64, device="cuda" if args.backend == "nccl" else "cpu")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         wall = float(tt.item())
+    if args.dump_outputs:
+        dump_outputs(pl, args.dump_outputs, f64)
     # The timed region above runs the sweep eagerly with a HIP event after every level step (per-level times).
-    # Outside it: the same sweep WITHOUT events, which the library replays from a captured hipGraph (sweeps of
+    # Outside it (--full): the same sweep WITHOUT events, which the library replays from a captured hipGraph (sweeps of
     # >= 8 level steps) -- what a caller of gen.phi gets; matters for workloads of many short launches.
     replay_ms = None
-    if world == 1 and not empty_shard:
+    if args.full and world == 1 and not empty_shard:
         for _ in range(2):
             compute()                                        # an eager run with these arguments, then the capture
         torch.cuda.synchronize()
@@ -589,7 +627,7 @@ def main():
 
     # N > 1: every rank copies ITS row block to its host (the 40 GB copy of cfg4 split N ways: the end-to-end win of the row shards)
     shard_d2h_ms = None
-    if world > 1 and not args.no_d2h and not f64:
+    if args.full and world > 1 and not args.no_d2h and not f64:
         import psutil
         t_own = 0.0
         fits_host = psutil.virtual_memory().available > (r1 - r0) * n * 4 * world + (16 << 30)      # (all ranks of the node copy at once)
@@ -660,7 +698,7 @@ def main():
             end_to_end["d2h_sample"] = f"every rank its own block of ~{(n + world - 1) // world} rows into a pageable host array, at the same time; MAX over the ranks"
             end_to_end["total_ms_plan_sweep_d2h"] = plan_ms + ms_per_step + shard_d2h_ms
             end_to_end["pairs_per_s"] = n * n / (end_to_end["total_ms_plan_sweep_d2h"] * 1e-3)
-        if world == 1 and not args.no_d2h and not f64:
+        if args.full and world == 1 and not args.no_d2h and not f64:
             import psutil
             need = n * n * 4
             if psutil.virtual_memory().available > need + (16 << 30):
@@ -746,20 +784,20 @@ def main():
                                         "implementation still has to move (lists instead of matrices for the leading sparse cuts, no dragged x dragged block for "
                                         "steps that stay in place); `frac` = the algorithmic one unless steps stay in place or it exceeds 1 (then it is no "
                                         "bandwidth figure); `real_traffic_frac`: measured HBM traffic")
-        if not args.no_cpu_baseline and world == 1 and not f64:       # rank 0 at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1 and not f64:       # rank 0 at N = 1 only
             out["cpu_baseline"] = cpu_baseline(ped, pro, sizes)
         settled_s = 0.0
-        if world == 1:
+        if args.full and world == 1:
             released = pl.device_bytes
             pl.close()                                     # (the measurements below make plans of their own: this one's memory first)
             pl = None
             settled_s += settle_after_release(released)
-        if world == 1 and not f64 and args.kernel == 0 and not args.no_sparse and not args.no_call_wall:
+        if args.full and world == 1 and not f64 and args.kernel == 0 and not args.no_sparse and not args.no_call_wall:
             # a one-shot call through the drop-in API (result left resident when it is too large to copy twice within the run)
             out["end_to_end"]["call_wall"] = call_walls(ped, pro, local_rank, with_d2h=n * n * 4 <= (2 << 30), reps=3 if n <= 20000 else 1)
             settled_s += settle_after_release(released)
             out["end_to_end"]["call_wall"]["waited_for_released_memory_s"] = round(settled_s, 2)
-        if args.workload == "cfg4" and world == 1 and not f64 and args.kernel == 0 and not args.no_others and not args.no_sparse and not ab_hooks:
+        if args.full and args.workload == "cfg4" and world == 1 and not f64 and args.kernel == 0 and not args.no_others and not args.no_sparse and not ab_hooks:
             # the other BASELINE.json configurations in the same process (each a few ms per sweep): driver-timed evidence for them
             others = {}
             for w in ("cfg2", "cfg3", "cfg3s", "cfg5"):

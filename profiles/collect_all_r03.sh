@@ -5,9 +5,9 @@
 set -u
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/r03_artifacts; rm -rf "$O"; mkdir -p "$O"
-python bench.py --steps 20 --warmup 5 > "$O/r03_bench_cfg4.json" 2> "$O/bench_cfg4.err"
-for w in cfg2 cfg3 cfg5; do python bench.py --workload $w --steps 20 --warmup 3 > "$O/r03_bench_$w.json" 2> "$O/bench_$w.err"; done
-python bench.py --workload cfg4o --steps 5 --warmup 1 --no-cpu-baseline > "$O/r03_bench_cfg4o.json" 2> "$O/bench_cfg4o.err"
+python bench.py --full --steps 20 --warmup 5 > "$O/r03_bench_cfg4.json" 2> "$O/bench_cfg4.err"
+for w in cfg2 cfg3 cfg5; do python bench.py --full --workload $w --steps 20 --warmup 3 > "$O/r03_bench_$w.json" 2> "$O/bench_$w.err"; done
+python bench.py --full --workload cfg4o --steps 5 --warmup 1 --no-cpu-baseline > "$O/r03_bench_cfg4o.json" 2> "$O/bench_cfg4o.err"
 for w in cfg4 cfg3 cfg2 cfg5 cfg4o; do
   bash profiles/collect.sh r03 $w > "$O/collect_$w.out" 2>&1
   python profiles/summarize.py r03 $w >> "$O/collect_$w.out" 2>&1
@@ -15,8 +15,8 @@ for w in cfg4 cfg3 cfg2 cfg5 cfg4o; do
   rm -rf gpurun_out/prof_r03_$w
 done
 # secondary paths
-for w in cfg3 cfg2; do python bench.py --workload $w --storage f64 --steps 10 --warmup 2 > "$O/r03_bench_${w}_f64.json" 2> "$O/bench_${w}_f64.err"; done
-rocprofv3 --kernel-trace --stats --output-format csv -d "$O/kt_f64" -- python3 bench.py --workload cfg3 --storage f64 --steps 5 --warmup 1 > "$O/kt_f64.log" 2>&1
+for w in cfg3 cfg2; do python bench.py --full --workload $w --storage f64 --steps 10 --warmup 2 > "$O/r03_bench_${w}_f64.json" 2> "$O/bench_${w}_f64.err"; done
+rocprofv3 --kernel-trace --stats --output-format csv -d "$O/kt_f64" -- python3 bench.py --full --workload cfg3 --storage f64 --steps 5 --warmup 1 > "$O/kt_f64.log" 2>&1
 find "$O/kt_f64" -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} "$O/r03_cfg3_f64_kernel_stats.csv"; rm -rf "$O/kt_f64"
 for w in sparse140 sparse2k; do python bench.py --workload $w --steps 5 --warmup 1 > "$O/r03_bench_$w.json" 2> "$O/bench_$w.err"; done
 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/kt_sparse" -- python3 bench.py --workload sparse140 --steps 3 --warmup 1 > "$O/kt_sparse.log" 2>&1

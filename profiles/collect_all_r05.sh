@@ -18,18 +18,18 @@ if [ "$PART" = prof ] || [ "$PART" = all ]; then
   done
 fi
 if [ "$PART" = bench ] || [ "$PART" = all ]; then
-  python bench.py --steps 20 --warmup 5 > "$O/${TAG}_bench_cfg4.json" 2> "$O/bench_cfg4.err"; echo "bench cfg4 (default line)"
-  python bench.py --steps 20 --warmup 5 --no-sparse --no-cpu-baseline --no-d2h > "$O/${TAG}_bench_cfg4_every_level_dense.json" 2>/dev/null; echo "bench cfg4 dense"
+  python bench.py --full --steps 20 --warmup 5 > "$O/${TAG}_bench_cfg4.json" 2> "$O/bench_cfg4.err"; echo "bench cfg4 (default line)"
+  python bench.py --full --steps 20 --warmup 5 --no-sparse --no-cpu-baseline --no-d2h > "$O/${TAG}_bench_cfg4_every_level_dense.json" 2>/dev/null; echo "bench cfg4 dense"
   for w in cfg2 cfg3 cfg3s cfg5; do
-    python bench.py --workload $w --steps 20 --warmup 3 > "$O/${TAG}_bench_$w.json" 2> "$O/bench_$w.err"
-    python bench.py --workload $w --steps 20 --warmup 3 --no-sparse --no-cpu-baseline > "$O/${TAG}_bench_${w}_every_level_dense.json" 2>/dev/null
+    python bench.py --full --workload $w --steps 20 --warmup 3 > "$O/${TAG}_bench_$w.json" 2> "$O/bench_$w.err"
+    python bench.py --full --workload $w --steps 20 --warmup 3 --no-sparse --no-cpu-baseline > "$O/${TAG}_bench_${w}_every_level_dense.json" 2>/dev/null
     echo "bench $w"
   done
-  for w in cfg2all cfg2q; do python bench.py --workload $w --steps 10 --warmup 2 --no-cpu-baseline > "$O/${TAG}_bench_$w.json" 2> "$O/bench_$w.err"; echo "bench $w"; done
-  python bench.py --workload cfg4o --steps 5 --warmup 1 --no-cpu-baseline > "$O/${TAG}_bench_cfg4o.json" 2> "$O/bench_cfg4o.err"; echo "bench cfg4o"
+  for w in cfg2all cfg2q; do python bench.py --full --workload $w --steps 10 --warmup 2 --no-cpu-baseline > "$O/${TAG}_bench_$w.json" 2> "$O/bench_$w.err"; echo "bench $w"; done
+  python bench.py --full --workload cfg4o --steps 5 --warmup 1 --no-cpu-baseline > "$O/${TAG}_bench_cfg4o.json" 2> "$O/bench_cfg4o.err"; echo "bench cfg4o"
   for w in cfg3 cfg2; do
-    python bench.py --workload $w --storage f64 --steps 10 --warmup 2 > "$O/${TAG}_bench_${w}_f64.json" 2> "$O/bench_${w}_f64.err"
-    python bench.py --workload $w --storage f64 --steps 10 --warmup 2 --no-sparse > "$O/${TAG}_bench_${w}_f64_every_level_dense.json" 2>/dev/null
+    python bench.py --full --workload $w --storage f64 --steps 10 --warmup 2 > "$O/${TAG}_bench_${w}_f64.json" 2> "$O/bench_${w}_f64.err"
+    python bench.py --full --workload $w --storage f64 --steps 10 --warmup 2 --no-sparse > "$O/${TAG}_bench_${w}_f64_every_level_dense.json" 2>/dev/null
   done
   for w in sparse140 sparse2k; do python bench.py --workload $w --steps 5 --warmup 1 > "$O/${TAG}_bench_$w.json" 2> "$O/bench_$w.err"; done
   python bench.py --workload cfg3 --exchange --steps 20 --warmup 3 > "$O/${TAG}_bench_panel_cfg3_w1.json" 2> "$O/panel_w1.err"

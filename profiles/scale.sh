@@ -27,7 +27,7 @@ for n in $NS; do
   if [ "$DRY" = 1 ]; then
     run "$n" "rows_n$n" --dry-run --workload "${SCALE_DRY_WORKLOAD:-cfg2}"
   else
-    run "$n" "rows_n$n" --steps "$STEPS" --warmup 2 --no-cpu-baseline --no-others
+    run "$n" "rows_n$n" --full --steps "$STEPS" --warmup 2 --no-cpu-baseline --no-others
     run "$n" "panels_cfg3s_n$n" --workload cfg3s --exchange --backend nccl --pg --steps "$STEPS" --warmup 2 --no-cpu-baseline
   fi
 done
