@@ -208,7 +208,9 @@ def phi(pedigree, probandIDs=None, verbose=False, compute=True, device=None, ker
     `pedigree[ID]` handles: the Float64 kinship of the pair, from one Float64 level sweep on the GPU
     (the reference's recursion is un-memoised and exponential on inbred pedigrees); bit-identical to
     the recursion while kinships are exactly representable in Float64 (pedigrees less than ~26
-    generations deep), within 1e-15 relative beyond.
+    generations deep).  Beyond, within 2 L 2^-53 relative of the exact kinship for L level steps
+    (observed: about 1 x 2^-53), and bit-identical to the same recursion memoised level by level
+    wherever the result is a normal double; below 2^-1022 subnormal, within 4 x 2^-1074.
 
     Returns the square float32 matrix of pairwise kinship coefficients between probands
     (rows/columns in `probandIDs` order, duplicates collapsed), or None when compute=False.
@@ -259,7 +261,8 @@ def f(pedigree, IDs, device=None):
     parents runs on the GPU with Float64 level matrices (GENPHI_FLAG_STORAGE_F64), the
     (father, mother) entries are read back (`genphi_result_entries`) and rounded to Float32 once:
     the same values bit for bit while kinships are exactly representable in Float64 (pedigrees
-    less than ~26 generations deep; beyond, within 1e-15 relative before the rounding).
+    less than ~26 generations deep; beyond, within 2 L 2^-53 relative of the exact kinship before
+    the rounding, L = level steps: within 1 Float32 ulp of the correctly rounded value after it).
     test/runtests.jl:47-48: f(ped, [1]) == [0.18359375], f(ped, [17]) == [0.].
     """
     IDs = np.asarray(IDs, dtype=np.int64)

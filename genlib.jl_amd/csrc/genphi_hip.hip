@@ -1403,7 +1403,10 @@ __global__ void level_naive_kernel(const LevelArgs p)
 // generations.  The same level sweep with Float64 level matrices reproduces them: every kinship
 // is a dyadic rational, exactly representable in Float64 while the pedigree is less than ~26
 // generations deep (then the sweep and the recursion are bit-identical whatever their order of
-// operations), and within a few ulp (<< 1e-12) beyond.  One thread per entry, four global gathers;
+// operations).  Beyond, the four terms are grouped as the recursion groups them and scaled once
+// (exact for normal doubles): bit-identical to the recursion memoised level by level (the oracle's
+// Float64 sweep) wherever the result is normal, within 2 L 2^-53 relative of the exact kinship
+// after L level steps; subnormal results are kept (no flush), within 4 x 2^-1074.  One thread per entry, four global gathers;
 // meant for the small proband sets of gen.f / pairwise queries, not for throughput.
 //   colmap: member index of output column j (the last level is delivered in proband order), or nullptr
 __global__ void level_naive64_kernel(const double *__restrict__ psi, long long ld_prev, int n_prev, double *__restrict__ out,
@@ -3458,6 +3461,10 @@ static int compute_f64(genphi_plan *p, int64_t r0, int64_t r1, int kernel, genph
             if (need[b]) { rc = ensure_doubles(&p->buf64[b], &p->buf64_doubles[b], need[b]); if (rc) return rc; }
     }
     const int64_t n0 = pl.cut_sizes[0], ld0 = pl.ld[0];
+    // LDS a workgroup may fill with staged Float64 source rows: 160 KB, or the GENPHI_LDS_CAP_FLOATS test budget (4 bytes a
+    // float), which sends small cuts through level_split64_kernel / level_naive64_kernel too
+    const size_t lds_budget = p->tun.lds_cap_floats >= 16 ? std::min<size_t>(160 * 1024, 4 * static_cast<size_t>(p->tun.lds_cap_floats))
+                                                           : 160 * 1024;
     if (timing) HIP_TRY(hipEventRecord(p->events[0], p->stream));
     if (sparse_k < 0) {
         HIP_TRY(hipMemsetAsync(p->buf64[0], 0, static_cast<size_t>((n0 + 1) * ld0) * sizeof(double), p->stream));
@@ -3488,7 +3495,7 @@ static int compute_f64(genphi_plan *p, int64_t r0, int64_t r1, int kernel, genph
         const int *k_colmap = (last && !pl.final_perm.empty()) ? p->d_final_perm : static_cast<const int *>(nullptr);
         const int lds_row64 = static_cast<int>((st.n_prev + 1 + 1) / 2 * 2);
         const size_t lds64 = 2 * static_cast<size_t>(lds_row64) * sizeof(double);
-        if (kernel != 1 && lds64 <= 160 * 1024 && rows_n > 0) {
+        if (kernel != 1 && lds64 <= lds_budget && rows_n > 0) {
             // both Float64 source rows fit in LDS (cuts up to 10,239 members): the row-staged kernel
             HIP_TRY(set_max_lds(reinterpret_cast<const void *>(level_full64_kernel), lds64));
             // (columns per thread <= kF64Cols, row pieces per thread <= kF64Pre for each of these block sizes)
@@ -3500,7 +3507,7 @@ static int compute_f64(genphi_plan *p, int64_t r0, int64_t r1, int kernel, genph
             hipLaunchKernelGGL(level_full64_kernel, dim3(static_cast<unsigned>(grid), static_cast<unsigned>(chunks)), dim3(bs), lds64, p->stream, psi,
                                static_cast<long long>(st.ld_prev), static_cast<int>(st.n_prev), out, static_cast<long long>(st.ld), d.srcA, d.srcB,
                                d.ord, k_rows, k_orows, k_colmap, static_cast<int>(st.n), lds_row64, rows_n);
-        } else if (kernel != 1 && static_cast<size_t>(lds_row64) * sizeof(double) <= 160 * 1024 && rows_n > 0 && st.n_prev < 65535) {
+        } else if (kernel != 1 && static_cast<size_t>(lds_row64) * sizeof(double) <= lds_budget && rows_n > 0 && st.n_prev < 65535) {
             // one Float64 source row fits (cuts up to 20,479 members): the one-row-at-a-time kernel, rows in the step's work order
             // (same A source adjacent) where the step has one
             const size_t lds1 = static_cast<size_t>(lds_row64) * sizeof(double);

@@ -151,7 +151,8 @@ Float64 kinship of a pair, as `GenLib.phi(individualᵢ, individualⱼ)` (src/co
 Float64 level sweep on the GPU instead of the un-memoised recursion.  (The reference's method needs no
 pedigree argument because its `Individual`s carry pointers to their parents; the flat arrays the
 library takes are built from the pedigree.)  Bit-identical while kinships are exactly representable in
-Float64 (pedigrees less than ~26 generations deep), within 1e-15 relative beyond.
+Float64 (pedigrees less than ~26 generations deep); beyond, within 2 L 2^-53 relative of the exact
+kinship after L level steps (subnormal results within 4 x 2^-1074).
 """
 function phi(individualᵢ::GenLib.Individual, individualⱼ::GenLib.Individual, pedigree::GenLib.Pedigree;
              device::Integer = -1)

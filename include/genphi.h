@@ -196,7 +196,8 @@ int genphi_result_to_host_f64(genphi_plan *plan, double *out);
  * level sweep over the individuals named, one lookup per pair.  out[k] = Phi(id_i[k], id_j[k])
  * (id_i[k] == id_j[k] gives the self-kinship 1/2 + Phi(father, mother)/2).  Bit-identical to the
  * recursion while every kinship is exactly representable in Float64 (pedigrees less than ~26
- * generations deep), within 1e-15 relative beyond.  Pedigree arguments as for genphi_plan_create;
+ * generations deep); beyond, within 2 L 2^-53 relative of the exact kinship after L level steps
+ * (subnormal results within 4 x 2^-1074, not flushed).  Pedigree arguments as for genphi_plan_create;
  * unknown ID -> GENPHI_ERR_UNKNOWN_ID.                                                              */
 int genphi_phi_pairs(int64_t n_ind, const int64_t *ind, const int64_t *father, const int64_t *mother,
                      int64_t n_pairs, const int64_t *id_i, const int64_t *id_j, double *out, int32_t device);

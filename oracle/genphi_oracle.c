@@ -435,6 +435,95 @@ int oracle_phi_compute_rows(oracle_ped *p, const oracle_levels *lv, int64_t n_ro
     return ORACLE_OK;
 }
 
+/* ------------------------------------------------------------------------------------ */
+/* Float64 mode: the same level sweep with a double level matrix and no rounding to Float32 between levels -- what the
+ * reference's Float64 pairwise recursion (src/compute.jl:66-95) and gen.f (:500-511) compute when the recursion is
+ * memoised level by level.  level_rec64 is level_rec with `const double *Psi`: same branch order, Float64 accumulator
+ * starting at 0., `/ 2` per climb.  The library's Float64 sweep (GENPHI_FLAG_STORAGE_F64) sums the four terms first and
+ * scales once; scaling by a power of two is exact for normal doubles, so the two agree bit for bit wherever the result
+ * is a normal double (tests/test_float64_parity.py).  Below 2^-1022 each `/ 2` here may round, the library's scale once. */
+static double level_rec64(const oracle_ped *p, int32_t i, int32_t j, const double *Psi, int64_t ld)
+{
+    double value = 0.;
+    const int32_t fi = p->founder_index[i], fj = p->founder_index[j];
+    if (fi != 0 && fj != 0) {                                      /* :108-110 */
+        value += Psi[(int64_t)(fi - 1) * ld + (fj - 1)];
+    } else if (fi != 0) {                                          /* :111-118 */
+        if (p->father[j] >= 0) value += level_rec64(p, i, p->father[j], Psi, ld) / 2;
+        if (p->mother[j] >= 0) value += level_rec64(p, i, p->mother[j], Psi, ld) / 2;
+    } else if (fj != 0) {                                          /* :119-126 */
+        if (p->father[i] >= 0) value += level_rec64(p, j, p->father[i], Psi, ld) / 2;
+        if (p->mother[i] >= 0) value += level_rec64(p, j, p->mother[i], Psi, ld) / 2;
+    } else {
+        if (i > j) {                                               /* :130-138 */
+            if (p->father[i] >= 0) value += level_rec64(p, p->father[i], j, Psi, ld) / 2;
+            if (p->mother[i] >= 0) value += level_rec64(p, p->mother[i], j, Psi, ld) / 2;
+        } else if (j > i) {                                        /* :139-147 */
+            if (p->father[j] >= 0) value += level_rec64(p, p->father[j], i, Psi, ld) / 2;
+            if (p->mother[j] >= 0) value += level_rec64(p, p->mother[j], i, Psi, ld) / 2;
+        } else {                                                   /* :148-154 */
+            value += 0.5;
+            if (p->father[i] >= 0 && p->mother[i] >= 0)
+                value += level_rec64(p, p->father[i], p->mother[i], Psi, ld) / 2;
+        }
+    }
+    return value;
+}
+
+/* oracle_phi_compute / oracle_phi_compute_rows in Float64: every level step in full (all of them when n_rows < 0), or the
+ * upper ones in full and the given rows of the last one.  out: n_L x n_L, or n_rows x n_L, Float64 row-major. */
+static int phi_compute64_impl(oracle_ped *p, const oracle_levels *lv, int64_t n_rows, const int64_t *rows, double *out)
+{
+    const int32_t L = lv->n_levels;
+    memset(p->founder_index, 0, (size_t)p->n * sizeof(int32_t));   /* fresh _index_pedigree :269 */
+    int64_t n1 = lv->cut[0].n;
+    double *Psi = (double *)calloc((size_t)(n1 * n1 + 1), sizeof(double));
+    if (!Psi) return ORACLE_ERR_ALLOC;
+    for (int64_t i = 0; i < n1; i++) Psi[i * n1 + i] = 0.5;        /* :272-274 */
+    int64_t ld = n1;
+    for (int32_t k = 0; k + 1 < L; k++) {                          /* :276 */
+        const ivec prev = lv->cut[k], next = lv->cut[k + 1];
+        for (int64_t t = 0; t < prev.n; t++) p->founder_index[prev.v[t]] = (int32_t)(t + 1);  /* :287-289 */
+        const int64_t n = next.n;
+        if (n_rows >= 0 && k + 2 == L) {                           /* the last step: the sampled rows only */
+            #pragma omp parallel for schedule(dynamic, 1)
+            for (int64_t q = 0; q < n_rows; q++) {
+                const int64_t r = rows[q];
+                for (int64_t j = 0; j < n; j++) {
+                    const int64_t a = r < j ? r : j, b = r < j ? j : r;
+                    out[q * n + j] = level_rec64(p, next.v[a], next.v[b], Psi, ld);
+                }
+            }
+            free(Psi);
+            return ORACLE_OK;
+        }
+        double *phi = (double *)malloc((size_t)(n * n + 1) * sizeof(double));
+        if (!phi) { free(Psi); return ORACLE_ERR_ALLOC; }
+        #pragma omp parallel for schedule(dynamic, 8) if (n >= 512)
+        for (int64_t i = 0; i < n; i++) {                          /* :293-299 */
+            for (int64_t j = i; j < n; j++) {
+                const double v = level_rec64(p, next.v[i], next.v[j], Psi, ld);   /* no rounding to Float32 */
+                phi[i * n + j] = v; phi[j * n + i] = v;
+            }
+        }
+        free(Psi); Psi = phi; ld = n;
+    }
+    if (n_rows < 0) memcpy(out, Psi, (size_t)(ld * ld) * sizeof(double));
+    else for (int64_t q = 0; q < n_rows; q++) memcpy(out + q * ld, Psi + rows[q] * ld, (size_t)ld * sizeof(double));   /* L == 1 */
+    free(Psi);
+    return ORACLE_OK;
+}
+
+int oracle_phi_compute64(oracle_ped *p, const oracle_levels *lv, double *out)
+{
+    return phi_compute64_impl(p, lv, -1, NULL, out);
+}
+
+int oracle_phi_compute_rows64(oracle_ped *p, const oracle_levels *lv, int64_t n_rows, const int64_t *rows, double *out)
+{
+    return phi_compute64_impl(p, lv, n_rows < 0 ? 0 : n_rows, rows, out);
+}
+
 /* Timing sample for bench.py's cpu_baseline (never a result): the pair kernel over n_rows rows x all columns of level
  * step k (cut k -> cut k + 1) with the real index structure of that step, on a matrix Psi of the real size that holds
  * arbitrary values -- the control flow and the memory accesses of src/compute.jl:105-158 depend on founder_index, father,

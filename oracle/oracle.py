@@ -14,6 +14,7 @@ _LIB = None
 
 _I64P = C.POINTER(C.c_int64)
 _F32P = C.POINTER(C.c_float)
+_F64P = C.POINTER(C.c_double)
 
 
 def build():
@@ -53,6 +54,8 @@ def lib():
         L.oracle_levels_cut_ids.restype = None
         L.oracle_phi_compute.argtypes = [C.c_void_p, C.c_void_p, _F32P, C.c_int32, _I64P]
         L.oracle_phi_compute_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, _I64P, _F32P, _I64P]
+        L.oracle_phi_compute64.argtypes = [C.c_void_p, C.c_void_p, _F64P]
+        L.oracle_phi_compute_rows64.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, _I64P, _F64P]
         L.oracle_time_level_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, _I64P, C.POINTER(C.c_double)]
         L.oracle_time_level_rows.restype = C.c_int64
         L.oracle_phi_mean.argtypes = [_F32P, C.c_int64]
@@ -206,6 +209,41 @@ class Pedigree:
             done = C.c_int64(0)
             if L.oracle_phi_compute_rows(self._h, lv, len(rows), _p(rows), out.ctypes.data_as(_F32P), C.byref(done)):
                 raise MemoryError("oracle_phi_compute_rows")
+        finally:
+            L.oracle_levels_free(lv)
+        return out
+
+    def phi64(self, pro=None):
+        """The level sweep in Float64 (oracle_phi_compute64): no rounding to Float32 between levels, the values of the
+        reference's Float64 pairwise recursion (src/compute.jl:66-95) computed level by level.  (N, N) float64."""
+        L = lib()
+        pro = self.pro() if pro is None else _i64(pro)
+        lv = C.c_void_p()
+        if L.oracle_levels_create(self._h, len(pro), _p(pro), C.byref(lv)):
+            raise OracleError("unknown proband ID")
+        try:
+            n = L.oracle_levels_cut_size(lv, L.oracle_levels_count(lv) - 1)
+            out = np.empty((n, n), dtype=np.float64)
+            if L.oracle_phi_compute64(self._h, lv, out.ctypes.data_as(_F64P)):
+                raise MemoryError("oracle_phi_compute64")
+        finally:
+            L.oracle_levels_free(lv)
+        return out
+
+    def phi_rows64(self, pro, rows):
+        """Rows `rows` (positions in `pro`) of phi64(pro), the last level step for those rows only.  (len(rows), N) float64."""
+        L = lib()
+        pro, rows = _i64(pro), _i64(rows)
+        lv = C.c_void_p()
+        if L.oracle_levels_create(self._h, len(pro), _p(pro), C.byref(lv)):
+            raise OracleError("unknown proband ID")
+        try:
+            n = L.oracle_levels_cut_size(lv, L.oracle_levels_count(lv) - 1)
+            if len(rows) and (rows.min() < 0 or rows.max() >= n):
+                raise IndexError("row out of range")
+            out = np.empty((len(rows), n), dtype=np.float64)
+            if L.oracle_phi_compute_rows64(self._h, lv, len(rows), _p(rows), out.ctypes.data_as(_F64P)):
+                raise MemoryError("oracle_phi_compute_rows64")
         finally:
             L.oracle_levels_free(lv)
         return out
