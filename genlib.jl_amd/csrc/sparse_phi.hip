@@ -433,6 +433,9 @@ std::mutex g_pin_mu;
 void *g_pin = nullptr;
 size_t g_pin_bytes = 0;
 constexpr size_t kPinCap = size_t(256) << 20;
+// largest old set of a wave built by sparse_row_fused_kernel: its T row (n_old floats, padded to quads) lives in LDS, at most
+// 144 KB = 36,864 floats (above 48 KB only after hipFuncSetAttribute).  Wider waves take the two-kernel form, T in HBM.
+constexpr int kFusedMaxOld = 36864;
 
 }  // namespace
 
@@ -715,7 +718,7 @@ static int sparse_impl(int64_t n_ind, const int64_t *ind, const int64_t *father,
     const bool timed = waves.size() <= 4096;
     size_t max_lds = 0;
     const bool no_fused = genphi::env_hook("GENPHI_SPARSE_NO_FUSED") != nullptr;      // (A/B and tests: the two-kernel form of a wave)
-    for (const Wave &w : waves) if (w.n_new > 0 && w.n_old <= 36864) max_lds = std::max(max_lds, static_cast<size_t>((w.n_old + 3) / 4 * 4) * sizeof(float));
+    for (const Wave &w : waves) if (w.n_new > 0 && w.n_old <= kFusedMaxOld) max_lds = std::max(max_lds, static_cast<size_t>((w.n_old + 3) / 4 * 4) * sizeof(float));
     for (int attempt = 0; attempt < 2; ++attempt) {               // (a second sweep only if the list of outliving entries overflowed)
         if (!st) SP_GO(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
         {   // ONE allocation for the two matrices, T, the index blob and the outliving-entry lists
@@ -755,7 +758,7 @@ static int sparse_impl(int64_t n_ind, const int64_t *ind, const int64_t *father,
             const int4 *d_par = reinterpret_cast<const int4 *>(d_blob + w.o_par);
             const int *d_keep = reinterpret_cast<const int *>(d_blob + w.o_keep), *d_newpos = reinterpret_cast<const int *>(d_blob + w.o_newpos);
             const int2 *d_meta_new = reinterpret_cast<const int2 *>(d_blob + w.o_meta_new), *d_meta_old = reinterpret_cast<const int2 *>(d_blob + w.o_meta_old);
-            const bool fused = !no_fused && w.n_new > 0 && w.n_old <= 36864;
+            const bool fused = !no_fused && w.n_new > 0 && w.n_old <= kFusedMaxOld;
             if (fused) {   // a new row end to end per workgroup (T stays in LDS) + survivors x survivors: ONE launch
                 const long long cb = w.n_surv > 0 ? static_cast<long long>(w.n_surv) * ((w.n_surv + 8 * kRowThreads - 1) / (8 * kRowThreads)) : 0;
                 const size_t lds = std::max<size_t>(16, static_cast<size_t>((w.n_old + 3) / 4 * 4) * sizeof(float));
@@ -776,7 +779,7 @@ static int sparse_impl(int64_t n_ind, const int64_t *ind, const int64_t *father,
             }
             if (w.n_new > 0) {
                 if (!fused) {
-                    const int lds_floats = w.n_old <= 36864 ? (w.n_old + 3) / 4 * 4 : 0;
+                    const int lds_floats = w.n_old <= kFusedMaxOld ? (w.n_old + 3) / 4 * 4 : 0;
                     hipLaunchKernelGGL(sparse_newnew_kernel, dim3(static_cast<unsigned>(w.n_new)), dim3(256), static_cast<size_t>(lds_floats) * sizeof(float), st,
                                        dM[cur], ld_cur, d_meta_old, w.n_old, d_par, d_meta_new, dT, ldT, w.n_new, w.n_old > 0 ? lds_floats : 0,
                                        dM[cur ^ 1], ld_next, w.n_surv, so);

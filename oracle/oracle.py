@@ -18,8 +18,8 @@ _F64P = C.POINTER(C.c_double)
 
 
 def build():
-    """Compile liboracle.so (gcc) and libsparse_oracle.so (g++) (idempotent)."""
-    for name, srcname in (("libsparse_oracle.so", "sparse_oracle.cpp"), ("liboracle.so", "genphi_oracle.c")):
+    """Compile liboracle.so (gcc), libsparse_oracle.so and libslot_oracle.so (g++) (idempotent)."""
+    for name, srcname in (("libsparse_oracle.so", "sparse_oracle.cpp"), ("libslot_oracle.so", "slot_oracle.cpp"), ("liboracle.so", "genphi_oracle.c")):
         so = os.path.join(_HERE, name)
         src = os.path.join(_HERE, srcname)
         if not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(src):
@@ -446,4 +446,98 @@ class SparsePhi:
         cap = _slib().sparse_oracle_entries(self._h, None, None, None, 0)
         r, c, v = np.zeros(cap, np.int64), np.zeros(cap, np.int64), np.zeros(cap, np.float32)
         _slib().sparse_oracle_entries(self._h, _p(r), _p(c), v.ctypes.data_as(_F32P), cap)
+        return r, c, v
+
+
+_SLOTLIB = None
+
+
+def _slotlib():
+    global _SLOTLIB
+    if _SLOTLIB is None:
+        build()
+        L = C.CDLL(os.path.join(_HERE, "libslot_oracle.so"))
+        L.slot_oracle_create.argtypes = [C.c_int64, _I64P, _I64P, _I64P, C.c_int64, _I64P, C.c_int, C.POINTER(C.c_int)]
+        L.slot_oracle_create.restype = C.c_void_p
+        L.slot_oracle_free.argtypes = [C.c_void_p]
+        L.slot_oracle_free.restype = None
+        L.slot_oracle_peak_live.argtypes = [C.c_void_p]
+        L.slot_oracle_peak_live.restype = C.c_int64
+        L.slot_oracle_get.argtypes = [C.c_void_p, C.c_int64, _I64P, _I64P, _F32P]
+        L.slot_oracle_get.restype = C.c_int64
+        L.slot_oracle_info.argtypes = [C.c_void_p, _I64P, _I64P, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        L.slot_oracle_info.restype = None
+        L.slot_oracle_entries.argtypes = [C.c_void_p, C.c_int64, _I64P, _I64P, _F32P]
+        L.slot_oracle_entries.restype = C.c_int64
+        _SLOTLIB = L
+    return _SLOTLIB
+
+
+class SlotSparsePhi:
+    """The same KinshipMatrix as SparsePhi (src/compute.jl:321-447), restated in oracle/slot_oracle.cpp with a dense matrix of
+    the live set (a slot per live individual, reused after it retires) instead of dictionaries: memory (peak live)^2 floats,
+    where the literal restatement needs one map entry per stored pair.  Vectorised accessors."""
+
+    def __init__(self, ped, pro=None):
+        pro = ped.pro() if pro is None else np.asarray(pro, dtype=np.int64)
+        self.pro = _i64(pro)
+        self.ids = np.array(list(dict.fromkeys(self.pro.tolist())), dtype=np.int64)      # distinct probands, first occurrence order
+        rc = C.c_int(0)
+        self._h = _slotlib().slot_oracle_create(len(ped.ind), _p(ped.ind), _p(ped.father), _p(ped.mother), len(self.pro), _p(self.pro),
+                                                usable_cpus(), C.byref(rc))
+        if not self._h:
+            if rc.value == 1:
+                raise KeyError("unknown proband ID")
+            raise (MemoryError if rc.value == 3 else ValueError)(f"slot_oracle_create rc={rc.value}")
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _slotlib().slot_oracle_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+    def peak_live(self):
+        """The largest live set of the queue walk (the matrix is peak_live^2 Float32)."""
+        return int(_slotlib().slot_oracle_peak_live(self._h))
+
+    def get(self, id1, id2):
+        """getindex for arrays of ID pairs (float32); KeyError for an ID that is not a proband."""
+        id1, id2 = _i64(np.atleast_1d(id1)), _i64(np.atleast_1d(id2))
+        out = np.empty(len(id1), dtype=np.float32)
+        bad = _slotlib().slot_oracle_get(self._h, len(id1), _p(id1), _p(id2), out.ctypes.data_as(_F32P))
+        if bad >= 0:
+            raise KeyError((int(id1[bad]), int(id2[bad])))
+        return out
+
+    def __getitem__(self, ids):
+        return float(self.get([ids[0]], [ids[1]])[0])
+
+    def matrix(self, ids=None):
+        """getindex for every pair of `ids` (default: the distinct probands), (len, len) float32."""
+        ids = self.ids if ids is None else _i64(ids)
+        return self.get(np.repeat(ids, len(ids)), np.tile(ids, len(ids))).reshape(len(ids), len(ids))
+
+    def info(self):
+        """(rows, stored entries, sum of all stored values, sum of the diagonal values)."""
+        nr, nz = C.c_int64(), C.c_int64()
+        sa, sd = C.c_double(), C.c_double()
+        _slotlib().slot_oracle_info(self._h, C.byref(nr), C.byref(nz), C.byref(sa), C.byref(sd))
+        return nr.value, nz.value, sa.value, sd.value
+
+    def show(self):
+        nr, nz, _, _ = self.info()
+        return f"{nr}×{nr} KinshipMatrix with {nz} stored entries."
+
+    def phi_mean(self):
+        nr, _, sa, sd = self.info()
+        return np.float32((sa - sd) / (nr * (nr - 1) / 2))
+
+    def entries(self):
+        """Every stored entry as (row rank, column rank, value) arrays, in no particular order."""
+        L = _slotlib()
+        n = L.slot_oracle_entries(self._h, 0, None, None, None)
+        r, c, v = np.zeros(n, np.int64), np.zeros(n, np.int64), np.zeros(n, np.float32)
+        L.slot_oracle_entries(self._h, n, _p(r), _p(c), v.ctypes.data_as(_F32P))
         return r, c, v
