@@ -14,6 +14,7 @@ meaning, printed lines and error behaviour as the reference:
     K = gen.sparse_phi(ped); K[1, 2]       # src/compute.jl:321-447, :31-46; gen.phiMean(K) :467-472
     gen.f(ped, [1])                        # src/compute.jl:500-511, from one Float64 GPU sweep over the parents
     gen.branching(ped, pro=[1])            # src/extract.jl:65-186, native pruning (csrc/loader.cpp)
+    gen.gc(ped)                            # src/compute.jl:518-595: genetic contributions (csrc/gc.hip)
 
 All kinship arithmetic runs in hand-written HIP kernels behind the C-ABI in
 include/genphi.h (csrc/genphi_hip.hip); there is no CPU fallback.
@@ -24,7 +25,7 @@ from collections import OrderedDict
 import numpy as np
 
 from . import _capi
-from ._capi import PhiPlan, KinshipMatrix, GenphiDeviceError, GenphiLibraryMissing  # noqa: F401
+from ._capi import PhiPlan, KinshipMatrix, GCPlan, GenphiDeviceError, GenphiLibraryMissing  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
@@ -295,6 +296,26 @@ def branching(pedigree, pro=None, ancestors=None):
     """
     return Pedigree(*_capi.branching(pedigree.ind, pedigree.father, pedigree.mother, pedigree.sex,
                                      pro=pro, ancestors=ancestors))
+
+
+def gc(pedigree, pro=None, ancestors=None, device=None):
+    """gen.gc(pedigree; pro = pro(pedigree), ancestors = founder(pedigree)) (src/compute.jl:518-595): the genetic
+    contribution of each ancestor (columns) to each proband (rows), a float32 array of shape (len(pro), len(ancestors)).
+
+    Entry [i, j] = sum over the descending paths from ancestors[j] to pro[i] of 0.5^length, computed on the GPU by a
+    Float64 recursion over the generation cuts (csrc/gc.hip) and rounded to float32 once.  As in the reference, only
+    leaves (individuals without children) receive contributions, and a proband listed again gets a row of zeros.  Equal
+    to the reference bit for bit while the sweep has at most 24 steps; deeper, the correctly rounded exact value (up to
+    52 steps; within 1 ulp beyond), where the reference's own path-by-path float32 sums may round differently
+    (include/genphi.h).  KeyError for an unknown ID.  Each call plans, sweeps and frees its own handle."""
+    probands = globals()["pro"](pedigree) if pro is None else np.ascontiguousarray(pro, dtype=np.int64)
+    ancestors = founder(pedigree) if ancestors is None else np.ascontiguousarray(ancestors, dtype=np.int64)
+    h = GCPlan(pedigree.ind, pedigree.father, pedigree.mother, probands, ancestors)
+    try:
+        h.compute(device=device)
+        return h.result_to_host()
+    finally:
+        h.close()
 
 
 def sparse_phi(pedigree, probandIDs=None, device=None):

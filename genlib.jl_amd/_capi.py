@@ -55,6 +55,7 @@ EXPORTED_SYMBOLS = [
     "genphi_panel_device_bytes", "genphi_panel_begin", "genphi_panel_pack", "genphi_panel_compute", "genphi_panel_pack_on", "genphi_panel_compute_on", "genphi_panel_sync",
     "genphi_panel_result_to_host",
     "genphi_panel_destroy",
+    "genphi_gc_create", "genphi_gc_compute", "genphi_gc_result_device", "genphi_gc_result_to_host", "genphi_gc_stats", "genphi_gc_destroy",
 ]
 
 _lib = None
@@ -192,6 +193,18 @@ def lib():
         L.genphi_panel_result_to_host.restype = C.c_int
         L.genphi_panel_destroy.argtypes = [C.c_void_p]
         L.genphi_panel_destroy.restype = None
+        L.genphi_gc_create.argtypes = [C.c_int64, _I64P, _I64P, _I64P, C.c_int64, _I64P, C.c_int64, _I64P, C.POINTER(C.c_void_p)]
+        L.genphi_gc_create.restype = C.c_int
+        L.genphi_gc_compute.argtypes = [C.c_void_p, C.c_int32]
+        L.genphi_gc_compute.restype = C.c_int
+        L.genphi_gc_result_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), _I64P]
+        L.genphi_gc_result_device.restype = C.c_int
+        L.genphi_gc_result_to_host.argtypes = [C.c_void_p, _F32P]
+        L.genphi_gc_result_to_host.restype = C.c_int
+        L.genphi_gc_stats.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), _I64P, C.POINTER(C.c_int32)]
+        L.genphi_gc_stats.restype = C.c_int
+        L.genphi_gc_destroy.argtypes = [C.c_void_p]
+        L.genphi_gc_destroy.restype = None
         L.genphi_last_error.restype = C.c_char_p
         L.genphi_version.restype = C.c_char_p
         _lib = L
@@ -701,3 +714,55 @@ class PanelPlan:
         if rc:
             _raise(rc)
         return out
+
+
+class GCPlan:
+    """gen.gc's handle (include/genphi.h, genphi_gc_*): planned on the host at construction (KeyError on an unknown proband or
+    ancestor, no GPU needed), swept on the GPU by compute()."""
+
+    def __init__(self, ind, father, mother, pro_ids, anc_ids):
+        L = lib()
+        ind, father, mother, pro_ids, anc_ids = _i64(ind), _i64(father), _i64(mother), _i64(pro_ids), _i64(anc_ids)
+        h = C.c_void_p()
+        rc = L.genphi_gc_create(len(ind), ind.ctypes.data_as(_I64P), father.ctypes.data_as(_I64P), mother.ctypes.data_as(_I64P),
+                                len(pro_ids), pro_ids.ctypes.data_as(_I64P), len(anc_ids), anc_ids.ctypes.data_as(_I64P), C.byref(h))
+        if rc:
+            _raise(rc)
+        self._h = h
+        self.shape = (len(pro_ids), len(anc_ids))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().genphi_gc_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+    def compute(self, device=None):
+        rc = lib().genphi_gc_compute(self._h, -1 if device is None else int(device))
+        if rc:
+            _raise(rc)
+
+    def result_device(self):
+        """(device pointer, row pitch in floats) of the resident result."""
+        p, ld = C.c_void_p(), C.c_int64()
+        rc = lib().genphi_gc_result_device(self._h, C.byref(p), C.byref(ld))
+        if rc:
+            _raise(rc)
+        return p.value, ld.value
+
+    def result_to_host(self):
+        out = np.empty(self.shape, dtype=np.float32)
+        rc = lib().genphi_gc_result_to_host(self._h, out.ctypes.data_as(_F32P))
+        if rc:
+            _raise(rc)
+        return out
+
+    def stats(self):
+        """dict(sweep_ms, algorithmic_bytes, peak_slots, panel_cols) of the last compute()."""
+        ms, ab, ps, pc = C.c_double(), C.c_double(), C.c_int64(), C.c_int32()
+        rc = lib().genphi_gc_stats(self._h, C.byref(ms), C.byref(ab), C.byref(ps), C.byref(pc))
+        if rc:
+            _raise(rc)
+        return {"sweep_ms": ms.value, "algorithmic_bytes": ab.value, "peak_slots": ps.value, "panel_cols": pc.value}

@@ -275,4 +275,30 @@ function branching(pedigree::GenLib.Pedigree; pro::Union{Vector{Int}, Nothing} =
     GenLib.genealogy(GenLib.DataFrame(ind = cols[1], father = cols[2], mother = cols[3], sex = cols[4]), sort = false)
 end
 
+"""
+    gc(pedigree::GenLib.Pedigree; pro = GenLib.pro(pedigree), ancestors = GenLib.founder(pedigree), device = -1)
+
+Genetic contributions of `ancestors` (columns) to `pro` (rows), `Matrix{Float32}`, as `GenLib.gc`
+(src/compute.jl:518-595): one Float64 recursion over the generation cuts on the GPU (csrc/gc.hip)
+instead of a depth-first walk of every path; the reference's zero rows (non-leaf and repeated
+probands) are kept.  Exact, rounded to Float32 once (include/genphi.h, genphi_gc_*).
+"""
+function gc(pedigree::GenLib.Pedigree; pro::Vector{Int} = GenLib.pro(pedigree),
+            ancestors::Vector{Int} = GenLib.founder(pedigree), device::Integer = -1)
+    ind, father, mother, _ = flatten(pedigree)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve ind father mother pro ancestors check(ccall((:genphi_gc_create, libgenphi), Cint,
+        (Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Int64, Ptr{Int64}, Int64, Ptr{Int64}, Ptr{Ptr{Cvoid}}),
+        length(ind), ind, father, mother, length(pro), pro, length(ancestors), ancestors, h))
+    try
+        check(ccall((:genphi_gc_compute, libgenphi), Cint, (Ptr{Cvoid}, Int32), h[], Int32(device)))
+        rowmajor = Matrix{Float32}(undef, length(ancestors), length(pro))     # the library writes pro x ancestors row-major
+        GC.@preserve rowmajor check(ccall((:genphi_gc_result_to_host, libgenphi), Cint, (Ptr{Cvoid}, Ptr{Float32}),
+                                          h[], rowmajor))
+        return permutedims(rowmajor)
+    finally
+        ccall((:genphi_gc_destroy, libgenphi), Cvoid, (Ptr{Cvoid},), h[])
+    end
+end
+
 end # module

@@ -342,6 +342,41 @@ int genphi_panel_sync(genphi_panel *p);
 int genphi_panel_result_to_host(genphi_panel *p, float *out);
 void genphi_panel_destroy(genphi_panel *p);
 
+/* ---- gen.gc: genetic contributions of ancestors to probands (csrc/gc.hip) -----------------------------------
+ * Replaces gc(pedigree; pro = pro(pedigree), ancestors = founder(pedigree)), src/compute.jl:518-595 (GENLIB's Congen).
+ * Result: Float32, n_pro x n_anc, row-major (ld = n_anc), rows in pro_ids order, columns in anc_ids order (a Julia
+ * Matrix{Float32}(undef, n_anc, n_pro) receives its transpose).  Entry [i][j] = sum over every descending path from
+ * anc_ids[j] to pro_ids[i] of 0.5^length.  The reference's rules, kept here:
+ *   - only LEAVES (individuals with no children anywhere in the pedigree) receive contributions: a proband with
+ *     children gets a row of zeros;
+ *   - the reference reads and resets a proband's accumulator after each ancestor, so a proband ID listed again gets a
+ *     row of zeros: only its first occurrence carries values;
+ *   - a duplicated ancestor gives identical columns; an ancestor that is itself a leaf proband gets 1 on its own row;
+ *     an ancestor with parents is allowed (its parents add nothing to its column); an ancestor with no path to a
+ *     proband gives a zero column; an unknown ID in pro_ids or anc_ids -> GENPHI_ERR_UNKNOWN_ID (KeyError);
+ *   - n_pro = 0 or n_anc = 0: an empty result of that shape.
+ * Exactness.  The sweep runs over the planner's generation cuts; after c steps every value is a multiple of 2^-c in
+ * [0, 1], and the rows are kept in Float64 and rounded to Float32 once.  So the result is the exact contribution
+ * correctly rounded to Float32 for sweeps of up to 52 steps, and within 1 Float32 ulp of it beyond (normal range).  The
+ * reference adds paths one at a time in Float32: its sums are exact, and equal to this result bit for bit, while the
+ * sweep has at most 24 steps (geneaJi, genea140, cfg3); deeper, its own rounding depends on the order of its paths and
+ * may differ from the correctly rounded value returned here.
+ *   create            host only (no GPU): checks IDs and pedigree order, plans cuts, rows and slots
+ *   compute           the sweep on `device` (-1 = current); the result stays resident on the device; GENPHI_ERR_ALLOC
+ *                     before any launch when the result or the slot rows do not fit
+ *   result_device     device pointer and row pitch (floats) of the resident result
+ *   result_to_host    out: n_pro x n_anc Float32, row-major
+ *   stats             device time of the last sweep (HIP events), its algorithmic bytes (source rows read and rows
+ *                     written at 8 bytes per column, plus the 4-byte result), the slot rows of one panel, the panel width */
+typedef struct genphi_gc genphi_gc;
+int genphi_gc_create(int64_t n_ind, const int64_t *ind, const int64_t *father, const int64_t *mother,
+                     int64_t n_pro, const int64_t *pro_ids, int64_t n_anc, const int64_t *anc_ids, genphi_gc **out);
+int genphi_gc_compute(genphi_gc *h, int32_t device);
+int genphi_gc_result_device(const genphi_gc *h, const float **d_ptr, int64_t *ld);
+int genphi_gc_result_to_host(genphi_gc *h, float *out);
+int genphi_gc_stats(const genphi_gc *h, double *sweep_ms, double *algorithmic_bytes, int64_t *peak_slots, int32_t *panel_cols);
+void genphi_gc_destroy(genphi_gc *h);
+
 /* Frees host and device memory of the plan (NULL is allowed). */
 void genphi_plan_destroy(genphi_plan *plan);
 
