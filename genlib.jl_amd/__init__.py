@@ -15,6 +15,7 @@ meaning, printed lines and error behaviour as the reference:
     gen.f(ped, [1])                        # src/compute.jl:500-511, from one Float64 GPU sweep over the parents
     gen.branching(ped, pro=[1])            # src/extract.jl:65-186, native pruning (csrc/loader.cpp)
     gen.gc(ped)                            # src/compute.jl:518-595: genetic contributions (csrc/gc.hip)
+    gen.occ(ped); gen.rec(ped)             # src/describe.jl:184-238, :133-145: occurrences, coverage (csrc/occ.hip)
 
 All kinship arithmetic runs in hand-written HIP kernels behind the C-ABI in
 include/genphi.h (csrc/genphi_hip.hip); there is no CPU fallback.
@@ -25,7 +26,7 @@ from collections import OrderedDict
 import numpy as np
 
 from . import _capi
-from ._capi import PhiPlan, KinshipMatrix, GCPlan, GenphiDeviceError, GenphiLibraryMissing  # noqa: F401
+from ._capi import PhiPlan, KinshipMatrix, GCPlan, OccPlan, RecPlan, GenphiDeviceError, GenphiLibraryMissing  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
@@ -314,6 +315,48 @@ def gc(pedigree, pro=None, ancestors=None, device=None):
     try:
         h.compute(device=device)
         return h.result_to_host()
+    finally:
+        h.close()
+
+
+def occ(pedigree, pro=None, ancestors=None, typeOcc="IND", device=None):
+    """gen.occ(pedigree; pro = pro(pedigree), ancestors = founder(pedigree), typeOcc = "IND") (src/describe.jl:184-238): how
+    many times each ancestor (rows) occurs in each proband's genealogy (columns), an int64 array of shape
+    (len(ancestors), len(pro)); typeOcc = "TOTAL": summed over the probands, shape (len(ancestors), 1).
+
+    Entry [j, i] = the number of ascending paths from pro[i] to ancestors[j] (1 for the proband itself), computed on the GPU
+    by an integer recursion over the generation cuts (csrc/occ.hip) with the reference's wrap-around: equal to the
+    reference bit for bit at any depth.  The "IND" array is a transposed view of the (len(pro), len(ancestors)) row-major
+    result, not a copy.  "TOTAL" is reduced on the device and never holds the full matrix.  As in the reference, every
+    proband counts (with or without children, each time it is listed), and of a duplicated ancestor only the first row
+    carries values.  KeyError for an unknown ID; ValueError for another typeOcc (the reference returns nothing).  Each call
+    plans, sweeps and frees its own handle."""
+    if typeOcc not in ("IND", "TOTAL"):
+        raise ValueError('typeOcc must be "IND" or "TOTAL", not %r' % (typeOcc,))
+    probands = globals()["pro"](pedigree) if pro is None else np.ascontiguousarray(pro, dtype=np.int64)
+    ancestors = founder(pedigree) if ancestors is None else np.ascontiguousarray(ancestors, dtype=np.int64)
+    h = OccPlan(pedigree.ind, pedigree.father, pedigree.mother, probands, ancestors, total_only=typeOcc == "TOTAL")
+    try:
+        h.compute(device=device)
+        return h.totals().reshape(-1, 1) if typeOcc == "TOTAL" else h.result_to_host().T
+    finally:
+        h.close()
+
+
+def rec(pedigree, probandIDs=None, ancestorIDs=None, device=None):
+    """gen.rec(pedigree, probandIDs = pro(pedigree), ancestorIDs = founder(pedigree)) (src/describe.jl:133-145): the coverage
+    of each ancestor, that is, how many of the probands descend from it; an int64 array of length len(ancestorIDs).
+
+    Computed on the GPU as ancestor bit sets by an OR recursion over the generation cuts and a column count over the
+    probands' rows (csrc/occ.hip); not derived from gen.occ, whose counts can wrap to 0.  As in the reference, descendants
+    are strict (an ancestor that is a proband does not count itself), a proband listed twice counts once, a proband ID that
+    is not in the pedigree is ignored, and a duplicated ancestor gives equal entries.  KeyError for an unknown ancestor ID."""
+    probandIDs = pro(pedigree) if probandIDs is None else np.ascontiguousarray(probandIDs, dtype=np.int64)
+    ancestorIDs = founder(pedigree) if ancestorIDs is None else np.ascontiguousarray(ancestorIDs, dtype=np.int64)
+    h = RecPlan(pedigree.ind, pedigree.father, pedigree.mother, probandIDs, ancestorIDs)
+    try:
+        h.compute(device=device)
+        return h.result()
     finally:
         h.close()
 

@@ -56,6 +56,8 @@ EXPORTED_SYMBOLS = [
     "genphi_panel_result_to_host",
     "genphi_panel_destroy",
     "genphi_gc_create", "genphi_gc_compute", "genphi_gc_result_device", "genphi_gc_result_to_host", "genphi_gc_stats", "genphi_gc_destroy",
+    "genphi_occ_create", "genphi_occ_compute", "genphi_occ_result_device", "genphi_occ_result_to_host", "genphi_occ_totals", "genphi_occ_stats", "genphi_occ_destroy",
+    "genphi_rec_create", "genphi_rec_compute", "genphi_rec_result", "genphi_rec_stats", "genphi_rec_destroy",
 ]
 
 _lib = None
@@ -205,6 +207,23 @@ def lib():
         L.genphi_gc_stats.restype = C.c_int
         L.genphi_gc_destroy.argtypes = [C.c_void_p]
         L.genphi_gc_destroy.restype = None
+        L.genphi_occ_create.argtypes = [C.c_int64, _I64P, _I64P, _I64P, C.c_int64, _I64P, C.c_int64, _I64P, C.c_int32, C.POINTER(C.c_void_p)]
+        L.genphi_occ_create.restype = C.c_int
+        L.genphi_rec_create.argtypes = [C.c_int64, _I64P, _I64P, _I64P, C.c_int64, _I64P, C.c_int64, _I64P, C.POINTER(C.c_void_p)]
+        L.genphi_rec_create.restype = C.c_int
+        L.genphi_occ_result_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), _I64P]
+        L.genphi_occ_result_device.restype = C.c_int
+        for kind in ("occ", "rec"):
+            fn = getattr(L, "genphi_%s_compute" % kind)
+            fn.argtypes, fn.restype = [C.c_void_p, C.c_int32], C.c_int
+            fn = getattr(L, "genphi_%s_stats" % kind)
+            fn.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), _I64P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _I64P]
+            fn.restype = C.c_int
+            fn = getattr(L, "genphi_%s_destroy" % kind)
+            fn.argtypes, fn.restype = [C.c_void_p], None
+        for name in ("genphi_occ_result_to_host", "genphi_occ_totals", "genphi_rec_result"):
+            fn = getattr(L, name)
+            fn.argtypes, fn.restype = [C.c_void_p, _I64P], C.c_int
         L.genphi_last_error.restype = C.c_char_p
         L.genphi_version.restype = C.c_char_p
         _lib = L
@@ -766,3 +785,116 @@ class GCPlan:
         if rc:
             _raise(rc)
         return {"sweep_ms": ms.value, "algorithmic_bytes": ab.value, "peak_slots": ps.value, "panel_cols": pc.value}
+
+
+GENPHI_OCC_TOTAL_ONLY = 1
+GENPHI_OCC_ROWS64 = 2
+
+
+def _sweep_stats(fn, h):
+    ms, ab, ps, pc, rb, nl = C.c_double(), C.c_double(), C.c_int64(), C.c_int32(), C.c_int32(), C.c_int64()
+    rc = fn(h, C.byref(ms), C.byref(ab), C.byref(ps), C.byref(pc), C.byref(rb), C.byref(nl))
+    if rc:
+        _raise(rc)
+    return {"sweep_ms": ms.value, "algorithmic_bytes": ab.value, "peak_slots": ps.value, "panel_cols": pc.value,
+            "row_bits": rb.value, "launches": nl.value}
+
+
+class OccPlan:
+    """gen.occ's handle (include/genphi.h, genphi_occ_*): planned on the host at construction (KeyError on an unknown proband or
+    ancestor, no GPU needed), swept on the GPU by compute().  total_only: the handle reduces the last step into the n_anc
+    totals on the device and holds no n_pro x n_anc result; rows64: 64-bit slot rows even where 32-bit rows are exact."""
+
+    def __init__(self, ind, father, mother, pro_ids, anc_ids, total_only=False, rows64=False):
+        L = lib()
+        ind, father, mother, pro_ids, anc_ids = _i64(ind), _i64(father), _i64(mother), _i64(pro_ids), _i64(anc_ids)
+        h = C.c_void_p()
+        flags = (GENPHI_OCC_TOTAL_ONLY if total_only else 0) | (GENPHI_OCC_ROWS64 if rows64 else 0)
+        rc = L.genphi_occ_create(len(ind), ind.ctypes.data_as(_I64P), father.ctypes.data_as(_I64P), mother.ctypes.data_as(_I64P),
+                                 len(pro_ids), pro_ids.ctypes.data_as(_I64P), len(anc_ids), anc_ids.ctypes.data_as(_I64P), flags, C.byref(h))
+        if rc:
+            _raise(rc)
+        self._h = h
+        self.total_only = bool(total_only)
+        self.shape = (len(pro_ids), len(anc_ids))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().genphi_occ_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+    def compute(self, device=None):
+        rc = lib().genphi_occ_compute(self._h, -1 if device is None else int(device))
+        if rc:
+            _raise(rc)
+
+    def result_device(self):
+        """(device pointer, row pitch in Int64 entries) of the resident result."""
+        p, ld = C.c_void_p(), C.c_int64()
+        rc = lib().genphi_occ_result_device(self._h, C.byref(p), C.byref(ld))
+        if rc:
+            _raise(rc)
+        return p.value, ld.value
+
+    def result_to_host(self):
+        """The n_pro x n_anc int64 result (rows = probands)."""
+        out = np.empty(self.shape, dtype=np.int64)
+        rc = lib().genphi_occ_result_to_host(self._h, out.ctypes.data_as(_I64P))
+        if rc:
+            _raise(rc)
+        return out
+
+    def totals(self):
+        """The n_anc int64 totals over the probands (on a handle with a full result: its column sums, taken on the device)."""
+        out = np.empty(self.shape[1], dtype=np.int64)
+        rc = lib().genphi_occ_totals(self._h, out.ctypes.data_as(_I64P))
+        if rc:
+            _raise(rc)
+        return out
+
+    def stats(self):
+        """dict(sweep_ms, algorithmic_bytes, peak_slots, panel_cols, row_bits, launches) of the last compute()."""
+        return _sweep_stats(lib().genphi_occ_stats, self._h)
+
+
+class RecPlan:
+    """gen.rec's handle (include/genphi.h, genphi_rec_*): planned on the host at construction (KeyError on an unknown ancestor;
+    unknown proband IDs are ignored), swept and counted on the GPU by compute()."""
+
+    def __init__(self, ind, father, mother, pro_ids, anc_ids):
+        L = lib()
+        ind, father, mother, pro_ids, anc_ids = _i64(ind), _i64(father), _i64(mother), _i64(pro_ids), _i64(anc_ids)
+        h = C.c_void_p()
+        rc = L.genphi_rec_create(len(ind), ind.ctypes.data_as(_I64P), father.ctypes.data_as(_I64P), mother.ctypes.data_as(_I64P),
+                                 len(pro_ids), pro_ids.ctypes.data_as(_I64P), len(anc_ids), anc_ids.ctypes.data_as(_I64P), C.byref(h))
+        if rc:
+            _raise(rc)
+        self._h = h
+        self.n_anc = len(anc_ids)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().genphi_rec_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+    def compute(self, device=None):
+        rc = lib().genphi_rec_compute(self._h, -1 if device is None else int(device))
+        if rc:
+            _raise(rc)
+
+    def result(self):
+        out = np.empty(self.n_anc, dtype=np.int64)
+        rc = lib().genphi_rec_result(self._h, out.ctypes.data_as(_I64P))
+        if rc:
+            _raise(rc)
+        return out
+
+    def stats(self):
+        """dict(sweep_ms, algorithmic_bytes, peak_slots, panel_cols, row_bits, launches) of the last compute()."""
+        return _sweep_stats(lib().genphi_rec_stats, self._h)

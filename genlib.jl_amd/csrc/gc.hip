@@ -12,13 +12,9 @@
 // the values of cut c are multiples of 2^-c in [0, 1]: the Float64 rows are exact for up to 52 steps, and the result is rounded
 // to Float32 once (see the contract in include/genphi.h).
 //
-// Host schedule (genphi_gc_create, no GPU):
-//   rows    only members that are a requested ancestor or descend from one are computed; every other row is zero ("none")
-//   slots   each computed member owns one Float64 row of a slot buffer from the step that creates it until its last cut has been
-//           read; members dragged from one cut to the next keep their slot (nothing is copied); a slot freed after step s is
-//           handed out from step s+1 on, never inside the launch that still reads it
-//   emit    the last step writes its rows straight into the Float32 result (n_pro x n_anc, row-major, ld = n_anc): only the first
-//           occurrence of a leaf proband gets values; the result is cleared once before the sweep
+// Host schedule (genphi_gc_create, no GPU): ancestor_sweep.h, shared with gen.occ and gen.rec, with gc's emission rule
+// (Emit::LeafFirst): the last step writes its rows straight into the Float32 result (n_pro x n_anc, row-major, ld = n_anc); only
+// the first occurrence of a leaf proband gets values; the result is cleared once before the sweep.  Slot rows are Float64.
 // Column panels: the columns are independent; a sweep runs over panels of C ancestor columns (slot memory peak_slots x C x 8
 // bytes per panel).  A launch can cover several panels through grid dimension y; by default panels are sized for the Infinity
 // Cache and swept one after the other (kPanelSlotBytes).
@@ -30,10 +26,10 @@
 #include <cstring>
 #include <new>
 #include <string>
-#include <unordered_map>
 #include <vector>
 
 #include "../../include/genphi.h"
+#include "ancestor_sweep.h"
 #include "devcache.h"
 #include "planner.h"
 
@@ -41,9 +37,9 @@ int genphi_set_error(int code, const std::string &msg);      // genphi_hip.hip
 
 namespace {
 
-// One item = one row a launch computes: (destination slot or result row, source slot A, source slot B, first one-hot entry);
-// -1 = the zero row.  The one-hot entries of item i are oh_cols[items[i].w .. items[i + 1].w) (global column indices,
-// ascending); every list of items ends with a sentinel whose .w closes the last one.
+static_assert(sizeof(genphi::SweepItem) == sizeof(int4), "items are uploaded as they are and read as int4");
+
+// One item (genphi::SweepItem, read as an int4) = one row a launch computes.
 //
 // LPR lanes per row (a power of two): each lane moves 16 bytes (two Float64 columns) per access, U accesses of each source row
 // in flight before any is used; a wave holds 64 / LPR rows (narrow panels: several rows per wave instead of idle lanes).
@@ -128,13 +124,7 @@ constexpr int64_t kPanelMinCols = 64;
 
 struct genphi_gc {
     int64_t n_pro = 0, n_anc = 0;
-    // host schedule
-    std::vector<int4> items;                 // every launch's items, each list closed by a sentinel
-    std::vector<int32_t> oh_cols;
-    std::vector<int64_t> list_begin;         // launch k: items [list_begin[k], list_begin[k + 1] - 1) (the last one a sentinel)
-    std::vector<char> list_to_result;
-    std::vector<double> list_srcs;           // source rows read, summed over the list's items (algorithmic bytes)
-    int64_t peak_slots = 0;
+    genphi::SweepSchedule sched;             // host schedule (ancestor_sweep.h, Emit::LeafFirst)
     int32_t panel_env = 0, group_env = 0;    // GENPHI_GC_PANEL / GENPHI_GC_PANELS_PER_LAUNCH (0 = default rule)
     // device
     int device = -1;
@@ -176,155 +166,15 @@ void release_device(genphi_gc *h)
         if (e_ != hipSuccess) return genphi_set_error(GENPHI_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
     } while (0)
 
-// ID -> rank (a direct table for dense non-negative IDs, else a hash map)
-struct Ranks {
-    std::vector<int32_t> table;
-    std::unordered_map<int64_t, int32_t> map;
-    bool direct = false;
-    void init(int64_t n, const int64_t *ind)
-    {
-        int64_t lo = INT64_MAX, hi = INT64_MIN;
-        for (int64_t i = 0; i < n; ++i) { lo = std::min(lo, ind[i]); hi = std::max(hi, ind[i]); }
-        direct = n > 0 && lo >= 0 && hi < 3 * n + 1024;
-        if (direct) {
-            table.assign(static_cast<size_t>(hi) + 1, -1);
-            for (int64_t i = 0; i < n; ++i) table[ind[i]] = static_cast<int32_t>(i);
-        } else {
-            map.reserve(static_cast<size_t>(n) * 2);
-            for (int64_t i = 0; i < n; ++i) map.emplace(ind[i], static_cast<int32_t>(i));
-        }
-    }
-    int32_t find(int64_t id) const
-    {
-        if (direct) return (id < 0 || id >= static_cast<int64_t>(table.size())) ? -1 : table[id];
-        auto it = map.find(id);
-        return it == map.end() ? -1 : it->second;
-    }
-};
-
 int plan_gc(genphi_gc *h, int64_t n_ind, const int64_t *ind, const int64_t *father, const int64_t *mother, int64_t n_pro,
             const int64_t *pro_ids, int64_t n_anc, const int64_t *anc_ids)
 {
-    genphi::PlanOptions opt;
-    opt.indices_only = true;
-    genphi::Plan plan;
+    genphi::SweepOptions opt;
+    opt.emit = genphi::Emit::LeafFirst;
     std::string err;
-    // (validates the pedigree -- order, duplicates -- and the proband IDs; the planner keeps first occurrences)
-    int rc = genphi::build_plan(n_ind, ind, father, mother, n_pro, pro_ids, opt, plan, err);
+    const int rc = genphi::plan_sweep(h->sched, n_ind, ind, father, mother, n_pro, pro_ids, n_anc, anc_ids, opt, err);
     if (rc) return genphi_set_error(rc, err);
-    Ranks ranks;
-    ranks.init(n_ind, ind);
-    std::vector<int32_t> anc_rank(n_anc);
-    for (int64_t j = 0; j < n_anc; ++j) {
-        anc_rank[j] = ranks.find(anc_ids[j]);
-        if (anc_rank[j] < 0) return genphi_set_error(GENPHI_ERR_UNKNOWN_ID, "KeyError: ancestor " + std::to_string(anc_ids[j]) + " not found");
-    }
     h->n_pro = n_pro; h->n_anc = n_anc;
-    const int L = plan.n_levels;
-    if (n_pro == 0 || n_anc == 0 || L == 0) return GENPHI_OK;
-
-    // parents as ranks (the planner checked that they exist and come first), leaves, relevance
-    std::vector<int32_t> fa(n_ind, -1), mo(n_ind, -1);
-    std::vector<char> has_child(n_ind, 0), rel(n_ind, 0);
-    for (int64_t i = 0; i < n_ind; ++i) {
-        if (father[i] != 0) { fa[i] = ranks.find(father[i]); has_child[fa[i]] = 1; }
-        if (mother[i] != 0) { mo[i] = ranks.find(mother[i]); has_child[mo[i]] = 1; }
-    }
-    // one-hot columns of each ancestor rank: CSR over the ranks that are requested (columns ascending)
-    std::vector<int32_t> oh_start(n_ind + 1, 0);
-    for (int64_t j = 0; j < n_anc; ++j) oh_start[anc_rank[j] + 1]++;
-    for (int64_t i = 0; i < n_ind; ++i) oh_start[i + 1] += oh_start[i];
-    std::vector<int32_t> oh_of(n_anc);
-    {
-        std::vector<int32_t> fill(oh_start.begin(), oh_start.end() - 1);
-        for (int64_t j = 0; j < n_anc; ++j) oh_of[fill[anc_rank[j]]++] = static_cast<int32_t>(j);
-    }
-    for (int64_t i = 0; i < n_ind; ++i)      // rank order: parents first
-        rel[i] = oh_start[i + 1] > oh_start[i] || (fa[i] >= 0 && rel[fa[i]]) || (mo[i] >= 0 && rel[mo[i]]);
-
-    // members of cut 0 (founders) by position, from the sources of cut 1 (every member of cut 0 is one of them)
-    std::vector<int32_t> cut0(plan.cut_sizes[0], -1);
-    if (L == 1) {
-        for (int64_t k = 0; k < plan.cut_sizes[0]; ++k) cut0[k] = plan.final_members[k];
-    } else {
-        const genphi::LevelStep &st = plan.steps[0];
-        const int32_t none = static_cast<int32_t>(st.n_prev);
-        for (int64_t k = 0; k < st.n; ++k) {
-            const int32_t o = st.ord[k];
-            if (o >= 0) { cut0[st.srcA[k]] = o; continue; }
-            const int32_t x = o & 0x7fffffff;
-            if (st.srcA[k] != none) cut0[st.srcA[k]] = fa[x] >= 0 ? fa[x] : mo[x];
-            if (st.srcB[k] != none) cut0[st.srcB[k]] = mo[x];
-        }
-    }
-    // result row of each distinct proband (its first occurrence in pro_ids)
-    std::vector<int32_t> out_row(n_ind, -1);
-    for (int64_t k = n_pro - 1; k >= 0; --k) out_row[ranks.find(pro_ids[k])] = static_cast<int32_t>(k);
-
-    auto add_item = [&](int32_t dst, int32_t A, int32_t B, int32_t x) {
-        h->items.push_back(make_int4(dst, A, B, static_cast<int>(h->oh_cols.size())));
-        for (int32_t q = oh_start[x]; q < oh_start[x + 1]; ++q) h->oh_cols.push_back(oh_of[q]);
-        h->list_srcs.back() += (A >= 0) + (B >= 0);
-    };
-    auto open_list = [&](bool to_result) {
-        h->list_begin.push_back(static_cast<int64_t>(h->items.size()));
-        h->list_to_result.push_back(to_result);
-        h->list_srcs.push_back(0.0);
-    };
-    auto close_list = [&]() { h->items.push_back(make_int4(-1, -1, -1, static_cast<int>(h->oh_cols.size()))); };
-    auto emitted = [&](int32_t x) { return rel[x] && !has_child[x]; };
-
-    // slots: a free list; slot_of_prev = slots of the members of the current source cut by position (-1 = zero row)
-    std::vector<int32_t> free_slots;
-    int32_t n_slots = 0;
-    auto take = [&]() -> int32_t {
-        if (!free_slots.empty()) { const int32_t s = free_slots.back(); free_slots.pop_back(); return s; }
-        return n_slots++;
-    };
-    std::vector<int32_t> slot_prev(plan.cut_sizes[0], -1);
-    open_list(L == 1);
-    for (int64_t k = 0; k < plan.cut_sizes[0]; ++k) {
-        const int32_t x = cut0[k];
-        if (L == 1) {
-            if (emitted(x)) add_item(out_row[x], -1, -1, x);
-        } else if (rel[x]) {
-            slot_prev[k] = take();
-            add_item(slot_prev[k], -1, -1, x);
-        }
-    }
-    close_list();
-    std::vector<int32_t> rows;
-    for (int s = 0; s + 1 < L; ++s) {
-        const genphi::LevelStep &st = plan.steps[s];
-        const bool last = s + 2 == L;
-        const int32_t none = static_cast<int32_t>(st.n_prev);
-        std::vector<int32_t> slot_cur(st.n, -1);
-        std::vector<char> kept(st.n_prev, 0);
-        rows.clear();
-        for (int64_t k = 0; k < st.n; ++k) {
-            const int32_t o = st.ord[k];
-            if (o >= 0) { slot_cur[k] = slot_prev[st.srcA[k]]; kept[st.srcA[k]] = 1; continue; }   // dragged: same slot
-            const int32_t x = o & 0x7fffffff;
-            if (last ? emitted(x) : rel[x]) rows.push_back(static_cast<int32_t>(k));
-        }
-        genphi::reuse_order(st, rows);                        // siblings adjacent: the shared source row is served by L2
-        open_list(last);
-        for (int32_t k : rows) {
-            const int32_t x = st.ord[k] & 0x7fffffff;
-            const int32_t A = st.srcA[k] == none ? -1 : slot_prev[st.srcA[k]];
-            const int32_t B = st.srcB[k] == none ? -1 : slot_prev[st.srcB[k]];
-            if (last) { add_item(out_row[x], A, B, x); continue; }
-            slot_cur[k] = take();
-            add_item(slot_cur[k], A, B, x);
-        }
-        close_list();
-        // members of the source cut that leave with this step: their slots serve the steps after it
-        for (int64_t q = 0; q < st.n_prev; ++q)
-            if (!kept[q] && slot_prev[q] >= 0) free_slots.push_back(slot_prev[q]);
-        slot_prev.swap(slot_cur);
-    }
-    h->peak_slots = n_slots;                                  // (slots are taken from the free list first: the most ever live at once)
-    h->list_begin.push_back(static_cast<int64_t>(h->items.size()));
     return GENPHI_OK;
 }
 
@@ -353,9 +203,9 @@ int compute_impl(genphi_gc *h, int32_t device)
         return genphi_set_error(GENPHI_ERR_ALLOC, "gen.gc: the result (" + std::to_string(res_bytes >> 20) + " MiB) does not fit on device " +
                                                       std::to_string(device));
     // panels: C columns each (GENPHI_GC_PANEL, else the default rule), G of them per launch (as many as the memory holds)
-    const int64_t S = std::max<int64_t>(h->peak_slots, 1);
+    const int64_t S = std::max<int64_t>(h->sched.peak_slots, 1);
     const double slot_room = usable - static_cast<double>(res_bytes) -
-                             16.0 * static_cast<double>(h->items.size()) - 4.0 * static_cast<double>(h->oh_cols.size()) - (64 << 20);
+                             16.0 * static_cast<double>(h->sched.items.size()) - 4.0 * static_cast<double>(h->sched.oh_cols.size()) - (64 << 20);
     int64_t C = h->panel_env > 0 ? h->panel_env : std::max<int64_t>(kPanelMinCols, static_cast<int64_t>(kPanelSlotBytes / (8.0 * S)));
     C = std::min(C, std::max<int64_t>(n_anc, 1));
     auto panel_bytes = [&](int64_t c) { return 8.0 * static_cast<double>(S) * static_cast<double>((c + 1) & ~int64_t(1)); };
@@ -381,12 +231,12 @@ int compute_impl(genphi_gc *h, int32_t device)
         h->slot_bytes = need_slots;
     }
     if (!h->d_result && res_bytes) GC_TRY(genphi::cached_malloc(reinterpret_cast<void **>(&h->d_result), res_bytes));
-    if (!h->d_items && !h->items.empty()) {
-        GC_TRY(genphi::cached_malloc(reinterpret_cast<void **>(&h->d_items), h->items.size() * sizeof(int4)));
-        GC_TRY(hipMemcpyAsync(h->d_items, h->items.data(), h->items.size() * sizeof(int4), hipMemcpyHostToDevice, h->stream));
-        if (!h->oh_cols.empty()) {
-            GC_TRY(genphi::cached_malloc(reinterpret_cast<void **>(&h->d_oh), h->oh_cols.size() * sizeof(int)));
-            GC_TRY(hipMemcpyAsync(h->d_oh, h->oh_cols.data(), h->oh_cols.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    if (!h->d_items && !h->sched.items.empty()) {
+        GC_TRY(genphi::cached_malloc(reinterpret_cast<void **>(&h->d_items), h->sched.items.size() * sizeof(int4)));
+        GC_TRY(hipMemcpyAsync(h->d_items, h->sched.items.data(), h->sched.items.size() * sizeof(int4), hipMemcpyHostToDevice, h->stream));
+        if (!h->sched.oh_cols.empty()) {
+            GC_TRY(genphi::cached_malloc(reinterpret_cast<void **>(&h->d_oh), h->sched.oh_cols.size() * sizeof(int)));
+            GC_TRY(hipMemcpyAsync(h->d_oh, h->sched.oh_cols.data(), h->sched.oh_cols.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
         }
     }
     h->panel_cols = static_cast<int32_t>(C);
@@ -397,17 +247,17 @@ int compute_impl(genphi_gc *h, int32_t device)
     if (res_bytes) GC_TRY(hipMemsetAsync(h->d_result, 0, res_bytes, h->stream));
     const int lpr = lanes_per_row(static_cast<int>(C));
     const int rows_per_block = 4 * (64 / lpr);
-    const int n_lists = static_cast<int>(h->list_to_result.size());
+    const int n_lists = static_cast<int>(h->sched.list_to_result.size());
     double bytes = static_cast<double>(res_bytes);
     for (int64_t g0 = 0; g0 < n_panels; g0 += G) {
         const int64_t g = std::min<int64_t>(G, n_panels - g0);
         double cols = 0.0;                                     // columns of the panels of this launch
         for (int64_t p = g0; p < g0 + g; ++p) cols += static_cast<double>(std::min<int64_t>(C, n_anc - p * C));
         for (int k = 0; k < n_lists; ++k) {
-            const int64_t b = h->list_begin[k], n_items = h->list_begin[k + 1] - 1 - b;
+            const int64_t b = h->sched.list_begin[k], n_items = h->sched.list_begin[k + 1] - 1 - b;
             if (n_items <= 0) continue;
-            const bool to_res = h->list_to_result[k];
-            bytes += cols * (8.0 * h->list_srcs[k] + (to_res ? 0.0 : 8.0 * static_cast<double>(n_items)));
+            const bool to_res = h->sched.list_to_result[k];
+            bytes += cols * (8.0 * h->sched.list_srcs[k] + (to_res ? 0.0 : 8.0 * static_cast<double>(n_items)));
             const dim3 grid(static_cast<unsigned>((n_items + rows_per_block - 1) / rows_per_block), static_cast<unsigned>(g));
             if (to_res)
                 launch_step<true>(lpr, grid, h->stream, h->d_items + b, h->d_oh, static_cast<int>(n_items), h->d_slots, stride, Cp,
@@ -499,7 +349,7 @@ int genphi_gc_stats(const genphi_gc *h, double *sweep_ms, double *algorithmic_by
     if (!h) return genphi_set_error(GENPHI_ERR_ARG, "genphi_gc_stats: NULL handle");
     if (sweep_ms) *sweep_ms = h->sweep_ms;
     if (algorithmic_bytes) *algorithmic_bytes = h->alg_bytes;
-    if (peak_slots) *peak_slots = h->peak_slots;
+    if (peak_slots) *peak_slots = h->sched.peak_slots;
     if (panel_cols) *panel_cols = h->panel_cols;
     return GENPHI_OK;
 }

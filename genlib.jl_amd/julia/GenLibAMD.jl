@@ -301,4 +301,60 @@ function gc(pedigree::GenLib.Pedigree; pro::Vector{Int} = GenLib.pro(pedigree),
     end
 end
 
+"""
+    occ(pedigree::GenLib.Pedigree; pro = GenLib.pro(pedigree), ancestors = GenLib.founder(pedigree), typeOcc = "IND", device = -1)
+
+Occurrences of `ancestors` (rows) in the genealogies of `pro` (columns), `Matrix{Int}`, as `GenLib.occ`
+(src/describe.jl:184-238): one integer recursion over the generation cuts on the GPU (csrc/occ.hip) instead of a
+walk of every ascending path; wrap-around as `Int`'s.  The library's `pro x ancestors` row-major result is the
+memory of a `Matrix{Int}(undef, length(ancestors), length(pro))`: no transpose.  `typeOcc = "TOTAL"`: the sums over
+the probands, reduced on the GPU, an `n x 1` matrix like the reference's `sum(..., dims = 2)`.
+"""
+function occ(pedigree::GenLib.Pedigree; pro::Vector{Int} = GenLib.pro(pedigree),
+             ancestors::Vector{Int} = GenLib.founder(pedigree), typeOcc::String = "IND", device::Integer = -1)
+    typeOcc == "IND" || typeOcc == "TOTAL" || throw(ArgumentError("typeOcc must be \"IND\" or \"TOTAL\""))
+    ind, father, mother, _ = flatten(pedigree)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve ind father mother pro ancestors check(ccall((:genphi_occ_create, libgenphi), Cint,
+        (Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Int64, Ptr{Int64}, Int64, Ptr{Int64}, Int32, Ptr{Ptr{Cvoid}}),
+        length(ind), ind, father, mother, length(pro), pro, length(ancestors), ancestors, Int32(typeOcc == "TOTAL" ? 1 : 0), h))
+    try
+        check(ccall((:genphi_occ_compute, libgenphi), Cint, (Ptr{Cvoid}, Int32), h[], Int32(device)))
+        if typeOcc == "TOTAL"
+            totals = Matrix{Int}(undef, length(ancestors), 1)
+            GC.@preserve totals check(ccall((:genphi_occ_totals, libgenphi), Cint, (Ptr{Cvoid}, Ptr{Int64}), h[], totals))
+            return totals
+        end
+        occurrences = Matrix{Int}(undef, length(ancestors), length(pro))
+        GC.@preserve occurrences check(ccall((:genphi_occ_result_to_host, libgenphi), Cint, (Ptr{Cvoid}, Ptr{Int64}),
+                                             h[], occurrences))
+        return occurrences
+    finally
+        ccall((:genphi_occ_destroy, libgenphi), Cvoid, (Ptr{Cvoid},), h[])
+    end
+end
+
+"""
+    rec(pedigree::GenLib.Pedigree, probandIDs = GenLib.pro(pedigree), ancestorIDs = GenLib.founder(pedigree); device = -1)
+
+Coverage of each ancestor, `Vector{Int}`, as `GenLib.rec` (src/describe.jl:133-145): how many of the probands descend
+from it.  Ancestor bit sets by an OR recursion over the generation cuts and a column count on the GPU (csrc/occ.hip).
+"""
+function rec(pedigree::GenLib.Pedigree, probandIDs::Vector{Int} = GenLib.pro(pedigree),
+             ancestorIDs::Vector{Int} = GenLib.founder(pedigree); device::Integer = -1)
+    ind, father, mother, _ = flatten(pedigree)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve ind father mother probandIDs ancestorIDs check(ccall((:genphi_rec_create, libgenphi), Cint,
+        (Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Int64, Ptr{Int64}, Int64, Ptr{Int64}, Ptr{Ptr{Cvoid}}),
+        length(ind), ind, father, mother, length(probandIDs), probandIDs, length(ancestorIDs), ancestorIDs, h))
+    try
+        check(ccall((:genphi_rec_compute, libgenphi), Cint, (Ptr{Cvoid}, Int32), h[], Int32(device)))
+        coverage = Vector{Int}(undef, length(ancestorIDs))
+        GC.@preserve coverage check(ccall((:genphi_rec_result, libgenphi), Cint, (Ptr{Cvoid}, Ptr{Int64}), h[], coverage))
+        return coverage
+    finally
+        ccall((:genphi_rec_destroy, libgenphi), Cvoid, (Ptr{Cvoid},), h[])
+    end
+end
+
 end # module

@@ -377,6 +377,69 @@ int genphi_gc_result_to_host(genphi_gc *h, float *out);
 int genphi_gc_stats(const genphi_gc *h, double *sweep_ms, double *algorithmic_bytes, int64_t *peak_slots, int32_t *panel_cols);
 void genphi_gc_destroy(genphi_gc *h);
 
+/* ---- gen.occ and gen.rec: occurrences and coverage of ancestors (csrc/occ.hip) ---------------------------------
+ * Replace occ(pedigree; pro = pro(pedigree), ancestors = founder(pedigree), typeOcc = "IND"), src/describe.jl:184-238, and
+ * rec(pedigree, probandIDs = pro(pedigree), ancestorIDs = founder(pedigree)), src/describe.jl:133-145.  Both run on the host
+ * schedule of gen.gc (csrc/ancestor_sweep.h): generation cuts, slot rows, column panels sized for the Infinity Cache.
+ *
+ * occ.  Entry [i][j] = the number of ascending paths from pro_ids[i] to anc_ids[j], by the recursion
+ * N[x] = N[father] + N[mother], then N[x][j] += 1 where anc_ids[j] == x.  Result: Int64, n_pro x n_anc, row-major
+ * (ld = n_anc), rows in pro_ids order, columns in anc_ids order: exactly the memory of the reference's
+ * Matrix{Int}(undef, n_anc, n_pro), which wraps it without a transpose.  The reference's rules, kept here:
+ *   - every proband carries values, with or without children; a proband listed again gets the same row again;
+ *   - a proband that is itself a requested ancestor counts the path of length 0 (1 on that entry);
+ *   - an ancestor with parents is allowed; its own ancestors may be requested too (paths run through it);
+ *   - a duplicated ancestor ID: only its FIRST column carries values, later ones are zero (the reference reads and resets
+ *     the ancestor's counter row by row) -- the opposite of gen.gc;
+ *   - an unknown ID in pro_ids or anc_ids -> GENPHI_ERR_UNKNOWN_ID (KeyError); n_pro = 0 or n_anc = 0: an empty result.
+ * Exactness.  Rows are unsigned 64-bit integers added with wrap-around.  Addition modulo 2^64 commutes with the recursion
+ * and the reference's Int wraps the same way, so the result equals the reference's bit for bit at any depth, read as Int64
+ * (2^63 paths read -2^63, 2^64 paths read 0).  In cut c every count is at most 2^c, so sweeps of at most 31 steps run on
+ * unsigned 32-bit slot rows (half the bytes, the same Int64 result) unless GENPHI_OCC_ROWS64 is given.
+ * TOTAL (the reference's sum(occ, dims = 2); a proband listed k times counts k times): a handle created with
+ * GENPHI_OCC_TOTAL_ONLY reduces the last step on the device into n_anc Int64 totals (per-row-group partial sums, then 64-bit
+ * integer atomics: the same bits on every run) and never allocates an n_pro x n_anc buffer.
+ *   create            host only (no GPU): checks IDs and pedigree order, plans cuts, rows and slots
+ *   compute           the sweep on `device` (-1 = current); the result stays resident; GENPHI_ERR_ALLOC before any launch
+ *                     when the result or the slot rows do not fit
+ *   result_device     device pointer and row pitch (Int64 entries) of the resident result (GENPHI_ERR_ARG on a TOTAL-only handle)
+ *   result_to_host    out: n_pro x n_anc Int64, row-major (GENPHI_ERR_ARG on a TOTAL-only handle)
+ *   totals            out: n_anc Int64; on a handle with a full result, its column sums taken on the device
+ *   stats             device time of the last sweep (HIP events), its algorithmic bytes (source rows read and rows written
+ *                     at the row width per panel column, plus the 8-byte result entries or totals), the slot rows of one
+ *                     panel, the panel width, the row width in bits (64 or 32) and the kernel launches of the sweep
+ *
+ * rec.  Entry [j] = the number of distinct pro_ids that descend from anc_ids[j], by the recursion R[x] = R[father] | R[mother],
+ * then R[x][j] = 1 where anc_ids[j] == x, on bit rows (64 ancestor columns per 64-bit word), followed by a column count over
+ * the probands' rows.  Not derived from occ: a path count can wrap to 0 while the ancestor is still an ancestor.  Rules kept:
+ *   - descendants are strict: an ancestor that is itself a proband does not count itself;
+ *   - a proband listed twice counts once; a proband ID that is not in the pedigree is ignored;
+ *   - a duplicated ancestor gives equal entries; probands with children count like any other;
+ *   - an unknown ancestor ID -> GENPHI_ERR_UNKNOWN_ID (KeyError).
+ *   result            out: n_anc Int64 (host)
+ *   stats             as above; algorithmic bytes at 8 bytes per 64 columns, plus one read of every proband row by the count;
+ *                     row width 64                                                                                       */
+#define GENPHI_OCC_TOTAL_ONLY 1   /* totals only: no n_pro x n_anc result exists */
+#define GENPHI_OCC_ROWS64 2       /* 64-bit slot rows even where 32-bit rows are exact */
+typedef struct genphi_occ genphi_occ;
+int genphi_occ_create(int64_t n_ind, const int64_t *ind, const int64_t *father, const int64_t *mother,
+                      int64_t n_pro, const int64_t *pro_ids, int64_t n_anc, const int64_t *anc_ids, int32_t flags, genphi_occ **out);
+int genphi_occ_compute(genphi_occ *h, int32_t device);
+int genphi_occ_result_device(const genphi_occ *h, const int64_t **d_ptr, int64_t *ld);
+int genphi_occ_result_to_host(genphi_occ *h, int64_t *out);
+int genphi_occ_totals(genphi_occ *h, int64_t *out);
+int genphi_occ_stats(const genphi_occ *h, double *sweep_ms, double *algorithmic_bytes, int64_t *peak_slots, int32_t *panel_cols,
+                     int32_t *row_bits, int64_t *launches);
+void genphi_occ_destroy(genphi_occ *h);
+typedef struct genphi_rec genphi_rec;
+int genphi_rec_create(int64_t n_ind, const int64_t *ind, const int64_t *father, const int64_t *mother,
+                      int64_t n_pro, const int64_t *pro_ids, int64_t n_anc, const int64_t *anc_ids, genphi_rec **out);
+int genphi_rec_compute(genphi_rec *h, int32_t device);
+int genphi_rec_result(genphi_rec *h, int64_t *out);
+int genphi_rec_stats(const genphi_rec *h, double *sweep_ms, double *algorithmic_bytes, int64_t *peak_slots, int32_t *panel_cols,
+                     int32_t *row_bits, int64_t *launches);
+void genphi_rec_destroy(genphi_rec *h);
+
 /* Frees host and device memory of the plan (NULL is allowed). */
 void genphi_plan_destroy(genphi_plan *plan);
 
