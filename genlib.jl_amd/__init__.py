@@ -16,6 +16,8 @@ meaning, printed lines and error behaviour as the reference:
     gen.branching(ped, pro=[1])            # src/extract.jl:65-186, native pruning (csrc/loader.cpp)
     gen.gc(ped)                            # src/compute.jl:518-595: genetic contributions (csrc/gc.hip)
     gen.occ(ped); gen.rec(ped)             # src/describe.jl:184-238, :133-145: occurrences, coverage (csrc/occ.hip)
+    gen.findMRCA(ped, [1, 2, 29])          # src/identify.jl:83-160: MRCAs and meioses; gen.meioses, gen.findDistance,
+                                           # gen.findFounders, gen.ancestor (csrc/dist.hip + csrc/loader.cpp)
 
 All kinship arithmetic runs in hand-written HIP kernels behind the C-ABI in
 include/genphi.h (csrc/genphi_hip.hip); there is no CPU fallback.
@@ -26,7 +28,7 @@ from collections import OrderedDict
 import numpy as np
 
 from . import _capi
-from ._capi import PhiPlan, KinshipMatrix, GCPlan, OccPlan, RecPlan, GenphiDeviceError, GenphiLibraryMissing  # noqa: F401
+from ._capi import PhiPlan, KinshipMatrix, GCPlan, OccPlan, RecPlan, DistPlan, GenphiDeviceError, GenphiLibraryMissing  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
@@ -359,6 +361,116 @@ def rec(pedigree, probandIDs=None, ancestorIDs=None, device=None):
         return h.result()
     finally:
         h.close()
+
+
+def meioses(pedigree, pro=None, ancestors=None, device=None):
+    """gen.meioses(pedigree; pro = pro(pedigree), ancestors = founder(pedigree)): the number of meioses on the shortest ascending
+    path from each proband (rows) to each ancestor (columns), an int16 array of shape (len(pro), len(ancestors)); 0 where the
+    proband is the ancestor, -1 where the ancestor is not an ancestor of the proband.
+
+    The reference has no matrix form of this: it is _findMinDistance (src/describe.jl:283-289) for every pair at once, computed on
+    the GPU by a min-plus recursion over the generation cuts (csrc/dist.hip) instead of an enumeration of every path.  Every
+    proband gets its row (with or without children, each time it is listed); a duplicated ancestor gives equal columns.  KeyError
+    for an unknown ID; ValueError for a pedigree of more than 32,767 generation steps.  Each call plans, sweeps and frees its own
+    handle."""
+    probands = globals()["pro"](pedigree) if pro is None else np.ascontiguousarray(pro, dtype=np.int64)
+    ancestors = founder(pedigree) if ancestors is None else np.ascontiguousarray(ancestors, dtype=np.int64)
+    h = DistPlan(pedigree.ind, pedigree.father, pedigree.mother, probands, ancestors)
+    try:
+        h.compute(device=device)
+        return h.result_to_host()
+    finally:
+        h.close()
+
+
+def _id_list(IDs):
+    return np.atleast_1d(np.asarray(IDs, dtype=np.int64)).ravel()
+
+
+def ancestor(pedigree, IDs):
+    """gen.ancestor(pedigree, ID) / gen.ancestor(pedigree, IDs) (src/identify.jl:164-199): the ancestors of one individual, or of
+    several (the union), ascending.  Strict: an individual is not its own ancestor.  Host only (csrc/loader.cpp).  KeyError for an
+    unknown ID."""
+    return _capi.ancestors(pedigree.ind, pedigree.father, pedigree.mother, _id_list(IDs))
+
+
+_MRCA_CANDIDATE_SEARCHES = 16          # ancestor sets looked at for the shortest candidate list (any one of them is a valid list)
+
+
+def _common_ancestors(pedigree, IDs, device):
+    """The individuals that are a strict ancestor of every one of IDs, ascending.  The common set lies inside the ancestors of any
+    single ID: the smallest such set among the first few IDs is the candidate list, and gen.rec (strict, distinct probands) counts,
+    per candidate, how many of the IDs descend from it."""
+    pedigree.positions(IDs)                                        # KeyError on an unknown ID (gen.rec ignores them)
+    distinct = np.unique(IDs)
+    if len(distinct) == 0:
+        return np.zeros(0, dtype=np.int64)
+    candidates = min((ancestor(pedigree, [i]) for i in distinct[:_MRCA_CANDIDATE_SEARCHES]), key=len)
+    if len(candidates) == 0:
+        return candidates
+    return candidates[rec(pedigree, distinct, candidates, device=device) == len(distinct)]
+
+
+def findFounders(pedigree, IDs, device=None):
+    """gen.findFounders(pedigree, IDs) (src/identify.jl:83-95): the founders from whom every one of IDs descends, ascending.  A
+    founder listed in IDs is not its own ancestor.  KeyError for an unknown ID."""
+    common = _common_ancestors(pedigree, _id_list(IDs), device)
+    pos = pedigree.positions(common)
+    return common[(pedigree.father[pos] == 0) & (pedigree.mother[pos] == 0)]
+
+
+class GenMatrix:
+    """The reference's GenMatrix (src/identify.jl:129-133): meioses[i, j] between individuals[i] (rows) and ancestors[j] (columns)."""
+
+    def __init__(self, individuals, ancestors, meioses):
+        self.individuals, self.ancestors, self.meioses = individuals, ancestors, meioses
+
+    def __repr__(self):
+        return "GenMatrix(individuals=%r, ancestors=%r, meioses=%r)" % (self.individuals.tolist(), self.ancestors.tolist(), self.meioses.tolist())
+
+
+def findMRCA(pedigree, IDs, device=None):
+    """gen.findMRCA(pedigree, IDs) (src/identify.jl:97-160): the most recent common ancestors (MRCAs) of IDs and the meioses
+    between each individual and each of them, as a GenMatrix: `individuals` = IDs as given (a repeated ID repeats its row),
+    `ancestors` ascending, `meioses` int64 of shape (len(IDs), len(ancestors)).
+
+    The common ancestors come from gen.rec over the ancestors of one of the IDs, the MRCAs are the common ancestors without a
+    common child (csrc/loader.cpp: equal to the reference's setdiff with the ancestors of the common set), and the distances are
+    one gen.meioses sweep (csrc/dist.hip) where the reference enumerates every ascending path per pair.  KeyError for an unknown
+    ID.  One deviation: for individuals without any common ancestor the reference (as far as its source reads; not run) calls
+    union() without arguments and throws; here the GenMatrix has no ancestors and a (len(IDs), 0) matrix."""
+    IDs = _id_list(IDs)
+    common = _common_ancestors(pedigree, IDs, device)
+    mrcas = _capi.mrca_filter(pedigree.ind, pedigree.father, pedigree.mother, common)
+    if len(mrcas) == 0 or len(IDs) == 0:
+        return GenMatrix(IDs, mrcas, np.zeros((len(IDs), len(mrcas)), dtype=np.int64))
+    return GenMatrix(IDs, mrcas, meioses(pedigree, IDs, mrcas, device=device).astype(np.int64))
+
+
+def findDistance(pedigree, IDs, ancestorID, device=None):
+    """gen.findDistance(pedigree, IDs, ancestorID) (src/describe.jl:291-300): the meioses between IDs[0] and IDs[1] through
+    ancestorID, that is, the sum of their shortest ascents to it (only the first two IDs are used; IndexError with fewer).  An ID
+    equal to ancestorID is at distance 0.  ValueError when ancestorID is not an ancestor of both (the reference takes the minimum
+    of an empty vector and throws); KeyError for an unknown ID."""
+    IDs = _id_list(IDs)
+    if len(IDs) < 2:
+        raise IndexError("findDistance needs two IDs, got %d" % len(IDs))
+    d = meioses(pedigree, IDs[:2], [int(ancestorID)], device=device)[:, 0]
+    if np.any(d < 0):
+        raise ValueError("%d is not an ancestor of %d" % (int(ancestorID), int(IDs[:2][d < 0][0])))
+    return int(d[0]) + int(d[1])
+
+
+def _findMinDistanceMRCA(pedigree, IDs, device=None):
+    """gen._findMinDistanceMRCA(pedigree, IDs) (src/identify.jl:105-114): the smallest findDistance of the first two IDs over the
+    MRCAs of all IDs.  ValueError without an MRCA; IndexError with fewer than two IDs."""
+    IDs = _id_list(IDs)
+    if len(IDs) < 2:
+        raise IndexError("_findMinDistanceMRCA needs two IDs, got %d" % len(IDs))
+    m = findMRCA(pedigree, IDs, device=device)
+    if len(m.ancestors) == 0:
+        raise ValueError("the individuals have no common ancestor")
+    return int((m.meioses[0] + m.meioses[1]).min())
 
 
 def sparse_phi(pedigree, probandIDs=None, device=None):

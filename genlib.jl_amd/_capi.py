@@ -58,6 +58,8 @@ EXPORTED_SYMBOLS = [
     "genphi_gc_create", "genphi_gc_compute", "genphi_gc_result_device", "genphi_gc_result_to_host", "genphi_gc_stats", "genphi_gc_destroy",
     "genphi_occ_create", "genphi_occ_compute", "genphi_occ_result_device", "genphi_occ_result_to_host", "genphi_occ_totals", "genphi_occ_stats", "genphi_occ_destroy",
     "genphi_rec_create", "genphi_rec_compute", "genphi_rec_result", "genphi_rec_stats", "genphi_rec_destroy",
+    "genphi_dist_create", "genphi_dist_compute", "genphi_dist_result_device", "genphi_dist_result_to_host", "genphi_dist_stats", "genphi_dist_destroy",
+    "genphi_ancestors", "genphi_mrca_filter",
 ]
 
 _lib = None
@@ -213,7 +215,17 @@ def lib():
         L.genphi_rec_create.restype = C.c_int
         L.genphi_occ_result_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), _I64P]
         L.genphi_occ_result_device.restype = C.c_int
-        for kind in ("occ", "rec"):
+        L.genphi_dist_create.argtypes = [C.c_int64, _I64P, _I64P, _I64P, C.c_int64, _I64P, C.c_int64, _I64P, C.POINTER(C.c_void_p)]
+        L.genphi_dist_create.restype = C.c_int
+        L.genphi_dist_result_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), _I64P]
+        L.genphi_dist_result_device.restype = C.c_int
+        L.genphi_dist_result_to_host.argtypes = [C.c_void_p, C.POINTER(C.c_int16)]
+        L.genphi_dist_result_to_host.restype = C.c_int
+        L.genphi_ancestors.argtypes = [C.c_int64, _I64P, _I64P, _I64P, C.c_int64, _I64P, _I64P, C.POINTER(_I64P)]
+        L.genphi_ancestors.restype = C.c_int
+        L.genphi_mrca_filter.argtypes = [C.c_int64, _I64P, _I64P, _I64P, C.c_int64, _I64P, _I64P, _I64P]
+        L.genphi_mrca_filter.restype = C.c_int
+        for kind in ("occ", "rec", "dist"):
             fn = getattr(L, "genphi_%s_compute" % kind)
             fn.argtypes, fn.restype = [C.c_void_p, C.c_int32], C.c_int
             fn = getattr(L, "genphi_%s_stats" % kind)
@@ -898,3 +910,83 @@ class RecPlan:
     def stats(self):
         """dict(sweep_ms, algorithmic_bytes, peak_slots, panel_cols, row_bits, launches) of the last compute()."""
         return _sweep_stats(lib().genphi_rec_stats, self._h)
+
+
+GENPHI_DIST_MAX_STEPS = 32767
+
+
+class DistPlan:
+    """gen.meioses' handle (include/genphi.h, genphi_dist_*): planned on the host at construction (KeyError on an unknown proband or
+    ancestor, ValueError for a sweep deeper than GENPHI_DIST_MAX_STEPS; no GPU needed), swept on the GPU by compute()."""
+
+    def __init__(self, ind, father, mother, pro_ids, anc_ids):
+        L = lib()
+        ind, father, mother, pro_ids, anc_ids = _i64(ind), _i64(father), _i64(mother), _i64(pro_ids), _i64(anc_ids)
+        h = C.c_void_p()
+        rc = L.genphi_dist_create(len(ind), ind.ctypes.data_as(_I64P), father.ctypes.data_as(_I64P), mother.ctypes.data_as(_I64P),
+                                  len(pro_ids), pro_ids.ctypes.data_as(_I64P), len(anc_ids), anc_ids.ctypes.data_as(_I64P), C.byref(h))
+        if rc:
+            _raise(rc)
+        self._h = h
+        self.shape = (len(pro_ids), len(anc_ids))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().genphi_dist_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+    def compute(self, device=None):
+        rc = lib().genphi_dist_compute(self._h, -1 if device is None else int(device))
+        if rc:
+            _raise(rc)
+
+    def result_device(self):
+        """(device pointer, row pitch in Int16 entries: n_anc rounded up to a multiple of 8) of the resident result."""
+        p, ld = C.c_void_p(), C.c_int64()
+        rc = lib().genphi_dist_result_device(self._h, C.byref(p), C.byref(ld))
+        if rc:
+            _raise(rc)
+        return p.value, ld.value
+
+    def result_to_host(self):
+        """The n_pro x n_anc int16 result (rows = probands, -1 = not an ancestor)."""
+        out = np.empty(self.shape, dtype=np.int16)
+        rc = lib().genphi_dist_result_to_host(self._h, out.ctypes.data_as(C.POINTER(C.c_int16)))
+        if rc:
+            _raise(rc)
+        return out
+
+    def stats(self):
+        """dict(sweep_ms, algorithmic_bytes, peak_slots, panel_cols, row_bits, launches) of the last compute()."""
+        return _sweep_stats(lib().genphi_dist_stats, self._h)
+
+
+def ancestors(ind, father, mother, ids):
+    """Sorted strict ancestors of `ids` (the union over them): genphi_ancestors, host only."""
+    L = lib()
+    ind, father, mother, ids = _i64(ind), _i64(father), _i64(mother), _i64(ids)
+    n, p = C.c_int64(), _I64P()
+    rc = L.genphi_ancestors(len(ind), ind.ctypes.data_as(_I64P), father.ctypes.data_as(_I64P), mother.ctypes.data_as(_I64P),
+                            len(ids), ids.ctypes.data_as(_I64P), C.byref(n), C.byref(p))
+    if rc:
+        _raise(rc)
+    try:
+        return np.ctypeslib.as_array(p, shape=(n.value,)).copy() if n.value else np.zeros(0, np.int64)
+    finally:
+        L.genphi_free(p)
+
+
+def mrca_filter(ind, father, mother, common):
+    """Of the common ancestors `common`, those without a common child, in the order given: genphi_mrca_filter, host only."""
+    L = lib()
+    ind, father, mother, common = _i64(ind), _i64(father), _i64(mother), _i64(common)
+    out = np.empty(max(len(common), 1), dtype=np.int64)
+    n = C.c_int64()
+    rc = L.genphi_mrca_filter(len(ind), ind.ctypes.data_as(_I64P), father.ctypes.data_as(_I64P), mother.ctypes.data_as(_I64P),
+                              len(common), common.ctypes.data_as(_I64P), C.byref(n), out.ctypes.data_as(_I64P))
+    if rc:
+        _raise(rc)
+    return out[:n.value].copy()

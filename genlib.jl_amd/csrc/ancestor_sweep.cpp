@@ -179,7 +179,7 @@ int plan_sweep(SweepSchedule &h, int64_t n_ind, const int64_t *ind, const int64_
         if (last && sopt.emit == Emit::EveryProband)
             // probands dragged into the last cut: their rows were finished by an earlier step and wait in their slots
             for (int64_t k = 0; k < st.n; ++k)
-                if (st.ord[k] >= 0 && slot_cur[k] >= 0) emit_rows(slot_cur[k], -1, st.ord[k], false);
+                if (st.ord[k] >= 0 && slot_cur[k] >= 0) emit_rows(slot_cur[k], sopt.mark_copies ? -2 : -1, st.ord[k], false);
         close_list();
         // members of the source cut that leave with this step: their slots serve the steps after it
         for (int64_t q = 0; q < st.n_prev; ++q)

@@ -1,6 +1,6 @@
-// ancestor_sweep.h -- host schedule of the ancestor x proband sweeps (gen.gc, gen.occ, gen.rec; no HIP here).
+// ancestor_sweep.h -- host schedule of the ancestor x proband sweeps (gen.gc, gen.occ, gen.rec, gen.meioses; no HIP here).
 //
-// All three are column-independent recursions over the generation cuts of the planner (build_plan, indices_only):
+// All four are column-independent recursions over the generation cuts of the planner (build_plan, indices_only):
 //     row[x] = combine(row[father], row[mother])   (a missing parent is the zero row),   then the one-hot columns j with
 //     ancestors[j] == x are set / incremented
 // and share everything but the arithmetic and the rule that says which rows reach the result:
@@ -37,6 +37,8 @@ struct SweepOptions {
     Emit emit = Emit::LeafFirst;
     bool first_onehot_only = false;   // a duplicated ancestor ID: only its first column gets the one-hot (occ: later rows are zero)
     bool drop_unknown_pro = false;    // proband IDs that are not in the pedigree are ignored instead of a KeyError (rec)
+    bool mark_copies = false;         // EveryProband: the copy items of the last list carry source B = -2 instead of -1 (meioses:
+                                      // a recursion whose step is not the identity on a single source has to tell them apart)
 };
 
 struct SweepSchedule {

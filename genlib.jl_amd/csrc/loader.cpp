@@ -7,6 +7,7 @@
 // depth 1).  The output is exactly what genphi_plan_create wants: ind / father / mother (/ sex)
 // in rank order.  Own design: one pass over a memory-resident buffer with a hand-rolled integer
 // scanner, iterative depth computation (no recursion: depth-1e6 chains are fine), counting sort.
+#include <algorithm>
 #include <climits>
 #include <cstdint>
 #include <cstdio>
@@ -23,6 +24,33 @@ extern int genphi_set_error(int code, const std::string &msg);   // genphi_hip.h
 namespace {
 
 struct Cols { std::vector<int64_t> ind, father, mother, sex; };
+
+// ID -> position for the searches below: a direct table when the IDs are non-negative and dense enough, else a hash map; -1 =
+// unknown.  Of a duplicated ID the last position counts.
+struct IdIndex {
+    std::vector<int32_t> table;
+    std::unordered_map<int64_t, int32_t> map;
+    bool direct = false;
+    void init(int64_t n, const int64_t *ind)
+    {
+        int64_t lo = INT64_MAX, hi = INT64_MIN;
+        for (int64_t i = 0; i < n; ++i) { lo = std::min(lo, ind[i]); hi = std::max(hi, ind[i]); }
+        direct = n > 0 && lo >= 0 && hi < 3 * n + 1024;
+        if (direct) {
+            table.assign(static_cast<size_t>(hi) + 1, -1);
+            for (int64_t i = 0; i < n; ++i) table[ind[i]] = static_cast<int32_t>(i);
+        } else {
+            map.reserve(static_cast<size_t>(n) * 2);
+            for (int64_t i = 0; i < n; ++i) map[ind[i]] = static_cast<int32_t>(i);
+        }
+    }
+    int32_t find(int64_t id) const
+    {
+        if (direct) return (id < 0 || id >= static_cast<int64_t>(table.size())) ? -1 : table[id];
+        auto it = map.find(id);
+        return it == map.end() ? -1 : it->second;
+    }
+};
 
 bool parse_tsv(const char *buf, size_t len, Cols &c, std::string &err)
 {
@@ -258,6 +286,78 @@ int genphi_branching(int64_t n_ind, const int64_t *ind, const int64_t *father, c
     }
     *n_out = m; *ind_out = a; *father_out = b; *mother_out = d;
     if (sex_out) *sex_out = e;
+    return GENPHI_OK;
+}
+
+// gen.ancestor (src/identify.jl:164-199): the strict ancestors of one ID, or the union over several, ascending.  The reference
+// searches a pointer graph with a stack and a Set per call; here the same stack search runs on positions with one visited flag
+// per individual.  No order of the pedigree is assumed.  *out is allocated by the library (genphi_free).
+int genphi_ancestors(int64_t n_ind, const int64_t *ind, const int64_t *father, const int64_t *mother, int64_t n_ids, const int64_t *ids,
+                     int64_t *n_out, int64_t **out)
+{
+    if (!n_out || !out || n_ind < 0 || n_ids < 0 || (n_ind > 0 && (!ind || !father || !mother)) || (n_ids > 0 && !ids))
+        return genphi_set_error(GENPHI_ERR_ARG, "genphi_ancestors: bad argument");
+    *n_out = 0; *out = nullptr;
+    IdIndex pos;                                     // (a direct table for dense IDs: no hashing on the search path)
+    pos.init(n_ind, ind);
+    std::vector<uint8_t> seen(n_ind, 0);
+    std::vector<int64_t> stack, found;
+    for (int64_t k = 0; k < n_ids; ++k) {
+        const int32_t r = pos.find(ids[k]);
+        if (r < 0) return genphi_set_error(GENPHI_ERR_UNKNOWN_ID, "KeyError: individual " + std::to_string(ids[k]) + " not found");
+        stack.push_back(r);                          // (an ID is not its own ancestor: it is searched, not flagged)
+    }
+    while (!stack.empty()) {
+        const int64_t i = stack.back();
+        stack.pop_back();
+        for (int side = 0; side < 2; ++side) {
+            const int64_t pid = side ? mother[i] : father[i];
+            if (pid == 0) continue;
+            const int32_t r = pos.find(pid);
+            if (r < 0)
+                return genphi_set_error(GENPHI_ERR_UNKNOWN_ID, "KeyError: parent " + std::to_string(pid) + " of " + std::to_string(ind[i]) + " not found");
+            if (seen[r]) continue;                   // its ancestors are on the stack or done
+            seen[r] = 1;
+            found.push_back(pid);
+            stack.push_back(r);
+        }
+    }
+    std::sort(found.begin(), found.end());
+    int64_t *a = static_cast<int64_t *>(std::malloc(sizeof(int64_t) * (found.empty() ? 1 : found.size())));
+    if (!a) return genphi_set_error(GENPHI_ERR_ALLOC, "out of memory");
+    std::copy(found.begin(), found.end(), a);
+    *n_out = static_cast<int64_t>(found.size()); *out = a;
+    return GENPHI_OK;
+}
+
+// The last step of _findMRCA (src/identify.jl:97-103): of the common ancestors of a group, keep those that are not an ancestor of
+// another common ancestor -- the reference's setdiff(common, ancestor(common)).  Every individual on a path between a common
+// ancestor and one of its ancestors is itself common (it is an ancestor of whoever the path leads down to), so a common ancestor
+// is "older" exactly when one of its CHILDREN is common: one pass over the parent arrays instead of a search per ancestor.
+// `common` must be closed in that sense (it is when it is the full intersection of ancestor sets).  out: room for n_common IDs;
+// the kept IDs in the order given.
+int genphi_mrca_filter(int64_t n_ind, const int64_t *ind, const int64_t *father, const int64_t *mother, int64_t n_common,
+                       const int64_t *common, int64_t *n_out, int64_t *out)
+{
+    if (!n_out || n_ind < 0 || n_common < 0 || (n_ind > 0 && (!ind || !father || !mother)) || (n_common > 0 && (!common || !out)))
+        return genphi_set_error(GENPHI_ERR_ARG, "genphi_mrca_filter: bad argument");
+    *n_out = 0;
+    IdIndex pos;
+    pos.init(n_ind, ind);
+    std::vector<uint8_t> older(n_ind, 0);
+    for (int64_t k = 0; k < n_common; ++k) {
+        const int32_t i = pos.find(common[k]);
+        if (i < 0) return genphi_set_error(GENPHI_ERR_UNKNOWN_ID, "KeyError: individual " + std::to_string(common[k]) + " not found");
+        for (int side = 0; side < 2; ++side) {
+            const int64_t pid = side ? mother[i] : father[i];
+            const int32_t r = pid == 0 ? -1 : pos.find(pid);
+            if (r >= 0) older[r] = 1;                        // a parent of a common ancestor
+        }
+    }
+    int64_t m = 0;
+    for (int64_t k = 0; k < n_common; ++k)
+        if (!older[pos.find(common[k])]) out[m++] = common[k];
+    *n_out = m;
     return GENPHI_OK;
 }
 

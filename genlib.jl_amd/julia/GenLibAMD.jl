@@ -357,4 +357,101 @@ function rec(pedigree::GenLib.Pedigree, probandIDs::Vector{Int} = GenLib.pro(ped
     end
 end
 
+"""
+    meioses(pedigree::GenLib.Pedigree; pro = GenLib.pro(pedigree), ancestors = GenLib.founder(pedigree), device = -1)
+
+Meioses on the shortest ascending path from each of `pro` (rows) to each of `ancestors` (columns), `Matrix{Int16}`; `0` where
+the proband is the ancestor, `-1` where it does not descend from it.  `GenLib._findMinDistance` (src/describe.jl:283-289) for
+every pair at once: one min-plus recursion over the generation cuts on the GPU (csrc/dist.hip) instead of an enumeration of
+every ascending path.  The library's result is proband-major; one `permutedims` makes it `pro x ancestors` in Julia's layout.
+"""
+function meioses(pedigree::GenLib.Pedigree; pro::Vector{Int} = GenLib.pro(pedigree),
+                 ancestors::Vector{Int} = GenLib.founder(pedigree), device::Integer = -1)
+    ind, father, mother, _ = flatten(pedigree)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve ind father mother pro ancestors check(ccall((:genphi_dist_create, libgenphi), Cint,
+        (Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Int64, Ptr{Int64}, Int64, Ptr{Int64}, Ptr{Ptr{Cvoid}}),
+        length(ind), ind, father, mother, length(pro), pro, length(ancestors), ancestors, h))
+    try
+        check(ccall((:genphi_dist_compute, libgenphi), Cint, (Ptr{Cvoid}, Int32), h[], Int32(device)))
+        rowmajor = Matrix{Int16}(undef, length(ancestors), length(pro))
+        GC.@preserve rowmajor check(ccall((:genphi_dist_result_to_host, libgenphi), Cint, (Ptr{Cvoid}, Ptr{Int16}), h[], rowmajor))
+        return permutedims(rowmajor)
+    finally
+        ccall((:genphi_dist_destroy, libgenphi), Cvoid, (Ptr{Cvoid},), h[])
+    end
+end
+
+"""
+    ancestor(pedigree::GenLib.Pedigree, IDs::Vector{Int})
+
+Sorted strict ancestors of `IDs` (their union), as `GenLib.ancestor` (src/identify.jl:164-199); host only (csrc/loader.cpp).
+"""
+function ancestor(pedigree::GenLib.Pedigree, IDs::Vector{Int})
+    ind, father, mother, _ = flatten(pedigree)
+    n = Ref{Int64}(0)
+    p = Ref{Ptr{Int64}}(C_NULL)
+    GC.@preserve ind father mother IDs check(ccall((:genphi_ancestors, libgenphi), Cint,
+        (Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Ptr{Int64}}),
+        length(ind), ind, father, mother, length(IDs), IDs, n, p))
+    try
+        return copy(unsafe_wrap(Array, p[], n[]))
+    finally
+        ccall((:genphi_free, libgenphi), Cvoid, (Ptr{Cvoid},), p[])
+    end
+end
+ancestor(pedigree::GenLib.Pedigree, ID::Int) = ancestor(pedigree, [ID])
+
+# the individuals that are a strict ancestor of every one of IDs: rec over the smallest single ancestor set
+function common_ancestors(pedigree::GenLib.Pedigree, IDs::Vector{Int}; device::Integer = -1)
+    foreach(ID -> pedigree[ID], IDs)                       # KeyError on an unknown ID (rec ignores them)
+    distinct = unique(IDs)
+    isempty(distinct) && return Int[]
+    candidates = argmin(length, [ancestor(pedigree, ID) for ID in distinct])
+    isempty(candidates) && return candidates
+    candidates[rec(pedigree, distinct, candidates; device = device) .== length(distinct)]
+end
+
+"""
+    findFounders(pedigree::GenLib.Pedigree, IDs::Vector{Int}; device = -1)
+
+Founders from whom every one of `IDs` descends, as `GenLib.findFounders` (src/identify.jl:83-95).
+"""
+function findFounders(pedigree::GenLib.Pedigree, IDs::Vector{Int}; device::Integer = -1)
+    [ID for ID in common_ancestors(pedigree, IDs; device = device)
+        if isnothing(pedigree[ID].father) && isnothing(pedigree[ID].mother)]
+end
+
+"""
+    findMRCA(pedigree::GenLib.Pedigree, IDs::Vector{Int}; device = -1)
+
+`GenLib.GenMatrix` of the meioses between `IDs` and their most recent common ancestors, as `GenLib.findMRCA`
+(src/identify.jl:135-160).  Common ancestors by `rec`, the MRCAs as the common ancestors without a common child
+(csrc/loader.cpp), the distances by one `meioses` sweep.  Without any common ancestor the matrix has no columns (the
+reference throws there).
+"""
+function findMRCA(pedigree::GenLib.Pedigree, IDs::Vector{Int}; device::Integer = -1)
+    common = common_ancestors(pedigree, IDs; device = device)
+    ind, father, mother, _ = flatten(pedigree)
+    mrcas = Vector{Int}(undef, length(common))
+    n = Ref{Int64}(0)
+    GC.@preserve ind father mother common mrcas check(ccall((:genphi_mrca_filter, libgenphi), Cint,
+        (Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}),
+        length(ind), ind, father, mother, length(common), common, n, mrcas))
+    resize!(mrcas, n[])
+    isempty(mrcas) && return GenLib.GenMatrix(IDs, mrcas, Matrix{Int}(undef, length(IDs), 0))
+    GenLib.GenMatrix(IDs, mrcas, Matrix{Int}(meioses(pedigree; pro = IDs, ancestors = mrcas, device = device)))
+end
+
+"""
+    findDistance(pedigree::GenLib.Pedigree, IDs::Vector{Int}, ancestorID::Int; device = -1)
+
+Meioses between `IDs[1]` and `IDs[2]` through `ancestorID`, as `GenLib.findDistance` (src/describe.jl:291-300).
+"""
+function findDistance(pedigree::GenLib.Pedigree, IDs::Vector{Int}, ancestorID::Int; device::Integer = -1)
+    d = meioses(pedigree; pro = IDs[1:2], ancestors = [ancestorID], device = device)
+    any(d .< 0) && throw(ArgumentError("$ancestorID is not an ancestor of both individuals"))
+    Int(d[1, 1]) + Int(d[2, 1])
+end
+
 end # module

@@ -440,6 +440,50 @@ int genphi_rec_stats(const genphi_rec *h, double *sweep_ms, double *algorithmic_
                      int32_t *row_bits, int64_t *launches);
 void genphi_rec_destroy(genphi_rec *h);
 
+/* ---- gen.meioses, gen.findMRCA: shortest ascents (csrc/dist.hip) and the host glue of the MRCA family (csrc/loader.cpp) -------
+ * Replace findMRCA / findDistance / findFounders / ancestor (src/identify.jl:83-199) and _findMinDistance (src/describe.jl:241-289).
+ *
+ * dist.  Entry [i][j] = the number of meioses on the SHORTEST ascending path from pro_ids[i] to anc_ids[j], by the min-plus
+ * recursion D[x] = min(D[father], D[mother]) + 1, then D[x][j] = 0 where anc_ids[j] == x, on the host schedule of gen.gc /
+ * gen.occ (csrc/ancestor_sweep.h).  Result: signed 16-bit, n_pro x n_anc, rows in pro_ids order (one row per occurrence), columns
+ * in anc_ids order; -1 = anc_ids[j] is neither pro_ids[i] nor one of its ancestors.  Rules:
+ *   - every proband gets its row, with or without children; a proband listed again gets the same row again;
+ *   - a proband that is itself a requested ancestor is at distance 0 from itself;
+ *   - an ancestor with parents is allowed and its own ancestors may be requested too; a duplicated ancestor gives equal columns;
+ *   - an unknown ID in pro_ids or anc_ids -> GENPHI_ERR_UNKNOWN_ID (KeyError); n_pro = 0 or n_anc = 0: an empty result.
+ * Depth.  A distance is at most the number of level steps of the sweep (generation cuts - 1).  Slot rows are unsigned 16-bit
+ * (65535 - distance, 0 = none) and the result is signed: sweeps of up to GENPHI_DIST_MAX_STEPS = 32767 steps are covered, and
+ * create returns GENPHI_ERR_ARG for a deeper one instead of wrapping.
+ *   create            host only (no GPU): checks IDs, pedigree order and depth, plans cuts, rows and slots
+ *   compute           the sweep on `device` (-1 = current); the result stays resident; GENPHI_ERR_ALLOC before any launch when
+ *                     the result or the slot rows do not fit
+ *   result_device     device pointer and row pitch in entries: ld = n_anc rounded up to a multiple of 8 (rows start on 16
+ *                     bytes); the entries [n_anc, ld) of a row are undefined
+ *   result_to_host    out: n_pro x n_anc Int16, row-major, packed (ld = n_anc)
+ *   stats             device time of the last sweep (HIP events), its algorithmic bytes (source rows read and rows written at 2
+ *                     bytes per panel column, plus the 2-byte result entries), the slot rows of one panel, the panel width, the
+ *                     row width in bits (16) and the kernel launches of the sweep
+ *
+ * genphi_ancestors    gen.ancestor: the strict ancestors of ids[0 .. n_ids) (the union over them), ascending; *out is allocated by
+ *                     the library (genphi_free).  Host only.  Unknown ID -> GENPHI_ERR_UNKNOWN_ID.
+ * genphi_mrca_filter  of the common ancestors of a group (the full intersection of their ancestor sets), those without a common
+ *                     child: the reference's setdiff(common, ancestor(common)) in one pass over the parent arrays.  out: room for
+ *                     n_common IDs; the kept IDs in the order given.  Host only.                                             */
+#define GENPHI_DIST_MAX_STEPS 32767
+typedef struct genphi_dist genphi_dist;
+int genphi_dist_create(int64_t n_ind, const int64_t *ind, const int64_t *father, const int64_t *mother,
+                       int64_t n_pro, const int64_t *pro_ids, int64_t n_anc, const int64_t *anc_ids, genphi_dist **out);
+int genphi_dist_compute(genphi_dist *h, int32_t device);
+int genphi_dist_result_device(const genphi_dist *h, const int16_t **d_ptr, int64_t *ld);
+int genphi_dist_result_to_host(genphi_dist *h, int16_t *out);
+int genphi_dist_stats(const genphi_dist *h, double *sweep_ms, double *algorithmic_bytes, int64_t *peak_slots, int32_t *panel_cols,
+                      int32_t *row_bits, int64_t *launches);
+void genphi_dist_destroy(genphi_dist *h);
+int genphi_ancestors(int64_t n_ind, const int64_t *ind, const int64_t *father, const int64_t *mother, int64_t n_ids,
+                     const int64_t *ids, int64_t *n_out, int64_t **out);
+int genphi_mrca_filter(int64_t n_ind, const int64_t *ind, const int64_t *father, const int64_t *mother, int64_t n_common,
+                       const int64_t *common, int64_t *n_out, int64_t *out);
+
 /* Frees host and device memory of the plan (NULL is allowed). */
 void genphi_plan_destroy(genphi_plan *plan);
 
