@@ -18,6 +18,8 @@ meaning, printed lines and error behaviour as the reference:
     gen.occ(ped); gen.rec(ped)             # src/describe.jl:184-238, :133-145: occurrences, coverage (csrc/occ.hip)
     gen.findMRCA(ped, [1, 2, 29])          # src/identify.jl:83-160: MRCAs and meioses; gen.meioses, gen.findDistance,
                                            # gen.findFounders, gen.ancestor (csrc/dist.hip + csrc/loader.cpp)
+    gen.completeness(ped); gen.depth(ped)  # src/describe.jl:73-125, :43-66: ascents by generation (csrc/completeness.hip);
+                                           # gen.nomen, gen.nowomen, gen.noind, ped.show() (src/describe.jl:6-36, src/create.jl:76-111)
 
 All kinship arithmetic runs in hand-written HIP kernels behind the C-ABI in
 include/genphi.h (csrc/genphi_hip.hip); there is no CPU fallback.
@@ -28,7 +30,7 @@ from collections import OrderedDict
 import numpy as np
 
 from . import _capi
-from ._capi import PhiPlan, KinshipMatrix, GCPlan, OccPlan, RecPlan, DistPlan, GenphiDeviceError, GenphiLibraryMissing  # noqa: F401
+from ._capi import PhiPlan, KinshipMatrix, GCPlan, OccPlan, RecPlan, DistPlan, CompletenessPlan, GenphiDeviceError, GenphiLibraryMissing  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
@@ -111,6 +113,21 @@ class Pedigree:
 
     def __repr__(self):
         return f"Pedigree({len(self)} individuals)"
+
+    def show(self):
+        """The text of the reference's Base.show(io, MIME"text/plain", pedigree) (src/create.jl:76-111), singular and plural forms
+        included.  As there, whoever is not a man counts as a woman, a subject is an individual without children, and the
+        generations are the depth of the deepest subject (one linear pass, csrc/loader.cpp, where the reference walks every path)."""
+        n = len(self)
+        relations = int(np.count_nonzero(self.father)) + int(np.count_nonzero(self.mother))
+        men = int(np.count_nonzero(self.sex == 1))
+        women = n - men
+        subjects = len(pro(self))
+        generations = _capi.genealogy_depth(self.ind, self.father, self.mother, leaves_only=True)
+        s = lambda k: "" if k == 1 else "s"  # noqa: E731
+        return ("A pedigree with:\n%d individual%s;\n%d parent-child relation%s;\n%d %s;\n%d %s;\n%d subject%s;\n%d generation%s."
+                % (n, s(n), relations, s(relations), men, "man" if men == 1 else "men", women, "woman" if women == 1 else "women",
+                   subjects, s(subjects), generations, s(generations)))
 
 
 def _read_table(source):
@@ -381,6 +398,85 @@ def meioses(pedigree, pro=None, ancestors=None, device=None):
         return h.result_to_host()
     finally:
         h.close()
+
+
+def completeness(pedigree, pro=None, genNo=None, type="MEAN", device=None):
+    """gen.completeness(pedigree, pro = pro(pedigree); genNo = Int[], type = "MEAN") (src/describe.jl:73-125): the completeness of
+    the probands' genealogies per generation (rows; the probands are generation 0), in percent: the known ancestors of
+    generation g, counted with multiplicity, out of 2^g.  type = "IND": a float64 array of shape (G, len(pro)), one column per
+    proband, G = 1 + the longest ascent of any listed proband; type = "MEAN" (the default): the mean over the probands, (G, 1).
+    genNo: the generations to return, in the order given, repeats allowed.
+
+    The counts are the number of ascending paths of exactly g meioses, computed on the GPU by an Int64 recursion over the
+    generation cuts (csrc/completeness.hip) where the reference walks every path; "IND" is converted on the device by the
+    reference's own operations (count / 2^g * 100) and is equal to the reference bit for bit.  It is a transposed view of the
+    (len(pro), G) row-major result, not a copy.  "MEAN" is formed from the per-generation totals, reduced on the device:
+    mean[g] = float(totals[g]) / 2^g * 100 / len(pro).  Every entry of the reference's matrix is 25 count / 2^(g - 2), exact in
+    Float64 while 25 count < 2^53, and so is every partial sum of a row while 25 totals[g] < 2^53: the reference's sequential
+    sum is then exact and the only rounding is the final division.  So "MEAN" is bit-identical to the reference whenever
+    25 totals[g] < 2^53 for every g (for example 1e5 probands down to 30 generations); beyond that it is within 2 ulp of the exact
+    rational mean (three roundings of half an ulp), where the reference's own sequential sum can be off by up to len(pro) / 2
+    ulp.  Where the totals could exceed Int64 ((G - 1) + ceil(log2(len(pro))) > 62), "MEAN" is the sequential sum of the "IND"
+    result in proband order, as in the reference.
+
+    As in the reference every proband gets its column (with or without children, each time it is listed).  KeyError for an
+    unknown proband; ValueError for an empty pro (the reference's maximum of an empty collection throws), for another type (the
+    reference returns nothing) and for more than 62 generations above the probands (the reference's 2^g overflows there);
+    IndexError for a generation outside 0 .. G - 1 (the reference's BoundsError).  Each call plans, sweeps and frees its own
+    handle."""
+    if type not in ("IND", "MEAN"):
+        raise ValueError('type must be "IND" or "MEAN", not %r' % (type,))
+    probands = globals()["pro"](pedigree) if pro is None else np.ascontiguousarray(pro, dtype=np.int64)
+    if len(probands) == 0:
+        raise ValueError("gen.completeness needs at least one proband")
+    args = (pedigree.ind, pedigree.father, pedigree.mother, probands)
+    h = None
+    if type == "MEAN":
+        try:
+            h = CompletenessPlan(*args, totals_only=True)
+        except ValueError:
+            h = None                                      # too deep (raised again below), or the totals could exceed Int64
+    if h is None:
+        h = CompletenessPlan(*args)
+    try:
+        G = h.generations
+        rows = None
+        if genNo is not None and len(genNo):
+            rows = np.asarray(genNo, dtype=np.int64).ravel()
+            if np.any((rows < 0) | (rows >= G)):
+                raise IndexError("generation %d is outside 0 .. %d" % (int(rows[(rows < 0) | (rows >= G)][0]), G - 1))
+        h.compute(device=device)
+        if type == "IND":
+            out = h.result_to_host().T
+        elif h.totals_only:
+            out = (h.totals().astype(np.float64) / np.ldexp(1.0, np.arange(G)) * 100.0 / len(probands)).reshape(-1, 1)
+        else:
+            out = (np.cumsum(h.result_to_host(), axis=0)[-1] / len(probands)).reshape(-1, 1)     # a sequential sum, proband order
+        return out if rows is None else out[rows, :]
+    finally:
+        h.close()
+
+
+def depth(pedigree):
+    """gen.depth(pedigree) (src/describe.jl:43-66): the number of generations of the pedigree, 1 + the longest ascent of any
+    individual (1 for a pedigree of founders, 0 for an empty one).  One linear pass on the host (csrc/loader.cpp) where the
+    reference recurses without memory; there is no arithmetic worth a kernel launch."""
+    return _capi.genealogy_depth(pedigree.ind, pedigree.father, pedigree.mother)
+
+
+def nomen(pedigree):
+    """gen.nomen(pedigree): the number of men, sex == 1 (src/describe.jl:6-14)."""
+    return int(np.count_nonzero(pedigree.sex == 1))
+
+
+def nowomen(pedigree):
+    """gen.nowomen(pedigree): the number of women, sex == 2 (src/describe.jl:21-29)."""
+    return int(np.count_nonzero(pedigree.sex == 2))
+
+
+def noind(pedigree):
+    """gen.noind(pedigree): the number of individuals (src/describe.jl:36)."""
+    return len(pedigree)
 
 
 def _id_list(IDs):

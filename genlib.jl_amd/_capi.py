@@ -60,6 +60,8 @@ EXPORTED_SYMBOLS = [
     "genphi_rec_create", "genphi_rec_compute", "genphi_rec_result", "genphi_rec_stats", "genphi_rec_destroy",
     "genphi_dist_create", "genphi_dist_compute", "genphi_dist_result_device", "genphi_dist_result_to_host", "genphi_dist_stats", "genphi_dist_destroy",
     "genphi_ancestors", "genphi_mrca_filter",
+    "genphi_comp_create", "genphi_comp_compute", "genphi_comp_generations", "genphi_comp_result_device", "genphi_comp_result_to_host",
+    "genphi_comp_counts_to_host", "genphi_comp_totals", "genphi_comp_stats", "genphi_comp_destroy", "genphi_genealogy_depth",
 ]
 
 _lib = None
@@ -225,6 +227,26 @@ def lib():
         L.genphi_ancestors.restype = C.c_int
         L.genphi_mrca_filter.argtypes = [C.c_int64, _I64P, _I64P, _I64P, C.c_int64, _I64P, _I64P, _I64P]
         L.genphi_mrca_filter.restype = C.c_int
+        L.genphi_comp_create.argtypes = [C.c_int64, _I64P, _I64P, _I64P, C.c_int64, _I64P, C.c_int32, C.POINTER(C.c_void_p)]
+        L.genphi_comp_create.restype = C.c_int
+        L.genphi_comp_compute.argtypes = [C.c_void_p, C.c_int32]
+        L.genphi_comp_compute.restype = C.c_int
+        L.genphi_comp_generations.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+        L.genphi_comp_generations.restype = C.c_int
+        L.genphi_comp_result_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), _I64P]
+        L.genphi_comp_result_device.restype = C.c_int
+        L.genphi_comp_result_to_host.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+        L.genphi_comp_result_to_host.restype = C.c_int
+        L.genphi_comp_counts_to_host.argtypes = [C.c_void_p, _I64P]
+        L.genphi_comp_counts_to_host.restype = C.c_int
+        L.genphi_comp_totals.argtypes = [C.c_void_p, _I64P]
+        L.genphi_comp_totals.restype = C.c_int
+        L.genphi_comp_stats.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), _I64P, C.POINTER(C.c_int32), _I64P]
+        L.genphi_comp_stats.restype = C.c_int
+        L.genphi_comp_destroy.argtypes = [C.c_void_p]
+        L.genphi_comp_destroy.restype = None
+        L.genphi_genealogy_depth.argtypes = [C.c_int64, _I64P, _I64P, _I64P, _I64P, C.c_int32]
+        L.genphi_genealogy_depth.restype = C.c_int
         for kind in ("occ", "rec", "dist"):
             fn = getattr(L, "genphi_%s_compute" % kind)
             fn.argtypes, fn.restype = [C.c_void_p, C.c_int32], C.c_int
@@ -962,6 +984,98 @@ class DistPlan:
     def stats(self):
         """dict(sweep_ms, algorithmic_bytes, peak_slots, panel_cols, row_bits, launches) of the last compute()."""
         return _sweep_stats(lib().genphi_dist_stats, self._h)
+
+
+GENPHI_COMP_MAX_GENERATIONS = 62
+GENPHI_COMP_FLAG_TOTALS_ONLY = 1
+
+
+class CompletenessPlan:
+    """gen.completeness' handle (include/genphi.h, genphi_comp_*): planned on the host at construction (KeyError on an unknown
+    proband, ValueError for more than GENPHI_COMP_MAX_GENERATIONS generations above the probands; no GPU needed), swept on the GPU by
+    compute().  totals_only: the handle reduces the last step into the per-generation totals on the device and holds no
+    (n_pro, generations) result; ValueError where those totals could exceed Int64."""
+
+    def __init__(self, ind, father, mother, pro_ids, totals_only=False):
+        L = lib()
+        ind, father, mother, pro_ids = _i64(ind), _i64(father), _i64(mother), _i64(pro_ids)
+        h = C.c_void_p()
+        rc = L.genphi_comp_create(len(ind), ind.ctypes.data_as(_I64P), father.ctypes.data_as(_I64P), mother.ctypes.data_as(_I64P),
+                                  len(pro_ids), pro_ids.ctypes.data_as(_I64P), GENPHI_COMP_FLAG_TOTALS_ONLY if totals_only else 0, C.byref(h))
+        if rc:
+            _raise(rc)
+        self._h = h
+        self.totals_only = bool(totals_only)
+        g = C.c_int32()
+        rc = L.genphi_comp_generations(h, C.byref(g))
+        if rc:
+            _raise(rc)
+        self.generations = int(g.value)          # 1 + the longest ascent of any listed proband
+        self.shape = (len(pro_ids), self.generations)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().genphi_comp_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+    def compute(self, device=None):
+        rc = lib().genphi_comp_compute(self._h, -1 if device is None else int(device))
+        if rc:
+            _raise(rc)
+
+    def result_device(self):
+        """(device pointer, row pitch in Float64 entries) of the resident result."""
+        p, ld = C.c_void_p(), C.c_int64()
+        rc = lib().genphi_comp_result_device(self._h, C.byref(p), C.byref(ld))
+        if rc:
+            _raise(rc)
+        return p.value, ld.value
+
+    def result_to_host(self):
+        """The (n_pro, generations) float64 result (rows = probands): the finished percentages."""
+        out = np.empty(self.shape, dtype=np.float64)
+        rc = lib().genphi_comp_result_to_host(self._h, out.ctypes.data_as(C.POINTER(C.c_double)))
+        if rc:
+            _raise(rc)
+        return out
+
+    def counts(self):
+        """The (n_pro, generations) int64 path counts."""
+        out = np.empty(self.shape, dtype=np.int64)
+        rc = lib().genphi_comp_counts_to_host(self._h, out.ctypes.data_as(_I64P))
+        if rc:
+            _raise(rc)
+        return out
+
+    def totals(self):
+        """The int64 path counts per generation, summed over the listed probands on the device."""
+        out = np.empty(self.generations, dtype=np.int64)
+        rc = lib().genphi_comp_totals(self._h, out.ctypes.data_as(_I64P))
+        if rc:
+            _raise(rc)
+        return out
+
+    def stats(self):
+        """dict(sweep_ms, algorithmic_bytes, peak_slots, row_entries, launches) of the last compute()."""
+        ms, ab, ps, re_, nl = C.c_double(), C.c_double(), C.c_int64(), C.c_int32(), C.c_int64()
+        rc = lib().genphi_comp_stats(self._h, C.byref(ms), C.byref(ab), C.byref(ps), C.byref(re_), C.byref(nl))
+        if rc:
+            _raise(rc)
+        return {"sweep_ms": ms.value, "algorithmic_bytes": ab.value, "peak_slots": ps.value, "row_entries": re_.value, "launches": nl.value}
+
+
+def genealogy_depth(ind, father, mother, leaves_only=False):
+    """1 + the longest ascent of any individual (leaves_only: of any individual without children): genphi_genealogy_depth, host only."""
+    ind, father, mother = _i64(ind), _i64(father), _i64(mother)
+    d = C.c_int64()
+    rc = lib().genphi_genealogy_depth(len(ind), ind.ctypes.data_as(_I64P), father.ctypes.data_as(_I64P), mother.ctypes.data_as(_I64P),
+                                      C.byref(d), 1 if leaves_only else 0)
+    if rc:
+        _raise(rc)
+    return int(d.value)
 
 
 def ancestors(ind, father, mother, ids):

@@ -56,7 +56,7 @@ int plan_sweep(SweepSchedule &h, int64_t n_ind, const int64_t *ind, const int64_
         h.anc_is_pro.resize(n_anc);
         for (int64_t j = 0; j < n_anc; ++j) h.anc_is_pro[j] = is_pro[anc_rank[j]];
     }
-    if (n_pro == 0 || n_anc == 0 || L == 0) return GENPHI_OK;
+    if (n_pro == 0 || (n_anc == 0 && !sopt.every_member) || L == 0) return GENPHI_OK;
 
     // parents as ranks (the planner checked that they exist and come first), leaves, relevance
     std::vector<int32_t> fa(n_ind, -1), mo(n_ind, -1);
@@ -75,7 +75,14 @@ int plan_sweep(SweepSchedule &h, int64_t n_ind, const int64_t *ind, const int64_
         for (int64_t j = 0; j < n_anc; ++j) oh_of[fill[anc_rank[j]]++] = static_cast<int32_t>(j);
     }
     for (int64_t i = 0; i < n_ind; ++i)      // rank order: parents first
-        rel[i] = oh_start[i + 1] > oh_start[i] || (fa[i] >= 0 && rel[fa[i]]) || (mo[i] >= 0 && rel[mo[i]]);
+        rel[i] = sopt.every_member || oh_start[i + 1] > oh_start[i] || (fa[i] >= 0 && rel[fa[i]]) || (mo[i] >= 0 && rel[mo[i]]);
+    if (sopt.every_member) {
+        // generations = 1 + the longest ascent of a listed proband, from the depths of the ranks (founders 1)
+        std::vector<int32_t> depth(n_ind, 1);
+        for (int64_t i = 0; i < n_ind; ++i)
+            depth[i] = 1 + std::max(fa[i] >= 0 ? depth[fa[i]] : 0, mo[i] >= 0 ? depth[mo[i]] : 0);
+        for (int64_t k = 0; k < n_pro; ++k) h.n_generations = std::max(h.n_generations, depth[ranks.find(pro_ids[k])]);
+    }
 
     // members of cut 0 (founders) by position, from the sources of cut 1 (every member of cut 0 is one of them)
     std::vector<int32_t> cut0(plan.cut_sizes[0], -1);

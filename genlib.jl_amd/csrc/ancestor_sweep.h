@@ -1,6 +1,7 @@
-// ancestor_sweep.h -- host schedule of the ancestor x proband sweeps (gen.gc, gen.occ, gen.rec, gen.meioses; no HIP here).
+// ancestor_sweep.h -- host schedule of the ancestor x proband sweeps (gen.gc, gen.occ, gen.rec, gen.meioses) and of the
+// generation x proband sweep of gen.completeness (SweepOptions::every_member); no HIP here.
 //
-// All four are column-independent recursions over the generation cuts of the planner (build_plan, indices_only):
+// The first four are column-independent recursions over the generation cuts of the planner (build_plan, indices_only):
 //     row[x] = combine(row[father], row[mother])   (a missing parent is the zero row),   then the one-hot columns j with
 //     ancestors[j] == x are set / incremented
 // and share everything but the arithmetic and the rule that says which rows reach the result:
@@ -39,6 +40,9 @@ struct SweepOptions {
     bool drop_unknown_pro = false;    // proband IDs that are not in the pedigree are ignored instead of a KeyError (rec)
     bool mark_copies = false;         // EveryProband: the copy items of the last list carry source B = -2 instead of -1 (meioses:
                                       // a recursion whose step is not the identity on a single source has to tell them apart)
+    bool every_member = false;        // completeness: the columns are generations, not ancestors.  Every member of every cut gets a row
+                                      // and a slot (nothing is "none"), no ancestor list and no one-hot columns exist (n_anc = 0 is
+                                      // valid, oh_cols stays empty); needs Emit::EveryProband.  n_generations is reported.
 };
 
 struct SweepSchedule {
@@ -52,6 +56,7 @@ struct SweepSchedule {
     int32_t n_steps = 0;                     // level steps of the sweep (cuts - 1)
     std::vector<int32_t> pro_slots;          // Emit::None: slots of the distinct probands whose row is not zero
     std::vector<char> anc_is_pro;            // per ancestor column: the ancestor is one of the probands
+    int32_t n_generations = 0;               // every_member: 1 + the longest ascent of any listed proband (0 without probands)
 };
 
 // ID -> rank (a direct table for dense non-negative IDs, else a hash map)

@@ -81,6 +81,30 @@ bool parse_tsv(const char *buf, size_t len, Cols &c, std::string &err)
     return true;
 }
 
+// depth(x) = 1 + max(depth(father), depth(mother)) (founders 1) from the parents' positions (-1 = unknown); explicit stack (no
+// recursion: depth-1e6 chains are fine); false: the pedigree contains a cycle
+bool ancestral_depths(const std::vector<int32_t> &pf, const std::vector<int32_t> &pm, std::vector<int32_t> &depth)
+{
+    const int64_t n = static_cast<int64_t>(pf.size());
+    depth.assign(n, 0);
+    std::vector<int32_t> state(n, 0), stack;
+    for (int64_t s0 = 0; s0 < n; ++s0) {
+        if (depth[s0]) continue;
+        stack.push_back(static_cast<int32_t>(s0));
+        while (!stack.empty()) {
+            const int32_t x = stack.back();
+            const int32_t f = pf[x], m = pm[x];
+            state[x] = 1;
+            if (f >= 0 && !depth[f]) { if (state[f]) return false; stack.push_back(f); continue; }
+            if (m >= 0 && !depth[m]) { if (state[m]) return false; stack.push_back(m); continue; }
+            const int32_t fd = f >= 0 ? depth[f] : 0, md = m >= 0 ? depth[m] : 0;
+            depth[x] = (fd > md ? fd : md) + 1;
+            stack.pop_back();
+        }
+    }
+    return true;
+}
+
 }  // namespace
 
 // Everything after the table is in memory: ID lookup, checks, depth sort (src/create.jl:196-254), output arrays in rank order.
@@ -124,22 +148,8 @@ static int order_and_emit(const Cols &c, int32_t sort, int64_t *n_out, int64_t *
     }
     std::vector<int64_t> order(n);
     if (sort) {
-        // depth(x) = 1 + max(depth(father), depth(mother)); explicit stack; a cycle is an error
-        std::vector<int32_t> depth(n, 0), state(n, 0), stack;
-        for (int64_t s0 = 0; s0 < n; ++s0) {
-            if (depth[s0]) continue;
-            stack.push_back(static_cast<int32_t>(s0));
-            while (!stack.empty()) {
-                const int32_t x = stack.back();
-                const int32_t f = pf[x], m = pm[x];
-                state[x] = 1;
-                if (f >= 0 && !depth[f]) { if (state[f]) return genphi_set_error(GENPHI_ERR_ARG, "pedigree contains a cycle"); stack.push_back(f); continue; }
-                if (m >= 0 && !depth[m]) { if (state[m]) return genphi_set_error(GENPHI_ERR_ARG, "pedigree contains a cycle"); stack.push_back(m); continue; }
-                const int32_t fd = f >= 0 ? depth[f] : 0, md = m >= 0 ? depth[m] : 0;
-                depth[x] = (fd > md ? fd : md) + 1;
-                stack.pop_back();
-            }
-        }
+        std::vector<int32_t> depth;
+        if (!ancestral_depths(pf, pm, depth)) return genphi_set_error(GENPHI_ERR_ARG, "pedigree contains a cycle");
         int32_t maxd = 0;
         for (int64_t i = 0; i < n; ++i) maxd = depth[i] > maxd ? depth[i] : maxd;
         std::vector<int64_t> cnt(static_cast<size_t>(maxd) + 2, 0);
@@ -286,6 +296,38 @@ int genphi_branching(int64_t n_ind, const int64_t *ind, const int64_t *father, c
     }
     *n_out = m; *ind_out = a; *father_out = b; *mother_out = d;
     if (sex_out) *sex_out = e;
+    return GENPHI_OK;
+}
+
+// gen.depth (src/describe.jl:43-66): the reference calls the un-memoised _max_depth for every individual -- every ascending path
+// of every individual is walked.  Here: the depth pass of the loader's sort, once, and a maximum.  leaves_only: the maximum over the
+// individuals without children (what Base.show(::Pedigree) prints, src/create.jl:76-111).  No arithmetic worth a launch: host only.
+int genphi_genealogy_depth(int64_t n_ind, const int64_t *ind, const int64_t *father, const int64_t *mother, int64_t *depth_out,
+                           int32_t leaves_only)
+{
+    if (!depth_out || n_ind < 0 || n_ind >= INT32_MAX || (n_ind > 0 && (!ind || !father || !mother)))
+        return genphi_set_error(GENPHI_ERR_ARG, "genphi_genealogy_depth: bad argument");
+    *depth_out = 0;
+    IdIndex pos;
+    pos.init(n_ind, ind);
+    std::vector<int32_t> pf(n_ind, -1), pm(n_ind, -1);
+    std::vector<uint8_t> has_child(n_ind, 0);
+    for (int64_t i = 0; i < n_ind; ++i)
+        for (int side = 0; side < 2; ++side) {
+            const int64_t pid = side ? mother[i] : father[i];
+            if (pid == 0) continue;
+            const int32_t r = pos.find(pid);
+            if (r < 0)
+                return genphi_set_error(GENPHI_ERR_UNKNOWN_ID, "KeyError: parent " + std::to_string(pid) + " of " + std::to_string(ind[i]) + " not found");
+            (side ? pm : pf)[i] = r;
+            has_child[r] = 1;
+        }
+    std::vector<int32_t> depth;
+    if (!ancestral_depths(pf, pm, depth)) return genphi_set_error(GENPHI_ERR_ARG, "pedigree contains a cycle");
+    int32_t maxd = 0;
+    for (int64_t i = 0; i < n_ind; ++i)
+        if (!(leaves_only && has_child[i]) && depth[i] > maxd) maxd = depth[i];
+    *depth_out = maxd;
     return GENPHI_OK;
 }
 

@@ -358,6 +358,68 @@ function rec(pedigree::GenLib.Pedigree, probandIDs::Vector{Int} = GenLib.pro(ped
 end
 
 """
+    completeness(pedigree::GenLib.Pedigree, pro = GenLib.pro(pedigree); genNo = Int[], type = "MEAN", device = -1)
+
+Completeness of the genealogies of `pro` per generation (rows; the probands are generation 0), in percent, as
+`GenLib.completeness` (src/describe.jl:73-125): one Int64 recursion over the generation cuts on the GPU
+(csrc/completeness.hip) instead of a walk of every ascending path.  `type = "IND"`: the library's `pro x generations`
+row-major result is the memory of a `Matrix{Float64}(undef, generations, length(pro))`: no transpose; bit-identical to the
+reference.  `type = "MEAN"`: from the per-generation totals reduced on the GPU, `totals[g] / 2^g * 100 / length(pro)`:
+bit-identical to the reference while `25 totals[g] < 2^53` for every `g`, within 2 ulp of the exact mean beyond
+(include/genphi.h); where the totals could exceed `Int64`, the reference's `sum(matrix, dims = 2) ./ length(pro)`.
+"""
+function completeness(pedigree::GenLib.Pedigree, pro::Vector{Int} = GenLib.pro(pedigree);
+                      genNo::Vector{Int} = Int[], type::String = "MEAN", device::Integer = -1)
+    type == "IND" || type == "MEAN" || throw(ArgumentError("type must be \"IND\" or \"MEAN\""))
+    isempty(pro) && throw(ArgumentError("reducing over an empty collection is not allowed"))
+    ind, father, mother, _ = flatten(pedigree)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    create(flags) = GC.@preserve ind father mother pro ccall((:genphi_comp_create, libgenphi), Cint,
+        (Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Int64, Ptr{Int64}, Int32, Ptr{Ptr{Cvoid}}),
+        length(ind), ind, father, mother, length(pro), pro, Int32(flags), h)
+    totals_only = type == "MEAN"
+    rc = create(totals_only ? 1 : 0)
+    if totals_only && rc == 6       # GENPHI_ERR_ARG: too deep (returned again below), or the totals could exceed Int64
+        totals_only = false
+        rc = create(0)
+    end
+    check(rc)
+    try
+        generations = Ref{Int32}(0)
+        check(ccall((:genphi_comp_generations, libgenphi), Cint, (Ptr{Cvoid}, Ptr{Int32}), h[], generations))
+        G = Int(generations[])
+        all(g -> 0 <= g < G, genNo) || throw(BoundsError(1:G, genNo .+ 1))
+        check(ccall((:genphi_comp_compute, libgenphi), Cint, (Ptr{Cvoid}, Int32), h[], Int32(device)))
+        if totals_only
+            totals = Vector{Int64}(undef, G)
+            GC.@preserve totals check(ccall((:genphi_comp_totals, libgenphi), Cint, (Ptr{Cvoid}, Ptr{Int64}), h[], totals))
+            matrix = reshape([totals[g + 1] / 2.0^g * 100 / length(pro) for g in 0:G-1], G, 1)
+        else
+            matrix = Matrix{Float64}(undef, G, length(pro))
+            GC.@preserve matrix check(ccall((:genphi_comp_result_to_host, libgenphi), Cint, (Ptr{Cvoid}, Ptr{Float64}), h[], matrix))
+            type == "MEAN" && (matrix = sum(matrix, dims = 2) ./ length(pro))
+        end
+        return isempty(genNo) ? matrix : matrix[genNo .+ 1, :]
+    finally
+        ccall((:genphi_comp_destroy, libgenphi), Cvoid, (Ptr{Cvoid},), h[])
+    end
+end
+
+"""
+    depth(pedigree::GenLib.Pedigree)
+
+The number of generations of the pedigree, as `GenLib.depth` (src/describe.jl:43-66): one linear pass on the host
+(csrc/loader.cpp) where the reference calls the un-memoised `_max_depth` for every individual.
+"""
+function depth(pedigree::GenLib.Pedigree)
+    ind, father, mother, _ = flatten(pedigree)
+    d = Ref{Int64}(0)
+    GC.@preserve ind father mother check(ccall((:genphi_genealogy_depth, libgenphi), Cint,
+        (Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Int32), length(ind), ind, father, mother, d, Int32(0)))
+    Int(d[])
+end
+
+"""
     meioses(pedigree::GenLib.Pedigree; pro = GenLib.pro(pedigree), ancestors = GenLib.founder(pedigree), device = -1)
 
 Meioses on the shortest ascending path from each of `pro` (rows) to each of `ancestors` (columns), `Matrix{Int16}`; `0` where

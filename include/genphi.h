@@ -484,6 +484,63 @@ int genphi_ancestors(int64_t n_ind, const int64_t *ind, const int64_t *father, c
 int genphi_mrca_filter(int64_t n_ind, const int64_t *ind, const int64_t *father, const int64_t *mother, int64_t n_common,
                        const int64_t *common, int64_t *n_out, int64_t *out);
 
+/* ---- gen.completeness and gen.depth: ascents by generation (csrc/completeness.hip, csrc/loader.cpp) ---------------------------
+ * Replace completeness(pedigree, pro = pro(pedigree); genNo, type), src/describe.jl:73-125, and depth(pedigree), src/describe.jl:43-66.
+ *
+ * comp.  Entry [i][g] = the number of ascending paths of exactly g meioses that start at pro_ids[i] (the reference's
+ * completeness[g] of that proband; 1 for g = 0), by the recursion P[x][0] = 1, P[x][g] = P[father][g - 1] + P[mother][g - 1] over
+ * the generation cuts, on the host schedule of gen.gc / gen.occ (csrc/ancestor_sweep.h, every member of every cut has a row).
+ * G = 1 + the longest ascent of any listed proband is the number of columns (1 when every proband is a founder).  Rules:
+ *   - every proband gets its row, with or without children; a proband listed again gets the same row again;
+ *   - an unknown ID in pro_ids -> GENPHI_ERR_UNKNOWN_ID (KeyError); n_pro = 0: G = 0 and an empty result.
+ * Exactness.  Counts are Int64 and P[x][g] <= 2^g: create returns GENPHI_ERR_ARG for more than GENPHI_COMP_MAX_GENERATIONS = 62
+ * generations above the probands (G > 63; the reference's own 2^row is an Int that turns negative at row 63).  The result is
+ * Float64, converted on the device by the reference's two operations in its order, (double)count / 2^g * 100.0: bit-identical to
+ * the reference's "IND" matrix at any permitted depth; generations beyond a proband's own depth are 0.0, generation 0 is 100.0.
+ * Totals (what the reference's "MEAN" sums): per generation, the counts summed over the rows (each listed occurrence counts),
+ * reduced on the device with 64-bit integer atomics (the same bits on every run).  A handle created with
+ * GENPHI_COMP_FLAG_TOTALS_ONLY reduces the last step directly and never allocates an n_pro x G buffer.  A total is at most
+ * n_pro 2^(G - 1): while (G - 1) + ceil(log2(n_pro)) <= 62 it cannot overflow; otherwise create with the flag, and totals on
+ * any handle, return GENPHI_ERR_ARG and the caller sums the result rows instead.
+ * MEAN from the totals: mean[g] = (double)totals[g] / 2^g * 100.0 / n_pro.  Every entry of the reference's matrix is
+ * 25 count / 2^(g - 2), exact in Float64 while 25 count < 2^53, and so is every partial sum of a row of generation g while
+ * 25 totals[g] < 2^53: the reference's sequential sum(matrix, dims = 2) is then exact in any order and the only rounding is the
+ * final division.  So the mean is bit-identical to the reference whenever 25 totals[g] < 2^53 for every g; beyond that it is
+ * within 2 ulp of the exact rational mean (three roundings of half an ulp: conversion, x 100, / n_pro), where the reference's own
+ * sequential sum can be off by up to n_pro / 2 ulp.
+ *   create            host only (no GPU): checks IDs, pedigree order and depth, plans cuts, rows and slots
+ *   generations       G; valid after create
+ *   compute           the sweep on `device` (-1 = current); the result stays resident; GENPHI_ERR_ALLOC before any launch when
+ *                     the slot rows and the result do not fit
+ *   result_device     device pointer and row pitch (ld = G) of the resident Float64 result (GENPHI_ERR_ARG on a totals-only handle)
+ *   result_to_host    out: n_pro x G Float64, row-major: the finished percentages
+ *   counts_to_host    out: n_pro x G Int64, row-major: the path counts
+ *   totals            out: G Int64
+ *   stats             device time of the last sweep (HIP events); its algorithmic bytes: 8 G (source rows read + slot rows
+ *                     written) plus what the last list writes (16 n_pro G: counts and percentages; totals only: 8 G); the
+ *                     slot rows; the entries of a slot row (G rounded up to 8); the kernel launches of the sweep
+ *
+ * genphi_genealogy_depth   gen.depth: 1 + the longest ascent of any individual (leaves_only = 0; founders count 1, an empty
+ *                     pedigree 0), or of any individual without children (leaves_only = 1: what the reference's show prints).
+ *                     One linear pass on the host where the reference recurses without memory; no order of the pedigree is
+ *                     assumed.  Unknown parent -> GENPHI_ERR_UNKNOWN_ID, a cycle -> GENPHI_ERR_ARG.                          */
+#define GENPHI_COMP_MAX_GENERATIONS 62
+#define GENPHI_COMP_FLAG_TOTALS_ONLY 1   /* totals only: no n_pro x G result exists */
+typedef struct genphi_comp genphi_comp;
+int genphi_comp_create(int64_t n_ind, const int64_t *ind, const int64_t *father, const int64_t *mother,
+                       int64_t n_pro, const int64_t *pro_ids, int32_t flags, genphi_comp **out);
+int genphi_comp_compute(genphi_comp *h, int32_t device);
+int genphi_comp_generations(const genphi_comp *h, int32_t *generations);
+int genphi_comp_result_device(const genphi_comp *h, const double **d_ptr, int64_t *ld);
+int genphi_comp_result_to_host(genphi_comp *h, double *out);
+int genphi_comp_counts_to_host(genphi_comp *h, int64_t *out);
+int genphi_comp_totals(genphi_comp *h, int64_t *out);
+int genphi_comp_stats(const genphi_comp *h, double *sweep_ms, double *algorithmic_bytes, int64_t *peak_slots, int32_t *row_entries,
+                      int64_t *launches);
+void genphi_comp_destroy(genphi_comp *h);
+int genphi_genealogy_depth(int64_t n_ind, const int64_t *ind, const int64_t *father, const int64_t *mother, int64_t *depth,
+                           int32_t leaves_only);
+
 /* Frees host and device memory of the plan (NULL is allowed). */
 void genphi_plan_destroy(genphi_plan *plan);
 
