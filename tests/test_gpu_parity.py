@@ -8,6 +8,8 @@ import os
 import numpy as np
 import pytest
 
+from random_pedigree import random_pedigree as _random_pedigree
+
 pytestmark = pytest.mark.gpu
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -543,29 +545,6 @@ def test_inbreeding_f_from_the_sweep(gen, oracle):
     with pytest.raises(ValueError):
         pl.result_entries([10], [3])                                       # row not resident
     pl.close()
-
-
-def _random_pedigree(rng, n, p_founder, p_one_parent, p_selfing, max_back):
-    """Arbitrary pedigree in id order (parents have smaller ids): overlapping generations,
-    one-parent individuals, founders anywhere, occasional selfing, sex not enforced."""
-    ind = np.arange(1, n + 1, dtype=np.int64)
-    fa = np.zeros(n, dtype=np.int64)
-    mo = np.zeros(n, dtype=np.int64)
-    for i in range(1, n):
-        if rng.random() < p_founder:
-            continue
-        lo = max(0, i - max_back)
-        f = int(rng.integers(lo, i)) + 1
-        m = int(rng.integers(lo, i)) + 1
-        r = rng.random()
-        if r < p_one_parent / 2:
-            f = 0
-        elif r < p_one_parent:
-            m = 0
-        elif rng.random() < p_selfing:
-            m = f
-        fa[i], mo[i] = f, m
-    return ind, fa, mo, np.ones(n, dtype=np.int64)
 
 
 def test_random_pedigrees_bit_exact(gen, oracle, monkeypatch):
