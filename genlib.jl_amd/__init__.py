@@ -594,3 +594,69 @@ def phiMean(phi_matrix):
     diagonal = np.float32(np.diagonal(m).sum(dtype=np.float32))
     total = np.float32(total - diagonal)
     return np.float32(total / np.float32(m.size - m.shape[0]))
+
+
+def _pop(filename):
+    """gen._pop(filename) (src/GenLib.jl:76-92): the population of each proband as a dict ID -> name, from a file with a header
+    line and two whitespace-separated fields per line (the reference's pop140.csv)."""
+    population = {}
+    with open(filename) as file:
+        next(file, None)
+        for line in file:
+            ind, name = line.split()
+            population[int(ind)] = name
+    return population
+
+
+def _group_order(groups, probandIDs=None):
+    """Host side of gen.phiMeanGroups: (names, IDs, labels).  names = the group names, sorted; IDs = the probands (each once) ordered
+    by (group name, ID), those in no group last; labels[i] = index in names of the group of IDs[i], -1 = in no group.  In this order
+    every group is one run, which is the form genphi_result_group_sums reads without a column table."""
+    if len(groups) == 0:
+        raise ValueError("groups is empty")
+    names = sorted(set(groups.values()))
+    index = {name: k for k, name in enumerate(names)}
+    ids = np.unique(np.fromiter(groups.keys(), dtype=np.int64, count=len(groups)) if probandIDs is None else np.asarray(probandIDs, dtype=np.int64))
+    labels = np.array([index[groups[i]] if i in groups else -1 for i in ids.tolist()], dtype=np.int32)
+    key = np.where(labels < 0, len(names), labels)
+    order = np.argsort(key, kind="stable")                 # (ids ascend already)
+    return names, ids[order], labels[order]
+
+
+class GroupMeans:
+    """What gen.phiMeanGroups returns: `names` (sorted), `sizes` (probands per group) and `mean`, the float64 table of mean kinships
+    (mean[a, a] within names[a], off-diagonal pairs only; mean[a, b] between names[a] and names[b]; NaN where there is no pair)."""
+
+    def __init__(self, names, sizes, mean):
+        self.names, self.sizes, self.mean = names, sizes, mean
+
+    def __repr__(self):
+        width = max(len(str(n)) for n in self.names)
+        lines = ["GroupMeans of %d groups (mean kinship within, on the diagonal, and between groups):" % len(self.names)]
+        for a, name in enumerate(self.names):
+            lines.append("%-*s n=%-6d %s" % (width, name, self.sizes[a], " ".join("%.6f" % v for v in self.mean[a])))
+        return "\n".join(lines)
+
+
+def phiMeanGroups(pedigree, groups, probandIDs=None, device=None):
+    """Mean kinship within and between groups of probands, e.g. the populations of gen._pop(pop140.csv): phiMean
+    (src/compute.jl:454-459) of every diagonal block of gen.phi and the plain mean of every other block, reduced on the device
+    from the resident matrix, which is never copied (genphi_result_group_sums; one pass over it).
+
+    groups: a mapping ID -> group name (any hashable, sortable value).  probandIDs: the probands of the sweep, by default the
+    keys of groups; IDs that are not in groups take part in the sweep but belong to no group.  Returns a GroupMeans.
+    KeyError for an unknown ID, ValueError for an empty groups."""
+    names, ids, labels = _group_order(groups, probandIDs)
+    pedigree.positions(ids)                                 # KeyError on an unknown ID
+    pl, key = _plan_for(pedigree, ids, device)
+    keep = False
+    try:
+        pl.compute_device(device=device)
+        sums, diag, _, sizes, _ = pl.group_sums(labels, len(names))
+        keep = key is not None and _keep_plan(pedigree, key, pl, ids)
+    finally:
+        if not keep:
+            if key is not None and key in pedigree._plans and pedigree._plans[key][0] is pl:
+                del pedigree._plans[key]
+            pl.close()
+    return GroupMeans(names, sizes, _capi.mean_from_group_sums(sums, diag, sizes))

@@ -23,6 +23,7 @@ GENPHI_MAX_STAT_LEVELS = 1024
 GENPHI_FLAG_NO_GRAPH = 1
 GENPHI_FLAG_STORAGE_F64 = 2
 GENPHI_FLAG_NO_SPARSE = 4
+GENPHI_GROUP_SUMS_MAX_GROUPS = 4096
 
 _I64P = C.POINTER(C.c_int64)
 _F32P = C.POINTER(C.c_float)
@@ -46,7 +47,7 @@ class GenphiStats(C.Structure):
 EXPORTED_SYMBOLS = [
     "genphi_plan_create", "genphi_plan_create_tuned", "genphi_tuning_create", "genphi_tuning_set", "genphi_tuning_destroy", "genphi_plan_levels", "genphi_plan_n_probands", "genphi_plan_step_mode", "genphi_plan_step_info", "genphi_plan_step_slots",
     "genphi_plan_algorithmic_bytes", "genphi_plan_device_bytes", "genphi_plan_device_bytes_needed", "genphi_plan_sparse_levels", "genphi_plan_step_walk", "genphi_plan_set_step_hook", "genphi_compute_device", "genphi_result_device",
-    "genphi_result_to_host", "genphi_result_to_host_f64", "genphi_phi_pairs", "genphi_result_sums", "genphi_result_entries",
+    "genphi_result_to_host", "genphi_result_to_host_f64", "genphi_phi_pairs", "genphi_result_sums", "genphi_result_group_sums", "genphi_result_entries",
     "genphi_compute_f32",
     "genphi_genealogy_read", "genphi_branching", "genphi_free", "genphi_release_cached", "genphi_cached_bytes", "genphi_plan_release_device", "genphi_plan_destroy",
     "genphi_last_error",
@@ -133,6 +134,9 @@ def lib():
         L.genphi_phi_pairs.restype = C.c_int
         L.genphi_result_sums.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), _I64P]
         L.genphi_result_sums.restype = C.c_int
+        L.genphi_result_group_sums.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double), _I64P, _I64P,
+                                               C.POINTER(C.c_int32)]
+        L.genphi_result_group_sums.restype = C.c_int
         L.genphi_result_entries.argtypes = [C.c_void_p, C.c_int64, _I64P, _I64P, C.POINTER(C.c_double)]
         L.genphi_result_entries.restype = C.c_int
         L.genphi_branching.argtypes = [C.c_int64, _I64P, _I64P, _I64P, _I64P, C.c_int64, _I64P, C.c_int64, _I64P,
@@ -567,9 +571,51 @@ class PhiPlan:
             raise ValueError("phi_mean needs all rows resident; combine result_sums() of the shards instead")
         return np.float32((a - d) / (n * n - n))
 
+    def group_sums(self, labels, n_groups=None):
+        """(sums, diag, rows_in_group, cols_in_group, form) of the resident Float32 result, reduced on the device
+        (genphi_result_group_sums): labels[i] in [0, n_groups) is the group of proband i, -1 = in no group; n_groups defaults to
+        1 + the largest label.  sums[a, b] = Float64 sum of Phi[i, j] over the resident rows i of group a and all columns j of
+        group b; diag[a] = sum of Phi[i, i] over the resident rows of a; form = 0 when every group is one run of the proband
+        order, else 1.  Row shards add their outputs."""
+        labels = np.ascontiguousarray(labels, dtype=np.int32)
+        if labels.ndim != 1 or len(labels) != self.n_probands:
+            raise ValueError("labels must hold one entry per proband (%d), got shape %s" % (self.n_probands, labels.shape))
+        g = int(n_groups) if n_groups is not None else (int(labels.max()) + 1 if len(labels) else 0)
+        if not 1 <= g <= GENPHI_GROUP_SUMS_MAX_GROUPS:                 # (checked here too: the outputs are sized by it)
+            raise ValueError("n_groups = %d outside [1, %d]" % (g, GENPHI_GROUP_SUMS_MAX_GROUPS))
+        sums, diag = np.zeros((g, g), dtype=np.float64), np.zeros(g, dtype=np.float64)
+        rows, cols, form = np.zeros(g, dtype=np.int64), np.zeros(g, dtype=np.int64), C.c_int32()
+        dp = C.POINTER(C.c_double)
+        rc = lib().genphi_result_group_sums(self._h, g, labels.ctypes.data_as(C.POINTER(C.c_int32)), sums.ctypes.data_as(dp),
+                                            diag.ctypes.data_as(dp), rows.ctypes.data_as(_I64P), cols.ctypes.data_as(_I64P), C.byref(form))
+        if rc:
+            _raise(rc)
+        return sums, diag, rows, cols, form.value
+
+    def phi_mean_groups(self, labels, n_groups=None):
+        """gen.phiMean per group and per pair of groups, from the resident (full) result without a device-to-host copy: a float64
+        (n_groups, n_groups) table.  [a, a] = (sums[a, a] - diag[a]) / (n_a (n_a - 1)), the reference's off-diagonal mean
+        (src/compute.jl:454-459) within group a; [a, b] = sums[a, b] / (n_a n_b); NaN where the denominator is 0."""
+        sums, diag, rows, cols, _ = self.group_sums(labels, n_groups)
+        if int(rows.sum()) != int(cols.sum()):
+            raise ValueError("phi_mean_groups needs all rows resident; combine group_sums() of the shards instead")
+        return mean_from_group_sums(sums, diag, cols)
+
     def compute(self, device=None, kernel=0, rows=None, timing=False, no_sparse=False):
         self.compute_device(device=device, kernel=kernel, rows=rows, timing=timing, no_sparse=no_sparse)
         return self.result_to_host()
+
+
+def mean_from_group_sums(sums, diag, sizes):
+    """The table of PhiPlan.phi_mean_groups from full-result group sums (or from the added outputs of row shards)."""
+    n = np.asarray(sizes, dtype=np.float64)
+    den = np.outer(n, n)
+    np.fill_diagonal(den, n * (n - 1))
+    num = np.array(sums, dtype=np.float64)
+    np.fill_diagonal(num, np.diagonal(num) - np.asarray(diag, dtype=np.float64))
+    out = np.full(num.shape, np.nan)
+    np.divide(num, den, out=out, where=den > 0)
+    return out
 
 
 def phi_pairs(ind, father, mother, id_i, id_j, device=None):

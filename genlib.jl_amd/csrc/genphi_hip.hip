@@ -1821,6 +1821,112 @@ __global__ void row_sums_kernel(const float *m, long long ld, int n, int row_beg
     if (threadIdx.x == 0) { row_sum[k] = part[0]; diag[k] = static_cast<double>(row[row_begin + k]); }
 }
 
+// Group sums of the resident result (genphi_result_group_sums): T = Phi B summed over blocks of rows.
+// A workgroup owns a block of at most kGsBlockRows resident rows of ONE group and a slab of column tiles (kGsTile columns
+// each).  Per tile a thread keeps the Float64 column sums of its quad over the block's rows, read in place with 16-byte
+// loads, row after row: the labels cost nothing there.  Once per tile (not per row) the 1,024 column sums go through LDS and
+// are folded by two host-built tables that are the same for every row: list A cuts the tile's labelled columns into pieces of
+// at most kGsPiece columns of one group, list B names the pieces of each group present in the tile (a group appears in it
+// once).  One thread owns a piece, then a group: no atomics, fixed summation order => reproducible.  GATHER = false (form
+// 0): every group is one run of columns and a piece is a stretch of the tile; GATHER = true (form 1): labels in any order, a
+// piece is a stretch of `perm`, the tile's columns sorted by group.  The column sums sit at i + i / 16 so that the piece
+// owners, 16 doubles apart, read distinct banks.  LDS and registers are the same for every n_groups: bins has the cap's size.
+constexpr int kGsMaxGroups = 4096;      // GENPHI_GROUP_SUMS_MAX_GROUPS
+constexpr int kGsTile = 1024;           // columns of a tile: 256 threads x one quad
+constexpr int kGsPiece = 16;
+constexpr int kGsBlockRows = 64;
+constexpr int kGsFan = 32;              // rows one thread of group_rows_reduce_kernel adds
+
+template <bool GATHER>
+__global__ void __launch_bounds__(256)
+group_tiles_kernel(const float *__restrict__ m, long long ld, int row_begin, const int *__restrict__ rowlist,
+                   const int2 *__restrict__ blocks /* first entry of rowlist, rows */, const int2 *__restrict__ tile_lists /* first A entry, first B entry; n_tiles + 1 */,
+                   const int *__restrict__ list_a /* first column | columns << 16 */, const int2 *__restrict__ list_b /* first piece | pieces << 16, group */,
+                   const unsigned short *__restrict__ perm, int n_tiles, int tiles_per_slab, int n_slabs, int n_groups,
+                   double *__restrict__ part /* [block x slab][n_groups + 1] */)
+{
+    __shared__ double bins[kGsMaxGroups + 1];
+    __shared__ double cs[kGsTile + kGsTile / 16];
+    __shared__ double pa[kGsTile];
+    const int tid = threadIdx.x;
+    const int blk = blockIdx.x / n_slabs, slab = blockIdx.x - blk * n_slabs;
+    const int2 b = blocks[blk];
+    const int *rows = rowlist + b.x;
+    const int nb = b.y;
+    for (int g = tid; g <= n_groups; g += 256) bins[g] = 0.0;
+    const int t_end = min(n_tiles, (slab + 1) * tiles_per_slab);
+    for (int t = slab * tiles_per_slab; t < t_end; ++t) {
+        const long long j = (long long)t * kGsTile + tid * 4;
+        double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+        if (j < ld) {                                                 // ld is a multiple of 64 and columns >= n are zero
+            const float *col = m + j;
+            int r = 0;
+            for (; r + 8 <= nb; r += 8) {
+                float4 v[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) v[u] = *reinterpret_cast<const float4 *>(col + (long long)rows[r + u] * ld);
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    a0 += static_cast<double>(v[u].x); a1 += static_cast<double>(v[u].y);
+                    a2 += static_cast<double>(v[u].z); a3 += static_cast<double>(v[u].w);
+                }
+            }
+            for (; r < nb; ++r) {
+                const float4 v = *reinterpret_cast<const float4 *>(col + (long long)rows[r] * ld);
+                a0 += static_cast<double>(v.x); a1 += static_cast<double>(v.y);
+                a2 += static_cast<double>(v.z); a3 += static_cast<double>(v.w);
+            }
+        }
+        const int c = tid * 4 + (tid >> 2);
+        cs[c] = a0; cs[c + 1] = a1; cs[c + 2] = a2; cs[c + 3] = a3;
+        __syncthreads();
+        const int2 l0 = tile_lists[t], l1 = tile_lists[t + 1];
+        const int n_a = l1.x - l0.x, n_b = l1.y - l0.y;
+        for (int i = tid; i < n_a; i += 256) {
+            const int w = list_a[l0.x + i], first = w & 0xffff, len = w >> 16;
+            double s = 0.0;
+            for (int k = 0; k < len; ++k) {
+                const int e = GATHER ? perm[(long long)t * kGsTile + first + k] : first + k;
+                s += cs[e + (e >> 4)];
+            }
+            pa[i] = s;
+        }
+        __syncthreads();
+        for (int i = tid; i < n_b; i += 256) {
+            const int2 w = list_b[l0.y + i];
+            const int first = w.x & 0xffff, len = w.x >> 16;
+            double s = 0.0;
+            for (int k = 0; k < len; ++k) s += pa[first + k];
+            bins[w.y] += s;                                           // the only owner of group w.y in this tile
+        }
+        // (the next tile writes cs before its barrier and pa after it: nothing of this tile is still being read by then)
+    }
+    if (slab == 0) {                                                  // diagonal entries of the block's rows, in row order
+        __syncthreads();
+        if (tid < nb) cs[tid] = static_cast<double>(m[(long long)rows[tid] * ld + row_begin + rows[tid]]);
+        __syncthreads();
+        if (tid == 0) {
+            double s = 0.0;
+            for (int k = 0; k < nb; ++k) s += cs[k];
+            bins[n_groups] = s;
+        }
+    }
+    __syncthreads();
+    double *out = part + (long long)blockIdx.x * (n_groups + 1);
+    for (int g = tid; g <= n_groups; g += 256) out[g] = bins[g];
+}
+
+// S = A^T T in fixed order: out[k][c] = in[beg[k]][c] + ... + in[beg[k + 1] - 1][c], one thread per entry, applied level by
+// level (at most kGsFan rows of one group per output row) until every group has one row.
+__global__ void group_rows_reduce_kernel(const double *__restrict__ in, double *__restrict__ out, const int *__restrict__ beg, int width)
+{
+    const int c = blockIdx.y * blockDim.x + threadIdx.x, k = blockIdx.x;
+    if (c >= width) return;
+    double s = 0.0;
+    for (int r = beg[k]; r < beg[k + 1]; ++r) s += in[(long long)r * width + c];
+    out[(long long)k * width + c] = s;
+}
+
 // out[k][c] = in[perm[row_begin + k]][perm[c]]: the last level of a WIDE step, computed in storage
 // order, delivered in proband order
 // A per-element global gather runs at ~0.4 TB/s (one cache line per lane).  Here a workgroup
@@ -4218,6 +4324,193 @@ int genphi_result_sums(genphi_plan *p, double *sum_all, double *sum_diag, int64_
     for (int64_t k = 0; k < nr; ++k) { sa += h[k]; sd += h[nr + k]; }
     if (sum_all) *sum_all = sa;
     if (sum_diag) *sum_diag = sd;
+    return GENPHI_OK;
+}
+
+// Group sums of the resident result.  Host side: the tables of group_tiles_kernel (rows sorted by group and cut into
+// blocks, the two lists of every column tile), the row ranges of every level of group_rows_reduce_kernel, one upload, the launches,
+// one copy of the n_groups x (n_groups + 1) table back.  Everything lives in the plan's scratch block.
+int genphi_result_group_sums(genphi_plan *p, int32_t n_groups, const int32_t *group, double *sums, double *diag,
+                             int64_t *rows_in_group, int64_t *cols_in_group, int32_t *form_out)
+{
+    if (!p) return fail(GENPHI_ERR_ARG, "plan is NULL");
+    if (n_groups < 1 || n_groups > kGsMaxGroups)
+        return fail(GENPHI_ERR_ARG, "genphi_result_group_sums: n_groups = " + std::to_string(n_groups) + " outside [1, " +
+                                    std::to_string(kGsMaxGroups) + "] (GENPHI_GROUP_SUMS_MAX_GROUPS)");
+    const int64_t N = p->plan.n_pro;
+    if (N > 0 && !group) return fail(GENPHI_ERR_ARG, "genphi_result_group_sums: group is NULL");
+    for (int64_t i = 0; i < N; ++i)
+        if (group[i] < -1 || group[i] >= n_groups)
+            return fail(GENPHI_ERR_ARG, "genphi_result_group_sums: label " + std::to_string(group[i]) + " of proband " + std::to_string(i) +
+                                        " outside [-1, " + std::to_string(n_groups) + ")");
+    if (p->res_f64) return fail(GENPHI_ERR_ARG, "genphi_result_group_sums works on the Float32 result (phiMean's input type, src/compute.jl:454)");
+    if (N > 0 && (!p->on_device || !p->result || p->res_n_rows == 0))
+        return fail(GENPHI_ERR_DEVICE, "no resident result: call genphi_compute_device first");
+    const int G = n_groups, W = G + 1;
+    const int64_t r0 = p->res_row_begin, nr = N > 0 ? p->res_n_rows : 0;
+
+    // labels: counts, and whether every group's columns are one run (form 0)
+    std::vector<int64_t> n_cols(G, 0), n_rows(G, 0);
+    int form = 0;
+    {
+        std::vector<char> closed(G, 0);
+        for (int64_t i = 0; i < N; ++i) {
+            const int g = group[i];
+            if (i > 0 && group[i - 1] >= 0 && group[i - 1] != g) closed[group[i - 1]] = 1;
+            if (g < 0) continue;
+            if (closed[g]) form = 1;
+            ++n_cols[g];
+            if (i >= r0 && i < r0 + nr) ++n_rows[g];
+        }
+    }
+    // resident rows sorted by group (stable), cut into blocks of one group and at most kGsBlockRows rows of even size
+    std::vector<int> rowlist;
+    std::vector<int2> blocks;
+    std::vector<int> cnt(G, 0);                       // rows of `part` per group
+    {
+        std::vector<int64_t> at(G + 1, 0);
+        for (int g = 0; g < G; ++g) at[g + 1] = at[g] + n_rows[g];
+        rowlist.resize(static_cast<size_t>(at[G]));
+        std::vector<int64_t> fill(at.begin(), at.end() - 1);
+        for (int64_t k = 0; k < nr; ++k)
+            if (group[r0 + k] >= 0) rowlist[static_cast<size_t>(fill[group[r0 + k]]++)] = static_cast<int>(k);
+        for (int g = 0; g < G; ++g) {
+            const int64_t n = n_rows[g], nb = (n + kGsBlockRows - 1) / kGsBlockRows;
+            int64_t first = at[g];
+            for (int64_t b = 0; b < nb; ++b) {
+                const int64_t len = n / nb + (b < n % nb ? 1 : 0);
+                blocks.push_back(make_int2(static_cast<int>(first), static_cast<int>(len)));
+                first += len;
+            }
+            cnt[g] = static_cast<int>(nb);
+        }
+    }
+    const int64_t n_blocks = static_cast<int64_t>(blocks.size());
+    auto deliver = [&](const double *tab) {           // tab: G x W (sums | diag), or NULL = zeros
+        for (int a = 0; a < G; ++a) {
+            if (sums) for (int b = 0; b < G; ++b) sums[static_cast<size_t>(a) * G + b] = tab ? tab[static_cast<size_t>(a) * W + b] : 0.0;
+            if (diag) diag[a] = tab ? tab[static_cast<size_t>(a) * W + G] : 0.0;
+            if (rows_in_group) rows_in_group[a] = n_rows[a];
+            if (cols_in_group) cols_in_group[a] = n_cols[a];
+        }
+        if (form_out) *form_out = form;
+    };
+    if (n_blocks == 0) { deliver(nullptr); return GENPHI_OK; }
+
+    // column tiles: pieces (list A) and the pieces of each group (list B), the same for every row
+    const int n_tiles = static_cast<int>((N + kGsTile - 1) / kGsTile);
+    std::vector<int2> tile_lists(static_cast<size_t>(n_tiles) + 1);
+    std::vector<int> list_a;
+    std::vector<int2> list_b;
+    std::vector<unsigned short> perm(form ? static_cast<size_t>(n_tiles) * kGsTile : 0, 0);
+    {
+        std::vector<unsigned short> seq;              // form 0: the tile's labelled columns; form 1: those sorted by group = perm
+        for (int t = 0; t < n_tiles; ++t) {
+            tile_lists[t] = make_int2(static_cast<int>(list_a.size()), static_cast<int>(list_b.size()));
+            const int64_t c0 = static_cast<int64_t>(t) * kGsTile;
+            const int tw = static_cast<int>(std::min<int64_t>(kGsTile, N - c0));
+            seq.clear();
+            for (int c = 0; c < tw; ++c) if (group[c0 + c] >= 0) seq.push_back(static_cast<unsigned short>(c));
+            if (form) {
+                std::stable_sort(seq.begin(), seq.end(), [&](unsigned short x, unsigned short y) { return group[c0 + x] < group[c0 + y]; });
+                std::copy(seq.begin(), seq.end(), perm.begin() + static_cast<size_t>(t) * kGsTile);
+            }
+            const int a0 = static_cast<int>(list_a.size());
+            for (size_t s = 0; s < seq.size();) {       // one group: its pieces, then its entry of list B
+                const int g = group[c0 + seq[s]];
+                const int first_piece = static_cast<int>(list_a.size()) - a0;
+                size_t e = s;
+                while (e < seq.size() && group[c0 + seq[e]] == g && (form || e == s || seq[e] == seq[e - 1] + 1)) ++e;
+                for (size_t q = s; q < e; q += kGsPiece)
+                    list_a.push_back((form ? static_cast<int>(q) : static_cast<int>(seq[q])) | static_cast<int>(std::min<size_t>(kGsPiece, e - q)) << 16);
+                list_b.push_back(make_int2(first_piece | (static_cast<int>(list_a.size()) - a0 - first_piece) << 16, g));
+                s = e;
+            }
+        }
+        tile_lists[n_tiles] = make_int2(static_cast<int>(list_a.size()), static_cast<int>(list_b.size()));
+    }
+    // enough workgroups to fill the device several times over: column slabs
+    const int64_t want_wgs = 24LL * std::max(p->n_cus, 1);
+    const int slabs_want = static_cast<int>(std::min<int64_t>(n_tiles, std::max<int64_t>(1, (want_wgs + n_blocks - 1) / n_blocks)));
+    const int tiles_per_slab = (n_tiles + slabs_want - 1) / slabs_want;
+    const int n_slabs = (n_tiles + tiles_per_slab - 1) / tiles_per_slab;
+    const int64_t n_part = n_blocks * n_slabs;
+    if (n_part > INT32_MAX / 2) return fail(GENPHI_ERR_ARG, "genphi_result_group_sums: too many row blocks");
+    // levels of the row reduction: at most kGsFan rows of one group per output row; the last level has one row per group
+    std::vector<std::vector<int>> level_beg;
+    std::vector<int64_t> level_rows;
+    for (int g = 0; g < G; ++g) cnt[g] *= n_slabs;
+    for (;;) {
+        const bool last = *std::max_element(cnt.begin(), cnt.end()) <= kGsFan;
+        std::vector<int> beg(1, 0);
+        int at = 0;
+        for (int g = 0; g < G; ++g) {
+            const int n = cnt[g], outs = last ? 1 : (n + kGsFan - 1) / kGsFan;
+            for (int o = 0; o < outs; ++o) {
+                at += last ? n : std::min(kGsFan, n - o * kGsFan);
+                beg.push_back(at);
+            }
+            cnt[g] = outs;
+        }
+        level_rows.push_back(static_cast<int64_t>(beg.size()) - 1);
+        level_beg.push_back(std::move(beg));
+        if (last) break;
+    }
+    // one blob of tables, then part and the two buffers of the reduction
+    std::vector<char> blob;
+    auto put = [&](const void *src, size_t bytes) {
+        const size_t off = blob.size();
+        blob.resize(off + al256(std::max<size_t>(bytes, 1)));
+        if (bytes) std::memcpy(blob.data() + off, src, bytes);
+        return off;
+    };
+    const size_t o_rows = put(rowlist.data(), rowlist.size() * sizeof(int));
+    const size_t o_blocks = put(blocks.data(), blocks.size() * sizeof(int2));
+    const size_t o_tiles = put(tile_lists.data(), tile_lists.size() * sizeof(int2));
+    const size_t o_a = put(list_a.data(), list_a.size() * sizeof(int));
+    const size_t o_b = put(list_b.data(), list_b.size() * sizeof(int2));
+    const size_t o_perm = put(perm.data(), perm.size() * sizeof(unsigned short));
+    std::vector<size_t> o_beg;
+    for (const auto &beg : level_beg) o_beg.push_back(put(beg.data(), beg.size() * sizeof(int)));
+    size_t buf_rows[2] = {0, 0};
+    for (size_t l = 0; l < level_rows.size(); ++l) buf_rows[l & 1] = std::max(buf_rows[l & 1], static_cast<size_t>(level_rows[l]));
+    const size_t o_part = blob.size();
+    const size_t o_buf0 = o_part + al256(static_cast<size_t>(n_part) * W * sizeof(double));
+    const size_t o_buf1 = o_buf0 + al256(buf_rows[0] * W * sizeof(double));
+    const size_t total = o_buf1 + al256(buf_rows[1] * W * sizeof(double));
+
+    HIP_TRY(hipSetDevice(p->device));
+    int rc = ensure_scratch(p, total);
+    if (rc) return rc;
+    char *d = p->scratch;
+    hipError_t e = hipMemcpyAsync(d, blob.data(), blob.size(), hipMemcpyHostToDevice, p->stream);
+    std::vector<double> tab(static_cast<size_t>(G) * W);
+    if (e == hipSuccess) {
+        double *part = reinterpret_cast<double *>(d + o_part);
+        double *buf[2] = {reinterpret_cast<double *>(d + o_buf0), reinterpret_cast<double *>(d + o_buf1)};
+        auto launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(n_part)), dim3(256), 0, p->stream, p->result,
+                               static_cast<long long>(p->res_ld), static_cast<int>(r0), reinterpret_cast<const int *>(d + o_rows),
+                               reinterpret_cast<const int2 *>(d + o_blocks), reinterpret_cast<const int2 *>(d + o_tiles),
+                               reinterpret_cast<const int *>(d + o_a), reinterpret_cast<const int2 *>(d + o_b),
+                               reinterpret_cast<const unsigned short *>(d + o_perm), n_tiles, tiles_per_slab, n_slabs, G, part);
+        };
+        if (form) launch(group_tiles_kernel<true>);
+        else launch(group_tiles_kernel<false>);
+        e = hipGetLastError();
+        const double *in = part;
+        for (size_t l = 0; l < level_rows.size() && e == hipSuccess; ++l) {
+            hipLaunchKernelGGL(group_rows_reduce_kernel, dim3(static_cast<unsigned>(level_rows[l]), static_cast<unsigned>((W + 255) / 256)),
+                               dim3(256), 0, p->stream, in, buf[l & 1], reinterpret_cast<const int *>(d + o_beg[l]), W);
+            e = hipGetLastError();
+            in = buf[l & 1];
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(tab.data(), in, tab.size() * sizeof(double), hipMemcpyDeviceToHost, p->stream);
+    }
+    const hipError_t es = hipStreamSynchronize(p->stream);            // (the blob is read until here)
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return fail(GENPHI_ERR_DEVICE, std::string("genphi_result_group_sums: ") + hipGetErrorString(e));
+    deliver(tab.data());
     return GENPHI_OK;
 }
 

@@ -201,6 +201,47 @@ function f(pedigree::GenLib.Pedigree, IDs::Vector{Int}; device::Integer = -1)
 end
 
 """
+    phiMeanGroups(pedigree::GenLib.Pedigree, groups::Dict{Int, String}, probandIDs::Vector{Int} = collect(keys(groups));
+                  device::Integer = -1)
+
+Mean kinship within and between groups of probands (e.g. `GenLib._pop(GenLib.pop140)`): `(names, sizes, mean)` with the
+names sorted and `mean` a `Matrix{Float64}`; `mean[a, a]` is `phiMean` (src/compute.jl:454-459) of the block of group `a`,
+`mean[a, b]` the plain mean of the block between `a` and `b`, `NaN` where there is no pair.  The matrix stays on the GPU:
+`genphi_result_group_sums` reduces it there.  Probands that are not in `groups` take part in the sweep but belong to no group.
+"""
+function phiMeanGroups(pedigree::GenLib.Pedigree, groups::Dict{Int, String}, probandIDs::Vector{Int} = collect(keys(groups));
+                       device::Integer = -1)
+    isempty(groups) && throw(ArgumentError("groups is empty"))
+    names = sort(unique(values(groups)))
+    index = Dict(name => Int32(k - 1) for (k, name) in enumerate(names))
+    label(ID) = haskey(groups, ID) ? index[groups[ID]] : Int32(-1)
+    # by (group name, ID), probands in no group last: every group is one run (form 0 of genphi_result_group_sums)
+    ordered = sort(unique(probandIDs), by = ID -> (label(ID) < 0 ? length(names) : Int(label(ID)), ID))
+    labels = Int32[label(ID) for ID in ordered]
+    foreach(ID -> pedigree[ID], ordered)                                    # KeyError on unknown ID
+    G = length(names)
+    plan = create_plan(pedigree, ordered, nothing)
+    sums = Matrix{Float64}(undef, G, G); diagonal = Vector{Float64}(undef, G); sizes = Vector{Int64}(undef, G)
+    try
+        opts = Ref(GenphiOpts(Int32(device), 0, 0, 0, 0, 0))
+        check(ccall((:genphi_compute_device, libgenphi), Cint, (Ptr{Cvoid}, Ptr{GenphiOpts}, Ptr{Cvoid}), plan, opts, C_NULL))
+        GC.@preserve labels sums diagonal sizes check(ccall((:genphi_result_group_sums, libgenphi), Cint,
+            (Ptr{Cvoid}, Int32, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int32}),
+            plan, Int32(G), labels, sums, diagonal, C_NULL, sizes, C_NULL))
+    finally
+        destroy_plan(plan)
+    end
+    # (sums arrives row-major: the transpose of the Julia matrix; all rows are resident, so it is symmetric up to the order of additions)
+    mean = Matrix{Float64}(undef, G, G)
+    for a in 1:G, b in 1:G
+        pairs = a == b ? sizes[a] * (sizes[a] - 1) : sizes[a] * sizes[b]
+        total = a == b ? sums[a, a] - diagonal[a] : sums[a, b]
+        mean[b, a] = pairs > 0 ? total / pairs : NaN
+    end
+    (names = names, sizes = sizes, mean = mean)
+end
+
+"""
     KinshipMatrix, sparse_phi(pedigree, probandIDs = GenLib.pro(pedigree); device = -1)
 
 As `GenLib.sparse_phi` / `GenLib.KinshipMatrix` (src/compute.jl:321-447, :31-46): `ϕ[ID₁, ID₂]`,

@@ -209,6 +209,29 @@ int genphi_phi_pairs(int64_t n_ind, const int64_t *ind, const int64_t *father, c
  * value agrees to Float32 rounding, exactly when the sums are exact (geneaJi: 0.171875).      */
 int genphi_result_sums(genphi_plan *plan, double *sum_all, double *sum_diag, int64_t *n_rows);
 
+/* The same for sub-populations: the sums of the resident result within and between groups of probands, reduced on the
+ * device in one more pass over the matrix.  What phiMean (src/compute.jl:454-459) gives per population when
+ * the probands carry a population name, as in the reference's pop140.csv (gen._pop, src/GenLib.jl:76-92).
+ *   group[i]          label of proband i (position as in genphi_plan_create, duplicates collapsed): 0 .. n_groups - 1, or
+ *                     -1 = in no group; N entries
+ *   sums[a][b]        Float64 sum of Phi[i][j] over the RESIDENT rows i of group a and all columns j of group b (n_groups x
+ *                     n_groups, row-major; the diagonal entries are included when a == b)
+ *   diag[a]           sum of Phi[i][i] over the resident rows of group a
+ *   rows_in_group[a]  resident rows of group a; cols_in_group[a]: probands of group a
+ *   form              0: every group's probands are one run of the proband order (runs of -1 anywhere); 1: any other labelling.
+ *                     Both forms give the same sums up to the order of the additions; form 1 reads a column order from a table.
+ * Any output pointer may be NULL.  Mean kinship within group a = (sums[a][a] - diag[a]) / (n_a (n_a - 1)), between a and b =
+ * sums[a][b] / (n_a n_b); with row shards the ranks add all four outputs.  The summation order depends on the plan, the
+ * resident rows and the labels alone (no floating-point atomics): the same call gives the same bits.  Every term is >= 0, so
+ * an entry is within (n - 1) 2^-53 relative of the exact sum of its n Float32 terms, and exact while the terms are dyadic
+ * numbers of few bits.  Device memory: tables of a few bytes per proband and partial sums of n_groups + 1 doubles for
+ * fewer than 2 (rows / 64 + n_groups) + 24 x compute units row blocks, in the plan's scratch block, kept between calls.
+ * GENPHI_ERR_ARG: n_groups outside [1, GENPHI_GROUP_SUMS_MAX_GROUPS], a label outside [-1, n_groups), a Float64 result
+ * (GENPHI_FLAG_STORAGE_F64); GENPHI_ERR_DEVICE: no resident result.                                                        */
+#define GENPHI_GROUP_SUMS_MAX_GROUPS 4096
+int genphi_result_group_sums(genphi_plan *plan, int32_t n_groups, const int32_t *group, double *sums, double *diag,
+                             int64_t *rows_in_group, int64_t *cols_in_group, int32_t *form);
+
 /* Point lookups in the resident result without moving the matrix: out[k] = Phi[rows[k], cols[k]]
  * (0-based positions in proband order, duplicates collapsed as in genphi_plan_create; rows must
  * lie in the resident row range).  This is what gen.f(pedigree, IDs) (src/compute.jl:500-511)
