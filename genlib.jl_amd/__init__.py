@@ -20,6 +20,7 @@ meaning, printed lines and error behaviour as the reference:
                                            # gen.findFounders, gen.ancestor (csrc/dist.hip + csrc/loader.cpp)
     gen.completeness(ped); gen.depth(ped)  # src/describe.jl:73-125, :43-66: ascents by generation (csrc/completeness.hip);
                                            # gen.nomen, gen.nowomen, gen.noind, ped.show() (src/describe.jl:6-36, src/create.jl:76-111)
+    gen.implex(ped)                        # GENLIB's gen.implex: distinct ancestors by generation (csrc/implex.hip)
 
 All kinship arithmetic runs in hand-written HIP kernels behind the C-ABI in
 include/genphi.h (csrc/genphi_hip.hip); there is no CPU fallback.
@@ -30,7 +31,7 @@ from collections import OrderedDict
 import numpy as np
 
 from . import _capi
-from ._capi import PhiPlan, KinshipMatrix, GCPlan, OccPlan, RecPlan, DistPlan, CompletenessPlan, GenphiDeviceError, GenphiLibraryMissing  # noqa: F401
+from ._capi import PhiPlan, KinshipMatrix, GCPlan, OccPlan, RecPlan, DistPlan, CompletenessPlan, ImplexPlan, GenphiDeviceError, GenphiLibraryMissing  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
@@ -452,6 +453,50 @@ def completeness(pedigree, pro=None, genNo=None, type="MEAN", device=None):
             out = (h.totals().astype(np.float64) / np.ldexp(1.0, np.arange(G)) * 100.0 / len(probands)).reshape(-1, 1)
         else:
             out = (np.cumsum(h.result_to_host(), axis=0)[-1] / len(probands)).reshape(-1, 1)     # a sequential sum, proband order
+        return out if rows is None else out[rows, :]
+    finally:
+        h.close()
+
+
+def implex(pedigree, pro=None, genNo=None, type="MEAN", onlyNewAnc=False, device=None):
+    """gen.implex(pedigree, pro = pro(pedigree); genNo = Int[], type = "MEAN", onlyNewAnc = false), GENLIB's gen.implex (the
+    reference has no form of it): the genealogical implex of the probands per generation (rows; the probands are generation 0), in
+    percent: the DISTINCT ancestors of generation g out of 2^g, where gen.completeness counts them with multiplicity; the gap
+    between the two curves is the pedigree collapse.  With A_0(p) = {p} and A_{g+1}(p) = the known parents of the members of
+    A_g(p), the count is |A_g(p)| (an individual can be in several A_g(p): generations overlap); onlyNewAnc=True counts
+    |A_g \\ (A_0 u .. u A_{g-1})|, every individual in the generation of its shortest ascent only.  type = "IND": a float64 array of
+    shape (G, len(pro)), one column per proband, G = 1 + the longest ascent of any listed proband (as gen.completeness);
+    type = "MEAN" (the default): the mean over the probands, (G, 1).  genNo: the generations to return, in the order given,
+    repeats allowed.
+
+    The counts come from a level-synchronous frontier over bit rows on the GPU (csrc/implex.hip): rows are individuals, columns
+    the listed probands as bits, and generation g ORs the rows of an individual's children of generation g - 1.  "IND" is
+    converted on the device by count / 2^g * 100 in that order and is a transposed view of the (len(pro), G) row-major result,
+    not a copy.  "MEAN" is float(totals[g]) / 2^g * 100 / len(pro) from the totals reduced on the device; totals[g] <=
+    len(pro) x the number of individuals, so 25 totals[g] < 2^53, everything before the division is exact and "MEAN" is the
+    correctly rounded exact rational mean.
+
+    Every proband gets its column (with or without children, each time it is listed).  KeyError for an unknown proband; ValueError
+    for an empty pro, for another type (GENLIB's "ALL" included) and for more than 62 generations above the probands; IndexError
+    for a generation outside 0 .. G - 1.  Each call plans, sweeps and frees its own handle."""
+    if type not in ("IND", "MEAN"):
+        raise ValueError('type must be "IND" or "MEAN", not %r' % (type,))
+    probands = globals()["pro"](pedigree) if pro is None else np.ascontiguousarray(pro, dtype=np.int64)
+    if len(probands) == 0:
+        raise ValueError("gen.implex needs at least one proband")
+    h = ImplexPlan(pedigree.ind, pedigree.father, pedigree.mother, probands, only_new=bool(onlyNewAnc))
+    try:
+        G = h.generations
+        rows = None
+        if genNo is not None and len(genNo):
+            rows = np.asarray(genNo, dtype=np.int64).ravel()
+            if np.any((rows < 0) | (rows >= G)):
+                raise IndexError("generation %d is outside 0 .. %d" % (int(rows[(rows < 0) | (rows >= G)][0]), G - 1))
+        h.compute(device=device)
+        if type == "IND":
+            out = h.result_to_host().T
+        else:
+            out = (h.totals().astype(np.float64) / np.ldexp(1.0, np.arange(G)) * 100.0 / len(probands)).reshape(-1, 1)
         return out if rows is None else out[rows, :]
     finally:
         h.close()

@@ -24,6 +24,7 @@ GENPHI_FLAG_NO_GRAPH = 1
 GENPHI_FLAG_STORAGE_F64 = 2
 GENPHI_FLAG_NO_SPARSE = 4
 GENPHI_GROUP_SUMS_MAX_GROUPS = 4096
+GENPHI_IMPLEX_FLAG_ONLY_NEW = 1
 
 _I64P = C.POINTER(C.c_int64)
 _F32P = C.POINTER(C.c_float)
@@ -63,6 +64,8 @@ EXPORTED_SYMBOLS = [
     "genphi_ancestors", "genphi_mrca_filter",
     "genphi_comp_create", "genphi_comp_compute", "genphi_comp_generations", "genphi_comp_result_device", "genphi_comp_result_to_host",
     "genphi_comp_counts_to_host", "genphi_comp_totals", "genphi_comp_stats", "genphi_comp_destroy", "genphi_genealogy_depth",
+    "genphi_implex_create", "genphi_implex_compute", "genphi_implex_generations", "genphi_implex_frontier_rows", "genphi_implex_counts",
+    "genphi_implex_result_to_host", "genphi_implex_totals", "genphi_implex_stats", "genphi_implex_destroy",
 ]
 
 _lib = None
@@ -251,6 +254,22 @@ def lib():
         L.genphi_comp_destroy.restype = None
         L.genphi_genealogy_depth.argtypes = [C.c_int64, _I64P, _I64P, _I64P, _I64P, C.c_int32]
         L.genphi_genealogy_depth.restype = C.c_int
+        L.genphi_implex_create.argtypes = [C.c_int64, _I64P, _I64P, _I64P, C.c_int64, _I64P, C.c_int32, C.POINTER(C.c_void_p)]
+        L.genphi_implex_create.restype = C.c_int
+        L.genphi_implex_compute.argtypes = [C.c_void_p, C.c_int32]
+        L.genphi_implex_compute.restype = C.c_int
+        L.genphi_implex_generations.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+        L.genphi_implex_generations.restype = C.c_int
+        for name in ("genphi_implex_frontier_rows", "genphi_implex_counts", "genphi_implex_totals"):
+            fn = getattr(L, name)
+            fn.argtypes, fn.restype = [C.c_void_p, _I64P], C.c_int
+        L.genphi_implex_result_to_host.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+        L.genphi_implex_result_to_host.restype = C.c_int
+        L.genphi_implex_stats.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                          _I64P, C.POINTER(C.c_int32), _I64P]
+        L.genphi_implex_stats.restype = C.c_int
+        L.genphi_implex_destroy.argtypes = [C.c_void_p]
+        L.genphi_implex_destroy.restype = None
         for kind in ("occ", "rec", "dist"):
             fn = getattr(L, "genphi_%s_compute" % kind)
             fn.argtypes, fn.restype = [C.c_void_p, C.c_int32], C.c_int
@@ -1111,6 +1130,78 @@ class CompletenessPlan:
         if rc:
             _raise(rc)
         return {"sweep_ms": ms.value, "algorithmic_bytes": ab.value, "peak_slots": ps.value, "row_entries": re_.value, "launches": nl.value}
+
+
+class ImplexPlan:
+    """gen.implex' handle (include/genphi.h, genphi_implex_*): planned on the host at construction (KeyError on an unknown proband,
+    ValueError for more than GENPHI_IMPLEX_MAX_GENERATIONS generations above the probands; no GPU needed), swept on the GPU by
+    compute().  only_new: an individual counts in the generation of its shortest ascent only (GENLIB's onlyNewAnc)."""
+
+    def __init__(self, ind, father, mother, pro_ids, only_new=False):
+        L = lib()
+        ind, father, mother, pro_ids = _i64(ind), _i64(father), _i64(mother), _i64(pro_ids)
+        h = C.c_void_p()
+        rc = L.genphi_implex_create(len(ind), ind.ctypes.data_as(_I64P), father.ctypes.data_as(_I64P), mother.ctypes.data_as(_I64P),
+                                    len(pro_ids), pro_ids.ctypes.data_as(_I64P), GENPHI_IMPLEX_FLAG_ONLY_NEW if only_new else 0, C.byref(h))
+        if rc:
+            _raise(rc)
+        self._h = h
+        self.only_new = bool(only_new)
+        g = C.c_int32()
+        rc = L.genphi_implex_generations(h, C.byref(g))
+        if rc:
+            _raise(rc)
+        self.generations = int(g.value)          # 1 + the longest ascent of any listed proband
+        self.shape = (len(pro_ids), self.generations)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().genphi_implex_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+    def _i64_out(self, fn, shape):
+        out = np.empty(shape, dtype=np.int64)
+        rc = fn(self._h, out.ctypes.data_as(_I64P))
+        if rc:
+            _raise(rc)
+        return out
+
+    def rows_per_generation(self):
+        """|U_g| per generation: the individuals at exactly g meioses from any listed proband (host only)."""
+        return self._i64_out(lib().genphi_implex_frontier_rows, self.generations)
+
+    def compute(self, device=None):
+        rc = lib().genphi_implex_compute(self._h, -1 if device is None else int(device))
+        if rc:
+            _raise(rc)
+
+    def counts(self):
+        """The (n_pro, generations) int64 counts of distinct ancestors."""
+        return self._i64_out(lib().genphi_implex_counts, self.shape)
+
+    def result_to_host(self):
+        """The (n_pro, generations) float64 result (rows = probands): the finished percentages."""
+        out = np.empty(self.shape, dtype=np.float64)
+        rc = lib().genphi_implex_result_to_host(self._h, out.ctypes.data_as(C.POINTER(C.c_double)))
+        if rc:
+            _raise(rc)
+        return out
+
+    def totals(self):
+        """The int64 counts per generation, summed over the listed probands on the device."""
+        return self._i64_out(lib().genphi_implex_totals, self.generations)
+
+    def stats(self):
+        """dict(sweep_ms, algorithmic_bytes, generations, panel_cols, panels, lanes_per_row, peak_rows) of the last compute()."""
+        ms, ab, g, pc, np_, lpr, pr = C.c_double(), C.c_double(), C.c_int32(), C.c_int32(), C.c_int64(), C.c_int32(), C.c_int64()
+        rc = lib().genphi_implex_stats(self._h, C.byref(ms), C.byref(ab), C.byref(g), C.byref(pc), C.byref(np_), C.byref(lpr), C.byref(pr))
+        if rc:
+            _raise(rc)
+        return {"sweep_ms": ms.value, "algorithmic_bytes": ab.value, "generations": g.value, "panel_cols": pc.value, "panels": np_.value,
+                "lanes_per_row": lpr.value, "peak_rows": pr.value}
 
 
 def genealogy_depth(ind, father, mother, leaves_only=False):

@@ -447,6 +447,45 @@ function completeness(pedigree::GenLib.Pedigree, pro::Vector{Int} = GenLib.pro(p
 end
 
 """
+    implex(pedigree::GenLib.Pedigree, pro = GenLib.pro(pedigree); genNo = Int[], type = "MEAN", onlyNewAnc = false, device = -1)
+
+Genealogical implex of `pro` per generation (rows; the probands are generation 0), in percent, as GENLIB's `gen.implex`
+(GenLib.jl has no form of it): the DISTINCT ancestors at exactly `g` meioses out of `2^g`, where `completeness` counts them with
+multiplicity; `onlyNewAnc = true` counts every individual in the generation of its shortest ascent only.  A level-synchronous
+frontier over bit rows on the GPU (csrc/implex.hip).  `type = "IND"`: the library's `pro x generations` row-major result is the
+memory of a `Matrix{Float64}(undef, generations, length(pro))`: no transpose.  `type = "MEAN"`: from the per-generation totals
+reduced on the GPU, `totals[g] / 2^g * 100 / length(pro)`, the correctly rounded exact mean (include/genphi.h).
+"""
+function implex(pedigree::GenLib.Pedigree, pro::Vector{Int} = GenLib.pro(pedigree);
+                genNo::Vector{Int} = Int[], type::String = "MEAN", onlyNewAnc::Bool = false, device::Integer = -1)
+    type == "IND" || type == "MEAN" || throw(ArgumentError("type must be \"IND\" or \"MEAN\""))
+    isempty(pro) && throw(ArgumentError("reducing over an empty collection is not allowed"))
+    ind, father, mother, _ = flatten(pedigree)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve ind father mother pro check(ccall((:genphi_implex_create, libgenphi), Cint,
+        (Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Int64, Ptr{Int64}, Int32, Ptr{Ptr{Cvoid}}),
+        length(ind), ind, father, mother, length(pro), pro, Int32(onlyNewAnc ? 1 : 0), h))
+    try
+        generations = Ref{Int32}(0)
+        check(ccall((:genphi_implex_generations, libgenphi), Cint, (Ptr{Cvoid}, Ptr{Int32}), h[], generations))
+        G = Int(generations[])
+        all(g -> 0 <= g < G, genNo) || throw(BoundsError(1:G, genNo .+ 1))
+        check(ccall((:genphi_implex_compute, libgenphi), Cint, (Ptr{Cvoid}, Int32), h[], Int32(device)))
+        if type == "MEAN"
+            totals = Vector{Int64}(undef, G)
+            GC.@preserve totals check(ccall((:genphi_implex_totals, libgenphi), Cint, (Ptr{Cvoid}, Ptr{Int64}), h[], totals))
+            matrix = reshape([totals[g + 1] / 2.0^g * 100 / length(pro) for g in 0:G-1], G, 1)
+        else
+            matrix = Matrix{Float64}(undef, G, length(pro))
+            GC.@preserve matrix check(ccall((:genphi_implex_result_to_host, libgenphi), Cint, (Ptr{Cvoid}, Ptr{Float64}), h[], matrix))
+        end
+        return isempty(genNo) ? matrix : matrix[genNo .+ 1, :]
+    finally
+        ccall((:genphi_implex_destroy, libgenphi), Cvoid, (Ptr{Cvoid},), h[])
+    end
+end
+
+"""
     depth(pedigree::GenLib.Pedigree)
 
 The number of generations of the pedigree, as `GenLib.depth` (src/describe.jl:43-66): one linear pass on the host

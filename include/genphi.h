@@ -564,6 +564,49 @@ void genphi_comp_destroy(genphi_comp *h);
 int genphi_genealogy_depth(int64_t n_ind, const int64_t *ind, const int64_t *father, const int64_t *mother, int64_t *depth,
                            int32_t leaves_only);
 
+/* ---- gen.implex: distinct ancestors by generation (csrc/implex.hip, csrc/implex.cpp) ---------------------------------------------
+ * GENLIB's gen.implex; the reference has no form of it, so this text is the definition.  A_0(p) = {p}, A_{g+1}(p) = the known
+ * parents of the members of A_g(p) (an individual can be in several A_g(p): generations overlap).
+ *   counts[i][g] = |A_g(pro_ids[i])|, the DISTINCT ancestors at exactly g meioses, where gen.completeness counts them with
+ *                  multiplicity (counts <= the counts of genphi_comp_*, equal while no ancestor repeats);
+ *   GENPHI_IMPLEX_FLAG_ONLY_NEW: counts[i][g] = |A_g \ (A_0 u .. u A_{g-1})|, the individuals whose SHORTEST ascent from the
+ *                  proband has g meioses (a breadth-first search); their sum over g >= 1 is the number of distinct ancestors.
+ * G = 1 + the longest ascent of any listed proband, the same G as genphi_comp_generations for the same arguments.  Rules as for
+ * comp: every proband gets its row, with or without children, each time it is listed; an unknown ID -> GENPHI_ERR_UNKNOWN_ID;
+ * n_pro = 0: G = 0 and an empty result; more than GENPHI_IMPLEX_MAX_GENERATIONS generations above the probands -> GENPHI_ERR_ARG.
+ * Method: rows are individuals, columns the listed probands as bits (64 per word).  The host plan lists per generation the union
+ * frontier U_g (the individuals at exactly g meioses from ANY listed proband) and per row of U_g its children in U_{g-1}; a step
+ * ORs the children's rows of the previous buffer into the row, a count kernel adds up the set bits per column.  Probands are
+ * swept in panels of a multiple of 64 columns.  Everything is integer: the same bits on every run.  The percentages are
+ * (double)count / 2^g * 100.0 in that order (generation 0 is 100.0, generations beyond a proband's depth 0.0).  A total is at most
+ * n_pro n_ind < 2^62.  MEAN from the totals: (double)totals[g] / 2^g * 100.0 / n_pro; 25 totals[g] < 2^53 always holds here, so
+ * everything before the division is exact and the mean is the correctly rounded exact rational.
+ *   create            host only (no GPU): checks IDs, pedigree order and depth; builds U_g and the child lists, O(sum |U_g|)
+ *   generations       G; valid after create
+ *   frontier_rows     out: G Int64, |U_g|; host only, valid after create
+ *   compute           the sweep on `device` (-1 = current); counts and percentages stay resident; GENPHI_ERR_ALLOC before any
+ *                     launch when the frontier rows of even a 64-column panel and the result do not fit
+ *   counts            out: n_pro x G Int64, row-major
+ *   result_to_host    out: n_pro x G Float64, row-major: the finished percentages
+ *   totals            out: G Int64: the column sums of the counts, reduced on the device (each listed occurrence counts)
+ *   stats             device time of the last sweep (HIP events); its algorithmic bytes, sum over g of (|U_g| + child list
+ *                     entries of U_g) x words of a panel row x 8, over the panels; G; the columns of a panel; the panels; the
+ *                     lanes per row of the step kernel; the largest |U_g|                                                       */
+#define GENPHI_IMPLEX_MAX_GENERATIONS 62
+#define GENPHI_IMPLEX_FLAG_ONLY_NEW 1   /* onlyNewAnc: count an individual in the generation of its shortest ascent only */
+typedef struct genphi_implex genphi_implex;
+int genphi_implex_create(int64_t n_ind, const int64_t *ind, const int64_t *father, const int64_t *mother,
+                         int64_t n_pro, const int64_t *pro_ids, int32_t flags, genphi_implex **out);
+int genphi_implex_compute(genphi_implex *h, int32_t device);
+int genphi_implex_generations(const genphi_implex *h, int32_t *generations);
+int genphi_implex_frontier_rows(const genphi_implex *h, int64_t *out);
+int genphi_implex_counts(genphi_implex *h, int64_t *out);
+int genphi_implex_result_to_host(genphi_implex *h, double *out);
+int genphi_implex_totals(genphi_implex *h, int64_t *out);
+int genphi_implex_stats(const genphi_implex *h, double *sweep_ms, double *algorithmic_bytes, int32_t *generations, int32_t *panel_cols,
+                        int64_t *panels, int32_t *lanes_per_row, int64_t *peak_rows);
+void genphi_implex_destroy(genphi_implex *h);
+
 /* Frees host and device memory of the plan (NULL is allowed). */
 void genphi_plan_destroy(genphi_plan *plan);
 
