@@ -834,374 +834,245 @@ class PanelPlan:
         return out
 
 
-class GCPlan:
-    """gen.gc's handle (include/genphi.h, genphi_gc_*): planned on the host at construction (KeyError on an unknown proband or
-    ancestor, no GPU needed), swept on the GPU by compute()."""
+class _SweepPlan:
+    """What the handles of the ancestor sweeps share: the handle, its create call, compute and destroy.  A subclass names its C
+    functions by _prefix (genphi_<prefix>_create, ...)."""
 
-    def __init__(self, ind, father, mother, pro_ids, anc_ids):
-        L = lib()
-        ind, father, mother, pro_ids, anc_ids = _i64(ind), _i64(father), _i64(mother), _i64(pro_ids), _i64(anc_ids)
+    _prefix = None
+    _h = None
+
+    def _fn(self, name):
+        return getattr(lib(), "genphi_%s_%s" % (self._prefix, name))
+
+    def _create(self, ind, father, mother, pro_ids, anc_ids=None, flags=None):
+        """genphi_<prefix>_create(n_ind, ind, father, mother, n_pro, pro[, n_anc, anc][, flags], &handle); returns the lengths of
+        the ID lists."""
+        fn = self._fn("create")
+        ind, father, mother = _i64(ind), _i64(father), _i64(mother)
+        args = [len(ind), ind.ctypes.data_as(_I64P), father.ctypes.data_as(_I64P), mother.ctypes.data_as(_I64P)]
+        lists = [_i64(ids) for ids in (pro_ids, anc_ids) if ids is not None]
+        for ids in lists:
+            args += [len(ids), ids.ctypes.data_as(_I64P)]
+        if flags is not None:
+            args.append(flags)
         h = C.c_void_p()
-        rc = L.genphi_gc_create(len(ind), ind.ctypes.data_as(_I64P), father.ctypes.data_as(_I64P), mother.ctypes.data_as(_I64P),
-                                len(pro_ids), pro_ids.ctypes.data_as(_I64P), len(anc_ids), anc_ids.ctypes.data_as(_I64P), C.byref(h))
+        rc = fn(*args, C.byref(h))
         if rc:
             _raise(rc)
         self._h = h
-        self.shape = (len(pro_ids), len(anc_ids))
+        return [len(ids) for ids in lists]
 
     def close(self):
-        if getattr(self, "_h", None):
-            lib().genphi_gc_destroy(self._h)
+        if self._h:
+            self._fn("destroy")(self._h)
             self._h = None
 
     def __del__(self):
         self.close()
 
     def compute(self, device=None):
-        rc = lib().genphi_gc_compute(self._h, -1 if device is None else int(device))
+        rc = self._fn("compute")(self._h, -1 if device is None else int(device))
         if rc:
             _raise(rc)
+
+    def _call(self, name, *args):
+        rc = self._fn(name)(self._h, *args)
+        if rc:
+            _raise(rc)
+
+    def _out(self, name, shape, dtype, ctype):
+        """An array of shape and dtype filled by genphi_<prefix>_<name>(handle, out)."""
+        out = np.empty(shape, dtype=dtype)
+        self._call(name, out.ctypes.data_as(C.POINTER(ctype)))
+        return out
+
+    def _result_device(self):
+        p, ld = C.c_void_p(), C.c_int64()
+        self._call("result_device", C.byref(p), C.byref(ld))
+        return p.value, ld.value
+
+    def _stats(self, **fields):
+        """dict(name = value) of genphi_<prefix>_stats(handle, &field, ...); fields: name = ctypes type, in the call's order."""
+        vals = [t() for t in fields.values()]
+        self._call("stats", *[C.byref(v) for v in vals])
+        return {k: v.value for k, v in zip(fields, vals)}
+
+    def _sweep_stats(self):
+        return self._stats(sweep_ms=C.c_double, algorithmic_bytes=C.c_double, peak_slots=C.c_int64, panel_cols=C.c_int32,
+                           row_bits=C.c_int32, launches=C.c_int64)
+
+
+class GCPlan(_SweepPlan):
+    """gen.gc's handle (include/genphi.h, genphi_gc_*): planned on the host at construction (KeyError on an unknown proband or
+    ancestor, no GPU needed), swept on the GPU by compute()."""
+
+    _prefix = "gc"
+
+    def __init__(self, ind, father, mother, pro_ids, anc_ids):
+        self.shape = tuple(self._create(ind, father, mother, pro_ids, anc_ids))
 
     def result_device(self):
         """(device pointer, row pitch in floats) of the resident result."""
-        p, ld = C.c_void_p(), C.c_int64()
-        rc = lib().genphi_gc_result_device(self._h, C.byref(p), C.byref(ld))
-        if rc:
-            _raise(rc)
-        return p.value, ld.value
+        return self._result_device()
 
     def result_to_host(self):
-        out = np.empty(self.shape, dtype=np.float32)
-        rc = lib().genphi_gc_result_to_host(self._h, out.ctypes.data_as(_F32P))
-        if rc:
-            _raise(rc)
-        return out
+        return self._out("result_to_host", self.shape, np.float32, C.c_float)
 
     def stats(self):
         """dict(sweep_ms, algorithmic_bytes, peak_slots, panel_cols) of the last compute()."""
-        ms, ab, ps, pc = C.c_double(), C.c_double(), C.c_int64(), C.c_int32()
-        rc = lib().genphi_gc_stats(self._h, C.byref(ms), C.byref(ab), C.byref(ps), C.byref(pc))
-        if rc:
-            _raise(rc)
-        return {"sweep_ms": ms.value, "algorithmic_bytes": ab.value, "peak_slots": ps.value, "panel_cols": pc.value}
+        return self._stats(sweep_ms=C.c_double, algorithmic_bytes=C.c_double, peak_slots=C.c_int64, panel_cols=C.c_int32)
 
 
 GENPHI_OCC_TOTAL_ONLY = 1
 GENPHI_OCC_ROWS64 = 2
 
 
-def _sweep_stats(fn, h):
-    ms, ab, ps, pc, rb, nl = C.c_double(), C.c_double(), C.c_int64(), C.c_int32(), C.c_int32(), C.c_int64()
-    rc = fn(h, C.byref(ms), C.byref(ab), C.byref(ps), C.byref(pc), C.byref(rb), C.byref(nl))
-    if rc:
-        _raise(rc)
-    return {"sweep_ms": ms.value, "algorithmic_bytes": ab.value, "peak_slots": ps.value, "panel_cols": pc.value,
-            "row_bits": rb.value, "launches": nl.value}
-
-
-class OccPlan:
+class OccPlan(_SweepPlan):
     """gen.occ's handle (include/genphi.h, genphi_occ_*): planned on the host at construction (KeyError on an unknown proband or
     ancestor, no GPU needed), swept on the GPU by compute().  total_only: the handle reduces the last step into the n_anc
     totals on the device and holds no n_pro x n_anc result; rows64: 64-bit slot rows even where 32-bit rows are exact."""
 
+    _prefix = "occ"
+
     def __init__(self, ind, father, mother, pro_ids, anc_ids, total_only=False, rows64=False):
-        L = lib()
-        ind, father, mother, pro_ids, anc_ids = _i64(ind), _i64(father), _i64(mother), _i64(pro_ids), _i64(anc_ids)
-        h = C.c_void_p()
-        flags = (GENPHI_OCC_TOTAL_ONLY if total_only else 0) | (GENPHI_OCC_ROWS64 if rows64 else 0)
-        rc = L.genphi_occ_create(len(ind), ind.ctypes.data_as(_I64P), father.ctypes.data_as(_I64P), mother.ctypes.data_as(_I64P),
-                                 len(pro_ids), pro_ids.ctypes.data_as(_I64P), len(anc_ids), anc_ids.ctypes.data_as(_I64P), flags, C.byref(h))
-        if rc:
-            _raise(rc)
-        self._h = h
+        self.shape = tuple(self._create(ind, father, mother, pro_ids, anc_ids,
+                                        flags=(GENPHI_OCC_TOTAL_ONLY if total_only else 0) | (GENPHI_OCC_ROWS64 if rows64 else 0)))
         self.total_only = bool(total_only)
-        self.shape = (len(pro_ids), len(anc_ids))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().genphi_occ_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        self.close()
-
-    def compute(self, device=None):
-        rc = lib().genphi_occ_compute(self._h, -1 if device is None else int(device))
-        if rc:
-            _raise(rc)
 
     def result_device(self):
         """(device pointer, row pitch in Int64 entries) of the resident result."""
-        p, ld = C.c_void_p(), C.c_int64()
-        rc = lib().genphi_occ_result_device(self._h, C.byref(p), C.byref(ld))
-        if rc:
-            _raise(rc)
-        return p.value, ld.value
+        return self._result_device()
 
     def result_to_host(self):
         """The n_pro x n_anc int64 result (rows = probands)."""
-        out = np.empty(self.shape, dtype=np.int64)
-        rc = lib().genphi_occ_result_to_host(self._h, out.ctypes.data_as(_I64P))
-        if rc:
-            _raise(rc)
-        return out
+        return self._out("result_to_host", self.shape, np.int64, C.c_int64)
 
     def totals(self):
         """The n_anc int64 totals over the probands (on a handle with a full result: its column sums, taken on the device)."""
-        out = np.empty(self.shape[1], dtype=np.int64)
-        rc = lib().genphi_occ_totals(self._h, out.ctypes.data_as(_I64P))
-        if rc:
-            _raise(rc)
-        return out
+        return self._out("totals", self.shape[1], np.int64, C.c_int64)
 
     def stats(self):
         """dict(sweep_ms, algorithmic_bytes, peak_slots, panel_cols, row_bits, launches) of the last compute()."""
-        return _sweep_stats(lib().genphi_occ_stats, self._h)
+        return self._sweep_stats()
 
 
-class RecPlan:
+class RecPlan(_SweepPlan):
     """gen.rec's handle (include/genphi.h, genphi_rec_*): planned on the host at construction (KeyError on an unknown ancestor;
     unknown proband IDs are ignored), swept and counted on the GPU by compute()."""
 
+    _prefix = "rec"
+
     def __init__(self, ind, father, mother, pro_ids, anc_ids):
-        L = lib()
-        ind, father, mother, pro_ids, anc_ids = _i64(ind), _i64(father), _i64(mother), _i64(pro_ids), _i64(anc_ids)
-        h = C.c_void_p()
-        rc = L.genphi_rec_create(len(ind), ind.ctypes.data_as(_I64P), father.ctypes.data_as(_I64P), mother.ctypes.data_as(_I64P),
-                                 len(pro_ids), pro_ids.ctypes.data_as(_I64P), len(anc_ids), anc_ids.ctypes.data_as(_I64P), C.byref(h))
-        if rc:
-            _raise(rc)
-        self._h = h
-        self.n_anc = len(anc_ids)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().genphi_rec_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        self.close()
-
-    def compute(self, device=None):
-        rc = lib().genphi_rec_compute(self._h, -1 if device is None else int(device))
-        if rc:
-            _raise(rc)
+        self.n_anc = self._create(ind, father, mother, pro_ids, anc_ids)[1]
 
     def result(self):
-        out = np.empty(self.n_anc, dtype=np.int64)
-        rc = lib().genphi_rec_result(self._h, out.ctypes.data_as(_I64P))
-        if rc:
-            _raise(rc)
-        return out
+        return self._out("result", self.n_anc, np.int64, C.c_int64)
 
     def stats(self):
         """dict(sweep_ms, algorithmic_bytes, peak_slots, panel_cols, row_bits, launches) of the last compute()."""
-        return _sweep_stats(lib().genphi_rec_stats, self._h)
+        return self._sweep_stats()
 
 
 GENPHI_DIST_MAX_STEPS = 32767
 
 
-class DistPlan:
+class DistPlan(_SweepPlan):
     """gen.meioses' handle (include/genphi.h, genphi_dist_*): planned on the host at construction (KeyError on an unknown proband or
     ancestor, ValueError for a sweep deeper than GENPHI_DIST_MAX_STEPS; no GPU needed), swept on the GPU by compute()."""
 
+    _prefix = "dist"
+
     def __init__(self, ind, father, mother, pro_ids, anc_ids):
-        L = lib()
-        ind, father, mother, pro_ids, anc_ids = _i64(ind), _i64(father), _i64(mother), _i64(pro_ids), _i64(anc_ids)
-        h = C.c_void_p()
-        rc = L.genphi_dist_create(len(ind), ind.ctypes.data_as(_I64P), father.ctypes.data_as(_I64P), mother.ctypes.data_as(_I64P),
-                                  len(pro_ids), pro_ids.ctypes.data_as(_I64P), len(anc_ids), anc_ids.ctypes.data_as(_I64P), C.byref(h))
-        if rc:
-            _raise(rc)
-        self._h = h
-        self.shape = (len(pro_ids), len(anc_ids))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().genphi_dist_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        self.close()
-
-    def compute(self, device=None):
-        rc = lib().genphi_dist_compute(self._h, -1 if device is None else int(device))
-        if rc:
-            _raise(rc)
+        self.shape = tuple(self._create(ind, father, mother, pro_ids, anc_ids))
 
     def result_device(self):
         """(device pointer, row pitch in Int16 entries: n_anc rounded up to a multiple of 8) of the resident result."""
-        p, ld = C.c_void_p(), C.c_int64()
-        rc = lib().genphi_dist_result_device(self._h, C.byref(p), C.byref(ld))
-        if rc:
-            _raise(rc)
-        return p.value, ld.value
+        return self._result_device()
 
     def result_to_host(self):
         """The n_pro x n_anc int16 result (rows = probands, -1 = not an ancestor)."""
-        out = np.empty(self.shape, dtype=np.int16)
-        rc = lib().genphi_dist_result_to_host(self._h, out.ctypes.data_as(C.POINTER(C.c_int16)))
-        if rc:
-            _raise(rc)
-        return out
+        return self._out("result_to_host", self.shape, np.int16, C.c_int16)
 
     def stats(self):
         """dict(sweep_ms, algorithmic_bytes, peak_slots, panel_cols, row_bits, launches) of the last compute()."""
-        return _sweep_stats(lib().genphi_dist_stats, self._h)
+        return self._sweep_stats()
 
 
 GENPHI_COMP_MAX_GENERATIONS = 62
 GENPHI_COMP_FLAG_TOTALS_ONLY = 1
 
 
-class CompletenessPlan:
+class _GenerationsPlan(_SweepPlan):
+    """The sweeps whose columns are generations: shape = (n_pro, generations)."""
+
+    def _create_generations(self, ind, father, mother, pro_ids, flags):
+        n_pro, = self._create(ind, father, mother, pro_ids, flags=flags)
+        g = C.c_int32()
+        self._call("generations", C.byref(g))
+        self.generations = int(g.value)          # 1 + the longest ascent of any listed proband
+        self.shape = (n_pro, self.generations)
+
+    def result_to_host(self):
+        """The (n_pro, generations) float64 result (rows = probands): the finished percentages."""
+        return self._out("result_to_host", self.shape, np.float64, C.c_double)
+
+
+class CompletenessPlan(_GenerationsPlan):
     """gen.completeness' handle (include/genphi.h, genphi_comp_*): planned on the host at construction (KeyError on an unknown
     proband, ValueError for more than GENPHI_COMP_MAX_GENERATIONS generations above the probands; no GPU needed), swept on the GPU by
     compute().  totals_only: the handle reduces the last step into the per-generation totals on the device and holds no
     (n_pro, generations) result; ValueError where those totals could exceed Int64."""
 
+    _prefix = "comp"
+
     def __init__(self, ind, father, mother, pro_ids, totals_only=False):
-        L = lib()
-        ind, father, mother, pro_ids = _i64(ind), _i64(father), _i64(mother), _i64(pro_ids)
-        h = C.c_void_p()
-        rc = L.genphi_comp_create(len(ind), ind.ctypes.data_as(_I64P), father.ctypes.data_as(_I64P), mother.ctypes.data_as(_I64P),
-                                  len(pro_ids), pro_ids.ctypes.data_as(_I64P), GENPHI_COMP_FLAG_TOTALS_ONLY if totals_only else 0, C.byref(h))
-        if rc:
-            _raise(rc)
-        self._h = h
+        self._create_generations(ind, father, mother, pro_ids, GENPHI_COMP_FLAG_TOTALS_ONLY if totals_only else 0)
         self.totals_only = bool(totals_only)
-        g = C.c_int32()
-        rc = L.genphi_comp_generations(h, C.byref(g))
-        if rc:
-            _raise(rc)
-        self.generations = int(g.value)          # 1 + the longest ascent of any listed proband
-        self.shape = (len(pro_ids), self.generations)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().genphi_comp_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        self.close()
-
-    def compute(self, device=None):
-        rc = lib().genphi_comp_compute(self._h, -1 if device is None else int(device))
-        if rc:
-            _raise(rc)
 
     def result_device(self):
         """(device pointer, row pitch in Float64 entries) of the resident result."""
-        p, ld = C.c_void_p(), C.c_int64()
-        rc = lib().genphi_comp_result_device(self._h, C.byref(p), C.byref(ld))
-        if rc:
-            _raise(rc)
-        return p.value, ld.value
-
-    def result_to_host(self):
-        """The (n_pro, generations) float64 result (rows = probands): the finished percentages."""
-        out = np.empty(self.shape, dtype=np.float64)
-        rc = lib().genphi_comp_result_to_host(self._h, out.ctypes.data_as(C.POINTER(C.c_double)))
-        if rc:
-            _raise(rc)
-        return out
+        return self._result_device()
 
     def counts(self):
         """The (n_pro, generations) int64 path counts."""
-        out = np.empty(self.shape, dtype=np.int64)
-        rc = lib().genphi_comp_counts_to_host(self._h, out.ctypes.data_as(_I64P))
-        if rc:
-            _raise(rc)
-        return out
+        return self._out("counts_to_host", self.shape, np.int64, C.c_int64)
 
     def totals(self):
         """The int64 path counts per generation, summed over the listed probands on the device."""
-        out = np.empty(self.generations, dtype=np.int64)
-        rc = lib().genphi_comp_totals(self._h, out.ctypes.data_as(_I64P))
-        if rc:
-            _raise(rc)
-        return out
+        return self._out("totals", self.generations, np.int64, C.c_int64)
 
     def stats(self):
         """dict(sweep_ms, algorithmic_bytes, peak_slots, row_entries, launches) of the last compute()."""
-        ms, ab, ps, re_, nl = C.c_double(), C.c_double(), C.c_int64(), C.c_int32(), C.c_int64()
-        rc = lib().genphi_comp_stats(self._h, C.byref(ms), C.byref(ab), C.byref(ps), C.byref(re_), C.byref(nl))
-        if rc:
-            _raise(rc)
-        return {"sweep_ms": ms.value, "algorithmic_bytes": ab.value, "peak_slots": ps.value, "row_entries": re_.value, "launches": nl.value}
+        return self._stats(sweep_ms=C.c_double, algorithmic_bytes=C.c_double, peak_slots=C.c_int64, row_entries=C.c_int32, launches=C.c_int64)
 
 
-class ImplexPlan:
+class ImplexPlan(_GenerationsPlan):
     """gen.implex' handle (include/genphi.h, genphi_implex_*): planned on the host at construction (KeyError on an unknown proband,
     ValueError for more than GENPHI_IMPLEX_MAX_GENERATIONS generations above the probands; no GPU needed), swept on the GPU by
     compute().  only_new: an individual counts in the generation of its shortest ascent only (GENLIB's onlyNewAnc)."""
 
+    _prefix = "implex"
+
     def __init__(self, ind, father, mother, pro_ids, only_new=False):
-        L = lib()
-        ind, father, mother, pro_ids = _i64(ind), _i64(father), _i64(mother), _i64(pro_ids)
-        h = C.c_void_p()
-        rc = L.genphi_implex_create(len(ind), ind.ctypes.data_as(_I64P), father.ctypes.data_as(_I64P), mother.ctypes.data_as(_I64P),
-                                    len(pro_ids), pro_ids.ctypes.data_as(_I64P), GENPHI_IMPLEX_FLAG_ONLY_NEW if only_new else 0, C.byref(h))
-        if rc:
-            _raise(rc)
-        self._h = h
+        self._create_generations(ind, father, mother, pro_ids, GENPHI_IMPLEX_FLAG_ONLY_NEW if only_new else 0)
         self.only_new = bool(only_new)
-        g = C.c_int32()
-        rc = L.genphi_implex_generations(h, C.byref(g))
-        if rc:
-            _raise(rc)
-        self.generations = int(g.value)          # 1 + the longest ascent of any listed proband
-        self.shape = (len(pro_ids), self.generations)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().genphi_implex_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        self.close()
-
-    def _i64_out(self, fn, shape):
-        out = np.empty(shape, dtype=np.int64)
-        rc = fn(self._h, out.ctypes.data_as(_I64P))
-        if rc:
-            _raise(rc)
-        return out
 
     def rows_per_generation(self):
         """|U_g| per generation: the individuals at exactly g meioses from any listed proband (host only)."""
-        return self._i64_out(lib().genphi_implex_frontier_rows, self.generations)
-
-    def compute(self, device=None):
-        rc = lib().genphi_implex_compute(self._h, -1 if device is None else int(device))
-        if rc:
-            _raise(rc)
+        return self._out("frontier_rows", self.generations, np.int64, C.c_int64)
 
     def counts(self):
         """The (n_pro, generations) int64 counts of distinct ancestors."""
-        return self._i64_out(lib().genphi_implex_counts, self.shape)
-
-    def result_to_host(self):
-        """The (n_pro, generations) float64 result (rows = probands): the finished percentages."""
-        out = np.empty(self.shape, dtype=np.float64)
-        rc = lib().genphi_implex_result_to_host(self._h, out.ctypes.data_as(C.POINTER(C.c_double)))
-        if rc:
-            _raise(rc)
-        return out
+        return self._out("counts", self.shape, np.int64, C.c_int64)
 
     def totals(self):
         """The int64 counts per generation, summed over the listed probands on the device."""
-        return self._i64_out(lib().genphi_implex_totals, self.generations)
+        return self._out("totals", self.generations, np.int64, C.c_int64)
 
     def stats(self):
         """dict(sweep_ms, algorithmic_bytes, generations, panel_cols, panels, lanes_per_row, peak_rows) of the last compute()."""
-        ms, ab, g, pc, np_, lpr, pr = C.c_double(), C.c_double(), C.c_int32(), C.c_int32(), C.c_int64(), C.c_int32(), C.c_int64()
-        rc = lib().genphi_implex_stats(self._h, C.byref(ms), C.byref(ab), C.byref(g), C.byref(pc), C.byref(np_), C.byref(lpr), C.byref(pr))
-        if rc:
-            _raise(rc)
-        return {"sweep_ms": ms.value, "algorithmic_bytes": ab.value, "generations": g.value, "panel_cols": pc.value, "panels": np_.value,
-                "lanes_per_row": lpr.value, "peak_rows": pr.value}
+        return self._stats(sweep_ms=C.c_double, algorithmic_bytes=C.c_double, generations=C.c_int32, panel_cols=C.c_int32, panels=C.c_int64,
+                           lanes_per_row=C.c_int32, peak_rows=C.c_int64)
 
 
 def genealogy_depth(ind, father, mother, leaves_only=False):

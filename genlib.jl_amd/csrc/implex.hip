@@ -26,19 +26,8 @@
 // as keeps one panel's two frontier buffers (and its seen matrix) within about 150 MiB (gc's rule).
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <cstdint>
-#include <cstdlib>
-#include <new>
-#include <string>
-#include <vector>
-
-#include "../../include/genphi.h"
-#include "devcache.h"
 #include "implex.h"
-#include "planner.h"
-
-int genphi_set_error(int code, const std::string &msg);      // genphi_hip.hip
+#include "sweep_device.h"
 
 namespace {
 
@@ -192,102 +181,42 @@ implex_colsum_kernel(const long long *__restrict__ counts, long long n_rows, int
     if (s) atomicAdd(&totals[g], s);
 }
 
-#define IMPLEX_LPR_SWITCH(lpr, CALL)                   \
-    switch (lpr) {                                     \
-    case 1: { constexpr int LPR = 1; CALL; } break;    \
-    case 2: { constexpr int LPR = 2; CALL; } break;    \
-    case 4: { constexpr int LPR = 4; CALL; } break;    \
-    case 8: { constexpr int LPR = 8; CALL; } break;    \
-    case 16: { constexpr int LPR = 16; CALL; } break;  \
-    case 32: { constexpr int LPR = 32; CALL; } break;  \
-    default: { constexpr int LPR = 64; CALL; } break;  \
-    }
-
-// gc's rule (gc.hip): the rows of one panel within about 150 MiB, so that the rows a step writes are still in the 256 MiB
-// Infinity Cache when the next step and the count read them.
-constexpr double kPanelBytes = 150.0 * 1048576.0;
+// gc's rule (sweep_panels.h): the rows of one panel within about 150 MiB, so that the rows a step writes are still in the 256 MiB
+// Infinity Cache when the next step and the count read them.  Sized here, in words of 64 probands: a panel is three buffers and
+// by default a power of two wide.
 constexpr int64_t kMaxPanelWords = 1 << 20;
-
-int pow2_at_least(int64_t n, int cap)
-{
-    int p = 1;
-    while (p < n && p < cap) p *= 2;
-    return p;
-}
 
 }  // namespace
 
-struct genphi_implex {
+struct genphi_implex : SweepDevice {         // d_slots: per panel of a launch: buffer 0, buffer 1, the seen matrix
     genphi::ImplexPlan plan;                 // host plan (implex.h)
     bool only_new = false;
     int32_t panel_env = 0, group_env = 0;    // GENPHI_IMPLEX_PANEL / GENPHI_IMPLEX_PANELS_PER_LAUNCH (0 = default rule)
-    // device
-    int device = -1;
-    hipStream_t stream = nullptr;
     long long *d_counts = nullptr;           // n_pro x G
     double *d_result = nullptr;              // n_pro x G percentages
     u64 *d_totals = nullptr;                 // G, on request
     int *d_occ_start = nullptr, *d_occ_cols = nullptr, *d_estart = nullptr, *d_child = nullptr, *d_seen_row = nullptr;
-    u64 *d_rows = nullptr;                   // per panel of a launch: buffer 0, buffer 1, the seen matrix
-    size_t rows_bytes = 0;
-    bool computed = false, totals_ready = false;
-    double sweep_ms = 0.0, alg_bytes = 0.0;
+    bool totals_ready = false;
     int32_t panel_cols = 0, lanes_per_row = 0;
     int64_t n_panels = 0;
+    genphi_implex() { own(&d_counts, &d_result, &d_totals, &d_occ_start, &d_occ_cols, &d_estart, &d_child, &d_seen_row); }
     size_t result_entries() const { return static_cast<size_t>(plan.n_pro) * static_cast<size_t>(plan.G); }
     bool empty() const { return plan.n_pro == 0 || plan.G == 0; }
 };
 
 namespace {
 
-void release_device(genphi_implex *h)
-{
-    if (h->device < 0) return;
-    int cur = 0;
-    (void)hipGetDevice(&cur);
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    void *blocks[] = {h->d_counts, h->d_result, h->d_totals, h->d_occ_start, h->d_occ_cols, h->d_estart, h->d_child, h->d_seen_row, h->d_rows};
-    for (void *p : blocks) (void)genphi::cached_free(p);
-    h->d_counts = nullptr; h->d_result = nullptr; h->d_totals = nullptr; h->d_occ_start = nullptr; h->d_occ_cols = nullptr;
-    h->d_estart = nullptr; h->d_child = nullptr; h->d_seen_row = nullptr; h->d_rows = nullptr; h->rows_bytes = 0;
-    if (h->stream) genphi::cached_stream_release(h->stream, h->device);
-    h->stream = nullptr;
-    (void)hipSetDevice(cur);
-    h->device = -1;
-    h->computed = false; h->totals_ready = false;
-}
-
-#define IMPLEX_TRY(expr)                                                                                        \
-    do {                                                                                                        \
-        hipError_t e_ = (expr);                                                                                 \
-        if (e_ != hipSuccess) return genphi_set_error(GENPHI_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-int upload(genphi_implex *h, int **dst, const std::vector<int32_t> &src)
-{
-    if (*dst || src.empty()) return GENPHI_OK;
-    IMPLEX_TRY(genphi::cached_malloc(reinterpret_cast<void **>(dst), src.size() * sizeof(int32_t)));
-    IMPLEX_TRY(hipMemcpyAsync(*dst, src.data(), src.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-    return GENPHI_OK;
-}
-
 int compute_impl(genphi_implex *h, int32_t device)
 {
-    if (device < 0) IMPLEX_TRY(hipGetDevice(&device));
-    if (h->device >= 0 && h->device != device) release_device(h);
-    IMPLEX_TRY(hipSetDevice(device));
-    h->device = device;
-    h->computed = false; h->totals_ready = false;
-    if (!h->stream) IMPLEX_TRY(genphi::cached_stream(&h->stream));
+    if (int rc = h->select(device)) return rc;
+    h->totals_ready = false;
     const genphi::ImplexPlan &pl = h->plan;
     const int G = pl.G;
     const int64_t n_pro = pl.n_pro;
     const size_t n_res = h->result_entries();
-    size_t free_b = 0, total_b = 0;
-    IMPLEX_TRY(hipMemGetInfo(&free_b, &total_b));
+    double usable = 0.0;
+    if (int rc = h->usable_bytes(usable, h->d_counts ? 16 * n_res : 0)) return rc;
     const double list_bytes = 4.0 * static_cast<double>(pl.occ_start.size() + pl.occ_cols.size() + pl.edge_start.size() + pl.child.size() + pl.seen_row.size());
-    const double usable = 0.9 * static_cast<double>(free_b + h->rows_bytes + (h->d_counts ? 16 * n_res : 0));
     const double room = usable - 16.0 * static_cast<double>(n_res) - (h->d_child ? 0.0 : list_bytes) - (64 << 20);
     // panels: W words (64 columns each) per row, at a pitch of whole 16-byte pairs
     const int64_t panel_rows = 2 * pl.peak_rows + (h->only_new ? pl.n_union : 0);
@@ -297,7 +226,7 @@ int compute_impl(genphi_implex *h, int32_t device)
     if (h->panel_env > 0) {
         W = std::min<int64_t>((static_cast<int64_t>(h->panel_env) + 63) / 64, kMaxPanelWords);       // (not cut to the probands: a test forces a kernel form by it)
     } else {
-        const int64_t budget = std::max<int64_t>(1, static_cast<int64_t>(kPanelBytes / (8.0 * static_cast<double>(panel_rows))));
+        const int64_t budget = std::max<int64_t>(1, static_cast<int64_t>(genphi::kPanelSlotBytes / (8.0 * static_cast<double>(panel_rows))));
         W = 1;
         while (2 * W <= budget && 2 * W <= kMaxPanelWords) W *= 2;                                     // a power of two: no idle lanes in a row
         W = std::min(W, needed);
@@ -315,39 +244,32 @@ int compute_impl(genphi_implex *h, int32_t device)
     const int Wp = static_cast<int>((W + 1) & ~int64_t(1)), P = Wp / 2;
     const long long panel_stride = static_cast<long long>(panel_rows) * Wp;        // words of one panel: buffer 0, buffer 1, seen
     const long long buf_words = static_cast<long long>(pl.peak_rows) * Wp;
-    const size_t need_rows = static_cast<size_t>(group) * static_cast<size_t>(panel_stride) * sizeof(u64);
-    if (need_rows > h->rows_bytes) {
-        (void)genphi::cached_free(h->d_rows);
-        h->d_rows = nullptr; h->rows_bytes = 0;
-        IMPLEX_TRY(genphi::cached_malloc(reinterpret_cast<void **>(&h->d_rows), need_rows));
-        h->rows_bytes = need_rows;
-    }
-    if (!h->d_totals) IMPLEX_TRY(genphi::cached_malloc(reinterpret_cast<void **>(&h->d_totals), static_cast<size_t>(G) * sizeof(u64)));
-    if (!h->d_counts) IMPLEX_TRY(genphi::cached_malloc(reinterpret_cast<void **>(&h->d_counts), n_res * sizeof(long long)));
-    if (!h->d_result) IMPLEX_TRY(genphi::cached_malloc(reinterpret_cast<void **>(&h->d_result), n_res * sizeof(double)));
+    if (int rc = h->reserve_slots(static_cast<size_t>(group) * static_cast<size_t>(panel_stride) * sizeof(u64))) return rc;
+    if (!h->d_totals) GENPHI_HIP_TRY(genphi::cached_malloc(reinterpret_cast<void **>(&h->d_totals), static_cast<size_t>(G) * sizeof(u64)));
+    if (!h->d_counts) GENPHI_HIP_TRY(genphi::cached_malloc(reinterpret_cast<void **>(&h->d_counts), n_res * sizeof(long long)));
+    if (!h->d_result) GENPHI_HIP_TRY(genphi::cached_malloc(reinterpret_cast<void **>(&h->d_result), n_res * sizeof(double)));
     int rc;
-    if ((rc = upload(h, &h->d_occ_start, pl.occ_start)) || (rc = upload(h, &h->d_occ_cols, pl.occ_cols)) ||
-        (rc = upload(h, &h->d_estart, pl.edge_start)) || (rc = upload(h, &h->d_child, pl.child)) ||
-        (h->only_new && (rc = upload(h, &h->d_seen_row, pl.seen_row))))
+    if ((rc = h->upload(&h->d_occ_start, pl.occ_start)) || (rc = h->upload(&h->d_occ_cols, pl.occ_cols)) ||
+        (rc = h->upload(&h->d_estart, pl.edge_start)) || (rc = h->upload(&h->d_child, pl.child)) ||
+        (h->only_new && (rc = h->upload(&h->d_seen_row, pl.seen_row))))
         return rc;
-    const int lpr = pow2_at_least(P, 64);                     // step: lanes per row, one 16-byte pair each
-    const int wpr = pow2_at_least(W, 64);                     // count: words of a row per group
+    const int lpr = lanes_per_row(P);                         // step: lanes per row, one 16-byte pair each
+    const int wpr = lanes_per_row(static_cast<int>(W));       // count: words of a row per group
     h->panel_cols = static_cast<int32_t>(C);
     h->lanes_per_row = lpr;
     h->n_panels = n_panels;
-    hipEvent_t e0, e1;
-    IMPLEX_TRY(hipEventCreate(&e0));
-    IMPLEX_TRY(hipEventCreate(&e1));
-    IMPLEX_TRY(hipEventRecord(e0, h->stream));
-    IMPLEX_TRY(hipMemsetAsync(h->d_counts, 0, n_res * sizeof(long long), h->stream));
+    SweepRun run;
+    if ((rc = run.begin(*h, 0.0))) return rc;
+    GENPHI_HIP_TRY(hipMemsetAsync(h->d_counts, 0, n_res * sizeof(long long), h->stream));
     const int step_rows = 4 * (64 / lpr), count_rows = (256 / wpr) * IMPLEX_COUNT_ROWS;
-    u64 *seen = h->only_new ? h->d_rows + 2 * buf_words : nullptr;
+    u64 *rows = static_cast<u64 *>(h->d_slots);
+    u64 *seen = h->only_new ? rows + 2 * buf_words : nullptr;
     for (int64_t g0 = 0; g0 < n_panels; g0 += group) {
         const unsigned np = static_cast<unsigned>(std::min<int64_t>(group, n_panels - g0));
         for (int g = 0; g < G; ++g) {
             const int n_rows = static_cast<int>(pl.rows[g]);
-            u64 *cur = h->d_rows + (g & 1) * buf_words;
-            const u64 *prev = h->d_rows + ((g & 1) ^ 1) * buf_words;
+            u64 *cur = rows + (g & 1) * buf_words;
+            const u64 *prev = rows + ((g & 1) ^ 1) * buf_words;
             if (g == 0) {
                 const dim3 grid(static_cast<unsigned>((static_cast<long long>(n_rows) * Wp + 255) / 256), np);
                 implex_init_kernel<<<grid, 256, 0, h->stream>>>(h->d_occ_start, h->d_occ_cols, n_rows, cur, panel_stride, Wp, static_cast<int>(C),
@@ -357,48 +279,27 @@ int compute_impl(genphi_implex *h, int32_t device)
                 const int *es = h->d_estart + pl.start_begin[g], *ch = h->d_child + pl.child_begin[g];
                 const int *sr = h->only_new ? h->d_seen_row + pl.row_begin[g] : nullptr;
                 if (h->only_new) {
-                    IMPLEX_LPR_SWITCH(lpr, (implex_step_kernel<LPR, true><<<grid, 256, 0, h->stream>>>(
+                    GENPHI_LPR_SWITCH(lpr, (implex_step_kernel<LPR, true><<<grid, 256, 0, h->stream>>>(
                                                es, ch, n_rows, reinterpret_cast<const ulonglong2 *>(prev), reinterpret_cast<ulonglong2 *>(cur),
                                                panel_stride / 2, P, sr, reinterpret_cast<ulonglong2 *>(seen), panel_stride / 2)));
                 } else {
-                    IMPLEX_LPR_SWITCH(lpr, (implex_step_kernel<LPR, false><<<grid, 256, 0, h->stream>>>(
+                    GENPHI_LPR_SWITCH(lpr, (implex_step_kernel<LPR, false><<<grid, 256, 0, h->stream>>>(
                                                es, ch, n_rows, reinterpret_cast<const ulonglong2 *>(prev), reinterpret_cast<ulonglong2 *>(cur),
                                                panel_stride / 2, P, nullptr, nullptr, 0)));
                 }
             }
-            IMPLEX_TRY(hipGetLastError());
+            GENPHI_HIP_TRY(hipGetLastError());
             const dim3 cgrid(static_cast<unsigned>((n_rows + count_rows - 1) / count_rows), static_cast<unsigned>((W + wpr - 1) / wpr), np);
-            IMPLEX_LPR_SWITCH(wpr, (implex_count_kernel<LPR><<<cgrid, 256, 0, h->stream>>>(cur, n_rows, panel_stride, Wp, static_cast<int>(C),
-                                                                                         static_cast<int>(n_pro), static_cast<int>(g0), G, g,
-                                                                                         reinterpret_cast<u64 *>(h->d_counts))));
-            IMPLEX_TRY(hipGetLastError());
+            GENPHI_LPR_SWITCH(wpr, (implex_count_kernel<LPR><<<cgrid, 256, 0, h->stream>>>(cur, n_rows, panel_stride, Wp, static_cast<int>(C),
+                                                                                          static_cast<int>(n_pro), static_cast<int>(g0), G, g,
+                                                                                          reinterpret_cast<u64 *>(h->d_counts))));
+            GENPHI_HIP_TRY(hipGetLastError());
         }
     }
     implex_finish_kernel<<<static_cast<unsigned>((n_res + 255) / 256), 256, 0, h->stream>>>(h->d_counts, static_cast<long long>(n_res), G, h->d_result);
-    IMPLEX_TRY(hipGetLastError());
-    IMPLEX_TRY(hipEventRecord(e1, h->stream));
-    IMPLEX_TRY(hipEventSynchronize(e1));
-    float ms = 0.f;
-    IMPLEX_TRY(hipEventElapsedTime(&ms, e0, e1));
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    h->sweep_ms = ms;
-    h->alg_bytes = 8.0 * static_cast<double>(W) * static_cast<double>(n_panels) * static_cast<double>(pl.sum_rows + pl.sum_edges);
-    h->computed = true;
-    return GENPHI_OK;
-}
-
-// bytes from the device (src) to the host
-int copy_out(genphi_implex *h, void *out, const void *src, size_t bytes)
-{
-    int cur = 0;
-    IMPLEX_TRY(hipGetDevice(&cur));
-    IMPLEX_TRY(hipSetDevice(h->device));
-    const hipError_t e = hipMemcpyAsync(out, src, bytes, hipMemcpyDeviceToHost, h->stream);
-    const hipError_t e2 = e == hipSuccess ? hipStreamSynchronize(h->stream) : e;
-    (void)hipSetDevice(cur);
-    if (e2 != hipSuccess) return genphi_set_error(GENPHI_ERR_DEVICE, std::string("gen.implex result copy: ") + hipGetErrorString(e2));
-    return GENPHI_OK;
+    GENPHI_HIP_TRY(hipGetLastError());
+    run.bytes = 8.0 * static_cast<double>(W) * static_cast<double>(n_panels) * static_cast<double>(pl.sum_rows + pl.sum_edges);
+    return run.end(*h);
 }
 
 }  // namespace
@@ -408,44 +309,23 @@ extern "C" {
 int genphi_implex_create(int64_t n_ind, const int64_t *ind, const int64_t *father, const int64_t *mother, int64_t n_pro,
                          const int64_t *pro_ids, int32_t flags, genphi_implex **out)
 {
-    if (!out) return genphi_set_error(GENPHI_ERR_ARG, "genphi_implex_create: out is NULL");
-    *out = nullptr;
-    if (flags & ~GENPHI_IMPLEX_FLAG_ONLY_NEW) return genphi_set_error(GENPHI_ERR_ARG, "genphi_implex_create: unknown flag");
-    if (n_ind < 0 || n_pro < 0 || (n_ind && (!ind || !father || !mother)) || (n_pro && !pro_ids))
-        return genphi_set_error(GENPHI_ERR_ARG, "genphi_implex_create: bad sizes or NULL arrays");
-    if (n_ind >= INT32_MAX || n_pro >= INT32_MAX)
-        return genphi_set_error(GENPHI_ERR_ARG, "genphi_implex_create: more than 2^31 - 2 individuals or probands");
-    genphi_implex *h = new (std::nothrow) genphi_implex();
-    if (!h) return genphi_set_error(GENPHI_ERR_ALLOC, "out of memory");
-    h->only_new = (flags & GENPHI_IMPLEX_FLAG_ONLY_NEW) != 0;
-    if (const char *e = genphi::env_hook("GENPHI_IMPLEX_PANEL")) h->panel_env = std::max(0, std::atoi(e));
-    if (const char *e = genphi::env_hook("GENPHI_IMPLEX_PANELS_PER_LAUNCH")) h->group_env = std::max(0, std::atoi(e));
-    int rc;
-    try {
+    if (out) *out = nullptr;
+    if (out && (flags & ~GENPHI_IMPLEX_FLAG_ONLY_NEW)) return genphi_set_error(GENPHI_ERR_ARG, "genphi_implex_create: unknown flag");
+    if (int rc = check_create_args("genphi_implex_create", n_ind, ind, father, mother, n_pro, pro_ids, 0, nullptr, out, 0)) return rc;
+    return create_entry(out, "gen.implex", [&](genphi_implex *h) {
+        h->only_new = (flags & GENPHI_IMPLEX_FLAG_ONLY_NEW) != 0;
+        h->panel_env = hook_count("GENPHI_IMPLEX_PANEL");
+        h->group_env = hook_count("GENPHI_IMPLEX_PANELS_PER_LAUNCH");
         std::string err;
-        rc = genphi::plan_implex(h->plan, n_ind, ind, father, mother, n_pro, pro_ids, GENPHI_IMPLEX_MAX_GENERATIONS, err);
-        if (rc) rc = genphi_set_error(rc, err);
-        else if (h->plan.seen_row.size() + static_cast<size_t>(h->plan.G) >= static_cast<size_t>(INT32_MAX) || h->plan.child.size() >= static_cast<size_t>(INT32_MAX))
-            rc = genphi_set_error(GENPHI_ERR_ALLOC, "gen.implex: the frontier lists of " + std::to_string(h->plan.G) + " generations exceed 2^31 entries");
-    } catch (const std::bad_alloc &) { rc = genphi_set_error(GENPHI_ERR_ALLOC, "out of memory while planning gen.implex"); }
-    if (rc) { delete h; return rc; }
-    *out = h;
-    return GENPHI_OK;
+        if (const int rc = genphi::plan_implex(h->plan, n_ind, ind, father, mother, n_pro, pro_ids, GENPHI_IMPLEX_MAX_GENERATIONS, err))
+            return genphi_set_error(rc, err);
+        if (h->plan.seen_row.size() + static_cast<size_t>(h->plan.G) >= static_cast<size_t>(INT32_MAX) || h->plan.child.size() >= static_cast<size_t>(INT32_MAX))
+            return genphi_set_error(GENPHI_ERR_ALLOC, "gen.implex: the frontier lists of " + std::to_string(h->plan.G) + " generations exceed 2^31 entries");
+        return GENPHI_OK;
+    });
 }
 
-int genphi_implex_compute(genphi_implex *h, int32_t device)
-{
-    if (!h) return genphi_set_error(GENPHI_ERR_ARG, "genphi_implex_compute: NULL handle");
-    if (h->empty()) { h->computed = true; h->sweep_ms = 0.0; h->alg_bytes = 0.0; return GENPHI_OK; }
-    int cur = 0;
-    if (hipGetDevice(&cur) != hipSuccess) return genphi_set_error(GENPHI_ERR_DEVICE, "gen.implex: no usable GPU");
-    int rc;
-    try {
-        rc = compute_impl(h, device);
-    } catch (const std::bad_alloc &) { rc = genphi_set_error(GENPHI_ERR_ALLOC, "out of host memory in gen.implex"); }
-    (void)hipSetDevice(cur);
-    return rc;
-}
+int genphi_implex_compute(genphi_implex *h, int32_t device) { return compute_entry(h, device, "genphi_implex_compute", "gen.implex", compute_impl); }
 
 int genphi_implex_generations(const genphi_implex *h, int32_t *generations)
 {
@@ -467,7 +347,7 @@ int genphi_implex_counts(genphi_implex *h, int64_t *out)
     if (!h || !h->computed) return genphi_set_error(GENPHI_ERR_ARG, "genphi_implex_counts: nothing computed");
     if (h->empty()) return GENPHI_OK;
     if (!out) return genphi_set_error(GENPHI_ERR_ARG, "genphi_implex_counts: out is NULL");
-    return copy_out(h, out, h->d_counts, h->result_entries() * sizeof(long long));
+    return h->copy_out(out, h->d_counts, h->result_entries() * sizeof(long long), "gen.implex");
 }
 
 int genphi_implex_result_to_host(genphi_implex *h, double *out)
@@ -475,7 +355,7 @@ int genphi_implex_result_to_host(genphi_implex *h, double *out)
     if (!h || !h->computed) return genphi_set_error(GENPHI_ERR_ARG, "genphi_implex_result_to_host: nothing computed");
     if (h->empty()) return GENPHI_OK;
     if (!out) return genphi_set_error(GENPHI_ERR_ARG, "genphi_implex_result_to_host: out is NULL");
-    return copy_out(h, out, h->d_result, h->result_entries() * sizeof(double));
+    return h->copy_out(out, h->d_result, h->result_entries() * sizeof(double), "gen.implex");
 }
 
 int genphi_implex_totals(genphi_implex *h, int64_t *out)
@@ -485,40 +365,31 @@ int genphi_implex_totals(genphi_implex *h, int64_t *out)
     if (!out) return genphi_set_error(GENPHI_ERR_ARG, "genphi_implex_totals: out is NULL");
     const size_t bytes = static_cast<size_t>(h->plan.G) * sizeof(int64_t);
     if (!h->totals_ready) {
-        int cur = 0;
-        IMPLEX_TRY(hipGetDevice(&cur));
-        IMPLEX_TRY(hipSetDevice(h->device));
-        hipError_t e = hipMemsetAsync(h->d_totals, 0, bytes, h->stream);
-        if (e == hipSuccess) {
+        const int rc = h->on_device("gen.implex totals", [&] {
+            const hipError_t e = hipMemsetAsync(h->d_totals, 0, bytes, h->stream);
+            if (e != hipSuccess) return e;
             implex_colsum_kernel<<<static_cast<unsigned>((h->plan.n_pro + 1023) / 1024), 256, 0, h->stream>>>(h->d_counts, h->plan.n_pro, h->plan.G, h->d_totals);
-            e = hipGetLastError();
-        }
-        (void)hipSetDevice(cur);
-        if (e != hipSuccess) return genphi_set_error(GENPHI_ERR_DEVICE, std::string("gen.implex totals: ") + hipGetErrorString(e));
+            return hipGetLastError();
+        });
+        if (rc) return rc;
         h->totals_ready = true;
     }
-    return copy_out(h, out, h->d_totals, bytes);
+    return h->copy_out(out, h->d_totals, bytes, "gen.implex");
 }
 
 int genphi_implex_stats(const genphi_implex *h, double *sweep_ms, double *algorithmic_bytes, int32_t *generations, int32_t *panel_cols,
                         int64_t *panels, int32_t *lanes_per_row, int64_t *peak_rows)
 {
     if (!h) return genphi_set_error(GENPHI_ERR_ARG, "genphi_implex_stats: NULL handle");
-    if (sweep_ms) *sweep_ms = h->sweep_ms;
-    if (algorithmic_bytes) *algorithmic_bytes = h->alg_bytes;
-    if (generations) *generations = h->plan.G;
-    if (panel_cols) *panel_cols = h->panel_cols;
-    if (panels) *panels = h->n_panels;
-    if (lanes_per_row) *lanes_per_row = h->lanes_per_row;
-    if (peak_rows) *peak_rows = h->plan.peak_rows;
+    h->stats(sweep_ms, algorithmic_bytes, nullptr);
+    put(generations, h->plan.G);
+    put(panel_cols, h->panel_cols);
+    put(panels, h->n_panels);
+    put(lanes_per_row, h->lanes_per_row);
+    put(peak_rows, h->plan.peak_rows);
     return GENPHI_OK;
 }
 
-void genphi_implex_destroy(genphi_implex *h)
-{
-    if (!h) return;
-    release_device(h);
-    delete h;
-}
+void genphi_implex_destroy(genphi_implex *h) { destroy_entry(h); }
 
 }  // extern "C"

@@ -29,7 +29,7 @@ LITERAL_MAX_STEPS = 24        # gc_literal (Float32 path sums) is exact up to he
 LITERAL_MAX_PATHS = 300_000   # ... and walks one path at a time
 
 # Panel widths that between them select every lanes-per-row instantiation (1, 2, 4, ..., 64) of a family's kernels, with odd widths, widths
-# that are no multiple of 8 and (dist) panels that start off a multiple of 8 columns.  The rules (lanes_per_row in gc.hip, occ.hip, dist.hip):
+# that are no multiple of 8 and (dist) panels that start off a multiple of 8 columns.  The rule (lanes_per_row in csrc/sweep_device.h) and its arguments:
 #   gc        the power of two >= ceil(C / 2) pairs of Float64 columns
 #   occ       >= ceil(C / 4) vectors of 32-bit counts, ceil(C / 2) of 64-bit counts;  rec: >= ceil(C / 128) vectors of two 64-column words
 #   meioses   >= ceil(C / 8) vectors of eight 16-bit entries

@@ -138,7 +138,7 @@ struct OptSet {
 };
 enum { kGC = 0, kOcc, kRec, kDist, kComp, kFamilies };
 
-// the options of the five callers, as gc.hip (plan_gc), occ.hip (create_impl), dist.hip (genphi_dist_create) and completeness.hip
+// the options of the five callers, as gc.hip (genphi_gc_create), occ.hip (create_impl), dist.hip (genphi_dist_create) and completeness.hip
 // (genphi_comp_create) set them
 std::vector<OptSet> caller_options()
 {

@@ -51,6 +51,7 @@ def _check_everything(gen, ped, pro, exact=None):
         _same(h.result_to_host(), np.ascontiguousarray(ind_matrix.T))
         _same(h.totals(), counts.sum(axis=0, dtype=np.int64))
         _same(h.totals(), counts.sum(axis=0, dtype=np.int64))          # asked again: the same
+        _same(h.result_to_host(), np.ascontiguousarray(ind_matrix.T))  # the column sums left the resident result alone
         st = h.stats()
     finally:
         h.close()
