@@ -21,6 +21,8 @@ meaning, printed lines and error behaviour as the reference:
     gen.completeness(ped); gen.depth(ped)  # src/describe.jl:73-125, :43-66: ascents by generation (csrc/completeness.hip);
                                            # gen.nomen, gen.nowomen, gen.noind, ped.show() (src/describe.jl:6-36, src/create.jl:76-111)
     gen.implex(ped)                        # GENLIB's gen.implex: distinct ancestors by generation (csrc/implex.hip)
+    gen.simuSample(ped); gen.simuProb(..)  # GENLIB's gene dropping: marked alleles of ancestors in the probands (csrc/simu.hip)
+    gen.descendant(ped, 1); gen.children(ped, 1)   # src/identify.jl:203-215, :77-80 (csrc/loader.cpp)
 
 All kinship arithmetic runs in hand-written HIP kernels behind the C-ABI in
 include/genphi.h (csrc/genphi_hip.hip); there is no CPU fallback.
@@ -31,7 +33,7 @@ from collections import OrderedDict
 import numpy as np
 
 from . import _capi
-from ._capi import PhiPlan, KinshipMatrix, GCPlan, OccPlan, RecPlan, DistPlan, CompletenessPlan, ImplexPlan, GenphiDeviceError, GenphiLibraryMissing  # noqa: F401
+from ._capi import PhiPlan, KinshipMatrix, GCPlan, OccPlan, RecPlan, DistPlan, CompletenessPlan, ImplexPlan, SimuPlan, GenphiDeviceError, GenphiLibraryMissing  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
@@ -502,6 +504,78 @@ def implex(pedigree, pro=None, genNo=None, type="MEAN", onlyNewAnc=False, device
         h.close()
 
 
+def _simu_plan(pedigree, pro, ancestors, stateAncestors, simulNo, seed, no_sample):
+    probands = globals()["pro"](pedigree) if pro is None else np.ascontiguousarray(pro, dtype=np.int64)
+    ancestors = founder(pedigree) if ancestors is None else np.ascontiguousarray(ancestors, dtype=np.int64)
+    states = np.ones(len(ancestors), dtype=np.int32) if stateAncestors is None else stateAncestors
+    return SimuPlan(pedigree.ind, pedigree.father, pedigree.mother, probands, ancestors, states, simul_no=simulNo, seed=seed,
+                    no_sample=no_sample)
+
+
+def simuSample(pedigree, pro=None, ancestors=None, stateAncestors=None, simulNo=5000, seed=None, device=None):
+    """gen.simuSample(pedigree, pro = pro(pedigree), ancestors = founder(pedigree), stateAncestors = all 1, simulNo = 5000), GENLIB's
+    gen.simuSample (the reference has no form of it): gene dropping.  Every ancestor carries stateAncestors[j] in {0, 1, 2} copies
+    of a marked allele; the alleles are dropped down the pedigree simulNo times, every meiosis passing on the paternal or the
+    maternal copy with probability 1/2.  Returns the int8 array of shape (len(pro), simulNo): the copies proband i carries in
+    simulation s.
+
+    A listed ancestor keeps its state in every simulation and blocks every path through it (its own parents are ignored, a
+    state-0 ancestor included).  The random bits are Philox4x32-10 keyed on (seed, the individual's ID, the parental side, the
+    absolute word of 64 simulations): the result is a pure function of the pedigree's relations, the ancestors with their states
+    and the seed (include/genphi.h) -- simulNo = 64 gives the first 64 columns of simulNo = 5000, a sub-list of probands gives
+    the same rows, and gen.branching(pedigree, pro=.., ancestors=..) first changes no row of the probands it keeps.  (Pruning drops
+    a proband that descends from no listed ancestor, whose row is zero, and an ancestor above no listed proband, which marks
+    no row; passing a dropped ID with the pruned pedigree is a KeyError, so pass the kept ones.)  seed=None draws 64 fresh bits (secrets.randbits); pass a seed to
+    repeat a run.  The sweep runs on the GPU, 64 simulations per word, level by level from the ancestors down (csrc/simu.hip).
+
+    GENLIB's probRecomb and probSurvival are not offered.  KeyError for an unknown ID; ValueError for a state outside 0..2, lists of
+    different length, an ancestor listed with two states, simulNo outside 1 .. 2^24, an empty pro or no ancestors.  Each call
+    plans, sweeps and frees its own handle."""
+    h = _simu_plan(pedigree, pro, ancestors, stateAncestors, simulNo, seed, False)
+    try:
+        h.compute(device=device)
+        return h.sample_to_host()
+    finally:
+        h.close()
+
+
+class SimuProb:
+    """What gen.simuProb returns: joint, the share of the simulations in which every proband i carries statePro[i] copies;
+    marginal[i], the share in which proband i does; by_number[k], the share in which exactly k probands do; simulNo and the seed
+    used.  Every probability is an integer count divided by simulNo once."""
+
+    def __init__(self, joint, marginal, by_number, simulNo, seed):
+        self.joint, self.marginal, self.by_number, self.simulNo, self.seed = joint, marginal, by_number, simulNo, seed
+
+    def __repr__(self):
+        return "SimuProb(joint=%r, simulNo=%d, seed=%d)" % (self.joint, self.simulNo, self.seed)
+
+
+def simuProb(pedigree, pro, statePro, ancestors, stateAncestors, simulNo=5000, seed=None, device=None):
+    """gen.simuProb(pedigree, pro, statePro, ancestors, stateAncestors, simulNo = 5000), GENLIB's gen.simuProb (the reference has no
+    form of it): the probability, estimated by gene dropping (gen.simuSample, with its rules, seed and errors), that proband i
+    carries statePro[i] in {0, 1, 2} copies of the alleles that the ancestors carry.  Returns a SimuProb: joint (all probands at
+    once), marginal (each proband alone) and by_number (exactly k of them, k = 0 .. len(pro)).
+
+    Counted on the GPU from the bit rows of the sweep (csrc/simu.hip); no (len(pro), simulNo) sample is ever held.  Each call
+    plans, sweeps and frees its own handle."""
+    h = _simu_plan(pedigree, pro, ancestors, stateAncestors, simulNo, seed, True)
+    try:
+        statePro = np.asarray(statePro).ravel()
+        if len(statePro) != h.n_pro:
+            raise ValueError("gen.simuProb: %d probands but %d states" % (h.n_pro, len(statePro)))
+        if len(statePro) and (not np.array_equal(statePro, statePro.astype(np.int64)) or statePro.min() < 0 or statePro.max() > 2):
+            raise ValueError("gen.simuProb: statePro must be 0, 1 or 2")
+        statePro = statePro.astype(np.int64)
+        h.compute(device=device)
+        S = h.simul_no
+        marginal = h.state_counts()[np.arange(h.n_pro), statePro] / float(S)
+        by_number = np.bincount(h.match_counts(statePro), minlength=h.n_pro + 1) / float(S)
+        return SimuProb(float(by_number[-1]), marginal, by_number, S, h.seed)
+    finally:
+        h.close()
+
+
 def depth(pedigree):
     """gen.depth(pedigree) (src/describe.jl:43-66): the number of generations of the pedigree, 1 + the longest ascent of any
     individual (1 for a pedigree of founders, 0 for an empty one).  One linear pass on the host (csrc/loader.cpp) where the
@@ -533,6 +607,19 @@ def ancestor(pedigree, IDs):
     several (the union), ascending.  Strict: an individual is not its own ancestor.  Host only (csrc/loader.cpp).  KeyError for an
     unknown ID."""
     return _capi.ancestors(pedigree.ind, pedigree.father, pedigree.mother, _id_list(IDs))
+
+
+def descendant(pedigree, IDs):
+    """gen.descendant(pedigree, ID) / gen.descendant(pedigree, IDs) (src/identify.jl:203-215): the descendants of one individual, or
+    of several (the union), ascending.  Strict: an individual is not its own descendant.  Host only (csrc/loader.cpp).  KeyError for
+    an unknown ID."""
+    return _capi.descendants(pedigree.ind, pedigree.father, pedigree.mother, _id_list(IDs))
+
+
+def children(pedigree, ID):
+    """gen.children(pedigree, ID) (src/identify.jl:77-80): the children of an individual, ascending.  Host only (csrc/loader.cpp).
+    KeyError for an unknown ID."""
+    return _capi.children(pedigree.ind, pedigree.father, pedigree.mother, int(ID))
 
 
 _MRCA_CANDIDATE_SEARCHES = 16          # ancestor sets looked at for the shortest candidate list (any one of them is a valid list)

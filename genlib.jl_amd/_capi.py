@@ -66,6 +66,8 @@ EXPORTED_SYMBOLS = [
     "genphi_comp_counts_to_host", "genphi_comp_totals", "genphi_comp_stats", "genphi_comp_destroy", "genphi_genealogy_depth",
     "genphi_implex_create", "genphi_implex_compute", "genphi_implex_generations", "genphi_implex_frontier_rows", "genphi_implex_counts",
     "genphi_implex_result_to_host", "genphi_implex_totals", "genphi_implex_stats", "genphi_implex_destroy",
+    "genphi_simu_create", "genphi_simu_levels", "genphi_simu_rows", "genphi_simu_compute", "genphi_simu_sample_to_host", "genphi_simu_state_counts",
+    "genphi_simu_match_counts", "genphi_simu_stats", "genphi_simu_destroy", "genphi_descendants", "genphi_children",
 ]
 
 _lib = None
@@ -270,6 +272,29 @@ def lib():
         L.genphi_implex_stats.restype = C.c_int
         L.genphi_implex_destroy.argtypes = [C.c_void_p]
         L.genphi_implex_destroy.restype = None
+        L.genphi_simu_create.argtypes = [C.c_int64, _I64P, _I64P, _I64P, C.c_int64, _I64P, C.c_int64, _I64P, _I32P, C.c_int64, C.c_uint64, C.c_int32,
+                                         C.POINTER(C.c_void_p)]
+        L.genphi_simu_create.restype = C.c_int
+        L.genphi_simu_levels.argtypes = [C.c_void_p, _I64P, _I32P, _I64P]
+        L.genphi_simu_levels.restype = C.c_int
+        L.genphi_simu_rows.argtypes = [C.c_void_p, _I64P, _I32P, _I32P, _I64P]
+        L.genphi_simu_rows.restype = C.c_int
+        L.genphi_simu_compute.argtypes = [C.c_void_p, C.c_int32]
+        L.genphi_simu_compute.restype = C.c_int
+        L.genphi_simu_sample_to_host.argtypes = [C.c_void_p, C.POINTER(C.c_int8)]
+        L.genphi_simu_sample_to_host.restype = C.c_int
+        L.genphi_simu_state_counts.argtypes = [C.c_void_p, _I64P]
+        L.genphi_simu_state_counts.restype = C.c_int
+        L.genphi_simu_match_counts.argtypes = [C.c_void_p, _I32P, _I32P]
+        L.genphi_simu_match_counts.restype = C.c_int
+        L.genphi_simu_stats.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), _I32P, _I32P, _I64P, _I32P, _I64P]
+        L.genphi_simu_stats.restype = C.c_int
+        L.genphi_simu_destroy.argtypes = [C.c_void_p]
+        L.genphi_simu_destroy.restype = None
+        L.genphi_descendants.argtypes = [C.c_int64, _I64P, _I64P, _I64P, C.c_int64, _I64P, _I64P, C.POINTER(_I64P)]
+        L.genphi_descendants.restype = C.c_int
+        L.genphi_children.argtypes = [C.c_int64, _I64P, _I64P, _I64P, C.c_int64, _I64P, C.POINTER(_I64P)]
+        L.genphi_children.restype = C.c_int
         for kind in ("occ", "rec", "dist"):
             fn = getattr(L, "genphi_%s_compute" % kind)
             fn.argtypes, fn.restype = [C.c_void_p, C.c_int32], C.c_int
@@ -1075,6 +1100,89 @@ class ImplexPlan(_GenerationsPlan):
                            lanes_per_row=C.c_int32, peak_rows=C.c_int64)
 
 
+GENPHI_SIMU_MAX_SIMULATIONS = 1 << 24
+GENPHI_SIMU_FLAG_NO_SAMPLE = 1
+
+
+class SimuPlan(_SweepPlan):
+    """The handle of gen.simuSample / gen.simuProb (include/genphi.h, genphi_simu_*): gene dropping.  Planned on the host at
+    construction (KeyError on an unknown proband or ancestor; ValueError for a state outside 0..2, lists of different length, an
+    ancestor listed with two states, simul_no outside 1 .. 2^24, no probands or no ancestors; no GPU needed), swept on the GPU by
+    compute().  seed=None draws 64 fresh bits; .seed reports the seed used.  no_sample: state and match counts only, no
+    (n_pro, simul_no) sample exists."""
+
+    _prefix = "simu"
+
+    def __init__(self, ind, father, mother, pro_ids, anc_ids, anc_states, simul_no=5000, seed=None, no_sample=False):
+        pro_ids, anc_ids = _i64(pro_ids).ravel(), _i64(anc_ids).ravel()
+        states = np.asarray(anc_states).ravel()
+        if len(states) != len(anc_ids):
+            raise ValueError("gen.simu: %d ancestors but %d states" % (len(anc_ids), len(states)))
+        if len(states) and not np.array_equal(states, states.astype(np.int32)):
+            raise ValueError("gen.simu: the states must be the integers 0, 1 or 2")
+        states = np.ascontiguousarray(states, dtype=np.int32)
+        if seed is None:
+            import secrets
+            seed = secrets.randbits(64)
+        self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.simul_no = int(simul_no)
+        self.no_sample = bool(no_sample)
+        ind, father, mother = _i64(ind), _i64(father), _i64(mother)
+        h = C.c_void_p()
+        rc = lib().genphi_simu_create(len(ind), ind.ctypes.data_as(_I64P), father.ctypes.data_as(_I64P), mother.ctypes.data_as(_I64P),
+                                      len(pro_ids), pro_ids.ctypes.data_as(_I64P), len(anc_ids), anc_ids.ctypes.data_as(_I64P),
+                                      states.ctypes.data_as(C.POINTER(C.c_int32)), self.simul_no, self.seed,
+                                      GENPHI_SIMU_FLAG_NO_SAMPLE if no_sample else 0, C.byref(h))
+        if rc:
+            _raise(rc)
+        self._h = h
+        self.n_pro = len(pro_ids)
+        n_live, levels = C.c_int64(), C.c_int32()
+        self._call("levels", C.byref(n_live), C.byref(levels), None)
+        self.n_live, self.levels = int(n_live.value), int(levels.value)
+
+    def rows_per_level(self):
+        """The live rows of every level (host only)."""
+        out = np.empty(self.levels, dtype=np.int64)
+        self._call("levels", None, None, out.ctypes.data_as(_I64P))
+        return out
+
+    def rows(self):
+        """dict(ids, father_rows, mother_rows, pro_positions) of the plan (host only): per live row, ordered by level, the ID and the
+        rows of its parents (-1 = a zero row); per listed proband its row, -1 = not live, -2 - state for a listed ancestor."""
+        ids, fa, mo = np.empty(self.n_live, np.int64), np.empty(self.n_live, np.int32), np.empty(self.n_live, np.int32)
+        pos = np.empty(self.n_pro, np.int64)
+        i32 = C.POINTER(C.c_int32)
+        self._call("rows", ids.ctypes.data_as(_I64P), fa.ctypes.data_as(i32), mo.ctypes.data_as(i32), pos.ctypes.data_as(_I64P))
+        return {"ids": ids, "father_rows": fa, "mother_rows": mo, "pro_positions": pos}
+
+    def sample_to_host(self):
+        """The (n_pro, simul_no) int8 sample: the copies proband i carries in simulation s.  ValueError under no_sample."""
+        return self._out("sample_to_host", (self.n_pro, self.simul_no), np.int8, C.c_int8)
+
+    def state_counts(self):
+        """The (n_pro, 3) int64 table: the simulations in which proband i carries 0, 1, 2 copies."""
+        return self._out("state_counts", (self.n_pro, 3), np.int64, C.c_int64)
+
+    def match_counts(self, state_pro):
+        """Per simulation, the listed probands i whose count equals state_pro[i]: int32 of length simul_no.  May be asked again with
+        other states (one panel: the resident rows are read; several panels: swept again)."""
+        state_pro = np.asarray(state_pro).ravel()
+        if len(state_pro) != self.n_pro:
+            raise ValueError("gen.simuProb: %d probands but %d states" % (self.n_pro, len(state_pro)))
+        if len(state_pro) and not np.array_equal(state_pro, state_pro.astype(np.int32)):
+            raise ValueError("gen.simuProb: the states must be the integers 0, 1 or 2")
+        state_pro = np.ascontiguousarray(state_pro, dtype=np.int32)
+        out = np.empty(self.simul_no, dtype=np.int32)
+        self._call("match_counts", state_pro.ctypes.data_as(C.POINTER(C.c_int32)), out.ctypes.data_as(C.POINTER(C.c_int32)))
+        return out
+
+    def stats(self):
+        """dict(sweep_ms, algorithmic_bytes, levels, panel_cols, panels, lanes_per_row, n_live) of the last compute()."""
+        return self._stats(sweep_ms=C.c_double, algorithmic_bytes=C.c_double, levels=C.c_int32, panel_cols=C.c_int32, panels=C.c_int64,
+                           lanes_per_row=C.c_int32, n_live=C.c_int64)
+
+
 def genealogy_depth(ind, father, mother, leaves_only=False):
     """1 + the longest ascent of any individual (leaves_only: of any individual without children): genphi_genealogy_depth, host only."""
     ind, father, mother = _i64(ind), _i64(father), _i64(mother)
@@ -1099,6 +1207,36 @@ def ancestors(ind, father, mother, ids):
         return np.ctypeslib.as_array(p, shape=(n.value,)).copy() if n.value else np.zeros(0, np.int64)
     finally:
         L.genphi_free(p)
+
+
+def _id_array(n, p):
+    """The library's malloc'ed ID list as an array of ours; the list is freed."""
+    try:
+        return np.ctypeslib.as_array(p, shape=(n.value,)).copy() if n.value else np.zeros(0, np.int64)
+    finally:
+        lib().genphi_free(p)
+
+
+def descendants(ind, father, mother, ids):
+    """Sorted strict descendants of `ids` (the union over them): genphi_descendants, host only."""
+    ind, father, mother, ids = _i64(ind), _i64(father), _i64(mother), _i64(ids)
+    n, p = C.c_int64(), _I64P()
+    rc = lib().genphi_descendants(len(ind), ind.ctypes.data_as(_I64P), father.ctypes.data_as(_I64P), mother.ctypes.data_as(_I64P),
+                                  len(ids), ids.ctypes.data_as(_I64P), C.byref(n), C.byref(p))
+    if rc:
+        _raise(rc)
+    return _id_array(n, p)
+
+
+def children(ind, father, mother, ID):
+    """Sorted children of ID: genphi_children, host only."""
+    ind, father, mother = _i64(ind), _i64(father), _i64(mother)
+    n, p = C.c_int64(), _I64P()
+    rc = lib().genphi_children(len(ind), ind.ctypes.data_as(_I64P), father.ctypes.data_as(_I64P), mother.ctypes.data_as(_I64P), int(ID),
+                               C.byref(n), C.byref(p))
+    if rc:
+        _raise(rc)
+    return _id_array(n, p)
 
 
 def mrca_filter(ind, father, mother, common):

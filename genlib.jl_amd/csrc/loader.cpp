@@ -372,6 +372,93 @@ int genphi_ancestors(int64_t n_ind, const int64_t *ind, const int64_t *father, c
     return GENPHI_OK;
 }
 
+// The downward walk of gen.descendant: the children of every individual as one list per parent (start[r] .. start[r + 1],
+// positions, in pedigree order; a child whose father is its mother is listed once).
+static int child_lists(const char *fn, const IdIndex &pos, int64_t n_ind, const int64_t *ind, const int64_t *father, const int64_t *mother,
+                       std::vector<int64_t> &start, std::vector<int32_t> &child)
+{
+    std::vector<int32_t> pf(n_ind, -1), pm(n_ind, -1);
+    start.assign(n_ind + 1, 0);
+    for (int64_t i = 0; i < n_ind; ++i)
+        for (int side = 0; side < 2; ++side) {
+            const int64_t pid = side ? mother[i] : father[i];
+            if (pid == 0 || (side && pid == father[i])) continue;
+            const int32_t r = pos.find(pid);
+            if (r < 0)
+                return genphi_set_error(GENPHI_ERR_UNKNOWN_ID, std::string(fn) + ": KeyError: parent " + std::to_string(pid) + " of " + std::to_string(ind[i]) + " not found");
+            (side ? pm : pf)[i] = r;
+            start[r + 1]++;
+        }
+    for (int64_t r = 0; r < n_ind; ++r) start[r + 1] += start[r];
+    child.resize(start[n_ind]);
+    std::vector<int64_t> fill(start.begin(), start.end() - 1);
+    for (int64_t i = 0; i < n_ind; ++i) {
+        if (pf[i] >= 0) child[fill[pf[i]]++] = static_cast<int32_t>(i);
+        if (pm[i] >= 0) child[fill[pm[i]]++] = static_cast<int32_t>(i);
+    }
+    return GENPHI_OK;
+}
+
+static int ids_out(std::vector<int64_t> &found, int64_t *n_out, int64_t **out)
+{
+    std::sort(found.begin(), found.end());
+    int64_t *a = static_cast<int64_t *>(std::malloc(sizeof(int64_t) * (found.empty() ? 1 : found.size())));
+    if (!a) return genphi_set_error(GENPHI_ERR_ALLOC, "out of memory");
+    std::copy(found.begin(), found.end(), a);
+    *n_out = static_cast<int64_t>(found.size()); *out = a;
+    return GENPHI_OK;
+}
+
+// gen.descendant (src/identify.jl:203-215): the strict descendants of one ID, or the union over several, ascending.  The
+// reference's stack search on positions with one visited flag per individual, as genphi_ancestors.  No order of the pedigree is
+// assumed.  *out is allocated by the library (genphi_free).
+int genphi_descendants(int64_t n_ind, const int64_t *ind, const int64_t *father, const int64_t *mother, int64_t n_ids, const int64_t *ids,
+                       int64_t *n_out, int64_t **out)
+{
+    if (!n_out || !out || n_ind < 0 || n_ind >= INT32_MAX || n_ids < 0 || (n_ind > 0 && (!ind || !father || !mother)) || (n_ids > 0 && !ids))
+        return genphi_set_error(GENPHI_ERR_ARG, "genphi_descendants: bad argument");
+    *n_out = 0; *out = nullptr;
+    IdIndex pos;
+    pos.init(n_ind, ind);
+    std::vector<int64_t> stack, found, start;
+    std::vector<int32_t> child;
+    for (int64_t k = 0; k < n_ids; ++k) {
+        const int32_t r = pos.find(ids[k]);
+        if (r < 0) return genphi_set_error(GENPHI_ERR_UNKNOWN_ID, "KeyError: individual " + std::to_string(ids[k]) + " not found");
+        stack.push_back(r);                          // (an ID is not its own descendant: it is searched, not flagged)
+    }
+    if (int rc = child_lists("genphi_descendants", pos, n_ind, ind, father, mother, start, child)) return rc;
+    std::vector<uint8_t> seen(n_ind, 0);
+    while (!stack.empty()) {
+        const int64_t i = stack.back();
+        stack.pop_back();
+        for (int64_t e = start[i]; e < start[i + 1]; ++e) {
+            const int32_t c = child[e];
+            if (seen[c]) continue;                   // its descendants are on the stack or done
+            seen[c] = 1;
+            found.push_back(ind[c]);
+            stack.push_back(c);
+        }
+    }
+    return ids_out(found, n_out, out);
+}
+
+// gen.children (src/identify.jl:77-80): the children of one ID, ascending: one scan of the parent arrays (a single query does not
+// pay for the child lists).  *out is allocated by the library (genphi_free).
+int genphi_children(int64_t n_ind, const int64_t *ind, const int64_t *father, const int64_t *mother, int64_t id, int64_t *n_out, int64_t **out)
+{
+    if (!n_out || !out || n_ind < 0 || n_ind >= INT32_MAX || (n_ind > 0 && (!ind || !father || !mother)))
+        return genphi_set_error(GENPHI_ERR_ARG, "genphi_children: bad argument");
+    *n_out = 0; *out = nullptr;
+    IdIndex pos;
+    pos.init(n_ind, ind);
+    if (id == 0 || pos.find(id) < 0) return genphi_set_error(GENPHI_ERR_UNKNOWN_ID, "KeyError: individual " + std::to_string(id) + " not found");
+    std::vector<int64_t> found;
+    for (int64_t i = 0; i < n_ind; ++i)
+        if (father[i] == id || mother[i] == id) found.push_back(ind[i]);
+    return ids_out(found, n_out, out);
+}
+
 // The last step of _findMRCA (src/identify.jl:97-103): of the common ancestors of a group, keep those that are not an ancestor of
 // another common ancestor -- the reference's setdiff(common, ancestor(common)).  Every individual on a path between a common
 // ancestor and one of its ancestors is itself common (it is an ancestor of whoever the path leads down to), so a common ancestor

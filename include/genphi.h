@@ -607,6 +607,79 @@ int genphi_implex_stats(const genphi_implex *h, double *sweep_ms, double *algori
                         int64_t *panels, int32_t *lanes_per_row, int64_t *peak_rows);
 void genphi_implex_destroy(genphi_implex *h);
 
+/* ---- gen.simuSample and gen.simuProb: gene dropping (csrc/simu.hip, csrc/simu.cpp, csrc/loader.cpp) ------------------------------
+ * GENLIB's gen.simuSample and gen.simuProb; the reference has no form of them, so this text is the definition.  Marked alleles of
+ * chosen ancestors are dropped down the pedigree S times and counted in the probands.
+ * Inputs: a pedigree; pro_ids, the listed probands (any individuals, repeats allowed); anc_ids with anc_states, each 0, 1 or 2:
+ * the copies of the marked allele the ancestor carries; simul_no = S >= 1; a 64-bit seed.
+ * State.  Every individual x has two bit rows over the simulations, P_x and M_x: bit s of P_x says that in simulation s the copy
+ * x received from its father is marked, M_x the same for its mother.  Simulation s is bit s % 64 of word w = s / 64.
+ * Rules.
+ *   - A listed ancestor with state t is fixed: t = 0: P = M = 0; t = 1: P = all ones, M = 0; t = 2: both all ones.  Its own
+ *     parents are ignored: a listed ancestor blocks every path through it, a state-0 ancestor included.
+ *   - Any other x with a known father f: P_x[w] = (T & P_f[w]) | (~T & M_f[w]) with T = R(seed, ID(x), 0, w); with a known
+ *     mother m the same from P_m, M_m with T = R(seed, ID(x), 1, w).  An unknown parent gives a zero row.  Under selfing
+ *     (father = mother) the two sides still draw independent words.
+ *   - The count of x in simulation s is bit(P_x) + bit(M_x), in {0, 1, 2}.  Bits at positions >= S are never counted.
+ * The random words.  R(seed, ID, side, w) is Philox4x32-10: multipliers M0 = 0xD2511F53, M1 = 0xCD9E8D57, Weyl constants
+ * 0x9E3779B9, 0xBB67AE85; a round is c <- (hi(M1 c2) ^ c1 ^ k0, lo(M1 c2), hi(M0 c0) ^ c3 ^ k1, lo(M0 c0)) and the key is bumped
+ * after each round; key = (seed low 32, seed high 32), counter = (ID low 32, ID high 32, w >> 1, side).  Of the four 32-bit
+ * outputs o0..o3, word w is o0 | o1 << 32 for even w and o2 | o3 << 32 for odd w: one block yields one 16-byte pair of words.
+ * Known answers (counter; key; output): 0,0,0,0; 0,0; 6627e8d5 e169c58d bc57ac4c 9b00dbd8.  All ffffffff; all ffffffff;
+ * 408f276d 41c83b0e a20bc7c6 6d5451fd.  243f6a88 85a308d3 13198a2e 03707344; a4093822 299f31d0; d16cfe09 94fdcceb 5001e420 24126ea1.
+ * Invariants.  The stream is keyed on the individual's ID and the absolute word index, not on a rank, a position in a pruned
+ * set, a panel or a launch: the result is a pure function of (pedigree relations, ancestors and states, seed).  So it does not
+ * depend on how the simulations are split into panels; S = 64 gives the first 64 columns of S = 5000; a sub-list of probands
+ * gives the same rows; pruning the pedigree to the paths between probands and ancestors first changes no row of the probands that pruning
+ * keeps (it drops a proband below no listed ancestor, whose row is zero, and an ancestor above no listed proband, which marks no
+ * row; a dropped ID is then unknown to the pruned pedigree).
+ * Errors.  An unknown ID -> GENPHI_ERR_UNKNOWN_ID.  GENPHI_ERR_ARG: a state outside 0..2; an ancestor listed twice with
+ * different states (equal repeats are allowed); S < 1 or S > GENPHI_SIMU_MAX_SIMULATIONS = 2^24; no probands; no ancestors.
+ * Method.  The live set L = the individuals that are reachable downwards from a listed ancestor of state >= 1 without passing
+ * through another listed ancestor (the carrier included) and that are a listed proband or an ancestor of one; everyone else has
+ * zero rows for certain and gets no row.  level = 0 for the listed ancestors in L, else 1 + the largest level of the live
+ * parents; one launch per level and panel.  Simulations are swept in panels of a multiple of 128 columns: one panel when the
+ * rows (2 x n_live x pairs x 16 bytes) and the results fit the free device memory, else the widest that fits.
+ *   create            host only (no GPU): checks IDs, states and pedigree order; plans L, the levels and the parent rows, O(n_ind).
+ *                     GENPHI_SIMU_FLAG_NO_SAMPLE: no Int8 sample is allocated or written
+ *   levels            n_live, the number of levels, and the rows of every level (room for that many); host only, any may be NULL
+ *   rows              host only, any may be NULL: per row (n_live, ordered by level) the ID and the rows of its father and mother
+ *                     (-1 = a zero row); per listed proband its row, -1 = not live (a row of zeros), or -2 - state for a listed
+ *                     ancestor (its count is its state in every simulation)
+ *   compute           the sweep on `device` (-1 = current); state counts and sample stay resident; GENPHI_ERR_ALLOC before any
+ *                     launch when the rows of even a 128-column panel and the results do not fit
+ *   sample_to_host    out: n_pro x S Int8, row-major: the count of proband i in simulation s; GENPHI_ERR_ARG under NO_SAMPLE
+ *   state_counts      out: n_pro x 3 Int64, row-major: the simulations in which proband i carries 0, 1, 2 copies
+ *   match_counts      state_pro: n_pro states in 0..2; out: S Int32: per simulation, the listed probands i whose count equals
+ *                     state_pro[i].  May be called repeatedly with other states: a sweep of one panel left its rows resident
+ *                     and they are only read; a sweep of several panels is swept again (the same bits) on every call
+ *   stats             device time of the last compute (HIP events); its algorithmic bytes (per live row above level 0: two
+ *                     parent rows read and one written, 32 bytes per pair of words, over the panels); the levels; the columns
+ *                     of a panel; the panels; the lanes per row of the step kernel; n_live                                      */
+#define GENPHI_SIMU_MAX_SIMULATIONS (1 << 24)
+#define GENPHI_SIMU_FLAG_NO_SAMPLE 1   /* state and match counts only */
+typedef struct genphi_simu genphi_simu;
+int genphi_simu_create(int64_t n_ind, const int64_t *ind, const int64_t *father, const int64_t *mother,
+                       int64_t n_pro, const int64_t *pro_ids, int64_t n_anc, const int64_t *anc_ids, const int32_t *anc_states,
+                       int64_t simul_no, uint64_t seed, int32_t flags, genphi_simu **out);
+int genphi_simu_levels(const genphi_simu *h, int64_t *n_live, int32_t *levels, int64_t *rows_per_level);
+int genphi_simu_rows(const genphi_simu *h, int64_t *row_ids, int32_t *father_rows, int32_t *mother_rows, int64_t *pro_positions);
+int genphi_simu_compute(genphi_simu *h, int32_t device);
+int genphi_simu_sample_to_host(genphi_simu *h, int8_t *out);
+int genphi_simu_state_counts(genphi_simu *h, int64_t *out);
+int genphi_simu_match_counts(genphi_simu *h, const int32_t *state_pro, int32_t *out);
+int genphi_simu_stats(const genphi_simu *h, double *sweep_ms, double *algorithmic_bytes, int32_t *levels, int32_t *panel_cols,
+                      int64_t *panels, int32_t *lanes_per_row, int64_t *n_live);
+void genphi_simu_destroy(genphi_simu *h);
+
+/* gen.descendant and gen.children (src/identify.jl:203-215, :77-80), host only: the strict descendants of ids[0 .. n_ids) (the
+ * union over them), and the children of one ID, ascending; *out is allocated by the library (genphi_free).  No order of the
+ * pedigree is assumed.  Unknown ID -> GENPHI_ERR_UNKNOWN_ID.                                                                  */
+int genphi_descendants(int64_t n_ind, const int64_t *ind, const int64_t *father, const int64_t *mother, int64_t n_ids,
+                       const int64_t *ids, int64_t *n_out, int64_t **out);
+int genphi_children(int64_t n_ind, const int64_t *ind, const int64_t *father, const int64_t *mother, int64_t id, int64_t *n_out,
+                    int64_t **out);
+
 /* Frees host and device memory of the plan (NULL is allowed). */
 void genphi_plan_destroy(genphi_plan *plan);
 
