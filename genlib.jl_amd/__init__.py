@@ -792,3 +792,66 @@ def phiMeanGroups(pedigree, groups, probandIDs=None, device=None):
                 del pedigree._plans[key]
             pl.close()
     return GroupMeans(names, sizes, _capi.mean_from_group_sums(sums, diag, sizes))
+
+
+class PhiOver:
+    """What gen.phiOver returns: the pairs of probands whose kinship is at or above the threshold, as parallel arrays sorted by
+    `row`, then `col`: `row` < `col` (int32, 0-based positions in the order of the probands), `pro1` / `pro2` (int64 IDs of those
+    positions, None when no IDs were given with a host matrix) and `kinship` (float32, the matrix entries bit for bit)."""
+
+    def __init__(self, threshold, row, col, pro1, pro2, kinship):
+        self.threshold, self.row, self.col, self.pro1, self.pro2, self.kinship = threshold, row, col, pro1, pro2, kinship
+
+    def __len__(self):
+        return len(self.row)
+
+    def __repr__(self):
+        lines = ["PhiOver: %d pairs with kinship >= %g" % (len(self), self.threshold)]
+        for k in range(min(len(self), 5)):
+            a, b = (self.row[k], self.col[k]) if self.pro1 is None else (self.pro1[k], self.pro2[k])
+            lines.append("%d %d %.6g" % (a, b, self.kinship[k]))
+        if len(self) > 5:
+            lines.append("...")
+        return "\n".join(lines)
+
+
+def phiOver(x, threshold, probandIDs=None, device=None):
+    """GENLIB's gen.phiOver(phiMatrix, threshold): the pairs of probands related at or above `threshold`.  Returns a PhiOver.
+
+    x a Pedigree: gen.phi's sweep for probandIDs (default gen.pro), then the selection on the device from the resident matrix,
+    which is never copied (genphi_result_over; two passes over its upper triangle).  x a host matrix (GENLIB's own
+    signature): the same selection in numpy on its strict upper triangle; pro1 / pro2 come from probandIDs if given.
+
+    The definition is this package's own: a pair (i, j) is listed when i < j and float64(Phi[i, j]) >= threshold, each pair
+    once, in row-major order, with 0-based positions (duplicate probandIDs collapsed, as gen.phi does).  GENLIB's R function could
+    not be consulted when this was written: its column names and its 1-based `line` / `column` are not reproduced.
+    ValueError for a NaN threshold, KeyError for an unknown proband ID."""
+    threshold = float(threshold)
+    if threshold != threshold:
+        raise ValueError("the threshold is NaN")
+    if isinstance(x, Pedigree):
+        ids = pro(x) if probandIDs is None else np.ascontiguousarray(probandIDs, dtype=np.int64)
+        x.positions(ids)                                        # KeyError on an unknown ID
+        pl, key = _plan_for(x, ids, device)
+        keep = False
+        try:
+            pl.compute_device(device=device)
+            row, col, val = pl.phi_over(threshold)
+            keep = key is not None and _keep_plan(x, key, pl, ids)
+        finally:
+            if not keep:
+                if key is not None and key in x._plans and x._plans[key][0] is pl:
+                    del x._plans[key]
+                pl.close()
+        _, first = np.unique(ids, return_index=True)
+        ids = ids[np.sort(first)]                               # duplicates collapse: first occurrences, in order
+        return PhiOver(threshold, row, col, ids[row], ids[col], val)
+    m = np.asarray(x, dtype=np.float32)
+    if m.ndim != 2 or m.shape[0] != m.shape[1]:
+        raise ValueError("gen.phiOver takes a Pedigree or a square kinship matrix, got shape %s" % (m.shape,))
+    ids = None if probandIDs is None else np.asarray(probandIDs, dtype=np.int64)
+    if ids is not None and ids.shape != (len(m),):
+        raise ValueError("probandIDs must name the %d rows of the matrix" % len(m))
+    row, col = np.nonzero(np.triu(m.astype(np.float64) >= threshold, 1))
+    row, col = row.astype(np.int32), col.astype(np.int32)
+    return PhiOver(threshold, row, col, None if ids is None else ids[row], None if ids is None else ids[col], m[row, col])

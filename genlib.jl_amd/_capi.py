@@ -48,7 +48,7 @@ class GenphiStats(C.Structure):
 EXPORTED_SYMBOLS = [
     "genphi_plan_create", "genphi_plan_create_tuned", "genphi_tuning_create", "genphi_tuning_set", "genphi_tuning_destroy", "genphi_plan_levels", "genphi_plan_n_probands", "genphi_plan_step_mode", "genphi_plan_step_info", "genphi_plan_step_slots",
     "genphi_plan_algorithmic_bytes", "genphi_plan_device_bytes", "genphi_plan_device_bytes_needed", "genphi_plan_sparse_levels", "genphi_plan_step_walk", "genphi_plan_set_step_hook", "genphi_compute_device", "genphi_result_device",
-    "genphi_result_to_host", "genphi_result_to_host_f64", "genphi_phi_pairs", "genphi_result_sums", "genphi_result_group_sums", "genphi_result_entries",
+    "genphi_result_to_host", "genphi_result_to_host_f64", "genphi_phi_pairs", "genphi_result_sums", "genphi_result_group_sums", "genphi_result_over", "genphi_result_entries",
     "genphi_compute_f32",
     "genphi_genealogy_read", "genphi_branching", "genphi_free", "genphi_release_cached", "genphi_cached_bytes", "genphi_plan_release_device", "genphi_plan_destroy",
     "genphi_last_error",
@@ -142,6 +142,8 @@ def lib():
         L.genphi_result_group_sums.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double), _I64P, _I64P,
                                                C.POINTER(C.c_int32)]
         L.genphi_result_group_sums.restype = C.c_int
+        L.genphi_result_over.argtypes = [C.c_void_p, C.c_double, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _F32P, _I64P]
+        L.genphi_result_over.restype = C.c_int
         L.genphi_result_entries.argtypes = [C.c_void_p, C.c_int64, _I64P, _I64P, C.POINTER(C.c_double)]
         L.genphi_result_entries.restype = C.c_int
         L.genphi_branching.argtypes = [C.c_int64, _I64P, _I64P, _I64P, _I64P, C.c_int64, _I64P, C.c_int64, _I64P,
@@ -644,6 +646,33 @@ class PhiPlan:
         if int(rows.sum()) != int(cols.sum()):
             raise ValueError("phi_mean_groups needs all rows resident; combine group_sums() of the shards instead")
         return mean_from_group_sums(sums, diag, cols)
+
+    def count_over(self, threshold):
+        """Number of pairs phi_over(threshold) lists: the counting pass of genphi_result_over alone, one read of the resident
+        upper triangle."""
+        n = C.c_int64()
+        rc = lib().genphi_result_over(self._h, float(threshold), 0, None, None, None, C.byref(n))
+        if rc:
+            _raise(rc)
+        return int(n.value)
+
+    def phi_over(self, threshold):
+        """(rows int32, cols int32, values float32): the pairs i < j of the RESIDENT rows with Phi[i, j] >= threshold, 0-based
+        positions in proband order, sorted by row, then column, selected on the device (genphi_result_over); the
+        matrix is not copied.  The lists of consecutive row shards concatenate to the list of the full result.  ValueError for
+        a NaN threshold or a Float64 result, GenphiDeviceError without a resident result."""
+        n = self.count_over(threshold)
+        rows, cols, vals = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32), np.empty(n, dtype=np.float32)
+        if n:
+            i32 = C.POINTER(C.c_int32)
+            got = C.c_int64()
+            rc = lib().genphi_result_over(self._h, float(threshold), n, rows.ctypes.data_as(i32), cols.ctypes.data_as(i32),
+                                          vals.ctypes.data_as(_F32P), C.byref(got))
+            if rc:
+                _raise(rc)
+            if got.value != n:
+                raise GenphiDeviceError("genphi_result_over counted %d pairs, then %d" % (n, got.value))
+        return rows, cols, vals
 
     def compute(self, device=None, kernel=0, rows=None, timing=False, no_sparse=False):
         self.compute_device(device=device, kernel=kernel, rows=rows, timing=timing, no_sparse=no_sparse)

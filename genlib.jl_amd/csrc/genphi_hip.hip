@@ -1821,6 +1821,86 @@ __global__ void row_sums_kernel(const float *m, long long ld, int n, int row_beg
     if (threadIdx.x == 0) { row_sum[k] = part[0]; diag[k] = static_cast<double>(row[row_begin + k]); }
 }
 
+// gen.phiOver support (genphi_result_over): the pairs (i, j), i < j < n, of the resident rows with
+// (double)Phi[i][j] >= t, listed by row, then by column.  One workgroup per resident row walks the columns right of the diagonal
+// in place, a tile of kOverTile columns at a time, one quad per thread.  The first quad of a row is loaded whole (16-byte
+// aligned; ld is a multiple of 64) and its columns <= i are masked out; so are the padding columns >= n, which a threshold
+// <= 0 would select.  over_count_kernel leaves one count per row; the host turns the counts into offsets; over_write_kernel
+// repeats the walk and gives every hit its place by an exclusive scan over the tile (three ballots over the bits of the
+// per-thread counts 0..4, the four wave totals through LDS): no atomics, so the order is row, column whatever the launch
+// geometry.  Both kernels test the same bits with the same expression, so the second pass finds what the first counted.
+constexpr int kOverTile = 1024;         // columns of a tile: 256 threads x one quad
+
+__device__ __forceinline__ unsigned over_hits(const float4 v, int jq, int i, int n, double t)
+{
+    // bit e = column jq + e is listed: right of the diagonal, left of the padding, at or above the threshold
+    const int lo = min(max(i + 1 - jq, 0), 4), hi = min(max(n - jq, 0), 4);
+    const unsigned valid = (0xFu << lo) & ~(0xFu << hi) & 0xFu;
+    const unsigned h = (static_cast<double>(v.x) >= t ? 1u : 0u) | (static_cast<double>(v.y) >= t ? 2u : 0u) |
+                       (static_cast<double>(v.z) >= t ? 4u : 0u) | (static_cast<double>(v.w) >= t ? 8u : 0u);
+    return h & valid;
+}
+
+__global__ __launch_bounds__(256) void over_count_kernel(const float *__restrict__ m, long long ld, int n, int row_begin, double t,
+                                                         long long *__restrict__ row_count)
+{
+    __shared__ int part[4];
+    const int k = blockIdx.x, i = row_begin + k;
+    const float *row = m + (long long)k * ld;
+    int cnt = 0;
+#pragma unroll 4
+    for (int jq = ((i + 1) & ~3) + (int)threadIdx.x * 4; jq < n; jq += kOverTile)
+        cnt += __popc(over_hits(*reinterpret_cast<const float4 *>(row + jq), jq, i, n, t));
+    for (int s = 32; s > 0; s >>= 1) cnt += __shfl_down(cnt, s);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) row_count[k] = (long long)part[0] + part[1] + part[2] + part[3];
+}
+
+// row_off: nr + 1 offsets (exclusive scan of the counts); total = row_off[nr], the entries of each output array
+__global__ __launch_bounds__(256) void over_write_kernel(const float *__restrict__ m, long long ld, int n, int row_begin, double t,
+                                                         const long long *__restrict__ row_off, long long total,
+                                                         int *__restrict__ out_row, int *__restrict__ out_col, float *__restrict__ out_val)
+{
+    __shared__ int wtot[2][4];
+    const int k = blockIdx.x, i = row_begin + k;
+    long long base = row_off[k];
+    if (row_off[k + 1] == base) return;                  // (the whole workgroup) a row without a hit is not read again
+    const float *row = m + (long long)k * ld;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+    int jq = ((i + 1) & ~3) + (int)threadIdx.x * 4;
+    float4 v = zero;
+    if (jq < n) v = *reinterpret_cast<const float4 *>(row + jq);
+    for (int j0 = (i + 1) & ~3, par = 0; j0 < n; j0 += kOverTile, jq += kOverTile, par ^= 1) {
+        float4 nxt = zero;
+        if (jq + kOverTile < n) nxt = *reinterpret_cast<const float4 *>(row + jq + kOverTile);      // in flight across the scan
+        const unsigned hits = over_hits(v, jq, i, n, t);              // (jq >= n: every column masked)
+        const int c = __popc(hits);
+        const unsigned long long b0 = __ballot(c & 1), b1 = __ballot(c & 2), b2 = __ballot(c & 4);
+        const unsigned long long below = (1ull << lane) - 1ull;
+        const int before = __popcll(b0 & below) + 2 * __popcll(b1 & below) + 4 * __popcll(b2 & below);
+        if (lane == 0) wtot[par][wave] = __popcll(b0) + 2 * __popcll(b1) + 4 * __popcll(b2);
+        __syncthreads();                                 // one barrier per tile: tile T + 2 reuses wtot[par] only after every wave passed T + 1's
+        int wbase = 0, tile_total = 0;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            const int x = wtot[par][w];
+            if (w < wave) wbase += x;
+            tile_total += x;
+        }
+        long long pos = base + wbase + before;
+        if (pos + c <= total) {                          // always true while counts and result belong together; never write past the lists
+            if (hits & 1u) { out_row[pos] = i; out_col[pos] = jq; out_val[pos] = v.x; ++pos; }
+            if (hits & 2u) { out_row[pos] = i; out_col[pos] = jq + 1; out_val[pos] = v.y; ++pos; }
+            if (hits & 4u) { out_row[pos] = i; out_col[pos] = jq + 2; out_val[pos] = v.z; ++pos; }
+            if (hits & 8u) { out_row[pos] = i; out_col[pos] = jq + 3; out_val[pos] = v.w; ++pos; }
+        }
+        base += tile_total;
+        v = nxt;
+    }
+}
+
 // Group sums of the resident result (genphi_result_group_sums): T = Phi B summed over blocks of rows.
 // A workgroup owns a block of at most kGsBlockRows resident rows of ONE group and a slab of column tiles (kGsTile columns
 // each).  Per tile a thread keeps the Float64 column sums of its quad over the block's rows, read in place with 16-byte
@@ -2352,6 +2432,13 @@ struct genphi_plan {
     bool res_f64 = false;                        // the resident result is the Float64 one
     size_t result_floats = 0, final_tmp_floats = 0;
     int64_t res_ld = 0, res_row_begin = 0, res_n_rows = 0;
+    bool res_known = false;                      // a genphi_compute_device call has set the resident row range (it may be empty)
+    // genphi_result_over: offsets (exclusive scan of the per-row counts, res_n_rows + 1 entries) of the last threshold counted on
+    // the resident result, so that a count-only call followed by a filling call runs the counting pass once.  Dropped whenever
+    // the result is recomputed or released.
+    std::vector<int64_t> over_off;
+    double over_threshold = 0.0;
+    bool over_valid = false;
     // zero-aware leading levels (sparse_levels.h): created and calibrated by the first product sweep of the plan
     genphi::SparseLevels *sparse = nullptr;
     bool sparse_tried = false;
@@ -2398,7 +2485,8 @@ static void free_device(genphi_plan *p)
     p->shard_cap = 0; p->shard_r0 = p->shard_r1 = -1;
     p->buf_floats[0] = p->buf_floats[1] = 0; p->level_bufs_ready = false;
     p->result_floats = p->final_tmp_floats = 0; p->scratch_bytes = 0;
-    p->res_ld = 0; p->res_row_begin = 0; p->res_n_rows = 0;
+    p->res_ld = 0; p->res_row_begin = 0; p->res_n_rows = 0; p->res_known = false;
+    p->over_valid = false; p->over_off.clear();
     genphi::cached_stream_release(p->stream, p->device);
     p->stream = nullptr;
     p->on_device = false;
@@ -3672,7 +3760,8 @@ int genphi_compute_device(genphi_plan *p, const genphi_opts *opts, genphi_stats 
         stats->algorithmic_bytes = pl.algorithmic_bytes;
         stats->max_cut = pl.max_cut;
     }
-    p->res_row_begin = r0; p->res_n_rows = r1 - r0;
+    p->res_row_begin = r0; p->res_n_rows = r1 - r0; p->res_known = true;
+    p->over_valid = false;                    // (genphi_result_over) counts of the previous result
     const int L = pl.n_levels;
     if (L == 0 || r1 == r0) { p->res_ld = 0; return GENPHI_OK; }
 
@@ -4324,6 +4413,71 @@ int genphi_result_sums(genphi_plan *p, double *sum_all, double *sum_diag, int64_
     for (int64_t k = 0; k < nr; ++k) { sa += h[k]; sd += h[nr + k]; }
     if (sum_all) *sum_all = sa;
     if (sum_diag) *sum_diag = sd;
+    return GENPHI_OK;
+}
+
+// gen.phiOver: counting pass -> offsets on the host (in row order, as genphi_result_sums adds its row sums) ->
+// writing pass into three lists in the plan's scratch block -> one copy per array the caller asked for.
+int genphi_result_over(genphi_plan *p, double threshold, int64_t cap, int32_t *rows, int32_t *cols, float *values, int64_t *n_pairs)
+{
+    if (!p) return fail(GENPHI_ERR_ARG, "plan is NULL");
+    if (n_pairs) *n_pairs = 0;
+    if (threshold != threshold) return fail(GENPHI_ERR_ARG, "genphi_result_over: the threshold is NaN");
+    if (cap < 0) return fail(GENPHI_ERR_ARG, "genphi_result_over: cap = " + std::to_string(cap) + " is negative");
+    const int64_t N = p->plan.n_pro, nr = p->res_n_rows;
+    if (N < 2 || (p->res_known && nr == 0)) return GENPHI_OK;
+    if (p->res_f64) return fail(GENPHI_ERR_ARG, "genphi_result_over works on the Float32 result (gen.phi's matrix)");
+    if (!p->on_device || !p->result || nr == 0) return fail(GENPHI_ERR_DEVICE, "no resident result: call genphi_compute_device first");
+    HIP_TRY(hipSetDevice(p->device));
+    const size_t off_bytes = (static_cast<size_t>(nr + 1) * sizeof(long long) + 255) / 256 * 256;
+    auto scratch = [&](size_t bytes, const char *what) {
+        if (ensure_scratch(p, bytes) == GENPHI_OK) return GENPHI_OK;
+        return fail(GENPHI_ERR_ALLOC, "genphi_result_over: " + std::to_string(bytes) + " bytes of device memory for " + what + ": " + g_last_error);
+    };
+    const long long ld = static_cast<long long>(p->res_ld);
+    const int n = static_cast<int>(N), r0 = static_cast<int>(p->res_row_begin);
+    const bool same = p->over_valid && static_cast<int64_t>(p->over_off.size()) == nr + 1 &&
+                      std::memcmp(&p->over_threshold, &threshold, sizeof(double)) == 0;
+    if (!same) {
+        p->over_valid = false;
+        int rc = scratch(off_bytes, "the per-row counts");
+        if (rc) return rc;
+        long long *d_cnt = reinterpret_cast<long long *>(p->scratch);
+        hipLaunchKernelGGL(over_count_kernel, dim3(static_cast<unsigned>(nr)), dim3(256), 0, p->stream, p->result, ld, n, r0, threshold, d_cnt);
+        hipError_t e = hipGetLastError();
+        std::vector<long long> h(static_cast<size_t>(nr));
+        if (e == hipSuccess) e = hipMemcpyAsync(h.data(), d_cnt, static_cast<size_t>(nr) * sizeof(long long), hipMemcpyDeviceToHost, p->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
+        if (e != hipSuccess) return fail(GENPHI_ERR_DEVICE, std::string("genphi_result_over (counting pass): ") + hipGetErrorString(e));
+        p->over_off.assign(static_cast<size_t>(nr) + 1, 0);
+        for (int64_t k = 0; k < nr; ++k) p->over_off[k + 1] = p->over_off[k] + h[k];
+        p->over_threshold = threshold;
+        p->over_valid = true;
+    }
+    const int64_t total = p->over_off[nr];
+    if (n_pairs) *n_pairs = total;
+    if (total == 0 || total > cap || (!rows && !cols && !values)) return GENPHI_OK;
+
+    const size_t list_bytes = (static_cast<size_t>(total) * 4 + 255) / 256 * 256;
+    int rc = scratch(off_bytes + 3 * list_bytes, "the list of pairs (12 bytes each)");
+    if (rc) return rc;
+    long long *d_off = reinterpret_cast<long long *>(p->scratch);
+    int *d_row = reinterpret_cast<int *>(p->scratch + off_bytes), *d_col = reinterpret_cast<int *>(p->scratch + off_bytes + list_bytes);
+    float *d_val = reinterpret_cast<float *>(p->scratch + off_bytes + 2 * list_bytes);
+    static_assert(sizeof(long long) == sizeof(int64_t), "the offsets are uploaded as they are");
+    hipError_t e = hipMemcpyAsync(d_off, p->over_off.data(), static_cast<size_t>(nr + 1) * sizeof(long long), hipMemcpyHostToDevice, p->stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(over_write_kernel, dim3(static_cast<unsigned>(nr)), dim3(256), 0, p->stream, p->result, ld, n, r0, threshold,
+                           d_off, static_cast<long long>(total), d_row, d_col, d_val);
+        e = hipGetLastError();
+    }
+    const size_t out_bytes = static_cast<size_t>(total) * 4;
+    if (e == hipSuccess && rows) e = hipMemcpyAsync(rows, d_row, out_bytes, hipMemcpyDeviceToHost, p->stream);
+    if (e == hipSuccess && cols) e = hipMemcpyAsync(cols, d_col, out_bytes, hipMemcpyDeviceToHost, p->stream);
+    if (e == hipSuccess && values) e = hipMemcpyAsync(values, d_val, out_bytes, hipMemcpyDeviceToHost, p->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
+    else (void)hipStreamSynchronize(p->stream);          // (the host vector and the caller's arrays outlive what was enqueued)
+    if (e != hipSuccess) return fail(GENPHI_ERR_DEVICE, std::string("genphi_result_over: ") + hipGetErrorString(e));
     return GENPHI_OK;
 }
 

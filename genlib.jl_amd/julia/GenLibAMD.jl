@@ -242,6 +242,37 @@ function phiMeanGroups(pedigree::GenLib.Pedigree, groups::Dict{Int, String}, pro
 end
 
 """
+    phiOver(pedigree::GenLib.Pedigree, threshold::Real, probandIDs::Vector{Int} = GenLib.pro(pedigree); device::Integer = -1)
+
+GENLIB's `gen.phiOver`: the pairs of probands with kinship at or above `threshold`, as `(row, col, pro1, pro2, kinship)`: positions
+`row < col` in the order of `unique(probandIDs)` (1-based here), the IDs at those positions and the `Float32` entries of `phi`, sorted
+by row, then column; each pair once.  The matrix stays on the GPU: `genphi_result_over` selects there, in two passes over its upper
+triangle (count, then write).  The reference has no `phiOver`; the definition (`>=`, the strict upper triangle, row-major order) is
+this package's own.
+"""
+function phiOver(pedigree::GenLib.Pedigree, threshold::Real, probandIDs::Vector{Int} = GenLib.pro(pedigree); device::Integer = -1)
+    isnan(threshold) && throw(ArgumentError("the threshold is NaN"))
+    ordered = unique(probandIDs)
+    foreach(ID -> pedigree[ID], ordered)                                    # KeyError on unknown ID
+    plan = create_plan(pedigree, ordered, nothing)
+    try
+        opts = Ref(GenphiOpts(Int32(device), 0, 0, 0, 0, 0))
+        check(ccall((:genphi_compute_device, libgenphi), Cint, (Ptr{Cvoid}, Ptr{GenphiOpts}, Ptr{Cvoid}), plan, opts, C_NULL))
+        n = Ref{Int64}(0)
+        over(cap, rows, cols, values) = check(ccall((:genphi_result_over, libgenphi), Cint,
+            (Ptr{Cvoid}, Float64, Int64, Ptr{Int32}, Ptr{Int32}, Ptr{Float32}, Ptr{Int64}),
+            plan, Float64(threshold), cap, rows, cols, values, n))
+        over(0, C_NULL, C_NULL, C_NULL)                                     # count only
+        rows = Vector{Int32}(undef, n[]); cols = Vector{Int32}(undef, n[]); kinship = Vector{Float32}(undef, n[])
+        GC.@preserve rows cols kinship over(length(rows), rows, cols, kinship)
+        row = Int.(rows) .+ 1; col = Int.(cols) .+ 1
+        return (row = row, col = col, pro1 = ordered[row], pro2 = ordered[col], kinship = kinship)
+    finally
+        destroy_plan(plan)
+    end
+end
+
+"""
     KinshipMatrix, sparse_phi(pedigree, probandIDs = GenLib.pro(pedigree); device = -1)
 
 As `GenLib.sparse_phi` / `GenLib.KinshipMatrix` (src/compute.jl:321-447, :31-46): `ϕ[ID₁, ID₂]`,

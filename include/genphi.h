@@ -232,6 +232,29 @@ int genphi_result_sums(genphi_plan *plan, double *sum_all, double *sum_diag, int
 int genphi_result_group_sums(genphi_plan *plan, int32_t n_groups, const int32_t *group, double *sums, double *diag,
                              int64_t *rows_in_group, int64_t *cols_in_group, int32_t *form);
 
+/* GENLIB's gen.phiOver(phiMatrix, threshold) on the resident result, without moving the matrix: the related pairs, selected on the
+ * device in two passes over the upper triangle.  The reference has no phiOver, so this text is the definition.
+ *   listed            every pair (i, j) with i in the resident rows [row_begin, row_begin + n_rows), i < j < N and
+ *                     (double)Phi[i][j] >= threshold: 0-based positions in proband order (duplicates collapsed as in
+ *                     genphi_plan_create), each unordered pair once, never the diagonal, never a padding column of the row pitch
+ *   order             by row, then by column; it depends on the result and the threshold alone (no atomics place an entry), so the
+ *                     same call returns the same bytes and the lists of consecutive row shards, concatenated, are the full list
+ *   threshold         any double but NaN; +infinity lists nothing, -infinity every pair
+ *   *n_pairs          always the total count (may be NULL)
+ *   rows, cols, values  caller-owned arrays of `cap` entries, each may be NULL.  With cap >= *n_pairs every array given receives
+ *                     *n_pairs entries, values[k] being the Float32 entry Phi[rows[k]][cols[k]] bit for bit; with cap < *n_pairs
+ *                     nothing is written.  All three NULL is the count-only call: the counting pass alone, one read of the
+ *                     upper triangle (2 N^2 bytes); a filling call reads it twice.  The library keeps the per-row counts of the
+ *                     last threshold until the result is recomputed or released: a count-only call followed by a filling call
+ *                     with the same threshold counts once.
+ * An empty result (no resident row, or N < 2) is GENPHI_OK with 0 pairs.  Device memory: 8 bytes per resident row and 12 bytes per
+ * listed pair, in the plan's scratch block, kept between calls.
+ * GENPHI_ERR_ARG: NULL plan, NaN threshold, cap < 0, a Float64 result (GENPHI_FLAG_STORAGE_F64); GENPHI_ERR_DEVICE: no resident
+ * result; GENPHI_ERR_ALLOC: the counts or the list do not fit in device memory (found before the writing pass is launched).  After
+ * any error the plan stays usable and the resident result is untouched.                                                          */
+int genphi_result_over(genphi_plan *plan, double threshold, int64_t cap, int32_t *rows, int32_t *cols, float *values,
+                       int64_t *n_pairs);
+
 /* Point lookups in the resident result without moving the matrix: out[k] = Phi[rows[k], cols[k]]
  * (0-based positions in proband order, duplicates collapsed as in genphi_plan_create; rows must
  * lie in the resident row range).  This is what gen.f(pedigree, IDs) (src/compute.jl:500-511)
