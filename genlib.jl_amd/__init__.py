@@ -855,3 +855,105 @@ def phiOver(x, threshold, probandIDs=None, device=None):
     row, col = np.nonzero(np.triu(m.astype(np.float64) >= threshold, 1))
     row, col = row.astype(np.int32), col.astype(np.int32)
     return PhiOver(threshold, row, col, None if ids is None else ids[row], None if ids is None else ids[col], m[row, col])
+
+
+DEFAULT_CI_PROB = (0.025, 0.05, 0.95, 0.975)
+
+
+class PhiCI:
+    """What gen.phiCI and gen.fCI return: `prob` and the `quantiles` of the bootstrap distribution at them (float64, linear
+    interpolation of the sorted values: R's type 7), `mean` (the observed statistic: gen.phiMean of the matrix, or the mean of
+    vectF), `thetastar` (float64, the statistic of each of the `b` resamples, in resample order) and the `seed` that repeats them."""
+
+    def __init__(self, prob, quantiles, mean, thetastar, b, seed):
+        self.prob, self.quantiles, self.mean, self.thetastar, self.b, self.seed = prob, quantiles, mean, thetastar, b, seed
+
+    def __repr__(self):
+        return "PhiCI: mean %.6g, b = %d\n" % (self.mean, self.b) + "\n".join("%g%% %.6g" % (100 * p, q) for p, q in zip(self.prob, self.quantiles))
+
+
+def _ci_args(prob, b, seed):
+    prob = np.atleast_1d(np.asarray(prob, dtype=np.float64))
+    if prob.ndim != 1 or not np.all((prob >= 0) & (prob <= 1)):            # (a NaN fails both comparisons)
+        raise ValueError("prob must lie in [0, 1]")
+    b = int(b)
+    if not 1 <= b < 2 ** 31:
+        raise ValueError("b = %d resamples: need 1 <= b < 2^31" % b)
+    if seed is None:
+        import secrets
+        seed = secrets.randbits(64)
+    return prob, b, int(seed) & 0xFFFFFFFFFFFFFFFF
+
+
+_CI_HOST_BLOCK = 256          # resamples per block of the host routes (a block of counts is n x 256 float64)
+
+
+def phiCI(x, prob=DEFAULT_CI_PROB, b=5000, seed=None, probandIDs=None, device=None):
+    """GENLIB's gen.phiCI(phiMatrix, prob, b = 5000): the bootstrap confidence interval of the mean kinship.  Returns a PhiCI.
+
+    A resample draws the N probands N times with replacement and takes gen.phiMean of the resampled matrix Phi[s, s]; with c[i]
+    the number of times proband i was drawn that is (c' Phi c - sum_i c[i] Phi[i, i]) / (N (N - 1)) (a proband drawn twice puts its
+    self-kinship at two off-diagonal positions, which stay in).  The draws are Philox4x32-10 keyed on (seed, resample, draw): a
+    pure function of (N, seed, resample), the same on the host and on the device (include/genphi.h).  seed=None draws 64 fresh
+    bits (secrets.randbits); .seed reports them.
+
+    x a Pedigree: gen.phi's sweep for probandIDs (default gen.pro), then genphi_result_bootstrap on the resident matrix, which is
+    never copied: a Float64 product of the matrix with the counts of a panel of resamples, fused with its reduction.
+    x a square host matrix (GENLIB's own signature): the same counts (genphi_bootstrap_counts) and numpy in Float64.
+
+    GENLIB's 3-D input (kinship by depth) and print.it are not offered.  ValueError for fewer than 2 probands, b < 1, a prob
+    outside [0, 1] or a matrix that is not square; KeyError for an unknown proband ID."""
+    prob, b, seed = _ci_args(prob, b, seed)
+    if isinstance(x, Pedigree):
+        ids = pro(x) if probandIDs is None else np.ascontiguousarray(probandIDs, dtype=np.int64)
+        x.positions(ids)                                        # KeyError on an unknown ID
+        n = len(np.unique(ids))
+        if n < 2:
+            raise ValueError("gen.phiCI needs at least 2 probands, got %d" % n)
+        pl, key = _plan_for(x, ids, device)
+        keep = False
+        try:
+            pl.compute_device(device=device)
+            total, diagonal, _ = pl.result_sums()
+            quad, own = pl.bootstrap(b, seed)
+            keep = key is not None and _keep_plan(x, key, pl, ids)
+        finally:
+            if not keep:
+                if key is not None and key in x._plans and x._plans[key][0] is pl:
+                    del x._plans[key]
+                pl.close()
+        mean = np.float32((total - diagonal) / (n * n - n))
+    else:
+        m = np.asarray(x)
+        if m.ndim != 2 or m.shape[0] != m.shape[1]:
+            raise ValueError("gen.phiCI takes a Pedigree or a square kinship matrix, got shape %s" % (m.shape,))
+        n = len(m)
+        if n < 2:
+            raise ValueError("gen.phiCI needs at least 2 probands, got %d" % n)
+        mean = phiMean(m)
+        m = m.astype(np.float64)
+        diag = np.ascontiguousarray(np.diagonal(m))
+        quad, own = np.empty(b, dtype=np.float64), np.empty(b, dtype=np.float64)
+        for first in range(0, b, _CI_HOST_BLOCK):
+            c = _capi.bootstrap_counts(n, seed, min(_CI_HOST_BLOCK, b - first), first).astype(np.float64)     # (resamples, n)
+            quad[first:first + len(c)] = np.einsum("ri,ri->r", c @ m, c)
+            own[first:first + len(c)] = c @ diag
+    theta = (quad - own) / (float(n) * (n - 1))
+    return PhiCI(prob, np.quantile(theta, prob), mean, theta, b, seed)
+
+
+def fCI(vectF, prob=DEFAULT_CI_PROB, b=5000, seed=None):
+    """GENLIB's gen.fCI(vectF, prob, b = 5000): the bootstrap confidence interval of the mean inbreeding.  vectF holds one inbreeding
+    coefficient per proband (gen.f); a resample draws the N probands N times with replacement, with gen.phiCI's draws, and takes
+    the mean sum_i c[i] F[i] / N.  On the host, in Float64.  Returns a PhiCI whose `mean` is the mean of vectF.
+    ValueError for fewer than 2 values, b < 1 or a prob outside [0, 1]."""
+    prob, b, seed = _ci_args(prob, b, seed)
+    F = np.asarray(vectF, dtype=np.float64)
+    if F.ndim != 1 or len(F) < 2:
+        raise ValueError("gen.fCI takes a vector of at least 2 inbreeding coefficients, got shape %s" % (F.shape,))
+    n = len(F)
+    theta = np.empty(b, dtype=np.float64)
+    for first in range(0, b, _CI_HOST_BLOCK):
+        c = _capi.bootstrap_counts(n, seed, min(_CI_HOST_BLOCK, b - first), first).astype(np.float64)
+        theta[first:first + len(c)] = (c @ F) / n
+    return PhiCI(prob, np.quantile(theta, prob), float(F.sum() / n), theta, b, seed)

@@ -48,7 +48,7 @@ class GenphiStats(C.Structure):
 EXPORTED_SYMBOLS = [
     "genphi_plan_create", "genphi_plan_create_tuned", "genphi_tuning_create", "genphi_tuning_set", "genphi_tuning_destroy", "genphi_plan_levels", "genphi_plan_n_probands", "genphi_plan_step_mode", "genphi_plan_step_info", "genphi_plan_step_slots",
     "genphi_plan_algorithmic_bytes", "genphi_plan_device_bytes", "genphi_plan_device_bytes_needed", "genphi_plan_sparse_levels", "genphi_plan_step_walk", "genphi_plan_set_step_hook", "genphi_compute_device", "genphi_result_device",
-    "genphi_result_to_host", "genphi_result_to_host_f64", "genphi_phi_pairs", "genphi_result_sums", "genphi_result_group_sums", "genphi_result_over", "genphi_result_entries",
+    "genphi_result_to_host", "genphi_result_to_host_f64", "genphi_phi_pairs", "genphi_result_sums", "genphi_result_group_sums", "genphi_result_over", "genphi_result_bootstrap", "genphi_bootstrap_counts", "genphi_result_entries",
     "genphi_compute_f32",
     "genphi_genealogy_read", "genphi_branching", "genphi_free", "genphi_release_cached", "genphi_cached_bytes", "genphi_plan_release_device", "genphi_plan_destroy",
     "genphi_last_error",
@@ -144,6 +144,10 @@ def lib():
         L.genphi_result_group_sums.restype = C.c_int
         L.genphi_result_over.argtypes = [C.c_void_p, C.c_double, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _F32P, _I64P]
         L.genphi_result_over.restype = C.c_int
+        L.genphi_result_bootstrap.argtypes = [C.c_void_p, C.c_uint64, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), _I64P]
+        L.genphi_result_bootstrap.restype = C.c_int
+        L.genphi_bootstrap_counts.argtypes = [C.c_int64, C.c_uint64, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]
+        L.genphi_bootstrap_counts.restype = C.c_int
         L.genphi_result_entries.argtypes = [C.c_void_p, C.c_int64, _I64P, _I64P, C.POINTER(C.c_double)]
         L.genphi_result_entries.restype = C.c_int
         L.genphi_branching.argtypes = [C.c_int64, _I64P, _I64P, _I64P, _I64P, C.c_int64, _I64P, C.c_int64, _I64P,
@@ -674,9 +678,39 @@ class PhiPlan:
                 raise GenphiDeviceError("genphi_result_over counted %d pairs, then %d" % (n, got.value))
         return rows, cols, vals
 
+    def bootstrap(self, b, seed, first=0):
+        """(quad, self): float64 arrays of b entries, the bootstrap resamples first .. first + b - 1 of the probands on the RESIDENT
+        rows (genphi_result_bootstrap; the matrix is not copied).  With c the counts of a resample
+        (bootstrap_counts), quad = sum over the resident rows i and all columns j of c[i] c[j] Phi[i, j] and
+        self = sum_i c[i] Phi[i, i]; both add over row shards, and phiMean of the resampled matrix is
+        (quad - self) / (N (N - 1)).  ValueError for b < 1, first < 0, fewer than 2 probands or a Float64 result,
+        GenphiDeviceError without a resident result."""
+        b, first = int(b), int(first)
+        if not (1 <= b < 2 ** 31 and 0 <= first < 2 ** 31):              # (c_int32 would wrap silently)
+            raise ValueError("bootstrap: b = %d, first = %d (need b >= 1, first >= 0, first + b < 2^31)" % (b, first))
+        quad, self_ = np.empty(b, dtype=np.float64), np.empty(b, dtype=np.float64)
+        dp = C.POINTER(C.c_double)
+        rc = lib().genphi_result_bootstrap(self._h, int(seed) & 0xFFFFFFFFFFFFFFFF, first, b, quad.ctypes.data_as(dp), self_.ctypes.data_as(dp), None)
+        if rc:
+            _raise(rc)
+        return quad, self_
+
     def compute(self, device=None, kernel=0, rows=None, timing=False, no_sparse=False):
         self.compute_device(device=device, kernel=kernel, rows=rows, timing=timing, no_sparse=no_sparse)
         return self.result_to_host()
+
+
+def bootstrap_counts(n, seed, b, first=0):
+    """int32 (b, n): how often each of n probands is drawn in the bootstrap resamples first .. first + b - 1 (genphi_bootstrap_counts,
+    host only): the draws of gen.phiCI / gen.fCI, a pure function of (n, seed, resample).  ValueError for n < 2, b < 1, first < 0."""
+    n, b, first = int(n), int(b), int(first)
+    if not (1 <= b < 2 ** 31 and 0 <= first < 2 ** 31 and 2 <= n < 2 ** 31):
+        raise ValueError("bootstrap_counts: n = %d, b = %d, first = %d (need n >= 2, b >= 1, first >= 0, all below 2^31)" % (n, b, first))
+    out = np.empty((b, n), dtype=np.int32)
+    rc = lib().genphi_bootstrap_counts(n, int(seed) & 0xFFFFFFFFFFFFFFFF, first, b, out.ctypes.data_as(C.POINTER(C.c_int32)))
+    if rc:
+        _raise(rc)
+    return out
 
 
 def mean_from_group_sums(sums, diag, sizes):

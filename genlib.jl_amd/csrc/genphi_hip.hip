@@ -53,6 +53,7 @@
 #include <vector>
 
 #include "../../include/genphi.h"
+#include "bootstrap.h"
 #include "panel_launch.h"
 #include "devcache.h"
 #include "planner.h"
@@ -2211,6 +2212,7 @@ struct Tuning {
     int sparse_arena = 0;          // GENPHI_SPARSE_ARENA     test: entries the row-list arenas start with (default 16 Mi; small values exercise their growth)
     int d2h_chunk_mb = 0;          // GENPHI_D2H_CHUNK_MB     tuning: size of a pinned staging chunk of genphi_result_to_host (default 16, 4 for results below 2 GB)
     int sparse_classes = -1;       // GENPHI_SPARSE_CLASSES   A/B + test: 1 / 0 = a row-list step is always / never one launch per class of row lengths (default: where lengths differ much)
+    int boot_panel = 0;            // GENPHI_BOOT_PANEL       tuning + test: resamples per panel of genphi_result_bootstrap, 1 .. 8192 (default: what keeps a panel's counts within 256 MiB)
 };
 
 // A set of "GENPHI_NAME" -> value settings handed to genphi_plan_create_tuned (include/genphi.h): the same knobs without the environment.
@@ -2226,7 +2228,7 @@ static const char *const kTuningNames[] = {
     "GENPHI_STAY_FAMILY", "GENPHI_MAX_GROUP", "GENPHI_MAX_RUN", "GENPHI_FULL_BS", "GENPHI_NO_IDENTITY", "GENPHI_CERT_MIN_EXP", "GENPHI_DBG_STEP",
     "GENPHI_NO_FAST", "GENPHI_MAX_CPT", "GENPHI_FAST_NT", "GENPHI_WIDE_ROUTE", "GENPHI_TT_NOALIGN", "GENPHI_NO_SHARD_PRUNE", "GENPHI_SHARD_FORCE",
     "GENPHI_SHARD_PRUNE_MIN_STEP", "GENPHI_NO_SMALL", "GENPHI_NO_GRAPH", "GENPHI_D2H_THREADS", "GENPHI_D2H_PAGEABLE", "GENPHI_D2H_SYM", "GENPHI_D2H_TILE",
-    "GENPHI_D2H_CHUNK_MB", "GENPHI_TEST_FAIL_ALLOC", "GENPHI_SPARSE_K", "GENPHI_SPARSE_PERMILLE", "GENPHI_SPARSE_MIN_CUT", "GENPHI_SPARSE_CHUNK", "GENPHI_SPARSE_CLASSES", "GENPHI_SPARSE_BATCH", "GENPHI_SPARSE_ARENA"};
+    "GENPHI_D2H_CHUNK_MB", "GENPHI_TEST_FAIL_ALLOC", "GENPHI_SPARSE_K", "GENPHI_SPARSE_PERMILLE", "GENPHI_SPARSE_MIN_CUT", "GENPHI_SPARSE_CHUNK", "GENPHI_SPARSE_CLASSES", "GENPHI_SPARSE_BATCH", "GENPHI_SPARSE_ARENA", "GENPHI_BOOT_PANEL"};
 
 // the settings of a plan: from a genphi_tuning when one is given, else from the environment -- which the library reads only under
 // GENPHI_ENV_HOOKS=1 (planner.h: env_hook)
@@ -2296,6 +2298,7 @@ static Tuning tuning_from(const genphi_tuning *tu)
     t.d2h_chunk_mb = geti("GENPHI_D2H_CHUNK_MB", 0);
     t.sparse_batch = geti("GENPHI_SPARSE_BATCH", 0);
     t.sparse_arena = geti("GENPHI_SPARSE_ARENA", 0);
+    t.boot_panel = std::max(0, geti("GENPHI_BOOT_PANEL", 0));
     return t;
 }
 
@@ -4478,6 +4481,42 @@ int genphi_result_over(genphi_plan *p, double threshold, int64_t cap, int32_t *r
     if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
     else (void)hipStreamSynchronize(p->stream);          // (the host vector and the caller's arrays outlive what was enqueued)
     if (e != hipSuccess) return fail(GENPHI_ERR_DEVICE, std::string("genphi_result_over: ") + hipGetErrorString(e));
+    return GENPHI_OK;
+}
+
+// gen.phiCI: the bootstrap resamples' quadratic forms over the resident rows; the kernels are in bootstrap.hip.
+int genphi_result_bootstrap(genphi_plan *p, uint64_t seed, int32_t first, int32_t n_boot, double *quad, double *self, int64_t *n_rows)
+{
+    if (!p) return fail(GENPHI_ERR_ARG, "plan is NULL");
+    if (n_rows) *n_rows = p->res_n_rows;
+    if (n_boot < 1 || first < 0 || first > INT32_MAX - n_boot)
+        return fail(GENPHI_ERR_ARG, "genphi_result_bootstrap: resamples first = " + std::to_string(first) + ", n_boot = " + std::to_string(n_boot) +
+                                        " (need first >= 0, n_boot >= 1, first + n_boot < 2^31)");
+    const int64_t N = p->plan.n_pro, nr = p->res_n_rows;
+    if (N < 2) return fail(GENPHI_ERR_ARG, "genphi_result_bootstrap: a resample needs at least 2 probands, the plan has " + std::to_string(N));
+    if (p->res_f64) return fail(GENPHI_ERR_ARG, "genphi_result_bootstrap works on the Float32 result (gen.phi's matrix)");
+    if (p->res_known && nr == 0) {                      // an empty shard adds nothing
+        if (quad) std::fill(quad, quad + n_boot, 0.0);
+        if (self) std::fill(self, self + n_boot, 0.0);
+        return GENPHI_OK;
+    }
+    if (!p->on_device || !p->result || nr == 0) return fail(GENPHI_ERR_DEVICE, "no resident result: call genphi_compute_device first");
+    if (p->res_ld < N || p->res_ld % 64 != 0) return fail(GENPHI_ERR_DEVICE, "genphi_result_bootstrap: unexpected row pitch " + std::to_string(p->res_ld));
+    HIP_TRY(hipSetDevice(p->device));
+    genphi::BootLaunch L;
+    L.stream = p->stream;
+    L.phi = p->result; L.ld = static_cast<long long>(p->res_ld);
+    L.n = static_cast<int>(N); L.row_begin = static_cast<int>(p->res_row_begin); L.n_rows = static_cast<int>(nr);
+    L.seed = seed; L.first = first; L.n_boot = n_boot;
+    L.panel = genphi::boot_panel(L.n, n_boot, p->tun.boot_panel);
+    L.quad = quad; L.self = self;
+    const size_t bytes = genphi::boot_scratch_bytes(L.n, L.n_rows, n_boot, L.panel);
+    if (ensure_scratch(p, bytes) != GENPHI_OK)
+        return fail(GENPHI_ERR_ALLOC, "genphi_result_bootstrap: " + std::to_string(bytes) + " bytes of device memory for the counts and partial sums of a panel of " +
+                                          std::to_string(L.panel) + " resamples: " + g_last_error);
+    L.scratch = p->scratch;
+    const hipError_t e = genphi::boot_launch(L);
+    if (e != hipSuccess) return fail(GENPHI_ERR_DEVICE, std::string("genphi_result_bootstrap: ") + hipGetErrorString(e));
     return GENPHI_OK;
 }
 

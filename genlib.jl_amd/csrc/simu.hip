@@ -23,6 +23,7 @@
 // Everything is integer and keyed on IDs and absolute word indices: the same bits on every run, with any panel width.
 #include <hip/hip_runtime.h>
 
+#include "bootstrap.h"
 #include "simu.h"
 #include "sweep_device.h"
 
@@ -30,21 +31,11 @@ namespace {
 
 typedef unsigned long long u64;
 
-// Philox4x32-10 (Salmon et al., SC'11): counter (c0..c3), key (k0, k1); the pair of 64-bit words o0 | o1 << 32, o2 | o3 << 32
+// Philox4x32-10: the block of bootstrap.h (shared with gen.phiCI's draws), as the 16-byte pair of words a lane stores
 __device__ __forceinline__ ulonglong2 philox_pair(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1)
 {
-    constexpr unsigned M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned hi0 = __umulhi(M0, c0), lo0 = M0 * c0, hi1 = __umulhi(M1, c2), lo1 = M1 * c2;
-        c0 = hi1 ^ c1 ^ k0;
-        c1 = lo1;
-        c2 = hi0 ^ c3 ^ k1;
-        c3 = lo0;
-        k0 += W0;
-        k1 += W1;
-    }
-    return make_ulonglong2(static_cast<u64>(c0) | (static_cast<u64>(c1) << 32), static_cast<u64>(c2) | (static_cast<u64>(c3) << 32));
+    const genphi::PhiloxPair p = genphi::philox_pair(c0, c1, c2, c3, k0, k1);
+    return make_ulonglong2(p.w0, p.w1);
 }
 
 // the columns < S of the absolute word w

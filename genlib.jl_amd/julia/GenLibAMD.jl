@@ -10,6 +10,7 @@
 module GenLibAMD
 
 import GenLib
+import Random, Statistics                  # (standard library: phiCI / fCI draw a seed and take quantiles)
 
 const libgenphi = get(ENV, "GENPHI_LIB", joinpath(@__DIR__, "..", "lib", "libgenphi.so"))
 
@@ -270,6 +271,61 @@ function phiOver(pedigree::GenLib.Pedigree, threshold::Real, probandIDs::Vector{
     finally
         destroy_plan(plan)
     end
+end
+
+"""
+    phiCI(pedigree::GenLib.Pedigree, probandIDs::Vector{Int} = GenLib.pro(pedigree); prob = [0.025, 0.05, 0.95, 0.975],
+          b::Integer = 5000, seed::Union{Nothing, UInt64} = nothing, device::Integer = -1)
+
+GENLIB's `gen.phiCI`: the bootstrap confidence interval of the mean kinship, as `(prob, quantiles, mean, thetastar, b, seed)`.  A
+resample draws the probands with replacement and takes `phiMean` of the resampled matrix; the matrix stays on the GPU:
+`genphi_result_bootstrap` draws there (Philox4x32-10 keyed on seed, resample and draw: `include/genphi.h`) and returns, per resample,
+the quadratic form of the counts and their weighted diagonal sum, accumulated in `Float64`.  Quantiles are by linear interpolation of
+the sorted values (R's type 7).  The reference has no `phiCI`; the definition is this package's own.
+"""
+function phiCI(pedigree::GenLib.Pedigree, probandIDs::Vector{Int} = GenLib.pro(pedigree); prob = [0.025, 0.05, 0.95, 0.975],
+               b::Integer = 5000, seed::Union{Nothing, UInt64} = nothing, device::Integer = -1)
+    all(p -> 0 <= p <= 1, prob) || throw(ArgumentError("prob must lie in [0, 1]"))
+    b >= 1 || throw(ArgumentError("b must be at least 1"))
+    ordered = unique(probandIDs)
+    foreach(ID -> pedigree[ID], ordered)                                    # KeyError on unknown ID
+    n = length(ordered)
+    n >= 2 || throw(ArgumentError("phiCI needs at least 2 probands"))
+    s = seed === nothing ? rand(Random.RandomDevice(), UInt64) : seed
+    plan = create_plan(pedigree, ordered, nothing)
+    try
+        opts = Ref(GenphiOpts(Int32(device), 0, 0, 0, 0, 0))
+        check(ccall((:genphi_compute_device, libgenphi), Cint, (Ptr{Cvoid}, Ptr{GenphiOpts}, Ptr{Cvoid}), plan, opts, C_NULL))
+        total = Ref{Float64}(0); diagonal = Ref{Float64}(0); rows = Ref{Int64}(0)
+        check(ccall((:genphi_result_sums, libgenphi), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}), plan, total, diagonal, rows))
+        quad = Vector{Float64}(undef, b); own = Vector{Float64}(undef, b)
+        GC.@preserve quad own check(ccall((:genphi_result_bootstrap, libgenphi), Cint,
+            (Ptr{Cvoid}, UInt64, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}), plan, s, Int32(0), Int32(b), quad, own, C_NULL))
+        thetastar = (quad .- own) ./ (Float64(n) * (n - 1))
+        return (prob = collect(Float64, prob), quantiles = Statistics.quantile(thetastar, prob), mean = Float32((total[] - diagonal[]) / (n * n - n)),
+                thetastar = thetastar, b = Int(b), seed = s)
+    finally
+        destroy_plan(plan)
+    end
+end
+
+"""
+    fCI(vectF::AbstractVector{<:Real}; prob = [0.025, 0.05, 0.95, 0.975], b::Integer = 5000, seed::Union{Nothing, UInt64} = nothing)
+
+GENLIB's `gen.fCI`: the bootstrap confidence interval of the mean inbreeding, with `phiCI`'s draws (`genphi_bootstrap_counts`, host only):
+the statistic of a resample is the mean of the drawn coefficients.
+"""
+function fCI(vectF::AbstractVector{<:Real}; prob = [0.025, 0.05, 0.95, 0.975], b::Integer = 5000, seed::Union{Nothing, UInt64} = nothing)
+    all(p -> 0 <= p <= 1, prob) || throw(ArgumentError("prob must lie in [0, 1]"))
+    b >= 1 || throw(ArgumentError("b must be at least 1"))
+    n = length(vectF)
+    n >= 2 || throw(ArgumentError("fCI needs at least 2 values"))
+    s = seed === nothing ? rand(Random.RandomDevice(), UInt64) : seed
+    counts = Matrix{Int32}(undef, n, b)                                     # column r = the counts of resample r (row-major b x n in C)
+    check(ccall((:genphi_bootstrap_counts, libgenphi), Cint, (Int64, UInt64, Int32, Int32, Ptr{Int32}), n, s, Int32(0), Int32(b), counts))
+    F = Float64.(vectF)
+    thetastar = vec(F' * counts) ./ n
+    return (prob = collect(Float64, prob), quantiles = Statistics.quantile(thetastar, prob), mean = sum(F) / n, thetastar = thetastar, b = Int(b), seed = s)
 end
 
 """

@@ -255,6 +255,49 @@ int genphi_result_group_sums(genphi_plan *plan, int32_t n_groups, const int32_t 
 int genphi_result_over(genphi_plan *plan, double threshold, int64_t cap, int32_t *rows, int32_t *cols, float *values,
                        int64_t *n_pairs);
 
+/* GENLIB's gen.phiCI(phiMatrix, prob, b) and gen.fCI(vectF, prob, b): bootstrap confidence intervals of the mean kinship and of the
+ * mean inbreeding.  The reference has neither, so this text is the definition.  N is the number of probands after
+ * duplicates collapse (genphi_plan_create), N >= 2.
+ *   the draws         resample r >= 0 draws the N probands N times with replacement.  Draw k in [0, N): one Philox4x32-10 block (the
+ *                     generator of genphi_simu_*, below) with counter (k >> 1, r, 0, 2) and key (seed low 32, seed high 32) gives
+ *                     the words W0 = o0 | o1 << 32 and W1 = o2 | o3 << 32; draw k uses W_(k & 1); the drawn position is
+ *                     s = (W * N) >> 64, the high half of the 128-bit product.  The fourth counter word 2 keeps these blocks apart
+ *                     from gene dropping's (0 and 1 there).  c_r[i] = the number of draws of resample r that gave i.  The counts are a
+ *                     pure function of (N, seed, r): not of b, of how resamples are grouped into panels, or of the resident rows.
+ *                     Known answers (N, seed, r, k -> s): 140, 0, 0, 0 -> 95;  140, 0, 0, 1 -> 115;
+ *                     100000, 0x123456789abcdef, 4999, 99999 -> 67714.
+ *   the statistic     theta_r = (sum_i sum_j c_r[i] c_r[j] Phi[i][j] - sum_i c_r[i] Phi[i][i]) / (N (N - 1)): phiMean
+ *                     (src/compute.jl:454-459) of the resampled matrix Phi[s, s].  A proband drawn twice puts its self-kinship at two
+ *                     off-diagonal positions of that matrix; those stay in.  For gen.fCI: theta_r = sum_i c_r[i] F[i] / N.
+ *   the interval      quantiles of theta_0 .. theta_(b-1) by linear interpolation of the sorted values (R's type 7, numpy.quantile's
+ *                     default), taken by the caller.
+ * genphi_bootstrap_counts: host only (no GPU).  counts[n_boot][n] (row-major) receives c_r for r = first .. first + n_boot - 1.
+ *   GENPHI_ERR_ARG: n outside [2, 2^31), n_boot < 1, first < 0, first + n_boot >= 2^31, counts NULL.
+ * genphi_result_bootstrap: on the resident Float32 result, without moving the matrix.  For r = first .. first + n_boot - 1:
+ *   quad[r - first]   sum over the resident rows i and all columns j < N of c_r[i] c_r[j] Phi[i][j]
+ *   self[r - first]   sum over the resident rows i of c_r[i] Phi[i][i]
+ *   *n_rows           the resident rows (may be NULL; quad and self may be NULL too)
+ *                     Both are additive over row shards, as genphi_result_sums is; theta_r = (quad - self) / (N (N - 1)) of the sums.
+ *                     `first` lets a caller split the resamples over calls: first = 37, n_boot = 20 gives entries 37 .. 56 of
+ *                     first = 0, n_boot = 64, bit for bit.
+ *   arithmetic        Float64 throughout: c_j Phi[i][j] is exact, accumulation is by fma in a fixed order (no floating-point
+ *                     atomics), so the same call returns the same bits.  All terms are >= 0: quad is within 3 n_rows N 2^-53
+ *                     relative of the exact sum, self within n_rows 2^-53; where every entry of Phi is a multiple of 2^-k and
+ *                     N^2 max(c)^2 2^k < 2^53 both are exact.
+ *   panels            resamples are worked off in panels (GENPHI_BOOT_PANEL; default: what keeps a panel's Int32 counts, 4 bytes per
+ *                     proband and resample, within 256 MiB, at least 128, at most 8192): counts on the device, then the product of
+ *                     the resident rows with the panel fused with its reduction, then a reduction of the row blocks' partials.
+ *                     Device memory: the counts of a panel, 16 bytes per (block of 128 resident rows, resample of a panel) and
+ *                     16 bytes per resample, in the plan's scratch block, kept between calls.  Work: 2 n_rows N n_boot Float64
+ *                     operations; symmetry is not used.
+ * An empty shard (no resident row after a genphi_compute_device call) is GENPHI_OK with zeros.
+ * GENPHI_ERR_ARG: NULL plan, n_boot < 1, first < 0, first + n_boot >= 2^31, N < 2, a Float64 result (GENPHI_FLAG_STORAGE_F64);
+ * GENPHI_ERR_DEVICE: no resident result; GENPHI_ERR_ALLOC: the scratch block does not fit in device memory (found before any
+ * launch).  After any error the plan stays usable and the resident result is untouched.                                         */
+int genphi_bootstrap_counts(int64_t n, uint64_t seed, int32_t first, int32_t n_boot, int32_t *counts);
+int genphi_result_bootstrap(genphi_plan *plan, uint64_t seed, int32_t first, int32_t n_boot, double *quad, double *self,
+                            int64_t *n_rows);
+
 /* Point lookups in the resident result without moving the matrix: out[k] = Phi[rows[k], cols[k]]
  * (0-based positions in proband order, duplicates collapsed as in genphi_plan_create; rows must
  * lie in the resident row range).  This is what gen.f(pedigree, IDs) (src/compute.jl:500-511)
