@@ -857,6 +857,83 @@ def phiOver(x, threshold, probandIDs=None, device=None):
     return PhiOver(threshold, row, col, None if ids is None else ids[row], None if ids is None else ids[col], m[row, col])
 
 
+class PhiNearest:
+    """What gen.phiNearest returns: for each of the N probands its `k` closest relatives, closest first.  `pro` (int64, the N IDs in
+    the order of the rows, None when no IDs were given with a host matrix), `index` (int32 (N, k), 0-based positions in that order),
+    `relative` (int64 (N, k), the IDs at those positions, None without `pro`) and `kinship` (float32 (N, k), the matrix entries bit
+    for bit)."""
+
+    def __init__(self, k, pro, index, relative, kinship):
+        self.k, self.pro, self.index, self.relative, self.kinship = k, pro, index, relative, kinship
+
+    def __len__(self):
+        return len(self.index)
+
+    def __repr__(self):
+        lines = ["PhiNearest: the %d nearest relatives of %d probands" % (self.k, len(self))]
+        for r in range(min(len(self), 5)):
+            who = r if self.pro is None else self.pro[r]
+            rel = self.index[r] if self.relative is None else self.relative[r]
+            lines.append("%d: %s" % (who, " ".join("%d (%.6g)" % (a, b) for a, b in zip(rel[:3], self.kinship[r, :3]))) +
+                         (" ..." if self.k > 3 else ""))
+        if len(self) > 5:
+            lines.append("...")
+        return "\n".join(lines)
+
+
+def phiNearest(x, k=10, probandIDs=None, device=None):
+    """Each proband's k closest relatives.  Returns a PhiNearest.  Neither GENLIB nor the reference has this function.
+
+    x a Pedigree: gen.phi's sweep for probandIDs (default gen.pro), then the selection on the device from the resident matrix,
+    which is never copied (genphi_result_nearest; one pass over its rows).  x a square host matrix: the same selection
+    in numpy; `pro` and `relative` come from probandIDs if given.
+
+    The candidates of proband i are the probands j != i, ordered by larger Phi[i, j] first and smaller position j first among
+    equal values; positions are 0-based in the order of the probands (duplicate probandIDs collapsed, as gen.phi does).  k is
+    clipped to N - 1.  ValueError for k < 1, for k > 64 after clipping, or for fewer than 2 probands; KeyError for an unknown
+    proband ID."""
+    k = int(k)
+    if k < 1:
+        raise ValueError("gen.phiNearest: k = %d, need k >= 1" % k)
+
+    def clipped(n):
+        if n < 2:
+            raise ValueError("gen.phiNearest: %d proband%s: nobody has a nearest relative" % (n, "" if n == 1 else "s"))
+        if min(k, n - 1) > _capi.GENPHI_NEAREST_MAX_K:
+            raise ValueError("gen.phiNearest: k = %d, at most %d" % (min(k, n - 1), _capi.GENPHI_NEAREST_MAX_K))
+        return min(k, n - 1)
+
+    if isinstance(x, Pedigree):
+        ids = pro(x) if probandIDs is None else np.ascontiguousarray(probandIDs, dtype=np.int64)
+        x.positions(ids)                                        # KeyError on an unknown ID
+        _, first = np.unique(ids, return_index=True)
+        uniq = ids[np.sort(first)]                              # duplicates collapse: first occurrences, in order
+        kk = clipped(len(uniq))
+        pl, key = _plan_for(x, ids, device)
+        keep = False
+        try:
+            pl.compute_device(device=device)
+            index, kinship = pl.nearest(kk)
+            keep = key is not None and _keep_plan(x, key, pl, ids)
+        finally:
+            if not keep:
+                if key is not None and key in x._plans and x._plans[key][0] is pl:
+                    del x._plans[key]
+                pl.close()
+        return PhiNearest(kk, uniq, index, uniq[index], kinship)
+    m = np.asarray(x, dtype=np.float32)
+    if m.ndim != 2 or m.shape[0] != m.shape[1]:
+        raise ValueError("gen.phiNearest takes a Pedigree or a square kinship matrix, got shape %s" % (m.shape,))
+    ids = None if probandIDs is None else np.asarray(probandIDs, dtype=np.int64)
+    if ids is not None and ids.shape != (len(m),):
+        raise ValueError("probandIDs must name the %d rows of the matrix" % len(m))
+    kk = clipped(len(m))
+    neg = -m.astype(np.float64)
+    np.fill_diagonal(neg, np.inf)                               # the diagonal comes last: never among the N - 1 candidates
+    index = np.argsort(neg, axis=1, kind="stable")[:, :kk].astype(np.int32)     # stable: equal values by smaller column
+    return PhiNearest(kk, ids, index, None if ids is None else ids[index], np.take_along_axis(m, index, axis=1))
+
+
 DEFAULT_CI_PROB = (0.025, 0.05, 0.95, 0.975)
 
 

@@ -24,6 +24,7 @@ GENPHI_FLAG_NO_GRAPH = 1
 GENPHI_FLAG_STORAGE_F64 = 2
 GENPHI_FLAG_NO_SPARSE = 4
 GENPHI_GROUP_SUMS_MAX_GROUPS = 4096
+GENPHI_NEAREST_MAX_K = 64
 GENPHI_IMPLEX_FLAG_ONLY_NEW = 1
 
 _I64P = C.POINTER(C.c_int64)
@@ -41,14 +42,15 @@ class GenphiOpts(C.Structure):
 class GenphiStats(C.Structure):
     _fields_ = [("n_steps", C.c_int32), ("timed", C.c_int32), ("total_ms", C.c_double),
                 ("final_ms", C.c_double), ("perm_ms", C.c_double), ("algorithmic_bytes", C.c_double), ("max_cut", C.c_int64),
-                ("level_ms", C.c_float * GENPHI_MAX_STAT_LEVELS), ("level_rows", C.c_int64 * GENPHI_MAX_STAT_LEVELS)]
+                ("level_ms", C.c_float * GENPHI_MAX_STAT_LEVELS), ("level_rows", C.c_int64 * GENPHI_MAX_STAT_LEVELS),
+                ("nearest_buf", C.c_int32)]
 
 
 # every symbol include/genphi.h declares (tests check that the library exports all of them)
 EXPORTED_SYMBOLS = [
     "genphi_plan_create", "genphi_plan_create_tuned", "genphi_tuning_create", "genphi_tuning_set", "genphi_tuning_destroy", "genphi_plan_levels", "genphi_plan_n_probands", "genphi_plan_step_mode", "genphi_plan_step_info", "genphi_plan_step_slots",
     "genphi_plan_algorithmic_bytes", "genphi_plan_device_bytes", "genphi_plan_device_bytes_needed", "genphi_plan_sparse_levels", "genphi_plan_step_walk", "genphi_plan_set_step_hook", "genphi_compute_device", "genphi_result_device",
-    "genphi_result_to_host", "genphi_result_to_host_f64", "genphi_phi_pairs", "genphi_result_sums", "genphi_result_group_sums", "genphi_result_over", "genphi_result_bootstrap", "genphi_bootstrap_counts", "genphi_result_entries",
+    "genphi_result_to_host", "genphi_result_to_host_f64", "genphi_phi_pairs", "genphi_result_sums", "genphi_result_group_sums", "genphi_result_over", "genphi_result_nearest", "genphi_result_bootstrap", "genphi_bootstrap_counts", "genphi_result_entries",
     "genphi_compute_f32",
     "genphi_genealogy_read", "genphi_branching", "genphi_free", "genphi_release_cached", "genphi_cached_bytes", "genphi_plan_release_device", "genphi_plan_destroy",
     "genphi_last_error",
@@ -148,6 +150,8 @@ def lib():
         L.genphi_result_bootstrap.restype = C.c_int
         L.genphi_bootstrap_counts.argtypes = [C.c_int64, C.c_uint64, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]
         L.genphi_bootstrap_counts.restype = C.c_int
+        L.genphi_result_nearest.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), _F32P]
+        L.genphi_result_nearest.restype = C.c_int
         L.genphi_result_entries.argtypes = [C.c_void_p, C.c_int64, _I64P, _I64P, C.POINTER(C.c_double)]
         L.genphi_result_entries.restype = C.c_int
         L.genphi_branching.argtypes = [C.c_int64, _I64P, _I64P, _I64P, _I64P, C.c_int64, _I64P, C.c_int64, _I64P,
@@ -677,6 +681,28 @@ class PhiPlan:
             if got.value != n:
                 raise GenphiDeviceError("genphi_result_over counted %d pairs, then %d" % (n, got.value))
         return rows, cols, vals
+
+    def nearest(self, k, cols=True, values=True):
+        """(cols int32 (rows, k), values float32 (rows, k)): the k closest relatives of every RESIDENT row, selected on the device
+        in one pass over the rows (genphi_result_nearest); the matrix is not copied.  The candidates of row i are
+        the probands j != i, by larger Phi[i, j] first and smaller j first among equal values; cols holds 0-based positions in
+        proband order, values the matrix entries bit for bit.  The outputs of consecutive row shards stack to the output of the
+        full result.  cols=False / values=False: that array is not fetched (None in its place).  ValueError for k outside
+        [1, min(N - 1, 64)] or a Float64 result, GenphiDeviceError without a resident result."""
+        k = int(k)
+        n = self.n_probands
+        if not 1 <= k <= min(n - 1, GENPHI_NEAREST_MAX_K):           # (checked here too: the outputs are sized by it)
+            raise ValueError("nearest: k = %d outside [1, %d]" % (k, min(n - 1, GENPHI_NEAREST_MAX_K)))
+        if not (cols or values):
+            raise ValueError("nearest: neither cols nor values asked for")
+        rows = 0 if getattr(self, "_f64", False) else self.result_device()[3]      # (a Float64 result: the call below refuses it)
+        c = np.empty((rows, k), dtype=np.int32) if cols else None
+        v = np.empty((rows, k), dtype=np.float32) if values else None
+        rc = lib().genphi_result_nearest(self._h, k, c.ctypes.data_as(C.POINTER(C.c_int32)) if cols else None,
+                                         v.ctypes.data_as(_F32P) if values else None)
+        if rc:
+            _raise(rc)
+        return c, v
 
     def bootstrap(self, b, seed, first=0):
         """(quad, self): float64 arrays of b entries, the bootstrap resamples first .. first + b - 1 of the probands on the RESIDENT

@@ -1902,6 +1902,151 @@ __global__ __launch_bounds__(256) void over_write_kernel(const float *__restrict
     }
 }
 
+// gen.phiNearest support (genphi_result_nearest): per resident row i its k best candidates -- the columns j < n,
+// j != i, by larger Phi[i][j] first and smaller j first among equal values.  Every entry of a sweep is >= +0, so the 64-bit key
+// (value bits << 32) | (0xFFFFFFFF - j) orders the candidates exactly so; no two keys of a row are equal and every key is > 0.
+// One workgroup per resident row walks the WHOLE row once, in place, a tile of kNearTile columns at a time (kNearQuads 16-byte
+// loads per thread, the next tile's in flight).  It keeps a buffer of `cap` keys in LDS and a threshold tau (0 at first): the keys
+// > tau of a tile are appended at places given by an exclusive scan over the tile (ballots over the bits of the per-thread counts,
+// the four wave totals through LDS, as over_write_kernel does: no atomics).  When a tile's keys do not all fit, the buffer is
+// filled to the brim, sorted (bitonic, descending), cut to its k largest, tau becomes the k-th largest -- a key <= tau can no
+// longer be among the k nearest -- and the rest of the tile is tested against the new tau and appended, as often as it takes.
+// At the end the survivors are sorted and the first k leave as (column, value).  What is selected and in which order is fixed by
+// the keys alone: cap, the tile and the order of appends change how often the buffer is cut, never the output.
+constexpr int kNearQuads = 4;                         // 16-byte loads per thread and tile
+constexpr int kNearTile = 256 * 4 * kNearQuads;       // columns of a tile
+constexpr int kNearBufMin = 128, kNearBufMax = 4096, kNearBufDefault = 1024;   // keys of the LDS buffer (GENPHI_NEAREST_BUF): powers of two, >= 2 x GENPHI_NEAREST_MAX_K
+
+// the buffer a plan uses: the hook's value clamped to [kNearBufMin, kNearBufMax] and rounded down to a power of two
+static int nearest_buf_entries(int hook)
+{
+    if (hook <= 0) return kNearBufDefault;
+    int b = kNearBufMin;
+    while (b * 2 <= std::min(hook, kNearBufMax)) b *= 2;
+    return b;
+}
+
+// descending bitonic sort of buf[0, P), P a power of two, by the 256 threads of the workgroup; ends with a barrier
+__device__ __forceinline__ void near_sort_desc(unsigned long long *buf, int P)
+{
+    for (int k2 = 2; k2 <= P; k2 <<= 1)
+        for (int j = k2 >> 1; j > 0; j >>= 1) {
+            for (int t = threadIdx.x; t < (P >> 1); t += 256) {
+                const int lo = ((t & ~(j - 1)) << 1) | (t & (j - 1)), hi = lo | j;
+                const unsigned long long a = buf[lo], b = buf[hi];
+                if ((lo & k2) == 0 ? a < b : a > b) { buf[lo] = b; buf[hi] = a; }
+            }
+            __syncthreads();
+        }
+}
+
+__device__ __forceinline__ unsigned long long near_key(float v, int j)
+{
+    return (static_cast<unsigned long long>(__float_as_uint(v)) << 32) | (0xFFFFFFFFu - static_cast<unsigned>(j));
+}
+
+// bit 4 q + e = column jq[q] + e is a candidate with a key > tau
+__device__ __forceinline__ unsigned near_hits(const float4 (&v)[kNearQuads], int jq0, int i, int n, unsigned long long tau)
+{
+    unsigned hits = 0;
+#pragma unroll
+    for (int q = 0; q < kNearQuads; ++q) {
+        const int jq = jq0 + q * 1024;
+        const int hi = min(max(n - jq, 0), 4), d = i - jq;
+        unsigned valid = ~(0xFu << hi) & 0xFu;                       // left of the padding
+        if (d >= 0 && d < 4) valid &= ~(1u << d);                    // not the diagonal
+        const unsigned h = (near_key(v[q].x, jq) > tau ? 1u : 0u) | (near_key(v[q].y, jq + 1) > tau ? 2u : 0u) |
+                           (near_key(v[q].z, jq + 2) > tau ? 4u : 0u) | (near_key(v[q].w, jq + 3) > tau ? 8u : 0u);
+        hits |= (h & valid) << (4 * q);
+    }
+    return hits;
+}
+
+// out_col / out_val: n_rows x k, row-major (either may be null); cap: keys of the dynamic LDS buffer, a power of two in
+// [kNearBufMin, kNearBufMax]; 1 <= k <= min(n - 1, 64)
+__global__ __launch_bounds__(256) void nearest_kernel(const float *__restrict__ m, long long ld, int n, int row_begin, int k, int cap,
+                                                      int *__restrict__ out_col, float *__restrict__ out_val)
+{
+    extern __shared__ unsigned long long near_buf[];                 // cap keys
+    __shared__ int wtot[2][4];
+    const int r = blockIdx.x, i = row_begin + r;
+    const float *row = m + (long long)r * ld;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+    unsigned long long tau = 0;
+    int cnt = 0, par = 0;                                            // keys in the buffer (the same in every thread)
+    float4 v[kNearQuads], nxt[kNearQuads];
+    int jq0 = (int)threadIdx.x * 4;
+#pragma unroll
+    for (int q = 0; q < kNearQuads; ++q) {
+        v[q] = zero;
+        if (jq0 + q * 1024 < n) v[q] = *reinterpret_cast<const float4 *>(row + jq0 + q * 1024);
+    }
+    for (int j0 = 0; j0 < n; j0 += kNearTile, jq0 += kNearTile) {
+#pragma unroll
+        for (int q = 0; q < kNearQuads; ++q) {
+            nxt[q] = zero;
+            if (jq0 + kNearTile + q * 1024 < n) nxt[q] = *reinterpret_cast<const float4 *>(row + jq0 + kNearTile + q * 1024);
+        }
+        unsigned pending = near_hits(v, jq0, i, n, tau);             // (a quad at or beyond n: every column masked)
+        for (;;) {
+            const int c = __popc(pending);                           // 0 .. 16
+            const unsigned long long b0 = __ballot(c & 1), b1 = __ballot(c & 2), b2 = __ballot(c & 4), b3 = __ballot(c & 8),
+                                     b4 = __ballot(c & 16);
+            const int before = __popcll(b0 & below) + 2 * __popcll(b1 & below) + 4 * __popcll(b2 & below) + 8 * __popcll(b3 & below) +
+                               16 * __popcll(b4 & below);
+            if (lane == 0) wtot[par][wave] = __popcll(b0) + 2 * __popcll(b1) + 4 * __popcll(b2) + 8 * __popcll(b3) + 16 * __popcll(b4);
+            __syncthreads();                                         // one barrier per round: round R + 2 reuses wtot[par] only after every wave passed R + 1's
+            int wbase = 0, total = 0;
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                const int x = wtot[par][w];
+                if (w < wave) wbase += x;
+                total += x;
+            }
+            par ^= 1;
+            if (total == 0) break;                                   // (the whole workgroup: total is the same in every thread)
+            int pos = cnt + wbase + before;
+#pragma unroll
+            for (int q = 0; q < kNearQuads; ++q) {
+                const int jq = jq0 + q * 1024;
+                const float e4[4] = {v[q].x, v[q].y, v[q].z, v[q].w};
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const unsigned bit = 1u << (4 * q + e);
+                    if (pending & bit) {
+                        if (pos < cap) { near_buf[pos] = near_key(e4[e], jq + e); pending &= ~bit; }   // never past the buffer
+                        ++pos;
+                    }
+                }
+            }
+            if (cnt + total <= cap) { cnt += total; break; }
+            // the buffer is full (cap keys) and some of the tile's keys wait: keep the k largest, raise tau, test the rest again
+            __syncthreads();
+            near_sort_desc(near_buf, cap);
+            tau = near_buf[k - 1];
+            cnt = k;
+            pending &= near_hits(v, jq0, i, n, tau);
+            // (the next round's appends go to places >= k; its barrier comes before any thread reads the buffer again)
+        }
+#pragma unroll
+        for (int q = 0; q < kNearQuads; ++q) v[q] = nxt[q];
+    }
+    // cnt >= k: a key is dropped only when k larger ones are known
+    int P = kNearBufMin;
+    while (P < cnt) P <<= 1;                                         // <= cap
+    for (int t = cnt + (int)threadIdx.x; t < P; t += 256) near_buf[t] = 0;      // below every key
+    __syncthreads();
+    near_sort_desc(near_buf, P);
+    if ((int)threadIdx.x < k) {
+        const unsigned long long key = near_buf[threadIdx.x];
+        const long long o = (long long)r * k + threadIdx.x;
+        if (out_col) out_col[o] = static_cast<int>(0xFFFFFFFFu - static_cast<unsigned>(key));
+        if (out_val) out_val[o] = __uint_as_float(static_cast<unsigned>(key >> 32));
+    }
+}
+
 // Group sums of the resident result (genphi_result_group_sums): T = Phi B summed over blocks of rows.
 // A workgroup owns a block of at most kGsBlockRows resident rows of ONE group and a slab of column tiles (kGsTile columns
 // each).  Per tile a thread keeps the Float64 column sums of its quad over the block's rows, read in place with 16-byte
@@ -2213,6 +2358,8 @@ struct Tuning {
     int d2h_chunk_mb = 0;          // GENPHI_D2H_CHUNK_MB     tuning: size of a pinned staging chunk of genphi_result_to_host (default 16, 4 for results below 2 GB)
     int sparse_classes = -1;       // GENPHI_SPARSE_CLASSES   A/B + test: 1 / 0 = a row-list step is always / never one launch per class of row lengths (default: where lengths differ much)
     int boot_panel = 0;            // GENPHI_BOOT_PANEL       tuning + test: resamples per panel of genphi_result_bootstrap, 1 .. 8192 (default: what keeps a panel's counts within 256 MiB)
+    int nearest_buf = kNearBufDefault;   // GENPHI_NEAREST_BUF      tuning + test: keys of the LDS buffer of genphi_result_nearest, a power of two in [128, 4096] (default 1024; the result does not
+                                   //                         depend on it: tests force 128 so that small inputs cut the buffer on every tile)
 };
 
 // A set of "GENPHI_NAME" -> value settings handed to genphi_plan_create_tuned (include/genphi.h): the same knobs without the environment.
@@ -2228,7 +2375,7 @@ static const char *const kTuningNames[] = {
     "GENPHI_STAY_FAMILY", "GENPHI_MAX_GROUP", "GENPHI_MAX_RUN", "GENPHI_FULL_BS", "GENPHI_NO_IDENTITY", "GENPHI_CERT_MIN_EXP", "GENPHI_DBG_STEP",
     "GENPHI_NO_FAST", "GENPHI_MAX_CPT", "GENPHI_FAST_NT", "GENPHI_WIDE_ROUTE", "GENPHI_TT_NOALIGN", "GENPHI_NO_SHARD_PRUNE", "GENPHI_SHARD_FORCE",
     "GENPHI_SHARD_PRUNE_MIN_STEP", "GENPHI_NO_SMALL", "GENPHI_NO_GRAPH", "GENPHI_D2H_THREADS", "GENPHI_D2H_PAGEABLE", "GENPHI_D2H_SYM", "GENPHI_D2H_TILE",
-    "GENPHI_D2H_CHUNK_MB", "GENPHI_TEST_FAIL_ALLOC", "GENPHI_SPARSE_K", "GENPHI_SPARSE_PERMILLE", "GENPHI_SPARSE_MIN_CUT", "GENPHI_SPARSE_CHUNK", "GENPHI_SPARSE_CLASSES", "GENPHI_SPARSE_BATCH", "GENPHI_SPARSE_ARENA", "GENPHI_BOOT_PANEL"};
+    "GENPHI_D2H_CHUNK_MB", "GENPHI_TEST_FAIL_ALLOC", "GENPHI_SPARSE_K", "GENPHI_SPARSE_PERMILLE", "GENPHI_SPARSE_MIN_CUT", "GENPHI_SPARSE_CHUNK", "GENPHI_SPARSE_CLASSES", "GENPHI_SPARSE_BATCH", "GENPHI_SPARSE_ARENA", "GENPHI_BOOT_PANEL", "GENPHI_NEAREST_BUF"};
 
 // the settings of a plan: from a genphi_tuning when one is given, else from the environment -- which the library reads only under
 // GENPHI_ENV_HOOKS=1 (planner.h: env_hook)
@@ -2299,6 +2446,7 @@ static Tuning tuning_from(const genphi_tuning *tu)
     t.sparse_batch = geti("GENPHI_SPARSE_BATCH", 0);
     t.sparse_arena = geti("GENPHI_SPARSE_ARENA", 0);
     t.boot_panel = std::max(0, geti("GENPHI_BOOT_PANEL", 0));
+    t.nearest_buf = nearest_buf_entries(geti("GENPHI_NEAREST_BUF", 0));
     return t;
 }
 
@@ -3762,6 +3910,7 @@ int genphi_compute_device(genphi_plan *p, const genphi_opts *opts, genphi_stats 
         stats->n_steps = std::max(pl.n_levels - 1, 0);
         stats->algorithmic_bytes = pl.algorithmic_bytes;
         stats->max_cut = pl.max_cut;
+        stats->nearest_buf = p->tun.nearest_buf;
     }
     p->res_row_begin = r0; p->res_n_rows = r1 - r0; p->res_known = true;
     p->over_valid = false;                    // (genphi_result_over) counts of the previous result
@@ -4517,6 +4666,39 @@ int genphi_result_bootstrap(genphi_plan *p, uint64_t seed, int32_t first, int32_
     L.scratch = p->scratch;
     const hipError_t e = genphi::boot_launch(L);
     if (e != hipSuccess) return fail(GENPHI_ERR_DEVICE, std::string("genphi_result_bootstrap: ") + hipGetErrorString(e));
+    return GENPHI_OK;
+}
+
+// gen.phiNearest: one launch, a workgroup per resident row, into two n_rows x k arrays in the plan's scratch block ->
+// one copy per array the caller asked for.
+int genphi_result_nearest(genphi_plan *p, int32_t k, int32_t *cols, float *values)
+{
+    if (!p) return fail(GENPHI_ERR_ARG, "plan is NULL");
+    if (!cols && !values) return fail(GENPHI_ERR_ARG, "genphi_result_nearest: cols and values are both NULL");
+    const int64_t N = p->plan.n_pro, nr = p->res_n_rows;
+    if (N < 2) return fail(GENPHI_ERR_ARG, "genphi_result_nearest: " + std::to_string(N) + " probands have no nearest relative");
+    if (k < 1 || k > std::min<int64_t>(N - 1, GENPHI_NEAREST_MAX_K))
+        return fail(GENPHI_ERR_ARG, "genphi_result_nearest: k = " + std::to_string(k) + " outside [1, " +
+                                    std::to_string(std::min<int64_t>(N - 1, GENPHI_NEAREST_MAX_K)) + "]");
+    if (p->res_f64) return fail(GENPHI_ERR_ARG, "genphi_result_nearest works on the Float32 result (gen.phi's matrix)");
+    if (p->res_known && nr == 0) return GENPHI_OK;
+    if (!p->on_device || !p->result || nr == 0) return fail(GENPHI_ERR_DEVICE, "no resident result: call genphi_compute_device first");
+    HIP_TRY(hipSetDevice(p->device));
+    const size_t out_bytes = static_cast<size_t>(nr) * static_cast<size_t>(k) * 4, arr_bytes = (out_bytes + 255) / 256 * 256;
+    if (ensure_scratch(p, 2 * arr_bytes) != GENPHI_OK)
+        return fail(GENPHI_ERR_ALLOC, "genphi_result_nearest: " + std::to_string(2 * arr_bytes) + " bytes of device memory for the output (8 bytes per row and neighbour): " + g_last_error);
+    int *d_col = reinterpret_cast<int *>(p->scratch);
+    float *d_val = reinterpret_cast<float *>(p->scratch + arr_bytes);
+    const int cap = p->tun.nearest_buf;
+    hipLaunchKernelGGL(nearest_kernel, dim3(static_cast<unsigned>(nr)), dim3(256), static_cast<size_t>(cap) * sizeof(unsigned long long), p->stream,
+                       p->result, static_cast<long long>(p->res_ld), static_cast<int>(N), static_cast<int>(p->res_row_begin), static_cast<int>(k), cap,
+                       cols ? d_col : nullptr, values ? d_val : nullptr);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess && cols) e = hipMemcpyAsync(cols, d_col, out_bytes, hipMemcpyDeviceToHost, p->stream);
+    if (e == hipSuccess && values) e = hipMemcpyAsync(values, d_val, out_bytes, hipMemcpyDeviceToHost, p->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
+    else (void)hipStreamSynchronize(p->stream);          // (the caller's arrays outlive what was enqueued)
+    if (e != hipSuccess) return fail(GENPHI_ERR_DEVICE, std::string("genphi_result_nearest: ") + hipGetErrorString(e));
     return GENPHI_OK;
 }
 

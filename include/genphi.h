@@ -71,6 +71,8 @@ typedef struct genphi_stats {
     float   level_ms[GENPHI_MAX_STAT_LEVELS]; /* per level step (first n_steps entries)     */
     int64_t level_rows[GENPHI_MAX_STAT_LEVELS]; /* output rows each level step computed (a row shard
                                         computes, above the last level, only the rows it descends from) */
+    int32_t nearest_buf;             /* candidate keys a workgroup of genphi_result_nearest holds on this plan (GENPHI_NEAREST_BUF;
+                                        the newest field: the struct grows at its end only)  */
 } genphi_stats;
 
 /* Replaces the host prologue of phi(): levelisation by parent steps and the cut sets
@@ -254,6 +256,28 @@ int genphi_result_group_sums(genphi_plan *plan, int32_t n_groups, const int32_t 
  * any error the plan stays usable and the resident result is untouched.                                                          */
 int genphi_result_over(genphi_plan *plan, double threshold, int64_t cap, int32_t *rows, int32_t *cols, float *values,
                        int64_t *n_pairs);
+
+/* The k closest relatives of every proband of the resident result, without moving the matrix: an n_rows x k answer that needs no
+ * threshold, selected on the device in one pass over the resident rows.  Neither GENLIB nor the reference has such a
+ * function, so this text is the definition.  N is the number of probands after duplicates collapse (genphi_plan_create).
+ *   candidates        of a resident row i: the columns j in [0, N) with j != i.  Never the diagonal, never a padding column of the
+ *                     row pitch.
+ *   order             by larger Phi[i][j] first; equal values by smaller j first.  Values are compared as numbers (every entry a
+ *                     sweep produces is >= +0), so the order is total and the answer unique.
+ *   the k nearest     of row i: the first k candidates in that order, delivered in that order.
+ *   k                 1 <= k <= min(N - 1, GENPHI_NEAREST_MAX_K)
+ *   cols, values      caller-owned, row-major n_rows x k; either may be NULL, not both.  cols holds 0-based positions in proband
+ *                     order, values[r][c] is the Float32 entry Phi[row_begin + r][cols[r][c]] bit for bit.  Row r of the output is
+ *                     resident row row_begin + r: the outputs of consecutive row shards, stacked, are the output of the full result.
+ * The answer depends on the matrix and k alone (no atomics, nothing depends on the launch geometry or on GENPHI_NEAREST_BUF): the
+ * same call returns the same bytes, and the first k' < k columns of a k call are the k' call.
+ * An empty shard (no resident row) is GENPHI_OK and writes nothing.  Device memory: 8 n_rows k bytes, in the plan's scratch block,
+ * kept between calls.  One read of the resident rows (4 n_rows N bytes).
+ * GENPHI_ERR_ARG: NULL plan, both arrays NULL, N < 2, k out of range, a Float64 result (GENPHI_FLAG_STORAGE_F64); GENPHI_ERR_DEVICE:
+ * no resident result; GENPHI_ERR_ALLOC: the output does not fit in device memory (found before the launch).  After any error the
+ * plan stays usable and the resident result is untouched.                                                                         */
+#define GENPHI_NEAREST_MAX_K 64
+int genphi_result_nearest(genphi_plan *plan, int32_t k, int32_t *cols, float *values);
 
 /* GENLIB's gen.phiCI(phiMatrix, prob, b) and gen.fCI(vectF, prob, b): bootstrap confidence intervals of the mean kinship and of the
  * mean inbreeding.  The reference has neither, so this text is the definition.  N is the number of probands after
