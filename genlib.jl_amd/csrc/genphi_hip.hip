@@ -3915,7 +3915,9 @@ int genphi_compute_device(genphi_plan *p, const genphi_opts *opts, genphi_stats 
     p->res_row_begin = r0; p->res_n_rows = r1 - r0; p->res_known = true;
     p->over_valid = false;                    // (genphi_result_over) counts of the previous result
     const int L = pl.n_levels;
-    if (L == 0 || r1 == r0) { p->res_ld = 0; return GENPHI_OK; }
+    // an empty result: no row, of either storage type (a Float64 result before it must not make the queries refuse it), the row pitch
+    // the same shard with rows would have
+    if (L == 0 || r1 == r0) { p->res_ld = L ? pl.ld[L - 1] : 0; p->res_f64 = false; return GENPHI_OK; }
 
     PhaseTrace trace;
     int rc = upload_plan(p, device);
@@ -4719,7 +4721,8 @@ int genphi_result_group_sums(genphi_plan *p, int32_t n_groups, const int32_t *gr
             return fail(GENPHI_ERR_ARG, "genphi_result_group_sums: label " + std::to_string(group[i]) + " of proband " + std::to_string(i) +
                                         " outside [-1, " + std::to_string(n_groups) + ")");
     if (p->res_f64) return fail(GENPHI_ERR_ARG, "genphi_result_group_sums works on the Float32 result (phiMean's input type, src/compute.jl:454)");
-    if (N > 0 && (!p->on_device || !p->result || p->res_n_rows == 0))
+    const bool empty_shard = p->res_known && p->res_n_rows == 0;          // adds nothing, as for the other queries: zeros, the column counts, the form
+    if (N > 0 && !empty_shard && (!p->on_device || !p->result || p->res_n_rows == 0))
         return fail(GENPHI_ERR_DEVICE, "no resident result: call genphi_compute_device first");
     const int G = n_groups, W = G + 1;
     const int64_t r0 = p->res_row_begin, nr = N > 0 ? p->res_n_rows : 0;

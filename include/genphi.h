@@ -179,7 +179,9 @@ double genphi_plan_algorithmic_bytes(const genphi_plan *plan);
 int genphi_compute_device(genphi_plan *plan, const genphi_opts *opts, genphi_stats *stats);
 
 /* Device pointer / row pitch (in floats) / first row and row count of the resident result
- * of the last genphi_compute_device (the rows of the shard it was asked for).               */
+ * of the last genphi_compute_device (the rows of the shard it was asked for).  The pitch is a
+ * multiple of 64 and at least N, also for an empty shard (n_rows = 0, which is a Float32 result
+ * whatever was resident before).                                                             */
 int genphi_result_device(const genphi_plan *plan, const float **d_ptr, int64_t *ld,
                          int64_t *row_begin, int64_t *n_rows);
 
@@ -228,6 +230,8 @@ int genphi_result_sums(genphi_plan *plan, double *sum_all, double *sum_diag, int
  * an entry is within (n - 1) 2^-53 relative of the exact sum of its n Float32 terms, and exact while the terms are dyadic
  * numbers of few bits.  Device memory: tables of a few bytes per proband and partial sums of n_groups + 1 doubles for
  * fewer than 2 (rows / 64 + n_groups) + 24 x compute units row blocks, in the plan's scratch block, kept between calls.
+ * An empty shard (no resident row after a genphi_compute_device call) is GENPHI_OK with zero sums, diag and rows_in_group;
+ * cols_in_group and form are those of the labels.
  * GENPHI_ERR_ARG: n_groups outside [1, GENPHI_GROUP_SUMS_MAX_GROUPS], a label outside [-1, n_groups), a Float64 result
  * (GENPHI_FLAG_STORAGE_F64); GENPHI_ERR_DEVICE: no resident result.                                                        */
 #define GENPHI_GROUP_SUMS_MAX_GROUPS 4096
