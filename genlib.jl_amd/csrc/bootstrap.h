@@ -1,6 +1,6 @@
 // bootstrap.h -- the random draws of gen.phiCI / gen.fCI (include/genphi.h, genphi_bootstrap_counts and genphi_result_bootstrap)
 // and the Philox4x32-10 block they share with gene dropping (simu.hip), written once for the host and the device so that the two
-// cannot drift apart; and the interface between the entry point in genphi_hip.hip and the kernels in bootstrap.hip.
+// cannot drift apart; and the interface between the entry point in result_queries.hip and the kernels in bootstrap.hip.
 #pragma once
 #include <cstddef>
 #include <cstdint>

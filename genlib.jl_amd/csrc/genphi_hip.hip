@@ -37,12 +37,13 @@
 //       [dragged, new] order (WIDE last step only): source row staged through LDS in segments,
 //       the chunk's perm words and values in registers, coalesced 16-byte loads and stores.
 //   No MFMA anywhere: this is a gather-average, HBM-bound.
+//
+// Only the sweep lives here.  What reads the finished resident result (genphi_result_*) is in result_queries.hip and
+// result_to_host.cpp, which see the plan through resident.h.
 #include <hip/hip_runtime.h>
-#include <immintrin.h>
 
 #include <algorithm>
 #include <atomic>
-#include <chrono>
 #include <cstdio>
 #include <cstring>
 #include <map>
@@ -53,12 +54,13 @@
 #include <vector>
 
 #include "../../include/genphi.h"
-#include "bootstrap.h"
 #include "panel_launch.h"
 #include "devcache.h"
 #include "planner.h"
+#include "resident.h"
 #include "sparse_levels.h"
 
+using genphi::al256;
 using genphi::LevelStep;
 using genphi::Plan;
 
@@ -1654,13 +1656,6 @@ __global__ void half_identity64_kernel(double *m, long long ld, int n, const int
     m[(long long)k * ld + k] = 0.5;
 }
 
-__global__ void gather_entries64_kernel(const double *__restrict__ m, const long long *__restrict__ off, long long n,
-                                        double *__restrict__ out)
-{
-    const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k < n) out[k] = m[off[k]];
-}
-
 // ---- SMALL: a run of consecutive level steps whose cuts have <= kSmallMax members, fused -----
 // Deep small pedigrees (hundreds of generations of a few dozen individuals: breeding lines,
 // cfg5) are launch-bound: a level is a few microseconds of work.  One workgroup keeps BOTH
@@ -1791,366 +1786,6 @@ __global__ void half_identity_kernel(float *m, long long ld, int n, const int *o
     const int r = row_begin + k;                 // matrix row
     const long long orow = out_rows ? out_rows[k] : r;
     if (r < n) m[orow * ld + r] = 0.5f;
-}
-
-// point lookups in the resident result (genphi_result_entries): out[k] = m[off[k]] widened
-__global__ void gather_entries_kernel(const float *__restrict__ m, const long long *__restrict__ off, long long n,
-                                      double *__restrict__ out)
-{
-    const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k < n) out[k] = static_cast<double>(m[off[k]]);
-}
-
-// phiMean support: Float64 sum of each resident row and its diagonal entry (row r0 + k holds
-// proband r0 + k).  One workgroup per row, fixed summation order => reproducible.
-__global__ void row_sums_kernel(const float *m, long long ld, int n, int row_begin, double *row_sum, double *diag)
-{
-    __shared__ double part[256];
-    const int k = blockIdx.x;
-    const float *row = m + (long long)k * ld;
-    double acc = 0.0;
-    for (int j = threadIdx.x * 4; j < n; j += blockDim.x * 4) {       // ld is a multiple of 64 and columns >= n are zero
-        const float4 v = *reinterpret_cast<const float4 *>(row + j);
-        acc += (static_cast<double>(v.x) + static_cast<double>(v.y)) + (static_cast<double>(v.z) + static_cast<double>(v.w));
-    }
-    part[threadIdx.x] = acc;
-    __syncthreads();
-    for (int s2 = blockDim.x >> 1; s2 > 0; s2 >>= 1) {
-        if ((int)threadIdx.x < s2) part[threadIdx.x] += part[threadIdx.x + s2];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) { row_sum[k] = part[0]; diag[k] = static_cast<double>(row[row_begin + k]); }
-}
-
-// gen.phiOver support (genphi_result_over): the pairs (i, j), i < j < n, of the resident rows with
-// (double)Phi[i][j] >= t, listed by row, then by column.  One workgroup per resident row walks the columns right of the diagonal
-// in place, a tile of kOverTile columns at a time, one quad per thread.  The first quad of a row is loaded whole (16-byte
-// aligned; ld is a multiple of 64) and its columns <= i are masked out; so are the padding columns >= n, which a threshold
-// <= 0 would select.  over_count_kernel leaves one count per row; the host turns the counts into offsets; over_write_kernel
-// repeats the walk and gives every hit its place by an exclusive scan over the tile (three ballots over the bits of the
-// per-thread counts 0..4, the four wave totals through LDS): no atomics, so the order is row, column whatever the launch
-// geometry.  Both kernels test the same bits with the same expression, so the second pass finds what the first counted.
-constexpr int kOverTile = 1024;         // columns of a tile: 256 threads x one quad
-
-__device__ __forceinline__ unsigned over_hits(const float4 v, int jq, int i, int n, double t)
-{
-    // bit e = column jq + e is listed: right of the diagonal, left of the padding, at or above the threshold
-    const int lo = min(max(i + 1 - jq, 0), 4), hi = min(max(n - jq, 0), 4);
-    const unsigned valid = (0xFu << lo) & ~(0xFu << hi) & 0xFu;
-    const unsigned h = (static_cast<double>(v.x) >= t ? 1u : 0u) | (static_cast<double>(v.y) >= t ? 2u : 0u) |
-                       (static_cast<double>(v.z) >= t ? 4u : 0u) | (static_cast<double>(v.w) >= t ? 8u : 0u);
-    return h & valid;
-}
-
-__global__ __launch_bounds__(256) void over_count_kernel(const float *__restrict__ m, long long ld, int n, int row_begin, double t,
-                                                         long long *__restrict__ row_count)
-{
-    __shared__ int part[4];
-    const int k = blockIdx.x, i = row_begin + k;
-    const float *row = m + (long long)k * ld;
-    int cnt = 0;
-#pragma unroll 4
-    for (int jq = ((i + 1) & ~3) + (int)threadIdx.x * 4; jq < n; jq += kOverTile)
-        cnt += __popc(over_hits(*reinterpret_cast<const float4 *>(row + jq), jq, i, n, t));
-    for (int s = 32; s > 0; s >>= 1) cnt += __shfl_down(cnt, s);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) row_count[k] = (long long)part[0] + part[1] + part[2] + part[3];
-}
-
-// row_off: nr + 1 offsets (exclusive scan of the counts); total = row_off[nr], the entries of each output array
-__global__ __launch_bounds__(256) void over_write_kernel(const float *__restrict__ m, long long ld, int n, int row_begin, double t,
-                                                         const long long *__restrict__ row_off, long long total,
-                                                         int *__restrict__ out_row, int *__restrict__ out_col, float *__restrict__ out_val)
-{
-    __shared__ int wtot[2][4];
-    const int k = blockIdx.x, i = row_begin + k;
-    long long base = row_off[k];
-    if (row_off[k + 1] == base) return;                  // (the whole workgroup) a row without a hit is not read again
-    const float *row = m + (long long)k * ld;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
-    int jq = ((i + 1) & ~3) + (int)threadIdx.x * 4;
-    float4 v = zero;
-    if (jq < n) v = *reinterpret_cast<const float4 *>(row + jq);
-    for (int j0 = (i + 1) & ~3, par = 0; j0 < n; j0 += kOverTile, jq += kOverTile, par ^= 1) {
-        float4 nxt = zero;
-        if (jq + kOverTile < n) nxt = *reinterpret_cast<const float4 *>(row + jq + kOverTile);      // in flight across the scan
-        const unsigned hits = over_hits(v, jq, i, n, t);              // (jq >= n: every column masked)
-        const int c = __popc(hits);
-        const unsigned long long b0 = __ballot(c & 1), b1 = __ballot(c & 2), b2 = __ballot(c & 4);
-        const unsigned long long below = (1ull << lane) - 1ull;
-        const int before = __popcll(b0 & below) + 2 * __popcll(b1 & below) + 4 * __popcll(b2 & below);
-        if (lane == 0) wtot[par][wave] = __popcll(b0) + 2 * __popcll(b1) + 4 * __popcll(b2);
-        __syncthreads();                                 // one barrier per tile: tile T + 2 reuses wtot[par] only after every wave passed T + 1's
-        int wbase = 0, tile_total = 0;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            const int x = wtot[par][w];
-            if (w < wave) wbase += x;
-            tile_total += x;
-        }
-        long long pos = base + wbase + before;
-        if (pos + c <= total) {                          // always true while counts and result belong together; never write past the lists
-            if (hits & 1u) { out_row[pos] = i; out_col[pos] = jq; out_val[pos] = v.x; ++pos; }
-            if (hits & 2u) { out_row[pos] = i; out_col[pos] = jq + 1; out_val[pos] = v.y; ++pos; }
-            if (hits & 4u) { out_row[pos] = i; out_col[pos] = jq + 2; out_val[pos] = v.z; ++pos; }
-            if (hits & 8u) { out_row[pos] = i; out_col[pos] = jq + 3; out_val[pos] = v.w; ++pos; }
-        }
-        base += tile_total;
-        v = nxt;
-    }
-}
-
-// gen.phiNearest support (genphi_result_nearest): per resident row i its k best candidates -- the columns j < n,
-// j != i, by larger Phi[i][j] first and smaller j first among equal values.  Every entry of a sweep is >= +0, so the 64-bit key
-// (value bits << 32) | (0xFFFFFFFF - j) orders the candidates exactly so; no two keys of a row are equal and every key is > 0.
-// One workgroup per resident row walks the WHOLE row once, in place, a tile of kNearTile columns at a time (kNearQuads 16-byte
-// loads per thread, the next tile's in flight).  It keeps a buffer of `cap` keys in LDS and a threshold tau (0 at first): the keys
-// > tau of a tile are appended at places given by an exclusive scan over the tile (ballots over the bits of the per-thread counts,
-// the four wave totals through LDS, as over_write_kernel does: no atomics).  When a tile's keys do not all fit, the buffer is
-// filled to the brim, sorted (bitonic, descending), cut to its k largest, tau becomes the k-th largest -- a key <= tau can no
-// longer be among the k nearest -- and the rest of the tile is tested against the new tau and appended, as often as it takes.
-// At the end the survivors are sorted and the first k leave as (column, value).  What is selected and in which order is fixed by
-// the keys alone: cap, the tile and the order of appends change how often the buffer is cut, never the output.
-constexpr int kNearQuads = 4;                         // 16-byte loads per thread and tile
-constexpr int kNearTile = 256 * 4 * kNearQuads;       // columns of a tile
-constexpr int kNearBufMin = 128, kNearBufMax = 4096, kNearBufDefault = 1024;   // keys of the LDS buffer (GENPHI_NEAREST_BUF): powers of two, >= 2 x GENPHI_NEAREST_MAX_K
-
-// the buffer a plan uses: the hook's value clamped to [kNearBufMin, kNearBufMax] and rounded down to a power of two
-static int nearest_buf_entries(int hook)
-{
-    if (hook <= 0) return kNearBufDefault;
-    int b = kNearBufMin;
-    while (b * 2 <= std::min(hook, kNearBufMax)) b *= 2;
-    return b;
-}
-
-// descending bitonic sort of buf[0, P), P a power of two, by the 256 threads of the workgroup; ends with a barrier
-__device__ __forceinline__ void near_sort_desc(unsigned long long *buf, int P)
-{
-    for (int k2 = 2; k2 <= P; k2 <<= 1)
-        for (int j = k2 >> 1; j > 0; j >>= 1) {
-            for (int t = threadIdx.x; t < (P >> 1); t += 256) {
-                const int lo = ((t & ~(j - 1)) << 1) | (t & (j - 1)), hi = lo | j;
-                const unsigned long long a = buf[lo], b = buf[hi];
-                if ((lo & k2) == 0 ? a < b : a > b) { buf[lo] = b; buf[hi] = a; }
-            }
-            __syncthreads();
-        }
-}
-
-__device__ __forceinline__ unsigned long long near_key(float v, int j)
-{
-    return (static_cast<unsigned long long>(__float_as_uint(v)) << 32) | (0xFFFFFFFFu - static_cast<unsigned>(j));
-}
-
-// bit 4 q + e = column jq[q] + e is a candidate with a key > tau
-__device__ __forceinline__ unsigned near_hits(const float4 (&v)[kNearQuads], int jq0, int i, int n, unsigned long long tau)
-{
-    unsigned hits = 0;
-#pragma unroll
-    for (int q = 0; q < kNearQuads; ++q) {
-        const int jq = jq0 + q * 1024;
-        const int hi = min(max(n - jq, 0), 4), d = i - jq;
-        unsigned valid = ~(0xFu << hi) & 0xFu;                       // left of the padding
-        if (d >= 0 && d < 4) valid &= ~(1u << d);                    // not the diagonal
-        const unsigned h = (near_key(v[q].x, jq) > tau ? 1u : 0u) | (near_key(v[q].y, jq + 1) > tau ? 2u : 0u) |
-                           (near_key(v[q].z, jq + 2) > tau ? 4u : 0u) | (near_key(v[q].w, jq + 3) > tau ? 8u : 0u);
-        hits |= (h & valid) << (4 * q);
-    }
-    return hits;
-}
-
-// out_col / out_val: n_rows x k, row-major (either may be null); cap: keys of the dynamic LDS buffer, a power of two in
-// [kNearBufMin, kNearBufMax]; 1 <= k <= min(n - 1, 64)
-__global__ __launch_bounds__(256) void nearest_kernel(const float *__restrict__ m, long long ld, int n, int row_begin, int k, int cap,
-                                                      int *__restrict__ out_col, float *__restrict__ out_val)
-{
-    extern __shared__ unsigned long long near_buf[];                 // cap keys
-    __shared__ int wtot[2][4];
-    const int r = blockIdx.x, i = row_begin + r;
-    const float *row = m + (long long)r * ld;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned long long below = (1ull << lane) - 1ull;
-    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
-    unsigned long long tau = 0;
-    int cnt = 0, par = 0;                                            // keys in the buffer (the same in every thread)
-    float4 v[kNearQuads], nxt[kNearQuads];
-    int jq0 = (int)threadIdx.x * 4;
-#pragma unroll
-    for (int q = 0; q < kNearQuads; ++q) {
-        v[q] = zero;
-        if (jq0 + q * 1024 < n) v[q] = *reinterpret_cast<const float4 *>(row + jq0 + q * 1024);
-    }
-    for (int j0 = 0; j0 < n; j0 += kNearTile, jq0 += kNearTile) {
-#pragma unroll
-        for (int q = 0; q < kNearQuads; ++q) {
-            nxt[q] = zero;
-            if (jq0 + kNearTile + q * 1024 < n) nxt[q] = *reinterpret_cast<const float4 *>(row + jq0 + kNearTile + q * 1024);
-        }
-        unsigned pending = near_hits(v, jq0, i, n, tau);             // (a quad at or beyond n: every column masked)
-        for (;;) {
-            const int c = __popc(pending);                           // 0 .. 16
-            const unsigned long long b0 = __ballot(c & 1), b1 = __ballot(c & 2), b2 = __ballot(c & 4), b3 = __ballot(c & 8),
-                                     b4 = __ballot(c & 16);
-            const int before = __popcll(b0 & below) + 2 * __popcll(b1 & below) + 4 * __popcll(b2 & below) + 8 * __popcll(b3 & below) +
-                               16 * __popcll(b4 & below);
-            if (lane == 0) wtot[par][wave] = __popcll(b0) + 2 * __popcll(b1) + 4 * __popcll(b2) + 8 * __popcll(b3) + 16 * __popcll(b4);
-            __syncthreads();                                         // one barrier per round: round R + 2 reuses wtot[par] only after every wave passed R + 1's
-            int wbase = 0, total = 0;
-#pragma unroll
-            for (int w = 0; w < 4; ++w) {
-                const int x = wtot[par][w];
-                if (w < wave) wbase += x;
-                total += x;
-            }
-            par ^= 1;
-            if (total == 0) break;                                   // (the whole workgroup: total is the same in every thread)
-            int pos = cnt + wbase + before;
-#pragma unroll
-            for (int q = 0; q < kNearQuads; ++q) {
-                const int jq = jq0 + q * 1024;
-                const float e4[4] = {v[q].x, v[q].y, v[q].z, v[q].w};
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const unsigned bit = 1u << (4 * q + e);
-                    if (pending & bit) {
-                        if (pos < cap) { near_buf[pos] = near_key(e4[e], jq + e); pending &= ~bit; }   // never past the buffer
-                        ++pos;
-                    }
-                }
-            }
-            if (cnt + total <= cap) { cnt += total; break; }
-            // the buffer is full (cap keys) and some of the tile's keys wait: keep the k largest, raise tau, test the rest again
-            __syncthreads();
-            near_sort_desc(near_buf, cap);
-            tau = near_buf[k - 1];
-            cnt = k;
-            pending &= near_hits(v, jq0, i, n, tau);
-            // (the next round's appends go to places >= k; its barrier comes before any thread reads the buffer again)
-        }
-#pragma unroll
-        for (int q = 0; q < kNearQuads; ++q) v[q] = nxt[q];
-    }
-    // cnt >= k: a key is dropped only when k larger ones are known
-    int P = kNearBufMin;
-    while (P < cnt) P <<= 1;                                         // <= cap
-    for (int t = cnt + (int)threadIdx.x; t < P; t += 256) near_buf[t] = 0;      // below every key
-    __syncthreads();
-    near_sort_desc(near_buf, P);
-    if ((int)threadIdx.x < k) {
-        const unsigned long long key = near_buf[threadIdx.x];
-        const long long o = (long long)r * k + threadIdx.x;
-        if (out_col) out_col[o] = static_cast<int>(0xFFFFFFFFu - static_cast<unsigned>(key));
-        if (out_val) out_val[o] = __uint_as_float(static_cast<unsigned>(key >> 32));
-    }
-}
-
-// Group sums of the resident result (genphi_result_group_sums): T = Phi B summed over blocks of rows.
-// A workgroup owns a block of at most kGsBlockRows resident rows of ONE group and a slab of column tiles (kGsTile columns
-// each).  Per tile a thread keeps the Float64 column sums of its quad over the block's rows, read in place with 16-byte
-// loads, row after row: the labels cost nothing there.  Once per tile (not per row) the 1,024 column sums go through LDS and
-// are folded by two host-built tables that are the same for every row: list A cuts the tile's labelled columns into pieces of
-// at most kGsPiece columns of one group, list B names the pieces of each group present in the tile (a group appears in it
-// once).  One thread owns a piece, then a group: no atomics, fixed summation order => reproducible.  GATHER = false (form
-// 0): every group is one run of columns and a piece is a stretch of the tile; GATHER = true (form 1): labels in any order, a
-// piece is a stretch of `perm`, the tile's columns sorted by group.  The column sums sit at i + i / 16 so that the piece
-// owners, 16 doubles apart, read distinct banks.  LDS and registers are the same for every n_groups: bins has the cap's size.
-constexpr int kGsMaxGroups = 4096;      // GENPHI_GROUP_SUMS_MAX_GROUPS
-constexpr int kGsTile = 1024;           // columns of a tile: 256 threads x one quad
-constexpr int kGsPiece = 16;
-constexpr int kGsBlockRows = 64;
-constexpr int kGsFan = 32;              // rows one thread of group_rows_reduce_kernel adds
-
-template <bool GATHER>
-__global__ void __launch_bounds__(256)
-group_tiles_kernel(const float *__restrict__ m, long long ld, int row_begin, const int *__restrict__ rowlist,
-                   const int2 *__restrict__ blocks /* first entry of rowlist, rows */, const int2 *__restrict__ tile_lists /* first A entry, first B entry; n_tiles + 1 */,
-                   const int *__restrict__ list_a /* first column | columns << 16 */, const int2 *__restrict__ list_b /* first piece | pieces << 16, group */,
-                   const unsigned short *__restrict__ perm, int n_tiles, int tiles_per_slab, int n_slabs, int n_groups,
-                   double *__restrict__ part /* [block x slab][n_groups + 1] */)
-{
-    __shared__ double bins[kGsMaxGroups + 1];
-    __shared__ double cs[kGsTile + kGsTile / 16];
-    __shared__ double pa[kGsTile];
-    const int tid = threadIdx.x;
-    const int blk = blockIdx.x / n_slabs, slab = blockIdx.x - blk * n_slabs;
-    const int2 b = blocks[blk];
-    const int *rows = rowlist + b.x;
-    const int nb = b.y;
-    for (int g = tid; g <= n_groups; g += 256) bins[g] = 0.0;
-    const int t_end = min(n_tiles, (slab + 1) * tiles_per_slab);
-    for (int t = slab * tiles_per_slab; t < t_end; ++t) {
-        const long long j = (long long)t * kGsTile + tid * 4;
-        double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-        if (j < ld) {                                                 // ld is a multiple of 64 and columns >= n are zero
-            const float *col = m + j;
-            int r = 0;
-            for (; r + 8 <= nb; r += 8) {
-                float4 v[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) v[u] = *reinterpret_cast<const float4 *>(col + (long long)rows[r + u] * ld);
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    a0 += static_cast<double>(v[u].x); a1 += static_cast<double>(v[u].y);
-                    a2 += static_cast<double>(v[u].z); a3 += static_cast<double>(v[u].w);
-                }
-            }
-            for (; r < nb; ++r) {
-                const float4 v = *reinterpret_cast<const float4 *>(col + (long long)rows[r] * ld);
-                a0 += static_cast<double>(v.x); a1 += static_cast<double>(v.y);
-                a2 += static_cast<double>(v.z); a3 += static_cast<double>(v.w);
-            }
-        }
-        const int c = tid * 4 + (tid >> 2);
-        cs[c] = a0; cs[c + 1] = a1; cs[c + 2] = a2; cs[c + 3] = a3;
-        __syncthreads();
-        const int2 l0 = tile_lists[t], l1 = tile_lists[t + 1];
-        const int n_a = l1.x - l0.x, n_b = l1.y - l0.y;
-        for (int i = tid; i < n_a; i += 256) {
-            const int w = list_a[l0.x + i], first = w & 0xffff, len = w >> 16;
-            double s = 0.0;
-            for (int k = 0; k < len; ++k) {
-                const int e = GATHER ? perm[(long long)t * kGsTile + first + k] : first + k;
-                s += cs[e + (e >> 4)];
-            }
-            pa[i] = s;
-        }
-        __syncthreads();
-        for (int i = tid; i < n_b; i += 256) {
-            const int2 w = list_b[l0.y + i];
-            const int first = w.x & 0xffff, len = w.x >> 16;
-            double s = 0.0;
-            for (int k = 0; k < len; ++k) s += pa[first + k];
-            bins[w.y] += s;                                           // the only owner of group w.y in this tile
-        }
-        // (the next tile writes cs before its barrier and pa after it: nothing of this tile is still being read by then)
-    }
-    if (slab == 0) {                                                  // diagonal entries of the block's rows, in row order
-        __syncthreads();
-        if (tid < nb) cs[tid] = static_cast<double>(m[(long long)rows[tid] * ld + row_begin + rows[tid]]);
-        __syncthreads();
-        if (tid == 0) {
-            double s = 0.0;
-            for (int k = 0; k < nb; ++k) s += cs[k];
-            bins[n_groups] = s;
-        }
-    }
-    __syncthreads();
-    double *out = part + (long long)blockIdx.x * (n_groups + 1);
-    for (int g = tid; g <= n_groups; g += 256) out[g] = bins[g];
-}
-
-// S = A^T T in fixed order: out[k][c] = in[beg[k]][c] + ... + in[beg[k + 1] - 1][c], one thread per entry, applied level by
-// level (at most kGsFan rows of one group per output row) until every group has one row.
-__global__ void group_rows_reduce_kernel(const double *__restrict__ in, double *__restrict__ out, const int *__restrict__ beg, int width)
-{
-    const int c = blockIdx.y * blockDim.x + threadIdx.x, k = blockIdx.x;
-    if (c >= width) return;
-    double s = 0.0;
-    for (int r = beg[k]; r < beg[k + 1]; ++r) s += in[(long long)r * width + c];
-    out[(long long)k * width + c] = s;
 }
 
 // out[k][c] = in[perm[row_begin + k]][perm[c]]: the last level of a WIDE step, computed in storage
@@ -2343,10 +1978,6 @@ struct Tuning {
     int shard_prune_min_step = 0;  // GENPHI_SHARD_PRUNE_MIN_STEP  debugging aid
     bool no_small = false;         // GENPHI_NO_SMALL         test: no fused small-level runs
     bool no_graph = false;         // GENPHI_NO_GRAPH         A-B: never replay a captured hipGraph
-    int d2h_threads = 0;           // GENPHI_D2H_THREADS      tuning: worker threads of genphi_result_to_host
-    bool d2h_pageable = false;     // GENPHI_D2H_PAGEABLE     A-B: no pinned staging ring
-    int d2h_sym = -1;              // GENPHI_D2H_SYM          opt-in: 1 = a full result crosses the link as upper-triangle tiles + a host mirror pass (default: every entry is copied)
-    int d2h_tile_rows = 0, d2h_tile_cols = 0;   // GENPHI_D2H_TILE "RxC"  test + tuning: tile of the symmetric copy (default 256 x 8192)
     int fail_alloc_at = 0;         // GENPHI_TEST_FAIL_ALLOC  test: the k-th device allocation of an upload fails (error-path test)
     int sparse_k = -2;             // GENPHI_SPARSE_K         A/B + test: last cut kept as row lists (sparse_levels.h): -1 = none (every level dense), k >= 0 = cuts 0..k
                                    //                         whatever their density (clamped to the eligible steps); default: by the calibration run's counts
@@ -2355,11 +1986,8 @@ struct Tuning {
     int sparse_chunk = 0;          // GENPHI_SPARSE_CHUNK     tuning: columns per workgroup of the sparse -> dense step
     int sparse_batch = 0;          // GENPHI_SPARSE_BATCH     A/B: list entries in flight per thread of a long row's workgroup, 4 or 8 (default 4; 8 measured slower)
     int sparse_arena = 0;          // GENPHI_SPARSE_ARENA     test: entries the row-list arenas start with (default 16 Mi; small values exercise their growth)
-    int d2h_chunk_mb = 0;          // GENPHI_D2H_CHUNK_MB     tuning: size of a pinned staging chunk of genphi_result_to_host (default 16, 4 for results below 2 GB)
+    genphi::ResultTuning res;      // the hooks of the resident-result queries (resident.h)
     int sparse_classes = -1;       // GENPHI_SPARSE_CLASSES   A/B + test: 1 / 0 = a row-list step is always / never one launch per class of row lengths (default: where lengths differ much)
-    int boot_panel = 0;            // GENPHI_BOOT_PANEL       tuning + test: resamples per panel of genphi_result_bootstrap, 1 .. 8192 (default: what keeps a panel's counts within 256 MiB)
-    int nearest_buf = kNearBufDefault;   // GENPHI_NEAREST_BUF      tuning + test: keys of the LDS buffer of genphi_result_nearest, a power of two in [128, 4096] (default 1024; the result does not
-                                   //                         depend on it: tests force 128 so that small inputs cut the buffer on every tile)
 };
 
 // A set of "GENPHI_NAME" -> value settings handed to genphi_plan_create_tuned (include/genphi.h): the same knobs without the environment.
@@ -2429,12 +2057,12 @@ static Tuning tuning_from(const genphi_tuning *tu)
     t.shard_prune_min_step = geti("GENPHI_SHARD_PRUNE_MIN_STEP", 0);
     t.no_small = has("GENPHI_NO_SMALL");
     t.no_graph = has("GENPHI_NO_GRAPH");
-    t.d2h_threads = geti("GENPHI_D2H_THREADS", 0);
-    t.d2h_pageable = has("GENPHI_D2H_PAGEABLE");
-    t.d2h_sym = geti("GENPHI_D2H_SYM", -1);
+    t.res.d2h_threads = geti("GENPHI_D2H_THREADS", 0);
+    t.res.d2h_pageable = has("GENPHI_D2H_PAGEABLE");
+    t.res.d2h_sym = geti("GENPHI_D2H_SYM", -1);
     if (const char *e = look("GENPHI_D2H_TILE")) {
         int r = 0, c = 0;
-        if (std::sscanf(e, "%dx%d", &r, &c) == 2 && r >= 1 && c >= 1) { t.d2h_tile_rows = r; t.d2h_tile_cols = c; }
+        if (std::sscanf(e, "%dx%d", &r, &c) == 2 && r >= 1 && c >= 1) { t.res.d2h_tile_rows = r; t.res.d2h_tile_cols = c; }
     }
     t.fail_alloc_at = geti("GENPHI_TEST_FAIL_ALLOC", 0);
     t.sparse_k = geti("GENPHI_SPARSE_K", -2);
@@ -2442,11 +2070,11 @@ static Tuning tuning_from(const genphi_tuning *tu)
     t.sparse_min_cut = geti("GENPHI_SPARSE_MIN_CUT", -1);
     t.sparse_chunk = geti("GENPHI_SPARSE_CHUNK", 0);
     t.sparse_classes = geti("GENPHI_SPARSE_CLASSES", -1);
-    t.d2h_chunk_mb = geti("GENPHI_D2H_CHUNK_MB", 0);
+    t.res.d2h_chunk_mb = geti("GENPHI_D2H_CHUNK_MB", 0);
     t.sparse_batch = geti("GENPHI_SPARSE_BATCH", 0);
     t.sparse_arena = geti("GENPHI_SPARSE_ARENA", 0);
-    t.boot_panel = std::max(0, geti("GENPHI_BOOT_PANEL", 0));
-    t.nearest_buf = nearest_buf_entries(geti("GENPHI_NEAREST_BUF", 0));
+    t.res.boot_panel = std::max(0, geti("GENPHI_BOOT_PANEL", 0));
+    t.res.nearest_buf = genphi::nearest_buf_entries(geti("GENPHI_NEAREST_BUF", 0));
     return t;
 }
 
@@ -2492,7 +2120,6 @@ static void build_groups(const LevelStep &s, const int *rows, const int *out_row
                            std::min(tun.max_group, s.pos_ord ? 8 : 4), tun.max_run, gl.w);
 }
 
-static size_t al256(size_t b) { return (b + 255) / 256 * 256; }
 static size_t groups_bytes(const GroupLists &gl)
 {
     return al256(gl.w.desc4.size() * sizeof(int)) + al256(gl.w.seg4.size() * sizeof(int)) + al256(gl.w.run.size() * sizeof(int));
@@ -2545,7 +2172,7 @@ struct genphi_plan {
     bool level_bufs_ready = false;         // buf[] / psi_p exist (ensure_level_buffers)
     int level_bufs_from = 0;               // ... buf[] sized for the dense matrices of cuts >= this one (the cuts before it live as row lists)
     int alloc_count = 0;                   // device allocations of uploads so far (GENPHI_TEST_FAIL_ALLOC)
-    char *scratch = nullptr;               // genphi_result_sums / _entries staging (grown on demand)
+    char *scratch = nullptr;               // the queries' staging block (resident_scratch: grown on demand)
     size_t scratch_bytes = 0;
     bool eager_valid = false;
     DeviceGroups shard_groups;      // SPLIT lists of the last step restricted to the shard (arrays inside d_shard_blob)
@@ -2584,17 +2211,19 @@ struct genphi_plan {
     size_t result_floats = 0, final_tmp_floats = 0;
     int64_t res_ld = 0, res_row_begin = 0, res_n_rows = 0;
     bool res_known = false;                      // a genphi_compute_device call has set the resident row range (it may be empty)
-    // genphi_result_over: offsets (exclusive scan of the per-row counts, res_n_rows + 1 entries) of the last threshold counted on
-    // the resident result, so that a count-only call followed by a filling call runs the counting pass once.  Dropped whenever
-    // the result is recomputed or released.
-    std::vector<int64_t> over_off;
-    double over_threshold = 0.0;
-    bool over_valid = false;
+    genphi::OverCache over;                      // genphi_result_over's offsets of the resident result: dropped with it (set_resident_rows)
     // zero-aware leading levels (sparse_levels.h): created and calibrated by the first product sweep of the plan
     genphi::SparseLevels *sparse = nullptr;
     bool sparse_tried = false;
     std::vector<hipEvent_t> events;
 };
+
+// The resident row range changes -- a compute call begins, the device is released -- and what was derived from the previous result goes.
+static void set_resident_rows(genphi_plan *p, int64_t row_begin, int64_t n_rows, bool known)
+{
+    p->res_row_begin = row_begin; p->res_n_rows = n_rows; p->res_known = known;
+    p->over.drop();
+}
 
 static void drop_graph(genphi_plan *p)
 {
@@ -2636,8 +2265,7 @@ static void free_device(genphi_plan *p)
     p->shard_cap = 0; p->shard_r0 = p->shard_r1 = -1;
     p->buf_floats[0] = p->buf_floats[1] = 0; p->level_bufs_ready = false;
     p->result_floats = p->final_tmp_floats = 0; p->scratch_bytes = 0;
-    p->res_ld = 0; p->res_row_begin = 0; p->res_n_rows = 0; p->res_known = false;
-    p->over_valid = false; p->over_off.clear();
+    p->res_ld = 0; set_resident_rows(p, 0, 0, false);
     genphi::cached_stream_release(p->stream, p->device);
     p->stream = nullptr;
     p->on_device = false;
@@ -3143,15 +2771,25 @@ static int ensure_floats(genphi_plan *p, float **ptr, size_t *have, size_t need)
     return GENPHI_OK;
 }
 
-static int ensure_scratch(genphi_plan *p, size_t bytes)
+// resident.h: what result_queries.hip and result_to_host.cpp see of a plan
+genphi::ResidentView genphi::resident_view(const genphi_plan *p)
 {
-    if (p->scratch_bytes >= bytes && p->scratch) return GENPHI_OK;
-    if (p->scratch) { HIP_TRY(genphi::cached_free(p->scratch)); p->scratch = nullptr; p->scratch_bytes = 0; }
-    const size_t want = std::max<size_t>(bytes, size_t(1) << 16);
-    HIP_TRY(genphi::cached_malloc(reinterpret_cast<void **>(&p->scratch), want));
-    p->scratch_bytes = want;
+    return ResidentView{p->device, p->n_cus, p->stream, p->plan.n_pro, p->result, p->result64, p->res_ld, p->res_row_begin, p->res_n_rows,
+                        p->on_device, p->res_f64, p->res_known, &p->tun.res};
+}
+int genphi::resident_scratch(genphi_plan *p, size_t bytes, char **scratch)
+{
+    *scratch = nullptr;
+    if (p->scratch_bytes < bytes || !p->scratch) {
+        if (p->scratch) { HIP_TRY(genphi::cached_free(p->scratch)); p->scratch = nullptr; p->scratch_bytes = 0; }
+        const size_t want = std::max<size_t>(bytes, size_t(1) << 16);
+        HIP_TRY(genphi::cached_malloc(reinterpret_cast<void **>(&p->scratch), want));
+        p->scratch_bytes = want;
+    }
+    *scratch = p->scratch;
     return GENPHI_OK;
 }
+genphi::OverCache &genphi::resident_over_cache(genphi_plan *p) { return p->over; }
 
 static hipError_t set_max_lds(const void *fn, size_t bytes)
 {
@@ -3910,10 +3548,9 @@ int genphi_compute_device(genphi_plan *p, const genphi_opts *opts, genphi_stats 
         stats->n_steps = std::max(pl.n_levels - 1, 0);
         stats->algorithmic_bytes = pl.algorithmic_bytes;
         stats->max_cut = pl.max_cut;
-        stats->nearest_buf = p->tun.nearest_buf;
+        stats->nearest_buf = p->tun.res.nearest_buf;
     }
-    p->res_row_begin = r0; p->res_n_rows = r1 - r0; p->res_known = true;
-    p->over_valid = false;                    // (genphi_result_over) counts of the previous result
+    set_resident_rows(p, r0, r1 - r0, true);
     const int L = pl.n_levels;
     // an empty result: no row, of either storage type (a Float64 result before it must not make the queries refuse it), the row pitch
     // the same shard with rows would have
@@ -4291,641 +3928,6 @@ int genphi_compute_device(genphi_plan *p, const genphi_opts *opts, genphi_stats 
         }
         stats->timed = 1;
     }
-    return GENPHI_OK;
-}
-
-int genphi_result_device(const genphi_plan *p, const float **d_ptr, int64_t *ld, int64_t *row_begin, int64_t *n_rows)
-{
-    if (!p) return fail(GENPHI_ERR_ARG, "plan is NULL");
-    if (p->res_f64) return fail(GENPHI_ERR_ARG, "the resident result is Float64 (GENPHI_FLAG_STORAGE_F64): use genphi_result_to_host_f64 / genphi_result_entries");
-    if (d_ptr) *d_ptr = p->result;
-    if (ld) *ld = p->res_ld;
-    if (row_begin) *row_begin = p->res_row_begin;
-    if (n_rows) *n_rows = p->res_n_rows;
-    return GENPHI_OK;
-}
-
-int genphi_result_to_host_f64(genphi_plan *p, double *out)
-{
-    if (!p) return fail(GENPHI_ERR_ARG, "plan is NULL");
-    if (p->res_n_rows == 0 || p->plan.n_pro == 0) return GENPHI_OK;
-    if (!out) return fail(GENPHI_ERR_ARG, "out is NULL");
-    if (!p->res_f64 || !p->on_device || !p->result64)
-        return fail(GENPHI_ERR_ARG, "no resident Float64 result: call genphi_compute_device with GENPHI_FLAG_STORAGE_F64 first");
-    HIP_TRY(hipSetDevice(p->device));
-    const size_t N = static_cast<size_t>(p->plan.n_pro);
-    HIP_TRY(hipMemcpy2D(out, N * sizeof(double), p->result64, static_cast<size_t>(p->res_ld) * sizeof(double), N * sizeof(double),
-                        static_cast<size_t>(p->res_n_rows), hipMemcpyDeviceToHost));
-    return GENPHI_OK;
-}
-
-}  // extern "C"
-// tmp[q * nr + r] = src[r * w + q] for q < 16 and the first nr - nr % 8 rows r (genphi_result_to_host's mirror pass): 8 x 8
-// transposes in AVX2 registers.  Returns the rows done.  (Host code of one function: the library is not built with -mavx2.)
-__attribute__((target("avx2"))) static size_t mirror_gather16_avx2(const float *src, size_t w, size_t nr, float *tmp)
-{
-    size_t r = 0;
-    for (; r + 8 <= nr; r += 8) {
-        for (int h = 0; h < 2; ++h) {                       // columns [8 h, 8 h + 8)
-            __m256 v[8];
-            for (int k = 0; k < 8; ++k) v[k] = _mm256_loadu_ps(src + (r + k) * w + 8 * h);
-            const __m256 t0 = _mm256_unpacklo_ps(v[0], v[1]), t1 = _mm256_unpackhi_ps(v[0], v[1]);
-            const __m256 t2 = _mm256_unpacklo_ps(v[2], v[3]), t3 = _mm256_unpackhi_ps(v[2], v[3]);
-            const __m256 t4 = _mm256_unpacklo_ps(v[4], v[5]), t5 = _mm256_unpackhi_ps(v[4], v[5]);
-            const __m256 t6 = _mm256_unpacklo_ps(v[6], v[7]), t7 = _mm256_unpackhi_ps(v[6], v[7]);
-            const __m256 u0 = _mm256_shuffle_ps(t0, t2, 0x44), u1 = _mm256_shuffle_ps(t0, t2, 0xee);
-            const __m256 u2 = _mm256_shuffle_ps(t1, t3, 0x44), u3 = _mm256_shuffle_ps(t1, t3, 0xee);
-            const __m256 u4 = _mm256_shuffle_ps(t4, t6, 0x44), u5 = _mm256_shuffle_ps(t4, t6, 0xee);
-            const __m256 u6 = _mm256_shuffle_ps(t5, t7, 0x44), u7 = _mm256_shuffle_ps(t5, t7, 0xee);
-            _mm256_storeu_ps(tmp + (8 * h + 0) * nr + r, _mm256_permute2f128_ps(u0, u4, 0x20));
-            _mm256_storeu_ps(tmp + (8 * h + 1) * nr + r, _mm256_permute2f128_ps(u1, u5, 0x20));
-            _mm256_storeu_ps(tmp + (8 * h + 2) * nr + r, _mm256_permute2f128_ps(u2, u6, 0x20));
-            _mm256_storeu_ps(tmp + (8 * h + 3) * nr + r, _mm256_permute2f128_ps(u3, u7, 0x20));
-            _mm256_storeu_ps(tmp + (8 * h + 4) * nr + r, _mm256_permute2f128_ps(u0, u4, 0x31));
-            _mm256_storeu_ps(tmp + (8 * h + 5) * nr + r, _mm256_permute2f128_ps(u1, u5, 0x31));
-            _mm256_storeu_ps(tmp + (8 * h + 6) * nr + r, _mm256_permute2f128_ps(u2, u6, 0x31));
-            _mm256_storeu_ps(tmp + (8 * h + 7) * nr + r, _mm256_permute2f128_ps(u3, u7, 0x31));
-        }
-    }
-    return r;
-}
-extern "C" {
-
-int genphi_result_to_host(genphi_plan *p, float *out)
-{
-    if (!p) return fail(GENPHI_ERR_ARG, "plan is NULL");
-    if (p->res_n_rows == 0 || p->plan.n_pro == 0) return GENPHI_OK;
-    if (!out) return fail(GENPHI_ERR_ARG, "out is NULL");
-    if (p->res_f64) {
-        // Float64 sweep: deliver RN32 of the Float64 values (ONE rounding, like gen.f, src/compute.jl:500-511)
-        const size_t n = static_cast<size_t>(p->res_n_rows) * static_cast<size_t>(p->plan.n_pro);
-        std::vector<double> tmp(n);
-        const int rc = genphi_result_to_host_f64(p, tmp.data());
-        if (rc) return rc;
-        for (size_t k = 0; k < n; ++k) out[k] = static_cast<float>(tmp[k]);
-        return GENPHI_OK;
-    }
-    if (!p->on_device || !p->result) return fail(GENPHI_ERR_DEVICE, "no resident result: call genphi_compute_device first");
-    HIP_TRY(hipSetDevice(p->device));
-    const size_t N = static_cast<size_t>(p->plan.n_pro);
-    const size_t rows = static_cast<size_t>(p->res_n_rows);
-    HIP_TRY(hipStreamSynchronize(p->stream));
-    // Large results go through a ring of pinned staging buffers: every worker thread owns a
-    // stream and two pinned chunks, the DMA engine fills one chunk (device pitch -> dense rows)
-    // while the thread copies the other into the caller's pageable array.  A plain hipMemcpy2D
-    // into pageable memory is staged by the runtime on ONE thread (~17 GB/s; 23 GB/s with 8
-    // concurrent calls); the PCIe Gen5 link carries more than twice that.
-    const size_t bytes = rows * N * sizeof(float);
-    // A FULL result is bit-symmetric (every level is: both (i, j) and (j, i) are the same Float64 expression), and the plain copy is
-    // bound by the PCIe link (55 GB/s into warm pages, 53 with first-touch page faults), so GENPHI_D2H_SYM=1 sends only the tiles on and
-    // above the diagonal across the link and lets the worker threads mirror them into the lower triangle on the host.  OPT-IN: measured
-    // at 1e5 probands (profiles/microbench/out/r04_d2h_symmetric_vs_plain_cfg4.out) it takes 440-1140 ms warm and 615-1420 ms into fresh
-    // pages against a steady 724 / 756 ms for the plain copy -- the mirror pass makes the HOST the bottleneck, and a GPU box gives the
-    // process 16 CPUs (cgroup quota): whenever the 16 workers, the Python thread and the runtime's helpers exceed it, the kernel throttles
-    // the lot.  On a host with cores to spare it is the faster path; here it is not reliably so, hence not the default.
-    bool sym = rows == N && p->res_row_begin == 0 && N >= 2 && !p->tun.d2h_pageable && p->tun.d2h_sym == 1;
-    int n_thr = 1;
-    if (bytes >= (size_t(64) << 20) || sym) {              // (one worker per 32 MB up to 8: the ring is kept between calls, so mid-size results use it too)
-        n_thr = sym ? 16 : static_cast<int>(std::min<size_t>(8, bytes >> 25));
-        if (p->tun.d2h_threads > 0) n_thr = std::max(1, std::min(32, p->tun.d2h_threads));
-    }
-    const size_t row_bytes = N * sizeof(float);
-    const size_t tile_r = p->tun.d2h_tile_rows > 0 ? static_cast<size_t>(p->tun.d2h_tile_rows) : 256;
-    const size_t tile_c = p->tun.d2h_tile_cols > 0 ? static_cast<size_t>(p->tun.d2h_tile_cols) : 8192;
-    // (16 MB chunks; 4 MB for results below 2 GB, whose workers have only a few chunks each to overlap the DMA with the host copy)
-    const size_t chunk_mb = p->tun.d2h_chunk_mb > 0 ? static_cast<size_t>(p->tun.d2h_chunk_mb) : (bytes < (size_t(2) << 30) ? 4 : 16);
-    const size_t chunk_rows = std::max<size_t>(1, (chunk_mb << 20) / row_bytes);
-    const size_t chunk_bytes = sym ? std::max<size_t>(tile_r * std::min(tile_c, N) * sizeof(float), 4096) : chunk_rows * row_bytes;
-    bool pinned = (n_thr > 1 || sym) && !p->tun.d2h_pageable;
-    // (the ring belongs to the device, not to the plan: pinning 256 MB costs 60-100 ms and unpinning them 80 ms -- per one-shot call
-    // when every plan had its own; devcache.h)
-    genphi::PinnedRing *ring = nullptr;
-    std::unique_lock<std::mutex> ring_lock;
-    if (pinned) {
-        ring = &genphi::pinned_ring(p->device);
-        ring_lock = std::unique_lock<std::mutex>(ring->mu);
-        if (!genphi::pinned_ring_reserve(*ring, static_cast<size_t>(2 * n_thr), chunk_bytes, static_cast<size_t>(n_thr))) {
-            pinned = false;                             // could not pin: fall back to direct copies
-            ring_lock.unlock();
-            ring = nullptr;
-        }
-    }
-    if (!pinned) sym = false;
-    std::vector<hipError_t> errs(n_thr, hipSuccess);
-    if (sym) {
-        // items: (row block I, column tile J) with the tile's columns clipped to [max(c0, a), c1): on or right of the diagonal block
-        struct Item { uint32_t a, b, cs, c1; };
-        std::vector<Item> items;
-        for (size_t a = 0; a < N; a += tile_r) {
-            const size_t b = std::min(N, a + tile_r);
-            for (size_t c0 = a / tile_c * tile_c; c0 < N; c0 += tile_c) {
-                const size_t cs = std::max(c0, a), c1 = std::min(N, c0 + tile_c);
-                items.push_back({static_cast<uint32_t>(a), static_cast<uint32_t>(b), static_cast<uint32_t>(cs), static_cast<uint32_t>(c1)});
-            }
-        }
-        std::atomic<size_t> next{0};
-        const size_t src_pitch = static_cast<size_t>(p->res_ld) * sizeof(float);
-        const bool avx2 = __builtin_cpu_supports("avx2") != 0;
-        auto worker = [&](int t) {
-            hipError_t e = hipSetDevice(p->device);
-            if (e != hipSuccess) { errs[t] = e; return; }
-            hipStream_t st = ring->stream[t];
-            float *pb[2] = {static_cast<float *>(ring->chunk[2 * t]), static_cast<float *>(ring->chunk[2 * t + 1])};
-            auto issue = [&](const Item &it, float *dst) {
-                const size_t w = it.c1 - it.cs;
-                return hipMemcpy2DAsync(dst, w * sizeof(float), p->result + static_cast<size_t>(it.a) * static_cast<size_t>(p->res_ld) + it.cs, src_pitch,
-                                        w * sizeof(float), it.b - it.a, hipMemcpyDeviceToHost, st);
-            };
-            // (waits sleep instead of spinning -- a blocking-sync event per buffer: the host side is the bottleneck of this copy,
-            // and a GPU box gives a process 16 CPUs; spinning waiters take them from the threads that mirror tiles)
-            hipEvent_t evb[2] = {nullptr, nullptr};
-            for (hipEvent_t &x : evb)
-                if ((e = hipEventCreateWithFlags(&x, hipEventBlockingSync | hipEventDisableTiming)) != hipSuccess) { errs[t] = e; return; }
-            size_t cur = next.fetch_add(1);
-            if (cur >= items.size()) { for (hipEvent_t x : evb) (void)hipEventDestroy(x); return; }
-            e = issue(items[cur], pb[0]);
-            if (e == hipSuccess) e = hipEventRecord(evb[0], st);
-            for (int k = 0; e == hipSuccess; ++k) {
-                e = hipEventSynchronize(evb[k & 1]);        // item `cur` has landed in pb[k & 1]
-                if (e != hipSuccess) break;
-                const size_t nxt = next.fetch_add(1);
-                if (nxt < items.size()) {                   // the DMA engine fills the other buffer meanwhile
-                    e = issue(items[nxt], pb[(k + 1) & 1]);
-                    if (e == hipSuccess) e = hipEventRecord(evb[(k + 1) & 1], st);
-                }
-                const Item it = items[cur];
-                const float *blk = pb[k & 1];
-                const size_t w = it.c1 - it.cs, nr = it.b - it.a;
-                for (size_t r = 0; r < nr; ++r)             // the tile itself
-                    std::memcpy(out + (it.a + r) * N + it.cs, blk + r * w, w * sizeof(float));
-                // its mirror image: columns right of the diagonal block become the rows' entries [a, b), 16 columns (a cache
-                // line of every tile row) at a time through a small buffer, written as runs of nr floats
-                const size_t ts = std::max<size_t>(it.cs, it.b);
-                constexpr size_t KB = 16;
-                static thread_local std::vector<float> tmp;
-                tmp.resize(KB * nr);
-                for (size_t cb0 = ts; cb0 < it.c1; cb0 += KB) {
-                    const size_t nb = std::min(KB, it.c1 - cb0);
-                    const float *src = blk + (cb0 - it.cs);
-                    if (nb == KB) {
-                        size_t r = 0;
-                        if (avx2) r = mirror_gather16_avx2(src, w, nr, tmp.data());       // 8 x 8 register transposes, whole multiples of 8 rows
-                        for (; r < nr; ++r) {
-                            const float *sr = src + r * w;
-#pragma unroll
-                            for (size_t q = 0; q < KB; ++q) tmp[q * nr + r] = sr[q];
-                        }
-                    } else {
-                        for (size_t r = 0; r < nr; ++r)
-                            for (size_t q = 0; q < nb; ++q) tmp[q * nr + r] = src[r * w + q];
-                    }
-                    for (size_t q = 0; q < nb; ++q) std::memcpy(out + (cb0 + q) * N + it.a, tmp.data() + q * nr, nr * sizeof(float));
-                }
-                if (nxt >= items.size()) break;
-                cur = nxt;
-            }
-            for (hipEvent_t x : evb) (void)hipEventDestroy(x);
-            errs[t] = e;
-        };
-        std::vector<std::thread> th;
-        for (int t = 0; t < n_thr; ++t) th.emplace_back(worker, t);
-        for (auto &x : th) x.join();
-        for (hipError_t e : errs)
-            if (e != hipSuccess) return fail(GENPHI_ERR_DEVICE, std::string("genphi_result_to_host: ") + hipGetErrorString(e));
-        return GENPHI_OK;
-    }
-    const bool d2h_stats = genphi::env_hook("GENPHI_D2H_STATS") != nullptr;
-    auto copy_block = [&](int t) {
-        const size_t r0 = rows * t / n_thr, r1 = rows * (t + 1) / n_thr;
-        if (r1 == r0) return;
-        hipError_t e = hipSetDevice(p->device);
-        if (e != hipSuccess) { errs[t] = e; return; }
-        const size_t src_pitch = static_cast<size_t>(p->res_ld) * sizeof(float);
-        if (!pinned) {
-            errs[t] = hipMemcpy2D(out + r0 * N, row_bytes, p->result + r0 * static_cast<size_t>(p->res_ld), src_pitch,
-                                  row_bytes, r1 - r0, hipMemcpyDeviceToHost);
-            return;
-        }
-        hipStream_t st = ring->stream[t];
-        char *pb[2] = {static_cast<char *>(ring->chunk[2 * t]), static_cast<char *>(ring->chunk[2 * t + 1])};
-        const size_t n_chunks = (r1 - r0 + chunk_rows - 1) / chunk_rows;
-        auto issue = [&](size_t c) {
-            const size_t a = r0 + c * chunk_rows, b = std::min(r1, a + chunk_rows);
-            return hipMemcpy2DAsync(pb[c & 1], row_bytes, p->result + a * static_cast<size_t>(p->res_ld), src_pitch,
-                                    row_bytes, b - a, hipMemcpyDeviceToHost, st);
-        };
-        e = issue(0);
-        double t_wait = 0.0, t_host = 0.0;
-        auto clk = [] { return std::chrono::steady_clock::now(); };
-        for (size_t c = 0; c < n_chunks && e == hipSuccess; ++c) {
-            const auto t0 = clk();
-            e = hipStreamSynchronize(st);               // chunk c has landed in pb[c & 1]
-            if (e != hipSuccess) break;
-            if (c + 1 < n_chunks) e = issue(c + 1);     // the DMA engine fills the other buffer meanwhile
-            const auto t1 = clk();
-            const size_t a = r0 + c * chunk_rows, b = std::min(r1, a + chunk_rows);
-            std::memcpy(out + a * N, pb[c & 1], (b - a) * row_bytes);
-            if (d2h_stats) { t_wait += std::chrono::duration<double, std::milli>(t1 - t0).count(); t_host += std::chrono::duration<double, std::milli>(clk() - t1).count(); }
-        }
-        if (d2h_stats) std::fprintf(stderr, "[genphi d2h] thread %d: %zu chunks, waiting for the DMA %.2f ms, copying into the caller's array %.2f ms\n", t, n_chunks, t_wait, t_host);
-        errs[t] = e;
-    };
-    if (n_thr == 1) copy_block(0);
-    else {
-        std::vector<std::thread> th;
-        for (int t = 0; t < n_thr; ++t) th.emplace_back(copy_block, t);
-        for (auto &x : th) x.join();
-    }
-    for (hipError_t e : errs)
-        if (e != hipSuccess) return fail(GENPHI_ERR_DEVICE, std::string("genphi_result_to_host: ") + hipGetErrorString(e));
-    return GENPHI_OK;
-}
-
-int genphi_result_sums(genphi_plan *p, double *sum_all, double *sum_diag, int64_t *n_rows_out)
-{
-    if (!p) return fail(GENPHI_ERR_ARG, "plan is NULL");
-    if (sum_all) *sum_all = 0.0;
-    if (sum_diag) *sum_diag = 0.0;
-    if (n_rows_out) *n_rows_out = p->res_n_rows;
-    if (p->res_n_rows == 0 || p->plan.n_pro == 0) return GENPHI_OK;
-    if (p->res_f64) return fail(GENPHI_ERR_ARG, "genphi_result_sums works on the Float32 result (phiMean's input type, src/compute.jl:454)");
-    if (!p->on_device || !p->result) return fail(GENPHI_ERR_DEVICE, "no resident result: call genphi_compute_device first");
-    HIP_TRY(hipSetDevice(p->device));
-    const int64_t nr = p->res_n_rows;
-    int rc = ensure_scratch(p, 2 * nr * sizeof(double));
-    if (rc) return rc;
-    double *d = reinterpret_cast<double *>(p->scratch);
-    hipLaunchKernelGGL(row_sums_kernel, dim3(static_cast<unsigned>(nr)), dim3(256), 0, p->stream, p->result,
-                       static_cast<long long>(p->res_ld), static_cast<int>(p->plan.n_pro), static_cast<int>(p->res_row_begin),
-                       d, d + nr);
-    hipError_t e = hipGetLastError();
-    std::vector<double> h(2 * nr);
-    if (e == hipSuccess) e = hipMemcpyAsync(h.data(), d, 2 * nr * sizeof(double), hipMemcpyDeviceToHost, p->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
-    if (e != hipSuccess) return fail(GENPHI_ERR_DEVICE, std::string("genphi_result_sums: ") + hipGetErrorString(e));
-    double sa = 0.0, sd = 0.0;                      // fixed order: reproducible
-    for (int64_t k = 0; k < nr; ++k) { sa += h[k]; sd += h[nr + k]; }
-    if (sum_all) *sum_all = sa;
-    if (sum_diag) *sum_diag = sd;
-    return GENPHI_OK;
-}
-
-// gen.phiOver: counting pass -> offsets on the host (in row order, as genphi_result_sums adds its row sums) ->
-// writing pass into three lists in the plan's scratch block -> one copy per array the caller asked for.
-int genphi_result_over(genphi_plan *p, double threshold, int64_t cap, int32_t *rows, int32_t *cols, float *values, int64_t *n_pairs)
-{
-    if (!p) return fail(GENPHI_ERR_ARG, "plan is NULL");
-    if (n_pairs) *n_pairs = 0;
-    if (threshold != threshold) return fail(GENPHI_ERR_ARG, "genphi_result_over: the threshold is NaN");
-    if (cap < 0) return fail(GENPHI_ERR_ARG, "genphi_result_over: cap = " + std::to_string(cap) + " is negative");
-    const int64_t N = p->plan.n_pro, nr = p->res_n_rows;
-    if (N < 2 || (p->res_known && nr == 0)) return GENPHI_OK;
-    if (p->res_f64) return fail(GENPHI_ERR_ARG, "genphi_result_over works on the Float32 result (gen.phi's matrix)");
-    if (!p->on_device || !p->result || nr == 0) return fail(GENPHI_ERR_DEVICE, "no resident result: call genphi_compute_device first");
-    HIP_TRY(hipSetDevice(p->device));
-    const size_t off_bytes = (static_cast<size_t>(nr + 1) * sizeof(long long) + 255) / 256 * 256;
-    auto scratch = [&](size_t bytes, const char *what) {
-        if (ensure_scratch(p, bytes) == GENPHI_OK) return GENPHI_OK;
-        return fail(GENPHI_ERR_ALLOC, "genphi_result_over: " + std::to_string(bytes) + " bytes of device memory for " + what + ": " + g_last_error);
-    };
-    const long long ld = static_cast<long long>(p->res_ld);
-    const int n = static_cast<int>(N), r0 = static_cast<int>(p->res_row_begin);
-    const bool same = p->over_valid && static_cast<int64_t>(p->over_off.size()) == nr + 1 &&
-                      std::memcmp(&p->over_threshold, &threshold, sizeof(double)) == 0;
-    if (!same) {
-        p->over_valid = false;
-        int rc = scratch(off_bytes, "the per-row counts");
-        if (rc) return rc;
-        long long *d_cnt = reinterpret_cast<long long *>(p->scratch);
-        hipLaunchKernelGGL(over_count_kernel, dim3(static_cast<unsigned>(nr)), dim3(256), 0, p->stream, p->result, ld, n, r0, threshold, d_cnt);
-        hipError_t e = hipGetLastError();
-        std::vector<long long> h(static_cast<size_t>(nr));
-        if (e == hipSuccess) e = hipMemcpyAsync(h.data(), d_cnt, static_cast<size_t>(nr) * sizeof(long long), hipMemcpyDeviceToHost, p->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
-        if (e != hipSuccess) return fail(GENPHI_ERR_DEVICE, std::string("genphi_result_over (counting pass): ") + hipGetErrorString(e));
-        p->over_off.assign(static_cast<size_t>(nr) + 1, 0);
-        for (int64_t k = 0; k < nr; ++k) p->over_off[k + 1] = p->over_off[k] + h[k];
-        p->over_threshold = threshold;
-        p->over_valid = true;
-    }
-    const int64_t total = p->over_off[nr];
-    if (n_pairs) *n_pairs = total;
-    if (total == 0 || total > cap || (!rows && !cols && !values)) return GENPHI_OK;
-
-    const size_t list_bytes = (static_cast<size_t>(total) * 4 + 255) / 256 * 256;
-    int rc = scratch(off_bytes + 3 * list_bytes, "the list of pairs (12 bytes each)");
-    if (rc) return rc;
-    long long *d_off = reinterpret_cast<long long *>(p->scratch);
-    int *d_row = reinterpret_cast<int *>(p->scratch + off_bytes), *d_col = reinterpret_cast<int *>(p->scratch + off_bytes + list_bytes);
-    float *d_val = reinterpret_cast<float *>(p->scratch + off_bytes + 2 * list_bytes);
-    static_assert(sizeof(long long) == sizeof(int64_t), "the offsets are uploaded as they are");
-    hipError_t e = hipMemcpyAsync(d_off, p->over_off.data(), static_cast<size_t>(nr + 1) * sizeof(long long), hipMemcpyHostToDevice, p->stream);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(over_write_kernel, dim3(static_cast<unsigned>(nr)), dim3(256), 0, p->stream, p->result, ld, n, r0, threshold,
-                           d_off, static_cast<long long>(total), d_row, d_col, d_val);
-        e = hipGetLastError();
-    }
-    const size_t out_bytes = static_cast<size_t>(total) * 4;
-    if (e == hipSuccess && rows) e = hipMemcpyAsync(rows, d_row, out_bytes, hipMemcpyDeviceToHost, p->stream);
-    if (e == hipSuccess && cols) e = hipMemcpyAsync(cols, d_col, out_bytes, hipMemcpyDeviceToHost, p->stream);
-    if (e == hipSuccess && values) e = hipMemcpyAsync(values, d_val, out_bytes, hipMemcpyDeviceToHost, p->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
-    else (void)hipStreamSynchronize(p->stream);          // (the host vector and the caller's arrays outlive what was enqueued)
-    if (e != hipSuccess) return fail(GENPHI_ERR_DEVICE, std::string("genphi_result_over: ") + hipGetErrorString(e));
-    return GENPHI_OK;
-}
-
-// gen.phiCI: the bootstrap resamples' quadratic forms over the resident rows; the kernels are in bootstrap.hip.
-int genphi_result_bootstrap(genphi_plan *p, uint64_t seed, int32_t first, int32_t n_boot, double *quad, double *self, int64_t *n_rows)
-{
-    if (!p) return fail(GENPHI_ERR_ARG, "plan is NULL");
-    if (n_rows) *n_rows = p->res_n_rows;
-    if (n_boot < 1 || first < 0 || first > INT32_MAX - n_boot)
-        return fail(GENPHI_ERR_ARG, "genphi_result_bootstrap: resamples first = " + std::to_string(first) + ", n_boot = " + std::to_string(n_boot) +
-                                        " (need first >= 0, n_boot >= 1, first + n_boot < 2^31)");
-    const int64_t N = p->plan.n_pro, nr = p->res_n_rows;
-    if (N < 2) return fail(GENPHI_ERR_ARG, "genphi_result_bootstrap: a resample needs at least 2 probands, the plan has " + std::to_string(N));
-    if (p->res_f64) return fail(GENPHI_ERR_ARG, "genphi_result_bootstrap works on the Float32 result (gen.phi's matrix)");
-    if (p->res_known && nr == 0) {                      // an empty shard adds nothing
-        if (quad) std::fill(quad, quad + n_boot, 0.0);
-        if (self) std::fill(self, self + n_boot, 0.0);
-        return GENPHI_OK;
-    }
-    if (!p->on_device || !p->result || nr == 0) return fail(GENPHI_ERR_DEVICE, "no resident result: call genphi_compute_device first");
-    if (p->res_ld < N || p->res_ld % 64 != 0) return fail(GENPHI_ERR_DEVICE, "genphi_result_bootstrap: unexpected row pitch " + std::to_string(p->res_ld));
-    HIP_TRY(hipSetDevice(p->device));
-    genphi::BootLaunch L;
-    L.stream = p->stream;
-    L.phi = p->result; L.ld = static_cast<long long>(p->res_ld);
-    L.n = static_cast<int>(N); L.row_begin = static_cast<int>(p->res_row_begin); L.n_rows = static_cast<int>(nr);
-    L.seed = seed; L.first = first; L.n_boot = n_boot;
-    L.panel = genphi::boot_panel(L.n, n_boot, p->tun.boot_panel);
-    L.quad = quad; L.self = self;
-    const size_t bytes = genphi::boot_scratch_bytes(L.n, L.n_rows, n_boot, L.panel);
-    if (ensure_scratch(p, bytes) != GENPHI_OK)
-        return fail(GENPHI_ERR_ALLOC, "genphi_result_bootstrap: " + std::to_string(bytes) + " bytes of device memory for the counts and partial sums of a panel of " +
-                                          std::to_string(L.panel) + " resamples: " + g_last_error);
-    L.scratch = p->scratch;
-    const hipError_t e = genphi::boot_launch(L);
-    if (e != hipSuccess) return fail(GENPHI_ERR_DEVICE, std::string("genphi_result_bootstrap: ") + hipGetErrorString(e));
-    return GENPHI_OK;
-}
-
-// gen.phiNearest: one launch, a workgroup per resident row, into two n_rows x k arrays in the plan's scratch block ->
-// one copy per array the caller asked for.
-int genphi_result_nearest(genphi_plan *p, int32_t k, int32_t *cols, float *values)
-{
-    if (!p) return fail(GENPHI_ERR_ARG, "plan is NULL");
-    if (!cols && !values) return fail(GENPHI_ERR_ARG, "genphi_result_nearest: cols and values are both NULL");
-    const int64_t N = p->plan.n_pro, nr = p->res_n_rows;
-    if (N < 2) return fail(GENPHI_ERR_ARG, "genphi_result_nearest: " + std::to_string(N) + " probands have no nearest relative");
-    if (k < 1 || k > std::min<int64_t>(N - 1, GENPHI_NEAREST_MAX_K))
-        return fail(GENPHI_ERR_ARG, "genphi_result_nearest: k = " + std::to_string(k) + " outside [1, " +
-                                    std::to_string(std::min<int64_t>(N - 1, GENPHI_NEAREST_MAX_K)) + "]");
-    if (p->res_f64) return fail(GENPHI_ERR_ARG, "genphi_result_nearest works on the Float32 result (gen.phi's matrix)");
-    if (p->res_known && nr == 0) return GENPHI_OK;
-    if (!p->on_device || !p->result || nr == 0) return fail(GENPHI_ERR_DEVICE, "no resident result: call genphi_compute_device first");
-    HIP_TRY(hipSetDevice(p->device));
-    const size_t out_bytes = static_cast<size_t>(nr) * static_cast<size_t>(k) * 4, arr_bytes = (out_bytes + 255) / 256 * 256;
-    if (ensure_scratch(p, 2 * arr_bytes) != GENPHI_OK)
-        return fail(GENPHI_ERR_ALLOC, "genphi_result_nearest: " + std::to_string(2 * arr_bytes) + " bytes of device memory for the output (8 bytes per row and neighbour): " + g_last_error);
-    int *d_col = reinterpret_cast<int *>(p->scratch);
-    float *d_val = reinterpret_cast<float *>(p->scratch + arr_bytes);
-    const int cap = p->tun.nearest_buf;
-    hipLaunchKernelGGL(nearest_kernel, dim3(static_cast<unsigned>(nr)), dim3(256), static_cast<size_t>(cap) * sizeof(unsigned long long), p->stream,
-                       p->result, static_cast<long long>(p->res_ld), static_cast<int>(N), static_cast<int>(p->res_row_begin), static_cast<int>(k), cap,
-                       cols ? d_col : nullptr, values ? d_val : nullptr);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess && cols) e = hipMemcpyAsync(cols, d_col, out_bytes, hipMemcpyDeviceToHost, p->stream);
-    if (e == hipSuccess && values) e = hipMemcpyAsync(values, d_val, out_bytes, hipMemcpyDeviceToHost, p->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
-    else (void)hipStreamSynchronize(p->stream);          // (the caller's arrays outlive what was enqueued)
-    if (e != hipSuccess) return fail(GENPHI_ERR_DEVICE, std::string("genphi_result_nearest: ") + hipGetErrorString(e));
-    return GENPHI_OK;
-}
-
-// Group sums of the resident result.  Host side: the tables of group_tiles_kernel (rows sorted by group and cut into
-// blocks, the two lists of every column tile), the row ranges of every level of group_rows_reduce_kernel, one upload, the launches,
-// one copy of the n_groups x (n_groups + 1) table back.  Everything lives in the plan's scratch block.
-int genphi_result_group_sums(genphi_plan *p, int32_t n_groups, const int32_t *group, double *sums, double *diag,
-                             int64_t *rows_in_group, int64_t *cols_in_group, int32_t *form_out)
-{
-    if (!p) return fail(GENPHI_ERR_ARG, "plan is NULL");
-    if (n_groups < 1 || n_groups > kGsMaxGroups)
-        return fail(GENPHI_ERR_ARG, "genphi_result_group_sums: n_groups = " + std::to_string(n_groups) + " outside [1, " +
-                                    std::to_string(kGsMaxGroups) + "] (GENPHI_GROUP_SUMS_MAX_GROUPS)");
-    const int64_t N = p->plan.n_pro;
-    if (N > 0 && !group) return fail(GENPHI_ERR_ARG, "genphi_result_group_sums: group is NULL");
-    for (int64_t i = 0; i < N; ++i)
-        if (group[i] < -1 || group[i] >= n_groups)
-            return fail(GENPHI_ERR_ARG, "genphi_result_group_sums: label " + std::to_string(group[i]) + " of proband " + std::to_string(i) +
-                                        " outside [-1, " + std::to_string(n_groups) + ")");
-    if (p->res_f64) return fail(GENPHI_ERR_ARG, "genphi_result_group_sums works on the Float32 result (phiMean's input type, src/compute.jl:454)");
-    const bool empty_shard = p->res_known && p->res_n_rows == 0;          // adds nothing, as for the other queries: zeros, the column counts, the form
-    if (N > 0 && !empty_shard && (!p->on_device || !p->result || p->res_n_rows == 0))
-        return fail(GENPHI_ERR_DEVICE, "no resident result: call genphi_compute_device first");
-    const int G = n_groups, W = G + 1;
-    const int64_t r0 = p->res_row_begin, nr = N > 0 ? p->res_n_rows : 0;
-
-    // labels: counts, and whether every group's columns are one run (form 0)
-    std::vector<int64_t> n_cols(G, 0), n_rows(G, 0);
-    int form = 0;
-    {
-        std::vector<char> closed(G, 0);
-        for (int64_t i = 0; i < N; ++i) {
-            const int g = group[i];
-            if (i > 0 && group[i - 1] >= 0 && group[i - 1] != g) closed[group[i - 1]] = 1;
-            if (g < 0) continue;
-            if (closed[g]) form = 1;
-            ++n_cols[g];
-            if (i >= r0 && i < r0 + nr) ++n_rows[g];
-        }
-    }
-    // resident rows sorted by group (stable), cut into blocks of one group and at most kGsBlockRows rows of even size
-    std::vector<int> rowlist;
-    std::vector<int2> blocks;
-    std::vector<int> cnt(G, 0);                       // rows of `part` per group
-    {
-        std::vector<int64_t> at(G + 1, 0);
-        for (int g = 0; g < G; ++g) at[g + 1] = at[g] + n_rows[g];
-        rowlist.resize(static_cast<size_t>(at[G]));
-        std::vector<int64_t> fill(at.begin(), at.end() - 1);
-        for (int64_t k = 0; k < nr; ++k)
-            if (group[r0 + k] >= 0) rowlist[static_cast<size_t>(fill[group[r0 + k]]++)] = static_cast<int>(k);
-        for (int g = 0; g < G; ++g) {
-            const int64_t n = n_rows[g], nb = (n + kGsBlockRows - 1) / kGsBlockRows;
-            int64_t first = at[g];
-            for (int64_t b = 0; b < nb; ++b) {
-                const int64_t len = n / nb + (b < n % nb ? 1 : 0);
-                blocks.push_back(make_int2(static_cast<int>(first), static_cast<int>(len)));
-                first += len;
-            }
-            cnt[g] = static_cast<int>(nb);
-        }
-    }
-    const int64_t n_blocks = static_cast<int64_t>(blocks.size());
-    auto deliver = [&](const double *tab) {           // tab: G x W (sums | diag), or NULL = zeros
-        for (int a = 0; a < G; ++a) {
-            if (sums) for (int b = 0; b < G; ++b) sums[static_cast<size_t>(a) * G + b] = tab ? tab[static_cast<size_t>(a) * W + b] : 0.0;
-            if (diag) diag[a] = tab ? tab[static_cast<size_t>(a) * W + G] : 0.0;
-            if (rows_in_group) rows_in_group[a] = n_rows[a];
-            if (cols_in_group) cols_in_group[a] = n_cols[a];
-        }
-        if (form_out) *form_out = form;
-    };
-    if (n_blocks == 0) { deliver(nullptr); return GENPHI_OK; }
-
-    // column tiles: pieces (list A) and the pieces of each group (list B), the same for every row
-    const int n_tiles = static_cast<int>((N + kGsTile - 1) / kGsTile);
-    std::vector<int2> tile_lists(static_cast<size_t>(n_tiles) + 1);
-    std::vector<int> list_a;
-    std::vector<int2> list_b;
-    std::vector<unsigned short> perm(form ? static_cast<size_t>(n_tiles) * kGsTile : 0, 0);
-    {
-        std::vector<unsigned short> seq;              // form 0: the tile's labelled columns; form 1: those sorted by group = perm
-        for (int t = 0; t < n_tiles; ++t) {
-            tile_lists[t] = make_int2(static_cast<int>(list_a.size()), static_cast<int>(list_b.size()));
-            const int64_t c0 = static_cast<int64_t>(t) * kGsTile;
-            const int tw = static_cast<int>(std::min<int64_t>(kGsTile, N - c0));
-            seq.clear();
-            for (int c = 0; c < tw; ++c) if (group[c0 + c] >= 0) seq.push_back(static_cast<unsigned short>(c));
-            if (form) {
-                std::stable_sort(seq.begin(), seq.end(), [&](unsigned short x, unsigned short y) { return group[c0 + x] < group[c0 + y]; });
-                std::copy(seq.begin(), seq.end(), perm.begin() + static_cast<size_t>(t) * kGsTile);
-            }
-            const int a0 = static_cast<int>(list_a.size());
-            for (size_t s = 0; s < seq.size();) {       // one group: its pieces, then its entry of list B
-                const int g = group[c0 + seq[s]];
-                const int first_piece = static_cast<int>(list_a.size()) - a0;
-                size_t e = s;
-                while (e < seq.size() && group[c0 + seq[e]] == g && (form || e == s || seq[e] == seq[e - 1] + 1)) ++e;
-                for (size_t q = s; q < e; q += kGsPiece)
-                    list_a.push_back((form ? static_cast<int>(q) : static_cast<int>(seq[q])) | static_cast<int>(std::min<size_t>(kGsPiece, e - q)) << 16);
-                list_b.push_back(make_int2(first_piece | (static_cast<int>(list_a.size()) - a0 - first_piece) << 16, g));
-                s = e;
-            }
-        }
-        tile_lists[n_tiles] = make_int2(static_cast<int>(list_a.size()), static_cast<int>(list_b.size()));
-    }
-    // enough workgroups to fill the device several times over: column slabs
-    const int64_t want_wgs = 24LL * std::max(p->n_cus, 1);
-    const int slabs_want = static_cast<int>(std::min<int64_t>(n_tiles, std::max<int64_t>(1, (want_wgs + n_blocks - 1) / n_blocks)));
-    const int tiles_per_slab = (n_tiles + slabs_want - 1) / slabs_want;
-    const int n_slabs = (n_tiles + tiles_per_slab - 1) / tiles_per_slab;
-    const int64_t n_part = n_blocks * n_slabs;
-    if (n_part > INT32_MAX / 2) return fail(GENPHI_ERR_ARG, "genphi_result_group_sums: too many row blocks");
-    // levels of the row reduction: at most kGsFan rows of one group per output row; the last level has one row per group
-    std::vector<std::vector<int>> level_beg;
-    std::vector<int64_t> level_rows;
-    for (int g = 0; g < G; ++g) cnt[g] *= n_slabs;
-    for (;;) {
-        const bool last = *std::max_element(cnt.begin(), cnt.end()) <= kGsFan;
-        std::vector<int> beg(1, 0);
-        int at = 0;
-        for (int g = 0; g < G; ++g) {
-            const int n = cnt[g], outs = last ? 1 : (n + kGsFan - 1) / kGsFan;
-            for (int o = 0; o < outs; ++o) {
-                at += last ? n : std::min(kGsFan, n - o * kGsFan);
-                beg.push_back(at);
-            }
-            cnt[g] = outs;
-        }
-        level_rows.push_back(static_cast<int64_t>(beg.size()) - 1);
-        level_beg.push_back(std::move(beg));
-        if (last) break;
-    }
-    // one blob of tables, then part and the two buffers of the reduction
-    std::vector<char> blob;
-    auto put = [&](const void *src, size_t bytes) {
-        const size_t off = blob.size();
-        blob.resize(off + al256(std::max<size_t>(bytes, 1)));
-        if (bytes) std::memcpy(blob.data() + off, src, bytes);
-        return off;
-    };
-    const size_t o_rows = put(rowlist.data(), rowlist.size() * sizeof(int));
-    const size_t o_blocks = put(blocks.data(), blocks.size() * sizeof(int2));
-    const size_t o_tiles = put(tile_lists.data(), tile_lists.size() * sizeof(int2));
-    const size_t o_a = put(list_a.data(), list_a.size() * sizeof(int));
-    const size_t o_b = put(list_b.data(), list_b.size() * sizeof(int2));
-    const size_t o_perm = put(perm.data(), perm.size() * sizeof(unsigned short));
-    std::vector<size_t> o_beg;
-    for (const auto &beg : level_beg) o_beg.push_back(put(beg.data(), beg.size() * sizeof(int)));
-    size_t buf_rows[2] = {0, 0};
-    for (size_t l = 0; l < level_rows.size(); ++l) buf_rows[l & 1] = std::max(buf_rows[l & 1], static_cast<size_t>(level_rows[l]));
-    const size_t o_part = blob.size();
-    const size_t o_buf0 = o_part + al256(static_cast<size_t>(n_part) * W * sizeof(double));
-    const size_t o_buf1 = o_buf0 + al256(buf_rows[0] * W * sizeof(double));
-    const size_t total = o_buf1 + al256(buf_rows[1] * W * sizeof(double));
-
-    HIP_TRY(hipSetDevice(p->device));
-    int rc = ensure_scratch(p, total);
-    if (rc) return rc;
-    char *d = p->scratch;
-    hipError_t e = hipMemcpyAsync(d, blob.data(), blob.size(), hipMemcpyHostToDevice, p->stream);
-    std::vector<double> tab(static_cast<size_t>(G) * W);
-    if (e == hipSuccess) {
-        double *part = reinterpret_cast<double *>(d + o_part);
-        double *buf[2] = {reinterpret_cast<double *>(d + o_buf0), reinterpret_cast<double *>(d + o_buf1)};
-        auto launch = [&](auto kernel) {
-            hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(n_part)), dim3(256), 0, p->stream, p->result,
-                               static_cast<long long>(p->res_ld), static_cast<int>(r0), reinterpret_cast<const int *>(d + o_rows),
-                               reinterpret_cast<const int2 *>(d + o_blocks), reinterpret_cast<const int2 *>(d + o_tiles),
-                               reinterpret_cast<const int *>(d + o_a), reinterpret_cast<const int2 *>(d + o_b),
-                               reinterpret_cast<const unsigned short *>(d + o_perm), n_tiles, tiles_per_slab, n_slabs, G, part);
-        };
-        if (form) launch(group_tiles_kernel<true>);
-        else launch(group_tiles_kernel<false>);
-        e = hipGetLastError();
-        const double *in = part;
-        for (size_t l = 0; l < level_rows.size() && e == hipSuccess; ++l) {
-            hipLaunchKernelGGL(group_rows_reduce_kernel, dim3(static_cast<unsigned>(level_rows[l]), static_cast<unsigned>((W + 255) / 256)),
-                               dim3(256), 0, p->stream, in, buf[l & 1], reinterpret_cast<const int *>(d + o_beg[l]), W);
-            e = hipGetLastError();
-            in = buf[l & 1];
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(tab.data(), in, tab.size() * sizeof(double), hipMemcpyDeviceToHost, p->stream);
-    }
-    const hipError_t es = hipStreamSynchronize(p->stream);            // (the blob is read until here)
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) return fail(GENPHI_ERR_DEVICE, std::string("genphi_result_group_sums: ") + hipGetErrorString(e));
-    deliver(tab.data());
-    return GENPHI_OK;
-}
-
-int genphi_result_entries(genphi_plan *p, int64_t n, const int64_t *rows, const int64_t *cols, double *out)
-{
-    if (!p) return fail(GENPHI_ERR_ARG, "plan is NULL");
-    if (n < 0 || (n > 0 && (!rows || !cols || !out))) return fail(GENPHI_ERR_ARG, "genphi_result_entries: bad argument");
-    if (n == 0) return GENPHI_OK;
-    if (!p->on_device || !(p->res_f64 ? static_cast<const void *>(p->result64) : static_cast<const void *>(p->result)))
-        return fail(GENPHI_ERR_DEVICE, "no resident result: call genphi_compute_device first");
-    const int64_t N = p->plan.n_pro, r0 = p->res_row_begin, nr = p->res_n_rows;
-    std::vector<long long> off(static_cast<size_t>(n));
-    for (int64_t k = 0; k < n; ++k) {
-        if (rows[k] < r0 || rows[k] >= r0 + nr || cols[k] < 0 || cols[k] >= N)
-            return fail(GENPHI_ERR_ARG, "genphi_result_entries: entry (" + std::to_string(rows[k]) + ", " + std::to_string(cols[k]) +
-                                        ") outside the resident rows [" + std::to_string(r0) + ", " + std::to_string(r0 + nr) + ") x [0, " + std::to_string(N) + ")");
-        off[k] = static_cast<long long>(rows[k] - r0) * p->res_ld + cols[k];
-    }
-    HIP_TRY(hipSetDevice(p->device));
-    const size_t off_bytes = (static_cast<size_t>(n) * sizeof(long long) + 255) / 256 * 256;
-    int rc = ensure_scratch(p, off_bytes + static_cast<size_t>(n) * sizeof(double));
-    if (rc) return rc;
-    long long *d_off = reinterpret_cast<long long *>(p->scratch);
-    double *d_val = reinterpret_cast<double *>(p->scratch + off_bytes);
-    hipError_t e = hipMemcpyAsync(d_off, off.data(), n * sizeof(long long), hipMemcpyHostToDevice, p->stream);
-    if (e == hipSuccess) {
-        if (p->res_f64)
-            hipLaunchKernelGGL(gather_entries64_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, p->stream,
-                               p->result64, d_off, n, d_val);
-        else
-            hipLaunchKernelGGL(gather_entries_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, p->stream,
-                               p->result, d_off, n, d_val);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d_val, n * sizeof(double), hipMemcpyDeviceToHost, p->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
-    if (e != hipSuccess) return fail(GENPHI_ERR_DEVICE, std::string("genphi_result_entries: ") + hipGetErrorString(e));
     return GENPHI_OK;
 }
 

@@ -1,7 +1,8 @@
 // Host-side sanitizer run ("use -fsanitize=address for the host planner"): the native loader and the planner, the only
 // host code on the gen.phi path that indexes by pedigree data, driven over the bundled genealogies and over random pedigrees with
 // every planner option, under AddressSanitizer + UndefinedBehaviorSanitizer.  Built and run by tests/test_host_sanitizers.py (CPU
-// only; GPU sanitizers are not available on this pool).  Links planner.cpp and loader.cpp directly -- no HIP, no oracle.
+// only; GPU sanitizers are not available on this pool).  Links planner.cpp and loader.cpp directly -- no HIP, no oracle.  Also the host
+// tables of genphi_result_group_sums (group_tables.cpp), over label vectors at every edge of theirs, with their invariants checked.
 //   usage: host_sanitize <genea140.csv> <geneaJi.csv>
 #include <algorithm>
 #include <cstdint>
@@ -11,6 +12,7 @@
 #include <string>
 #include <vector>
 
+#include "../genlib.jl_amd/csrc/group_tables.h"
 #include "../genlib.jl_amd/csrc/planner.h"
 #include "../include/genphi.h"
 
@@ -80,10 +82,108 @@ static std::vector<int64_t> probands_of(const std::vector<int64_t> &ind, const s
     return pro;
 }
 
+// build_group_tables on one label vector; what the kernels rely on, checked.  Returns 1 on a broken invariant.
+static int group_tables_case(const char *what, const std::vector<int32_t> &lab, int G, int64_t r0, int64_t nr, int min_levels = 1)
+{
+    using namespace genphi;
+    const int64_t N = static_cast<int64_t>(lab.size());
+    GroupTables t;
+    build_group_tables(lab.data(), G, N, r0, nr, 256, t);
+    auto bad = [&](const char *why) { std::fprintf(stderr, "group tables, %s: %s\n", what, why); return 1; };
+    // counts; the row list holds every labelled resident row once, by group; blocks cut it into <= kGsBlockRows rows of one group
+    std::vector<int64_t> n_cols(G, 0), n_rows(G, 0);
+    for (int64_t i = 0; i < N; ++i) if (lab[i] >= 0) { ++n_cols[lab[i]]; if (i >= r0 && i < r0 + nr) ++n_rows[lab[i]]; }
+    if (t.n_cols != n_cols || t.n_rows != n_rows) return bad("counts");
+    std::vector<int> seen_row(static_cast<size_t>(nr), 0);
+    size_t at = 0;
+    std::vector<int> blocks_of(G, 0);
+    for (const GsPair &b : t.blocks) {
+        if (b.x != static_cast<int>(at) || b.y < 1 || b.y > kGsBlockRows || at + b.y > t.rowlist.size()) return bad("a block's range");
+        const int g = lab[r0 + t.rowlist[at]];
+        for (int k = 0; k < b.y; ++k) {
+            const int r = t.rowlist[at + k];
+            if (r < 0 || r >= nr || lab[r0 + r] != g || (at + k > 0 && lab[r0 + t.rowlist[at + k - 1]] > g)) return bad("a block's rows");
+            ++seen_row[r];
+        }
+        ++blocks_of[g];
+        at += b.y;
+    }
+    if (at != t.rowlist.size()) return bad("the blocks do not cover the row list");
+    for (int64_t r = 0; r < nr; ++r) if (seen_row[r] != (lab[r0 + r] >= 0 ? 1 : 0)) return bad("a resident row is not listed exactly once");
+    if (t.blocks.empty()) return t.level_rows.empty() && t.list_a.empty() ? 0 : bad("tables without a block");
+    // tiles: monotone offsets; every labelled column in exactly one piece of <= kGsPiece columns of its group; every piece in one entry of list B
+    if (t.n_tiles != (N + kGsTile - 1) / kGsTile || static_cast<int>(t.tile_lists.size()) != t.n_tiles + 1) return bad("tile count");
+    if (t.perm.size() != (t.form ? static_cast<size_t>(t.n_tiles) * kGsTile : 0)) return bad("perm size");
+    std::vector<int> seen_col(static_cast<size_t>(N), 0);
+    for (int tl = 0; tl < t.n_tiles; ++tl) {
+        const GsPair l0 = t.tile_lists[tl], l1 = t.tile_lists[tl + 1];
+        if (l1.x < l0.x || l1.y < l0.y || l1.x > static_cast<int>(t.list_a.size()) || l1.y > static_cast<int>(t.list_b.size())) return bad("tile offsets");
+        int next_piece = 0;
+        std::vector<char> group_in_tile(G, 0);
+        for (int i = l0.y; i < l1.y; ++i) {
+            const int first = t.list_b[i].x & 0xffff, len = t.list_b[i].x >> 16, g = t.list_b[i].y;
+            if (first != next_piece || len < 1 || g < 0 || g >= G || group_in_tile[g]) return bad("list B");
+            group_in_tile[g] = 1;
+            for (int q = first; q < first + len; ++q) {
+                if (l0.x + q >= l1.x) return bad("list B names a piece outside the tile");
+                const int w = t.list_a[l0.x + q], c_first = w & 0xffff, c_len = w >> 16;
+                if (c_len < 1 || c_len > kGsPiece || c_first + c_len > kGsTile) return bad("a piece's length");
+                for (int k = 0; k < c_len; ++k) {
+                    const int64_t c = static_cast<int64_t>(tl) * kGsTile + (t.form ? t.perm[static_cast<size_t>(tl) * kGsTile + c_first + k] : c_first + k);
+                    if (c >= N || lab[c] != g) return bad("a piece's column");
+                    ++seen_col[c];
+                }
+            }
+            next_piece = first + len;
+        }
+        if (next_piece != l1.x - l0.x) return bad("list B does not cover the tile's pieces");
+    }
+    if (t.tile_lists[0].x != 0 || t.tile_lists[0].y != 0 || t.tile_lists[t.n_tiles].x != static_cast<int>(t.list_a.size()) ||
+        t.tile_lists[t.n_tiles].y != static_cast<int>(t.list_b.size())) return bad("tile offsets' ends");
+    for (int64_t c = 0; c < N; ++c) if (seen_col[c] != (lab[c] >= 0 ? 1 : 0)) return bad("a labelled column is not in exactly one piece");
+    // slabs and the levels of the reduction: each level's offsets monotone, <= kGsFan rows per output except in the last, which has G rows
+    if (t.tiles_per_slab < 1 || t.n_slabs < 1 || static_cast<int64_t>(t.n_slabs) * t.tiles_per_slab < t.n_tiles ||
+        static_cast<int64_t>(t.n_slabs - 1) * t.tiles_per_slab >= t.n_tiles || t.n_part != static_cast<int64_t>(t.blocks.size()) * t.n_slabs) return bad("slabs");
+    if (t.level_rows.size() != t.level_beg.size() || static_cast<int>(t.level_rows.size()) < min_levels) return bad("levels");
+    int64_t in_rows = t.n_part;
+    for (size_t l = 0; l < t.level_beg.size(); ++l) {
+        const std::vector<int> &beg = t.level_beg[l];
+        if (static_cast<int64_t>(beg.size()) != t.level_rows[l] + 1 || beg.front() != 0 || beg.back() != in_rows) return bad("a level's ends");
+        for (size_t k = 0; k + 1 < beg.size(); ++k) if (beg[k + 1] < beg[k] || beg[k + 1] - beg[k] > kGsFan) return bad("a level's offsets");
+        in_rows = t.level_rows[l];
+    }
+    if (in_rows != G) return bad("the last level does not have n_groups rows");
+    const std::vector<int> &lb = t.level_beg.back();
+    if (t.level_beg.size() == 1) for (int g = 0; g < G; ++g) if (lb[g + 1] - lb[g] != blocks_of[g] * t.n_slabs) return bad("a group's rows of part");
+    return 0;
+}
+
+static int group_tables_all()
+{
+    int bad = 0;
+    auto labels = [](int64_t n, auto f) { std::vector<int32_t> v(static_cast<size_t>(n)); for (int64_t i = 0; i < n; ++i) v[i] = f(i); return v; };
+    bad |= group_tables_case("one group, all labelled", labels(100, [](int64_t) { return 0; }), 1, 0, 100);
+    bad |= group_tables_case("labels all -1", labels(100, [](int64_t) { return -1; }), 3, 0, 100);
+    bad |= group_tables_case("interleaved (form 1)", labels(2500, [](int64_t i) { return i % 7 == 6 ? -1 : static_cast<int>(i % 3); }), 3, 0, 2500);
+    bad |= group_tables_case("one run per group (form 0)", labels(2500, [](int64_t i) { return i < 40 ? -1 : static_cast<int>((i - 40) / 500); }), 5, 0, 2500);
+    for (int64_t n : {1, 1023, 1024, 1025}) {
+        bad |= group_tables_case("N at the tile edge, runs", labels(n, [n](int64_t i) { return static_cast<int>(2 * i / n); }), 2, 0, n);
+        bad |= group_tables_case("N at the tile edge, interleaved", labels(n, [](int64_t i) { return static_cast<int>(i % 2); }), 2, 0, n);
+    }
+    bad |= group_tables_case("a group of 65 rows", labels(200, [](int64_t i) { return i < 65 ? 0 : (i < 129 ? 1 : -1); }), 2, 0, 200);
+    bad |= group_tables_case("two levels of the reduction", labels(3000, [](int64_t) { return 0; }), 1, 0, 3000, 2);
+    bad |= group_tables_case("two levels, interleaved", labels(5000, [](int64_t i) { return static_cast<int>(i % 2); }), 2, 0, 5000, 2);
+    bad |= group_tables_case("a shard that misses a group", labels(900, [](int64_t i) { return static_cast<int>(i / 300); }), 3, 10, 200);
+    bad |= group_tables_case("a shard of unlabelled rows", labels(900, [](int64_t i) { return i < 100 ? -1 : 0; }), 1, 0, 100);
+    bad |= group_tables_case("an empty shard", labels(900, [](int64_t i) { return static_cast<int>(i % 4); }), 4, 450, 0);
+    std::printf("group tables: %s\n", bad ? "FAILED" : "ok");
+    return bad;
+}
+
 int main(int argc, char **argv)
 {
     if (argc < 3) { std::fprintf(stderr, "usage: host_sanitize genea140.csv geneaJi.csv\n"); return 2; }
-    int bad = 0;
+    int bad = group_tables_all();
     for (int f = 1; f <= 2; ++f)
         for (int sort = 0; sort <= 1; ++sort) {
             int64_t n = 0, *ind = nullptr, *fa = nullptr, *mo = nullptr, *sex = nullptr;

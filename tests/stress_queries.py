@@ -11,7 +11,8 @@ genphi_result_sums, genphi_result_group_sums, genphi_result_over, genphi_result_
 oracles of tests/*_oracle.py applied to that host copy.
 
 What the queries rely on and no interface states: the padding columns [N, ld) of every resident row are +0 after every
-delivery path, ld % 64 == 0, and res_ld / res_row_begin / res_n_rows / over_valid follow every compute.  A stale positive float in the
+delivery path, ld % 64 == 0, and res_ld / res_row_begin / res_n_rows and the phiOver offset cache (genphi_plan::over, dropped by
+set_resident_rows) follow every compute.  A stale positive float in the
 padding shows in the sums and the bootstrap, a wrong row_begin in every list.
 
 No tolerance but the two derived rules that are in the tree with their derivation: group_sums_oracle.gamma for the Float64 sums and the
