@@ -57,6 +57,7 @@
 #include "panel_launch.h"
 #include "devcache.h"
 #include "planner.h"
+#include "shard_lists.h"
 #include "resident.h"
 #include "sparse_levels.h"
 
@@ -734,7 +735,7 @@ level_split_fast_kernel(const LevelArgs p, const int4 *__restrict__ desc, const 
     constexpr int NQ = CPT / 4;
 
     // ---- stage state (all wave-uniform).  An item is (run, column chunk); a run is a list of segments (see
-    //      GroupLists): the first one stages its hub row (stage A), every child with a B source is a stage B, and
+    //      WalkLists): the first one stages its hub row (stage A), every child with a B source is a stage B, and
     //      the expansion of a segment's last B row becomes the hub of a following type-1 segment for free. ----
     // (few scalars are kept across stages -- the kernel is at the SGPR limit, and a scalar spilled to a VGPR lane costs
     // a vector register of the column state; what a stage needs beyond them is re-read from the scalar cache)
@@ -2084,9 +2085,6 @@ static Tuning tuning_from(const genphi_tuning *tu)
 //   run  : first segment of every run + terminator
 // level_split_fast_kernel takes runs as its items, level_split_kernel (grouping-exact: it keeps one 32-bit rank
 // mask per child in 4 VGPRs, hence segments of at most 4 children) single segments.
-struct GroupLists {
-    genphi::WalkLists w;
-};
 struct DeviceGroups {
     int4 *desc = nullptr, *seg = nullptr;
     int4 *run = nullptr;       // (first segment, hub row | n0 << 16, its rows [z, w)) per run + terminator
@@ -2111,28 +2109,51 @@ struct DeviceStep {
     int nn = -1;               // index of the new x new sub-step in genphi_plan::nn_steps / nn_dsteps
 };
 
-static void build_groups(const LevelStep &s, const int *rows, const int *out_rows, int n_rows, GroupLists &gl, const Tuning &tun)
+// Lays arrays out in ONE device allocation, each on a 256-byte boundary.  The same layout code runs twice: first against a packer
+// without memory -- put() only adds up the size (blob_size) --, then, after the allocation, against the host image and the device
+// address.  The size of a blob so comes from the code that fills it; a layout that differs between the passes sets `overrun`
+// instead of writing past the image.
+struct BlobPacker {
+    char *host = nullptr, *dev = nullptr;      // both null: the counting pass
+    size_t size = 0, off = 0;
+    bool overrun = false;
+    // copies n elements and reserves `room` >= n of them (0: n); the writing pass sets `dst` to the device address of the array (the
+    // counting pass writes nothing: a size query leaves the plan as it is)
+    template <class D, class T>
+    void put(D *&dst, const T *src, size_t n, size_t room = 0)
+    {
+        const size_t bytes = al256(std::max(room, n) * sizeof(T));
+        if (host && ((room && n > room) || off + bytes > size)) { overrun = true; return; }
+        if (host && n) std::memcpy(host + off, src, n * sizeof(T));
+        if (host) dst = reinterpret_cast<D *>(dev + off);
+        off += bytes;
+    }
+    // the host image of an array put() returned (the writing pass)
+    template <class T>
+    T *image(T *d) const { return reinterpret_cast<T *>(host + (reinterpret_cast<char *>(d) - dev)); }
+};
+template <class Layout>
+static size_t blob_size(Layout &&layout) { BlobPacker count; layout(count); return count.off; }
+// ... the writing pass into the host image `img` (pageable: synchronise before it goes out of scope) and its copy to the allocation `dev`
+template <class Layout>
+static int blob_upload(Layout &&layout, std::vector<char> &img, char *dev, size_t bytes, hipStream_t stream)
 {
-    // segments are capped -- the grouping-exact kernel keeps one 32-bit rank mask per child in 4 VGPRs, so <= 4 children where it
-    // needs them (cut not in rank order), <= 8 where the position test replaces them -- and so are runs: a workgroup walks a
-    // run's stages one after the other, so one huge run would be a serial tail
-    genphi::build_hub_walk(s.srcA.data(), s.srcB.data(), s.ord.data(), static_cast<int32_t>(s.n_prev), rows, out_rows, n_rows,
-                           std::min(tun.max_group, s.pos_ord ? 8 : 4), tun.max_run, gl.w);
+    img.assign(bytes, 0);
+    BlobPacker w{img.data(), dev, bytes};
+    layout(w);
+    if (w.overrun) return fail(GENPHI_ERR_DEVICE, "internal: a device blob was laid out differently from its size");
+    HIP_TRY(hipMemcpyAsync(dev, img.data(), bytes, hipMemcpyHostToDevice, stream));
+    return GENPHI_OK;
 }
 
-static size_t groups_bytes(const GroupLists &gl)
+static void put_groups(const genphi::WalkLists &w, DeviceGroups &d, BlobPacker &bp)
 {
-    return al256(gl.w.desc4.size() * sizeof(int)) + al256(gl.w.seg4.size() * sizeof(int)) + al256(gl.w.run.size() * sizeof(int));
-}
-// put(src, bytes) copies into the host image of a device blob and returns the device address
-template <class Put>
-static void put_groups(const GroupLists &gl, DeviceGroups &d, Put &&put)
-{
-    d.desc = reinterpret_cast<int4 *>(put(gl.w.desc4.data(), gl.w.desc4.size() * sizeof(int)));
-    d.seg = reinterpret_cast<int4 *>(put(gl.w.seg4.data(), gl.w.seg4.size() * sizeof(int)));
-    d.run = reinterpret_cast<int4 *>(put(gl.w.run.data(), gl.w.run.size() * sizeof(int)));
-    d.n_segs = static_cast<int>(gl.w.seg4.size() / 4) - 2;
-    d.n_runs = static_cast<int>(gl.w.run.size() / 4) - 1;
+    bp.put(d.desc, w.desc4.data(), w.desc4.size());
+    bp.put(d.seg, w.seg4.data(), w.seg4.size());
+    bp.put(d.run, w.run.data(), w.run.size());
+    if (!bp.host) return;
+    d.n_segs = static_cast<int>(w.seg4.size() / 4) - 2;
+    d.n_runs = static_cast<int>(w.run.size() / 4) - 1;
 }
 
 struct genphi_plan {
@@ -2448,14 +2469,14 @@ int genphi_plan_step_walk(const genphi_plan *plan, int32_t step, int64_t *n_rows
         return fail(GENPHI_ERR_ARG, "genphi_plan_step_walk: bad argument");
     const LevelStep &s = plan->plan.steps[step];
     if (s.mode != genphi::kModeSplit) return fail(GENPHI_ERR_ARG, "genphi_plan_step_walk: not a SPLIT step");
-    GroupLists gl;
-    build_groups(s, s.work.data(), nullptr, static_cast<int>(s.work.size()), gl, plan->tun);
-    if (n_rows) *n_rows = static_cast<int64_t>(gl.w.desc4.size() / 4);
-    if (n_segs) *n_segs = static_cast<int64_t>(gl.w.seg4.size() / 4) - 2;
-    if (n_runs) *n_runs = static_cast<int64_t>(gl.w.run.size() / 4) - 1;
-    if (desc4) std::memcpy(desc4, gl.w.desc4.data(), gl.w.desc4.size() * sizeof(int32_t));
-    if (seg4) std::memcpy(seg4, gl.w.seg4.data(), gl.w.seg4.size() * sizeof(int32_t));
-    if (run4) std::memcpy(run4, gl.w.run.data(), gl.w.run.size() * sizeof(int32_t));
+    genphi::WalkLists w;
+    genphi::walk_lists(s, s.work.data(), nullptr, static_cast<int>(s.work.size()), plan->tun.max_group, plan->tun.max_run, w);
+    if (n_rows) *n_rows = static_cast<int64_t>(w.desc4.size() / 4);
+    if (n_segs) *n_segs = static_cast<int64_t>(w.seg4.size() / 4) - 2;
+    if (n_runs) *n_runs = static_cast<int64_t>(w.run.size() / 4) - 1;
+    if (desc4) std::memcpy(desc4, w.desc4.data(), w.desc4.size() * sizeof(int32_t));
+    if (seg4) std::memcpy(seg4, w.seg4.data(), w.seg4.size() * sizeof(int32_t));
+    if (run4) std::memcpy(run4, w.run.data(), w.run.size() * sizeof(int32_t));
     return GENPHI_OK;
 }
 
@@ -2514,15 +2535,13 @@ static int upload_plan_impl(genphi_plan *p, int device)
 
     trace.mark("  upload: device, stream");
     const Plan &pl = p->plan;
-    auto al = [](size_t b) { return (b + 255) / 256 * 256; };
-    size_t total = 256;
     // every step to upload: the plan's steps, then the new x new sub-steps of the WIDE ones
     p->nn_steps.clear();
     for (const LevelStep &s : pl.steps)
         if (s.mode == genphi::kModeWide && !s.nn.empty()) p->nn_steps.push_back(&s.nn[0]);
     const size_t n_main = pl.steps.size(), n_all = n_main + p->nn_steps.size();
     auto step_at = [&](size_t k) -> const LevelStep & { return k < n_main ? pl.steps[k] : *p->nn_steps[k - n_main]; };
-    std::vector<GroupLists> step_groups(n_all);
+    std::vector<genphi::WalkLists> step_groups(n_all);
     {   // the hub walks of the SPLIT steps are independent of each other: a few host threads (24 -> ~7 ms of a first call on cfg4)
         // (the leading steps that may run on row lists -- sparse_levels.h -- get their walk lists when a sweep first runs them densely:
         // ensure_groups; genea140: five of its SPLIT steps, 1-2 ms of every one-shot call, never do)
@@ -2537,7 +2556,7 @@ static int upload_plan_impl(genphi_plan *p, int device)
             try {
                 for (size_t q = next.fetch_add(1); q < split_steps.size(); q = next.fetch_add(1)) {
                     const LevelStep &s = step_at(split_steps[q]);
-                    build_groups(s, s.work.data(), nullptr, static_cast<int>(s.work.size()), step_groups[split_steps[q]], p->tun);
+                    genphi::walk_lists(s, s.work.data(), nullptr, static_cast<int>(s.work.size()), p->tun.max_group, p->tun.max_run, step_groups[split_steps[q]]);
                 }
             } catch (const std::bad_alloc &) { oom[t] = 1; }
         };
@@ -2549,90 +2568,81 @@ static int upload_plan_impl(genphi_plan *p, int device)
         }
         for (char e : oom) if (e) return fail(GENPHI_ERR_ALLOC, "out of memory while building the work lists");
     }
-    for (size_t k = 0; k < n_all; ++k) {
-        const LevelStep &s = step_at(k);
-        total += 3 * al(s.n * sizeof(int)) + 2 * al((s.n + idx_pad(s)) * sizeof(int));
-        if (s.mode == genphi::kModeSplit && !step_groups[k].w.run.empty()) total += groups_bytes(step_groups[k]);
-        if (s.mode == genphi::kModeWide)
-            total += al(s.n * sizeof(int4)) + al(s.parents.size() * sizeof(int4)) + al(s.parents.size() * sizeof(int)) +
-                     al((s.n - s.n_dragged) * sizeof(int)) + al((s.n_dragged / 8192 + 2) * sizeof(int)) + al(s.n_dragged * sizeof(int)) +
-                     al(s.blk_slot.size() * sizeof(int)) + al((s.live_ranges.size() / 2 + static_cast<size_t>(s.stay ? s.P : 0) / 128 + 1) * sizeof(int2));
-    }
-    total += al(pl.final_perm.size() * sizeof(int)) + al(pl.final_slots.size() * sizeof(int));
     trace.mark("  upload: walk lists (host)");
-    HIP_TRY(plan_malloc(p, reinterpret_cast<void **>(&p->idx_blob), total));
-    p->idx_blob_bytes = total;
-    trace.mark("  upload: hipMalloc index blob");
-    std::vector<char> host(total, 0);
-    size_t off = 0;
-    auto put = [&](const void *src, size_t bytes, size_t pad_bytes = 0) -> char * {
-        char *d = p->idx_blob + off;
-        if (bytes) std::memcpy(host.data() + off, src, bytes);
-        off += al(bytes + pad_bytes);
-        return d;
-    };
     p->dsteps.assign(n_main, DeviceStep());
     p->nn_dsteps.assign(n_all - n_main, DeviceStep());
-    int nn_next = 0;
-    for (size_t k = 0; k < n_all; ++k) {
-        const LevelStep &s = step_at(k);
-        DeviceStep &d = k < n_main ? p->dsteps[k] : p->nn_dsteps[k - n_main];
-        d.srcA = reinterpret_cast<int *>(put(s.srcA.data(), s.n * sizeof(int)));
-        d.srcB = reinterpret_cast<int *>(put(s.srcB.data(), s.n * sizeof(int)));
-        d.ord = reinterpret_cast<int *>(put(s.ord.data(), s.n * sizeof(int), idx_pad(s) * sizeof(int)));
-        d.work = reinterpret_cast<int *>(put(s.work.data(), s.work.size() * sizeof(int)));
-        d.pk = reinterpret_cast<unsigned *>(put(s.pk.data(), s.pk.size() * sizeof(unsigned), idx_pad(s) * sizeof(unsigned)));
-        if (!s.pk.empty()) {      // padding entries point both sources at the zero column
-            unsigned *hp = reinterpret_cast<unsigned *>(host.data() + (reinterpret_cast<char *>(d.pk) - p->idx_blob));
-            const unsigned zero_pk = static_cast<unsigned>(s.n_prev) | (static_cast<unsigned>(s.n_prev) << 16);
-            for (size_t k2 = s.pk.size(); k2 < s.pk.size() + idx_pad(s); ++k2) hp[k2] = zero_pk;
-        }
-        if (s.mode == genphi::kModeSplit && !step_groups[k].w.run.empty()) put_groups(step_groups[k], d.groups, put);
-        if (s.mode == genphi::kModeWide) {
+    // the index blob: per step its five index arrays (ord and pk padded for the kernels' unconditional gathers), the walk lists of a
+    // SPLIT step, the descriptors of a WIDE one (built in the writing pass only; `room` is what the counting pass reserves for them)
+    auto layout = [&](BlobPacker &bp) {
+        int nn_next = 0;
+        for (size_t k = 0; k < n_all; ++k) {
+            const LevelStep &s = step_at(k);
+            DeviceStep &d = k < n_main ? p->dsteps[k] : p->nn_dsteps[k - n_main];
+            const size_t n = static_cast<size_t>(s.n), padded = n + idx_pad(s);
+            bp.put(d.srcA, s.srcA.data(), n);
+            bp.put(d.srcB, s.srcB.data(), n);
+            bp.put(d.ord, s.ord.data(), n, padded);
+            bp.put(d.work, s.work.data(), s.work.size(), n);
+            bp.put(d.pk, s.pk.data(), s.pk.size(), padded);
+            if (bp.host && !bp.overrun && !s.pk.empty()) {      // padding entries point both sources at the zero column
+                const unsigned zero_pk = static_cast<unsigned>(s.n_prev) | (static_cast<unsigned>(s.n_prev) << 16);
+                std::fill_n(bp.image(d.pk) + s.pk.size(), idx_pad(s), zero_pk);
+            }
+            if (s.mode == genphi::kModeSplit && !step_groups[k].run.empty()) put_groups(step_groups[k], d.groups, bp);
+            if (s.mode != genphi::kModeWide) continue;
             // (a source cut stored by slot: sources, parents and "none" are slots of its P x P matrix; a step that stays in
             // place writes row r of its cut to the member's slot)
             const int none = s.src_slots ? s.P : static_cast<int>(s.n_prev);
             const int32_t *sA = s.src_slots ? s.absA.data() : s.srcA.data(), *sB = s.src_slots ? s.absB.data() : s.srcB.data();
             const int32_t *par = s.src_slots ? s.parents_abs.data() : s.parents.data();
-            std::vector<int4> rd(s.n), pd(s.parents.size());
-            std::vector<int> nr(s.n - s.n_dragged);
-            for (int64_t r = 0; r < s.n; ++r)              // dragged: weight 1; new: weight 1/2 (columns here are dragged: weight 1)
-                rd[r] = make_int4(sA[r], sB[r], s.stay ? s.out_slots[r] : static_cast<int>(r), s.ord[r] < 0 ? -1 : 0);
-            for (size_t u = 0; u < s.parents.size(); ++u) pd[u] = make_int4(par[u], none, static_cast<int>(u), 0);
-            for (size_t r = 0; r < nr.size(); ++r) nr[r] = static_cast<int>(s.n_dragged + r);
-            d.rowdesc = reinterpret_cast<int4 *>(put(rd.data(), rd.size() * sizeof(int4)));
-            d.pardesc = reinterpret_cast<int4 *>(put(pd.data(), pd.size() * sizeof(int4)));
-            d.parents = reinterpret_cast<int *>(put(par, s.parents.size() * sizeof(int)));
-            d.newrows = reinterpret_cast<int *>(put(nr.data(), nr.size() * sizeof(int)));
-            d.idx = reinterpret_cast<int *>(put(sA, s.n_dragged * sizeof(int)));
-            d.blk_slot = reinterpret_cast<int *>(put(s.blk_slot.data(), s.blk_slot.size() * sizeof(int)));
-            {   // column tiles of rows_avg_t_kernel over all live ranges (one launch per step)
-                std::vector<int2> tl;
+            const size_t n_par = s.parents.size(), n_new = static_cast<size_t>(s.n - s.n_dragged);
+            std::vector<int4> rd, pd;
+            std::vector<int> nr, ps;
+            std::vector<int2> tl;
+            if (bp.host) {
+                rd.resize(n); pd.resize(n_par); nr.resize(n_new);
+                for (int64_t r = 0; r < s.n; ++r)              // dragged: weight 1; new: weight 1/2 (columns here are dragged: weight 1)
+                    rd[r] = make_int4(sA[r], sB[r], s.stay ? s.out_slots[r] : static_cast<int>(r), s.ord[r] < 0 ? -1 : 0);
+                for (size_t u = 0; u < n_par; ++u) pd[u] = make_int4(par[u], none, static_cast<int>(u), 0);
+                for (size_t r = 0; r < n_new; ++r) nr[r] = static_cast<int>(s.n_dragged + r);
+                // column tiles of rows_avg_t_kernel over all live ranges (one launch per step)
                 long long cols_live = 0;
                 for (size_t h = 0; h + 1 < s.live_ranges.size(); h += 2) cols_live += s.live_ranges[h + 1] - s.live_ranges[h];
                 d.tile_cols = p->tun.stay_tile ? p->tun.stay_tile : ((cols_live / 256 + 1) * static_cast<long long>(s.blk_slot.size()) < 8192 ? 128 : 256);
                 for (size_t h = 0; h + 1 < s.live_ranges.size(); h += 2)
                     for (int c0 = s.live_ranges[h]; c0 < s.live_ranges[h + 1]; c0 += d.tile_cols) tl.push_back(make_int2(c0, s.live_ranges[h + 1]));
                 d.n_tiles = static_cast<int>(tl.size());
-                d.tiles = reinterpret_cast<int2 *>(put(tl.data(), tl.size() * sizeof(int2)));
+                // drag_rows_kernel: parents inside the source window of each chunk of 8192 dragged columns
+                const int64_t chunk = 8192, nch = (s.n_dragged + chunk - 1) / chunk;
+                ps.assign(nch + 1, 0);
+                size_t pi = 0;
+                for (int64_t c = 1; c < nch; ++c) {
+                    while (pi < n_par && s.parents[pi] < s.srcA[c * chunk]) ++pi;
+                    ps[c] = static_cast<int>(pi);
+                }
+                ps[nch] = static_cast<int>(n_par);
             }
-            // drag_rows_kernel: parents inside the source window of each chunk of 8192 dragged columns
-            const int64_t chunk = 8192, nch = (s.n_dragged + chunk - 1) / chunk;
-            std::vector<int> ps(nch + 1, 0);
-            size_t pi = 0;
-            for (int64_t c = 1; c < nch; ++c) {
-                while (pi < s.parents.size() && s.parents[pi] < s.srcA[c * chunk]) ++pi;
-                ps[c] = static_cast<int>(pi);
-            }
-            ps[nch] = static_cast<int>(s.parents.size());
-            d.pstart = reinterpret_cast<int *>(put(ps.data(), ps.size() * sizeof(int)));
-            if (!s.nn.empty()) d.nn = nn_next++;
+            bp.put(d.rowdesc, rd.data(), rd.size(), n);
+            bp.put(d.pardesc, pd.data(), pd.size(), n_par);
+            bp.put(d.parents, par, n_par);
+            bp.put(d.newrows, nr.data(), nr.size(), n_new);
+            bp.put(d.idx, sA, static_cast<size_t>(s.n_dragged));
+            bp.put(d.blk_slot, s.blk_slot.data(), s.blk_slot.size());
+            bp.put(d.tiles, tl.data(), tl.size(), s.live_ranges.size() / 2 + static_cast<size_t>(s.stay ? s.P : 0) / 128 + 1);
+            bp.put(d.pstart, ps.data(), ps.size(), static_cast<size_t>(s.n_dragged / 8192 + 2));
+            if (!s.nn.empty() && bp.host) d.nn = nn_next++;
         }
-    }
-    p->d_final_perm = reinterpret_cast<int *>(put(pl.final_perm.data(), pl.final_perm.size() * sizeof(int)));
-    p->d_final_slots = reinterpret_cast<int *>(put(pl.final_slots.data(), pl.final_slots.size() * sizeof(int)));
+        bp.put(p->d_final_perm, pl.final_perm.data(), pl.final_perm.size());
+        bp.put(p->d_final_slots, pl.final_slots.data(), pl.final_slots.size());
+    };
+    const size_t total = blob_size(layout) + 256;
+    HIP_TRY(plan_malloc(p, reinterpret_cast<void **>(&p->idx_blob), total));
+    p->idx_blob_bytes = total;
+    trace.mark("  upload: hipMalloc index blob");
+    std::vector<char> host;
+    const int lrc = blob_upload(layout, host, p->idx_blob, total, p->stream);
+    if (lrc) return lrc;
     trace.mark("  upload: host image");
-    HIP_TRY(hipMemcpyAsync(p->idx_blob, host.data(), total, hipMemcpyHostToDevice, p->stream));
     HIP_TRY(hipStreamSynchronize(p->stream));      // `host` goes out of scope
     trace.mark("  upload: copy to device");
 
@@ -2952,23 +2962,17 @@ static int ensure_groups(genphi_plan *p, int step)
     const LevelStep &s = p->plan.steps[step];
     DeviceStep &d = p->dsteps[step];
     if (s.mode != genphi::kModeSplit || d.groups.desc != nullptr) return GENPHI_OK;
-    GroupLists gl;
-    build_groups(s, s.work.data(), nullptr, static_cast<int>(s.work.size()), gl, p->tun);
-    const size_t gb = groups_bytes(gl);
+    genphi::WalkLists w;
+    genphi::walk_lists(s, s.work.data(), nullptr, static_cast<int>(s.work.size()), p->tun.max_group, p->tun.max_run, w);
+    auto layout = [&](BlobPacker &bp) { put_groups(w, d.groups, bp); };
+    const size_t gb = blob_size(layout);
     char *blob = nullptr;
     HIP_TRY(plan_malloc(p, reinterpret_cast<void **>(&blob), gb));
     p->lazy_blobs.push_back(blob);
     p->lazy_bytes += gb;
-    std::vector<char> img(gb, 0);
-    size_t off = 0;
-    auto put = [&](const void *src, size_t bytes) -> char * {
-        char *dst = blob + off;
-        if (bytes) std::memcpy(img.data() + off, src, bytes);
-        off += al256(bytes);
-        return dst;
-    };
-    put_groups(gl, d.groups, put);
-    HIP_TRY(hipMemcpyAsync(blob, img.data(), gb, hipMemcpyHostToDevice, p->stream));
+    std::vector<char> img;
+    const int rc = blob_upload(layout, img, blob, gb, p->stream);
+    if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(p->stream));          // `img` goes out of scope
     return GENPHI_OK;
 }
@@ -3531,18 +3535,32 @@ static int compute_f64(genphi_plan *p, int64_t r0, int64_t r1, int kernel, genph
     return GENPHI_OK;
 }
 
-extern "C" {
+// ---- one Float32 sweep (genphi_compute_device), phase by phase ------------------------------
 
-int genphi_compute_device(genphi_plan *p, const genphi_opts *opts, genphi_stats *stats)
+// The constants of one call
+struct SweepCall {
+    int kernel = 0;
+    int64_t r0 = 0, n_rows = 0;      // the shard: rows [r0, r0 + n_rows) of the proband matrix
+    int sparse_k = -1;               // cuts 0..sparse_k are row lists (sparse_levels.h); -1: every level is a dense matrix
+    // last step WIDE: the whole level (every row, [dragged, new] storage order) goes to final_tmp, then the shard's rows are delivered in
+    // proband order (deliver_proband_order) ...
+    bool need_perm = false;
+    // ... unless the proband cut STAYED IN PLACE at the end of a run (Plan::final_slots): the last step then writes only the new probands'
+    // rows and columns into the run's matrix and the delivery reads from there, by slot -- one pass instead of a compaction + a
+    // permutation (genea140 with every individual a proband: the last step 7.7 -> ... ms).  The per-entry sweep (kernel = 1) knows no slots.
+    bool last_by_slot = false;
+    bool timing = false;
+    std::vector<int> ev_after;       // event recorded after step k (timing)
+};
+
+// Argument check, the stats header and the rows the result will hold; *empty: no row to compute (nothing else to do)
+static int begin_call(genphi_plan *p, const genphi_opts *opts, genphi_stats *stats, SweepCall &c, bool *empty)
 {
-    if (!p) return fail(GENPHI_ERR_ARG, "plan is NULL");
     const Plan &pl = p->plan;
-    const int device = opts ? opts->device : -1;
-    const int kernel = opts ? opts->kernel : 0;
-    const bool timing = opts && opts->timing && stats;
     int64_t r0 = 0, r1 = pl.n_pro;
     if (opts && opts->row_end > 0) { r0 = opts->row_begin; r1 = opts->row_end; }
     if (r0 < 0 || r1 > pl.n_pro || r0 > r1) return fail(GENPHI_ERR_ARG, "row shard out of range");
+    c.kernel = opts ? opts->kernel : 0; c.r0 = r0; c.n_rows = r1 - r0; c.timing = opts && opts->timing && stats;
     if (stats) {
         std::memset(stats, 0, sizeof(*stats));
         stats->n_steps = std::max(pl.n_levels - 1, 0);
@@ -3554,46 +3572,37 @@ int genphi_compute_device(genphi_plan *p, const genphi_opts *opts, genphi_stats 
     const int L = pl.n_levels;
     // an empty result: no row, of either storage type (a Float64 result before it must not make the queries refuse it), the row pitch
     // the same shard with rows would have
-    if (L == 0 || r1 == r0) { p->res_ld = L ? pl.ld[L - 1] : 0; p->res_f64 = false; return GENPHI_OK; }
+    *empty = L == 0 || r1 == r0;
+    if (*empty) { p->res_ld = L ? pl.ld[L - 1] : 0; p->res_f64 = false; }
+    return GENPHI_OK;
+}
 
-    PhaseTrace trace;
-    int rc = upload_plan(p, device);
+// Everything a Float32 sweep writes to: sparse levels, level buffers, timing events, the result, final_tmp, the shard's row arrays
+static int prepare_buffers(genphi_plan *p, SweepCall &c, bool no_sparse, PhaseTrace &trace)
+{
+    const Plan &pl = p->plan;
+    const int L = pl.n_levels, n_steps = L - 1;
+    p->stay_active = c.kernel != 1;             // the per-entry kernel sweep (kernel = 1) knows no slots: every level is written compactly
+    int rc = ensure_sparse_levels(p, c.kernel, trace);
     if (rc) return rc;
-    trace.mark("upload_plan");
-    p->res_f64 = opts && (opts->flags & GENPHI_FLAG_STORAGE_F64);
-    if (p->res_f64) {
-        p->res_ld = pl.ld[L - 1];
-        return compute_f64(p, r0, r1, kernel, stats, timing, opts && (opts->flags & GENPHI_FLAG_NO_SPARSE));
-    }
-    if (p->popt.indices_only) return fail(GENPHI_ERR_ARG, "internal: an indices-only plan serves Float64-storage sweeps only");
-    p->stay_active = kernel != 1;             // the per-entry kernel sweep (kernel = 1) knows no slots: every level is written compactly
-    const int n_steps = L - 1;
-    rc = ensure_sparse_levels(p, kernel, trace);
-    if (rc) return rc;
-    const int sparse_k = (kernel == 0 && p->sparse && !(opts && (opts->flags & GENPHI_FLAG_NO_SPARSE))) ? genphi::sparse_levels_k(p->sparse) : -1;
-    rc = ensure_level_buffers(p, sparse_k + 1);       // (cuts 0..sparse_k never exist as matrices)
+    c.sparse_k = (c.kernel == 0 && p->sparse && !no_sparse) ? genphi::sparse_levels_k(p->sparse) : -1;
+    rc = ensure_level_buffers(p, c.sparse_k + 1);       // (cuts 0..sparse_k never exist as matrices)
     if (rc) return rc;
     trace.mark("ensure_level_buffers");
-    if (timing && n_steps + 2 > GENPHI_MAX_STAT_LEVELS) return fail(GENPHI_ERR_ARG, "too many levels for timing stats");
-    if (timing) {
+    if (c.timing && n_steps + 2 > GENPHI_MAX_STAT_LEVELS) return fail(GENPHI_ERR_ARG, "too many levels for timing stats");
+    if (c.timing) {
         while (static_cast<int>(p->events.size()) < n_steps + 3) {
             hipEvent_t e; HIP_TRY(hipEventCreate(&e)); p->events.push_back(e);
         }
     }
-
-    const int64_t N = pl.n_pro, ldN = pl.ld[L - 1], n_rows = r1 - r0;
+    const int64_t N = pl.n_pro, ldN = pl.ld[L - 1], n_rows = c.n_rows;
     rc = ensure_floats(p, &p->result, &p->result_floats, static_cast<size_t>(n_rows * ldN));
     if (rc) return rc;
     trace.mark("result buffer");
     p->res_ld = ldN;
-    // last step WIDE: the whole level (every row, [dragged, new] storage order) goes to final_tmp,
-    // then rows [r0, r1) are delivered in proband order by colperm_kernel
-    const bool need_perm = !pl.final_perm.empty();
-    // ... unless the proband cut STAYED IN PLACE at the end of a run (Plan::final_slots): the last step then writes only the new probands'
-    // rows and columns into the run's matrix and colperm_kernel delivers from there, by slot -- one pass instead of a compaction + a
-    // permutation (genea140 with every individual a proband: the last step 7.7 -> ... ms).  The per-entry sweep (kernel = 1) knows no slots.
-    const bool last_by_slot = need_perm && !pl.final_slots.empty() && p->stay_active;
-    if (need_perm && !last_by_slot) {
+    c.need_perm = !pl.final_perm.empty();
+    c.last_by_slot = c.need_perm && !pl.final_slots.empty() && p->stay_active;
+    if (c.need_perm && !c.last_by_slot) {
         rc = ensure_floats(p, &p->final_tmp, &p->final_tmp_floats, static_cast<size_t>((N + 1) * ldN) + kTailPadFloats);
         if (rc) return rc;
     }
@@ -3606,13 +3615,25 @@ int genphi_compute_device(genphi_plan *p, const genphi_opts *opts, genphi_stats 
         HIP_TRY(genphi::cached_malloc(reinterpret_cast<void **>(&p->d_shard_out_rows), n_rows * sizeof(int)));
         p->shard_cap = n_rows; p->shard_r0 = p->shard_r1 = -1;
     }
+    c.ev_after.resize(std::max(n_steps, 1));
+    for (int k = 0; k < static_cast<int>(c.ev_after.size()); ++k) c.ev_after[k] = k + 1;
+    return GENPHI_OK;
+}
+
+// The device half of shard_lists.h: the work lists of rows [r0, r0 + n_rows), unless the plan already holds them
+static int ensure_shard_lists(genphi_plan *p, const SweepCall &c)
+{
+    const Plan &pl = p->plan;
+    const int n_steps = pl.n_levels - 1;
+    const int64_t r0 = c.r0, r1 = c.r0 + c.n_rows, n_rows = c.n_rows;
+    if (p->shard_r0 == r0 && p->shard_r1 == r1) return GENPHI_OK;
+    drop_graph(p);                               // shard lists and sh_blob are rewritten / reallocated below
     // The whole result by a row-kernel last step in proband order: the step's own work order and walk lists (built by the planner and the
     // upload for exactly these rows) ARE the shard's -- no second reuse order, hub walk and upload (7 ms of a first call at 1e5 probands)
-    const bool whole_by_rows = r0 == 0 && r1 == pl.n_pro && !need_perm && n_steps > 0 && pl.steps[n_steps - 1].mode != genphi::kModeWide &&
+    const bool whole_by_rows = r0 == 0 && r1 == pl.n_pro && !c.need_perm && n_steps > 0 && pl.steps[n_steps - 1].mode != genphi::kModeWide &&
                                static_cast<int64_t>(pl.steps[n_steps - 1].work.size()) == n_rows &&
                                (pl.steps[n_steps - 1].mode != genphi::kModeSplit || p->dsteps[n_steps - 1].groups.desc != nullptr);
-    if ((p->shard_r0 != r0 || p->shard_r1 != r1) && whole_by_rows) {
-        drop_graph(p);
+    if (whole_by_rows) {
         const int *work = p->dsteps[n_steps - 1].work;
         HIP_TRY(hipMemcpyAsync(p->d_shard_rows, work, n_rows * sizeof(int), hipMemcpyDeviceToDevice, p->stream));
         HIP_TRY(hipMemcpyAsync(p->d_shard_out_rows, work, n_rows * sizeof(int), hipMemcpyDeviceToDevice, p->stream));      // (output row = storage row)
@@ -3620,315 +3641,293 @@ int genphi_compute_device(genphi_plan *p, const genphi_opts *opts, genphi_stats 
         (void)genphi::cached_free(p->sh_blob); p->sh_blob = nullptr; p->sh_valid = false;
         p->sh_steps.assign(std::max(n_steps, 1), genphi_plan::ShardStep());
         p->shard_r0 = r0; p->shard_r1 = r1;
-    }
-    if (p->shard_r0 != r0 || p->shard_r1 != r1) {
-        drop_graph(p);                               // shard lists and sh_blob are rewritten / reallocated below
-        // work order of the shard: the planner's reuse order (sibling groups, chained along
-        // shared B sources) restricted to the shard's rows
-        std::vector<int> rows(n_rows), orows(n_rows);
-        std::vector<std::pair<int, int>> key(n_rows);   // (storage row, out row)
-        for (int64_t k = 0; k < n_rows; ++k) {
-            const int r = static_cast<int>(r0 + k);
-            key[k] = {need_perm ? pl.final_perm[r] : r, static_cast<int>(k)};
-        }
-        if (n_steps > 0) {
-            const LevelStep &s = pl.steps[n_steps - 1];
-            if (s.mode != genphi::kModeWide) {          // (a WIDE last step computes every row, in storage order)
-                std::vector<int32_t> ord(n_rows);
-                std::vector<int> out_of(s.n, -1);
-                for (int64_t k = 0; k < n_rows; ++k) { ord[k] = key[k].first; out_of[key[k].first] = key[k].second; }
-                genphi::reuse_order(s, ord);
-                for (int64_t k = 0; k < n_rows; ++k) key[k] = {ord[k], out_of[ord[k]]};
-            }
-        }
-        for (int64_t k = 0; k < n_rows; ++k) { rows[k] = key[k].first; orows[k] = key[k].second; }
-        HIP_TRY(hipMemcpyAsync(p->d_shard_rows, rows.data(), n_rows * sizeof(int), hipMemcpyHostToDevice, p->stream));
-        HIP_TRY(hipMemcpyAsync(p->d_shard_out_rows, orows.data(), n_rows * sizeof(int), hipMemcpyHostToDevice, p->stream));
-        p->shard_groups = DeviceGroups();
-        std::vector<char> gimg;
-        if (n_steps > 0 && pl.steps[n_steps - 1].mode == genphi::kModeSplit) {
-            GroupLists gl;
-            build_groups(pl.steps[n_steps - 1], rows.data(), orows.data(), static_cast<int>(n_rows), gl, p->tun);
-            const size_t gb = groups_bytes(gl);
-            if (gb > p->shard_blob_bytes) {
-                if (p->d_shard_blob) { HIP_TRY(genphi::cached_free(p->d_shard_blob)); p->d_shard_blob = nullptr; p->shard_blob_bytes = 0; }
-                HIP_TRY(genphi::cached_malloc(reinterpret_cast<void **>(&p->d_shard_blob), gb));
-                p->shard_blob_bytes = gb;
-            }
-            gimg.assign(gb, 0);
-            size_t goff = 0;
-            auto gput = [&](const void *src, size_t bytes) -> char * {
-                char *d = p->d_shard_blob + goff;
-                if (bytes) std::memcpy(gimg.data() + goff, src, bytes);
-                goff += al256(bytes);
-                return d;
-            };
-            put_groups(gl, p->shard_groups, gput);
-            HIP_TRY(hipMemcpyAsync(p->d_shard_blob, gimg.data(), gb, hipMemcpyHostToDevice, p->stream));
-        }
-        HIP_TRY(hipStreamSynchronize(p->stream));      // host vectors go out of scope
-        p->shard_r0 = r0; p->shard_r1 = r1;
-
-        // upper levels restricted to the ancestors of the shard (walk the sources backwards)
-        (void)genphi::cached_free(p->sh_blob); p->sh_blob = nullptr; p->sh_valid = false;
-        p->sh_steps.assign(std::max(n_steps, 1), genphi_plan::ShardStep());
-        const bool sharded = n_rows < pl.n_pro && n_steps >= 2 && !p->tun.no_shard_prune;
-        if (sharded) {
-            std::vector<std::vector<int>> host_rows(n_steps);
-            std::vector<GroupLists> host_gl(n_steps);
-            std::vector<char> need(pl.steps[n_steps - 1].n_prev + 1, 0);            // members of cut n_steps-1
-            {
-                const LevelStep &sl = pl.steps[n_steps - 1];
-                if (sl.mode == genphi::kModeWide) std::fill(need.begin(), need.end(), 1);
-                else for (int64_t k = 0; k < n_rows; ++k) {
-                    const int i = rows[k];
-                    if (sl.srcA[i] < sl.n_prev) need[sl.srcA[i]] = 1;
-                    if (sl.srcB[i] < sl.n_prev) need[sl.srcB[i]] = 1;
-                }
-            }
-            size_t total = 256;
-            auto al = [](size_t b) { return (b + 255) / 256 * 256; };
-            for (int st = n_steps - 2; st >= 0; --st) {
-                const LevelStep &sv = pl.steps[st];                                // produces cut st+1 (n = sv.n)
-                std::vector<char> need_prev(sv.n_prev + 1, 0);
-                std::vector<int> &rw = host_rows[st];
-                if (p->tun.shard_force_step == st && p->tun.shard_force_row >= 0 && p->tun.shard_force_row < static_cast<int>(need.size()))
-                    need[p->tun.shard_force_row] = 1;                                  // debugging aid
-                if (sv.mode == genphi::kModeWide) {                                  // computes every row, reads every row
-                    std::fill(need_prev.begin(), need_prev.end(), 1);
-                    need.swap(need_prev);
-                    continue;
-                }
-                for (int32_t i : sv.work)                                           // keep the planner's reuse order
-                    if (need[i]) {
-                        rw.push_back(i);
-                        if (sv.srcA[i] < sv.n_prev) need_prev[sv.srcA[i]] = 1;
-                        if (sv.srcB[i] < sv.n_prev) need_prev[sv.srcB[i]] = 1;
-                    }
-                if (sv.mode == genphi::kModeSplit) {
-                    build_groups(sv, rw.data(), nullptr, static_cast<int>(rw.size()), host_gl[st], p->tun);
-                    total += groups_bytes(host_gl[st]);
-                }
-                total += al(rw.size() * sizeof(int));
-                need.swap(need_prev);
-            }
-            HIP_TRY(genphi::cached_malloc(reinterpret_cast<void **>(&p->sh_blob), total));
-            std::vector<char> host(total, 0);
-            size_t off = 0;
-            auto put = [&](const void *src, size_t bytes) -> char * {
-                char *d = p->sh_blob + off;
-                if (bytes) std::memcpy(host.data() + off, src, bytes);
-                off += al(bytes);
-                return d;
-            };
-            for (int st = 0; st + 1 < n_steps; ++st) {
-                genphi_plan::ShardStep &sh = p->sh_steps[st];
-                sh.n_rows = static_cast<int>(host_rows[st].size());
-                sh.rows = reinterpret_cast<int *>(put(host_rows[st].data(), host_rows[st].size() * sizeof(int)));
-                if (!host_gl[st].w.run.empty()) put_groups(host_gl[st], sh.groups, put);
-            }
-            HIP_TRY(hipMemcpyAsync(p->sh_blob, host.data(), total, hipMemcpyHostToDevice, p->stream));
-            HIP_TRY(hipStreamSynchronize(p->stream));
-            p->sh_valid = true;
-        }
-    }
-
-    trace.mark("shard lists");
-    // ---- the sweep: every launch of one gen.phi, in stream order ------------------------------
-    const int prune_min_step = p->tun.shard_prune_min_step;                     // debugging aid
-    const bool small_off = p->tun.no_small;                                      // test hook: per-level launches only
-    std::vector<int> ev_after(std::max(n_steps, 1));                             // event recorded after step k (timing)
-    for (int k = 0; k < static_cast<int>(ev_after.size()); ++k) ev_after[k] = k + 1;
-    const std::vector<int> &bid = p->buf_of[p->stay_active ? 0 : 1];       // level buffer of every cut
-    auto enqueue = [&]() -> int {
-        HIP_TRY(hipMemsetAsync(p->d_queues, 0, p->sweep_words * sizeof(int), p->stream));      // queues, group counts, certificates: one array
-        if (n_steps == 0) {
-            // all probands parentless: result = 1/2 I (src/compute.jl:271-274, loop skipped)
-            HIP_TRY(hipMemsetAsync(p->result, 0, static_cast<size_t>(n_rows * ldN) * sizeof(float), p->stream));
-            hipLaunchKernelGGL(half_identity_kernel, dim3(static_cast<unsigned>((n_rows + 255) / 256)), dim3(256), 0,
-                               p->stream, p->result, ldN, static_cast<int>(N), p->d_shard_out_rows,
-                               static_cast<int>(n_rows), static_cast<int>(r0));
-            HIP_TRY(hipGetLastError());
-        } else {
-            // Psi_1 = 1/2 I over the top founders
-            // (materialised only for kernels that read it: level_identity_kernel and the fused
-            //  small-level run start from the indices)
-            const int64_t n0 = pl.cut_sizes[0], ld0 = pl.ld[0];
-            if (kernel == 1 || (!identity_source(0, p->tun) && sparse_k < 0)) {
-                HIP_TRY(hipMemsetAsync(p->buf[0], 0, static_cast<size_t>((n0 + 1) * ld0) * sizeof(float), p->stream));
-                hipLaunchKernelGGL(half_identity_kernel, dim3(static_cast<unsigned>((n0 + 255) / 256)), dim3(256), 0,
-                                   p->stream, p->buf[0], ld0, static_cast<int>(n0), static_cast<const int *>(nullptr),
-                                   static_cast<int>(n0), 0);
-                HIP_TRY(hipGetLastError());
-            }
-            for (int s = 0; s < n_steps; ++s) {
-                const LevelStep &st = pl.steps[s];
-                const float *psi = p->buf[bid[s]];
-                const bool last = s == n_steps - 1;
-                if (p->step_hook) p->step_hook(s, n_steps, p->step_hook_user);
-                if (s <= sparse_k) {
-                    // cuts 0..sparse_k are row lists: a list step, or (s == sparse_k) the step that writes cut s+1 as a dense matrix
-                    std::string serr;
-                    rc = s < sparse_k ? genphi::sparse_levels_enqueue_step(p->sparse, s, p->stream, serr)
-                                      : genphi::sparse_levels_enqueue_dense(p->sparse, p->buf[bid[s + 1]], false, false, st.ld, st.width, p->stream, serr);
-                    if (rc == GENPHI_OK && s == sparse_k) rc = genphi::sparse_levels_enqueue_flags(p->sparse, p->stream, serr);
-                    if (rc) return fail(rc, "sparse levels: " + serr);
-                    if (timing) HIP_TRY(hipEventRecord(p->events[s + 1], p->stream));
-                    continue;
-                }
-                // a run of >= 2 small intermediate steps goes through ONE launch (levels_small_kernel)
-                if (kernel == 0 && !small_off) {
-                    int e = s;
-                    // (a step that reads or writes by slot -- tiny LDS budgets in tests make WIDE steps of small cuts -- is not a small step)
-                    while (e < n_steps - 1 && pl.steps[e].n_prev <= kSmallMax && pl.steps[e].n <= kSmallMax && !pl.steps[e].src_slots && !pl.steps[e].stay) ++e;
-                    if (e - s >= 2) {
-                        const size_t lds = (2 * kSmallPitch * kSmallPitch + 3 * kSmallMax) * sizeof(float);
-                        HIP_TRY(set_max_lds(reinterpret_cast<const void *>(levels_small_kernel), lds));
-                        // (the hook of every step the fused run covers, BEFORE the run is handed to the GPU: include/genphi.h promises that order)
-                        if (p->step_hook) for (int k = s + 1; k < e; ++k) p->step_hook(k, n_steps, p->step_hook_user);
-                        hipLaunchKernelGGL(levels_small_kernel, dim3(1), dim3(1024), lds, p->stream, p->d_small + s, e - s,
-                                           psi, static_cast<long long>(pl.ld[s]), s == 0 ? 1 : 0, p->buf[bid[e]],
-                                           static_cast<long long>(pl.ld[e]), p->d_cert + p->cert_off[e], cert_threshold(p->tun));
-                        HIP_TRY(hipGetLastError());
-                        // per-level timing: ONE event for the run, booked on its first step (an event
-                        // record costs more than a fused level)
-                        if (timing) {
-                            HIP_TRY(hipEventRecord(p->events[e], p->stream));
-                            for (int k = s; k < e; ++k) ev_after[k] = e;
-                        }
-                        s = e - 1;
-                        continue;
-                    }
-                }
-                if (!last) {
-                    float *out = p->buf[bid[s + 1]];
-                    if (st.mode == genphi::kModeWide) {
-                        // the first in-place step of a run: the all-zero "none" row P of the run's matrix
-                        if (p->stay_active && st.stay && !(s > 0 && pl.steps[s - 1].stay))
-                            HIP_TRY(hipMemsetAsync(out + static_cast<long long>(st.P) * st.ld, 0, static_cast<size_t>(st.ld) * sizeof(float), p->stream));
-                        rc = launch_wide_level(p, s, psi, out, kernel);
-                    }
-                    else if (p->sh_valid && p->sh_steps[s].rows && s >= prune_min_step)
-                        rc = launch_level(p, main_ctx(p, s), psi, out, p->sh_steps[s].rows, nullptr, p->sh_steps[s].n_rows, kernel,
-                                          p->sh_steps[s].groups);
-                    else {
-                        rc = ensure_groups(p, s);
-                        if (rc == GENPHI_OK)
-                            rc = launch_level(p, main_ctx(p, s), psi, out, p->dsteps[s].work, nullptr, static_cast<int>(st.n), kernel,
-                                              p->dsteps[s].groups);
-                    }
-                    if (rc) return rc;
-                    // the all-zero "none" row of this level (FULL / SPLIT / WIDE launches write it themselves)
-                    if (kernel == 1 && st.mode != genphi::kModeWide)
-                        HIP_TRY(hipMemsetAsync(out + st.n * st.ld, 0, static_cast<size_t>(st.ld) * sizeof(float), p->stream));
-                } else {
-                    float *lvl = last_by_slot ? p->buf[bid[s + 1]] : p->final_tmp;      // (in place: the run's own matrix)
-                    if (need_perm)
-                        rc = launch_wide_level(p, s, psi, lvl, kernel);
-                    else
-                        rc = launch_level(p, main_ctx(p, s), psi, p->result, p->d_shard_rows, p->d_shard_out_rows,
-                                          static_cast<int>(n_rows), kernel, p->shard_groups);
-                    if (rc) return rc;
-                    if (timing) HIP_TRY(hipEventRecord(p->events[n_steps + 1], p->stream));
-                    if (need_perm) {
-                        // columns per thread (registers: 2 per column) and LDS segments of the source row
-                        const int per_thread = static_cast<int>((ldN + 1023) / 1024);
-                        const int n_chunks = (per_thread + 43) / 44;            // 44 columns per thread fit without spills (128 VGPRs; 48 spill):
-                                                                                // one chunk -- every source row staged once -- up to 45,056 columns
-                        const int cpt = ((per_thread + n_chunks - 1) / n_chunks + 3) / 4 * 4;
-                        const int seg_floats = 36864;
-                        const int n_segs = static_cast<int>((ldN + seg_floats - 1) / seg_floats);
-                        const size_t lds = static_cast<size_t>(std::min<int64_t>(seg_floats, ldN)) * sizeof(float);
-                        const dim3 grid(static_cast<unsigned>(n_rows * n_chunks));
-                        if (n_chunks == 1 && ldN < 65535 && !p->tun.colperm_plain) {
-                            // one chunk, 16-bit source columns: the persistent pipelined form
-                            const int seg_p = 32768;                      // 16 float4 per thread and piece (18 -- 36,864 floats -- spill)
-                            const int n_segs_p = static_cast<int>((ldN + seg_p - 1) / seg_p);
-                            const size_t lds_p = static_cast<size_t>(std::min<int64_t>(seg_p, ldN)) * sizeof(float);
-                            HIP_TRY(set_max_lds(reinterpret_cast<const void *>(colperm_pipe_kernel<512, 88, 16>), lds_p));
-                            hipLaunchKernelGGL((colperm_pipe_kernel<512, 88, 16>), dim3(static_cast<unsigned>(std::min<int64_t>(n_rows, p->n_cus))), dim3(512), lds_p, p->stream,
-                                               lvl, p->result, ldN, static_cast<int>(N), last_by_slot ? p->d_final_slots : p->d_final_perm, seg_p, n_segs_p,
-                                               static_cast<int>(r0), static_cast<int>(n_rows));
-                        } else
-#define GENPHI_CP(C) if (cpt <= C) { HIP_TRY(set_max_lds(reinterpret_cast<const void *>(colperm_kernel<C>), lds)); \
-                        hipLaunchKernelGGL(colperm_kernel<C>, grid, dim3(1024), lds, p->stream, lvl, p->result, ldN, \
-                                           static_cast<int>(N), last_by_slot ? p->d_final_slots : p->d_final_perm, n_chunks, seg_floats, n_segs, static_cast<int>(r0)); } else
-                        GENPHI_CP(8) GENPHI_CP(16) GENPHI_CP(24) GENPHI_CP(32) GENPHI_CP(40) GENPHI_CP(44)
-                        return fail(GENPHI_ERR_ARG, "internal: colperm geometry");
-#undef GENPHI_CP
-                        HIP_TRY(hipGetLastError());
-                    }
-                }
-                if (timing) HIP_TRY(hipEventRecord(p->events[s + 1], p->stream));
-            }
-        }
         return GENPHI_OK;
-    };
-
-    // A sweep is 1 + L-1 small launches; deep pedigrees (hundreds of tiny levels) are bound by
-    // launch overhead.  After one eager run with the same arguments (which sizes buffers and
-    // opts kernels into their LDS), the sweep is captured into a hipGraph and replayed.
-    // Timing runs stay eager (they need events between the launches).
-    const bool graphs_off = p->tun.no_graph;
-    const long long key[5] = {kernel, static_cast<long long>(r0), static_cast<long long>(r1), (need_perm ? 1 : 0) | (sparse_k >= 0 ? 2 : 0), p->alloc_gen};
-    const bool same_as_eager = p->eager_valid && std::memcmp(key, p->eager_key, sizeof(key)) == 0;
-    const bool use_graph = !timing && !graphs_off && !(opts && (opts->flags & GENPHI_FLAG_NO_GRAPH)) && same_as_eager && n_steps >= 8 && !p->step_hook;
-    if (timing) HIP_TRY(hipEventRecord(p->events[0], p->stream));
-    if (use_graph) {
-        if (!p->graph_exec || std::memcmp(key, p->graph_key, sizeof(key)) != 0) {
-            if (p->graph_exec) { (void)hipGraphExecDestroy(p->graph_exec); p->graph_exec = nullptr; }
-            HIP_TRY(hipStreamBeginCapture(p->stream, hipStreamCaptureModeThreadLocal));
-            const int erc = enqueue();
-            hipGraph_t graph = nullptr;
-            const hipError_t ce = hipStreamEndCapture(p->stream, &graph);
-            if (erc != GENPHI_OK) { if (graph) (void)hipGraphDestroy(graph); return erc; }
-            if (ce != hipSuccess) return fail(GENPHI_ERR_DEVICE, std::string("hipStreamEndCapture: ") + hipGetErrorString(ce));
-            const hipError_t ie = hipGraphInstantiate(&p->graph_exec, graph, nullptr, nullptr, 0);
-            (void)hipGraphDestroy(graph);
-            if (ie != hipSuccess) { p->graph_exec = nullptr; return fail(GENPHI_ERR_DEVICE, std::string("hipGraphInstantiate: ") + hipGetErrorString(ie)); }
-            std::memcpy(p->graph_key, key, sizeof(key));
+    }
+    const genphi::ShardOptions so{p->tun.max_group, p->tun.max_run, p->tun.no_shard_prune, p->tun.shard_force_step, p->tun.shard_force_row};
+    genphi::ShardLists sl;
+    genphi::build_shard_lists(pl, r0, r1, so, sl);
+    std::vector<char> img;
+    // the last step
+    HIP_TRY(hipMemcpyAsync(p->d_shard_rows, sl.rows.data(), n_rows * sizeof(int), hipMemcpyHostToDevice, p->stream));
+    HIP_TRY(hipMemcpyAsync(p->d_shard_out_rows, sl.out_rows.data(), n_rows * sizeof(int), hipMemcpyHostToDevice, p->stream));
+    p->shard_groups = DeviceGroups();
+    if (n_steps > 0 && pl.steps[n_steps - 1].mode == genphi::kModeSplit) {
+        auto layout = [&](BlobPacker &bp) { put_groups(sl.last_walk, p->shard_groups, bp); };
+        const size_t gb = blob_size(layout);
+        if (gb > p->shard_blob_bytes) {
+            if (p->d_shard_blob) { HIP_TRY(genphi::cached_free(p->d_shard_blob)); p->d_shard_blob = nullptr; p->shard_blob_bytes = 0; }
+            HIP_TRY(genphi::cached_malloc(reinterpret_cast<void **>(&p->d_shard_blob), gb));
+            p->shard_blob_bytes = gb;
         }
-        HIP_TRY(hipGraphLaunch(p->graph_exec, p->stream));
-    } else {
-        rc = enqueue();
+        const int rc = blob_upload(layout, img, p->d_shard_blob, gb, p->stream);
+        if (rc) return rc;
+    }
+    HIP_TRY(hipStreamSynchronize(p->stream));      // the host lists are rewritten / go out of scope
+    p->shard_r0 = r0; p->shard_r1 = r1;
+
+    // the upper levels
+    (void)genphi::cached_free(p->sh_blob); p->sh_blob = nullptr; p->sh_valid = false;
+    p->sh_steps.assign(std::max(n_steps, 1), genphi_plan::ShardStep());
+    if (!sl.pruned) return GENPHI_OK;
+    auto layout = [&](BlobPacker &bp) {
+        for (int st = 0; st + 1 < n_steps; ++st) {
+            genphi_plan::ShardStep &sh = p->sh_steps[st];
+            if (bp.host) sh.n_rows = static_cast<int>(sl.upper[st].rows.size());
+            bp.put(sh.rows, sl.upper[st].rows.data(), sl.upper[st].rows.size());
+            if (!sl.upper[st].walk.run.empty()) put_groups(sl.upper[st].walk, sh.groups, bp);
+        }
+    };
+    const size_t total = blob_size(layout) + 256;
+    HIP_TRY(genphi::cached_malloc(reinterpret_cast<void **>(&p->sh_blob), total));
+    const int rc = blob_upload(layout, img, p->sh_blob, total, p->stream);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    p->sh_valid = true;
+    return GENPHI_OK;
+}
+
+// a pruned upper step runs the shard's list instead of its own (GENPHI_SHARD_PRUNE_MIN_STEP: debugging aid)
+static bool runs_shard_list(const genphi_plan *p, int s) { return p->plan.steps[s].mode != genphi::kModeWide && p->sh_valid && p->sh_steps[s].rows && s >= p->tun.shard_prune_min_step; }
+
+// Rows [r0, r0 + n_rows) of the proband matrix from the last level `lvl` (compact [dragged, new] order, or the run's slot matrix), in
+// proband order
+static int deliver_proband_order(genphi_plan *p, const SweepCall &c, const float *lvl)
+{
+    const int64_t N = p->plan.n_pro, ldN = p->plan.ld[p->plan.n_levels - 1], n_rows = c.n_rows;
+    const int *perm = c.last_by_slot ? p->d_final_slots : p->d_final_perm;
+    // columns per thread (registers: 2 per column) and LDS segments of the source row
+    const int per_thread = static_cast<int>((ldN + 1023) / 1024);
+    const int n_chunks = (per_thread + 43) / 44;            // 44 columns per thread fit without spills (128 VGPRs; 48 spill):
+                                                            // one chunk -- every source row staged once -- up to 45,056 columns
+    const int cpt = ((per_thread + n_chunks - 1) / n_chunks + 3) / 4 * 4;
+    if (n_chunks == 1 && ldN < 65535 && !p->tun.colperm_plain) {
+        // one chunk, 16-bit source columns: the persistent pipelined form
+        const int seg_p = 32768;                      // 16 float4 per thread and piece (18 -- 36,864 floats -- spill)
+        const int n_segs_p = static_cast<int>((ldN + seg_p - 1) / seg_p);
+        const size_t lds_p = static_cast<size_t>(std::min<int64_t>(seg_p, ldN)) * sizeof(float);
+        HIP_TRY(set_max_lds(reinterpret_cast<const void *>(colperm_pipe_kernel<512, 88, 16>), lds_p));
+        hipLaunchKernelGGL((colperm_pipe_kernel<512, 88, 16>), dim3(static_cast<unsigned>(std::min<int64_t>(n_rows, p->n_cus))), dim3(512), lds_p, p->stream,
+                           lvl, p->result, ldN, static_cast<int>(N), perm, seg_p, n_segs_p, static_cast<int>(c.r0), static_cast<int>(n_rows));
+        HIP_TRY(hipGetLastError());
+        return GENPHI_OK;
+    }
+    const int seg_floats = 36864;
+    const int n_segs = static_cast<int>((ldN + seg_floats - 1) / seg_floats);
+    const size_t lds = static_cast<size_t>(std::min<int64_t>(seg_floats, ldN)) * sizeof(float);
+    const dim3 grid(static_cast<unsigned>(n_rows * n_chunks));
+    static const struct { int cpt; decltype(&colperm_kernel<8>) kern; } forms[] = {{8, colperm_kernel<8>}, {16, colperm_kernel<16>}, {24, colperm_kernel<24>},
+                                                                                   {32, colperm_kernel<32>}, {40, colperm_kernel<40>}, {44, colperm_kernel<44>}};
+    for (const auto &f : forms) {
+        if (cpt > f.cpt) continue;
+        HIP_TRY(set_max_lds(reinterpret_cast<const void *>(f.kern), lds));
+        hipLaunchKernelGGL(f.kern, grid, dim3(1024), lds, p->stream, lvl, p->result, ldN, static_cast<int>(N), perm, n_chunks, seg_floats, n_segs,
+                           static_cast<int>(c.r0));
+        HIP_TRY(hipGetLastError());
+        return GENPHI_OK;
+    }
+    return fail(GENPHI_ERR_ARG, "internal: colperm geometry");
+}
+
+// The sweep: every launch of one gen.phi, in stream order
+static int enqueue_sweep(genphi_plan *p, SweepCall &c)
+{
+    const Plan &pl = p->plan;
+    const int n_steps = pl.n_levels - 1, kernel = c.kernel, sparse_k = c.sparse_k;
+    const bool timing = c.timing;
+    const int64_t N = pl.n_pro, ldN = pl.ld[pl.n_levels - 1], n_rows = c.n_rows;
+    const std::vector<int> &bid = p->buf_of[p->stay_active ? 0 : 1];       // level buffer of every cut
+    int rc;
+    HIP_TRY(hipMemsetAsync(p->d_queues, 0, p->sweep_words * sizeof(int), p->stream));      // queues, group counts, certificates: one array
+    if (n_steps == 0) {
+        // all probands parentless: result = 1/2 I (src/compute.jl:271-274, loop skipped)
+        HIP_TRY(hipMemsetAsync(p->result, 0, static_cast<size_t>(n_rows * ldN) * sizeof(float), p->stream));
+        hipLaunchKernelGGL(half_identity_kernel, dim3(static_cast<unsigned>((n_rows + 255) / 256)), dim3(256), 0,
+                           p->stream, p->result, ldN, static_cast<int>(N), p->d_shard_out_rows,
+                           static_cast<int>(n_rows), static_cast<int>(c.r0));
+        HIP_TRY(hipGetLastError());
+        return GENPHI_OK;
+    }
+    // Psi_1 = 1/2 I over the top founders
+    // (materialised only for kernels that read it: level_identity_kernel and the fused
+    //  small-level run start from the indices)
+    const int64_t n0 = pl.cut_sizes[0], ld0 = pl.ld[0];
+    if (kernel == 1 || (!identity_source(0, p->tun) && sparse_k < 0)) {
+        HIP_TRY(hipMemsetAsync(p->buf[0], 0, static_cast<size_t>((n0 + 1) * ld0) * sizeof(float), p->stream));
+        hipLaunchKernelGGL(half_identity_kernel, dim3(static_cast<unsigned>((n0 + 255) / 256)), dim3(256), 0,
+                           p->stream, p->buf[0], ld0, static_cast<int>(n0), static_cast<const int *>(nullptr),
+                           static_cast<int>(n0), 0);
+        HIP_TRY(hipGetLastError());
+    }
+    for (int s = 0; s < n_steps; ++s) {
+        const LevelStep &st = pl.steps[s];
+        const float *psi = p->buf[bid[s]];
+        if (p->step_hook) p->step_hook(s, n_steps, p->step_hook_user);
+        if (s <= sparse_k) {
+            // cuts 0..sparse_k are row lists: a list step, or (s == sparse_k) the step that writes cut s+1 as a dense matrix
+            std::string serr;
+            rc = s < sparse_k ? genphi::sparse_levels_enqueue_step(p->sparse, s, p->stream, serr)
+                              : genphi::sparse_levels_enqueue_dense(p->sparse, p->buf[bid[s + 1]], false, false, st.ld, st.width, p->stream, serr);
+            if (rc == GENPHI_OK && s == sparse_k) rc = genphi::sparse_levels_enqueue_flags(p->sparse, p->stream, serr);
+            if (rc) return fail(rc, "sparse levels: " + serr);
+            if (timing) HIP_TRY(hipEventRecord(p->events[s + 1], p->stream));
+            continue;
+        }
+        // a run of >= 2 small intermediate steps goes through ONE launch (levels_small_kernel; GENPHI_NO_SMALL: per-level launches only)
+        // (a step that reads or writes by slot -- tiny LDS budgets in tests make WIDE steps of small cuts -- is not a small step)
+        int e = s;
+        while (kernel == 0 && !p->tun.no_small && e < n_steps - 1 && pl.steps[e].n_prev <= kSmallMax && pl.steps[e].n <= kSmallMax &&
+               !pl.steps[e].src_slots && !pl.steps[e].stay) ++e;
+        if (e - s >= 2) {
+            const size_t lds = (2 * kSmallPitch * kSmallPitch + 3 * kSmallMax) * sizeof(float);
+            HIP_TRY(set_max_lds(reinterpret_cast<const void *>(levels_small_kernel), lds));
+            // (the hook of every step the fused run covers, BEFORE the run is handed to the GPU: include/genphi.h promises that order)
+            if (p->step_hook) for (int k = s + 1; k < e; ++k) p->step_hook(k, n_steps, p->step_hook_user);
+            hipLaunchKernelGGL(levels_small_kernel, dim3(1), dim3(1024), lds, p->stream, p->d_small + s, e - s,
+                               psi, static_cast<long long>(pl.ld[s]), s == 0 ? 1 : 0, p->buf[bid[e]],
+                               static_cast<long long>(pl.ld[e]), p->d_cert + p->cert_off[e], cert_threshold(p->tun));
+            HIP_TRY(hipGetLastError());
+            // per-level timing: ONE event for the run, booked on its first step (an event
+            // record costs more than a fused level)
+            if (timing) {
+                HIP_TRY(hipEventRecord(p->events[e], p->stream));
+                for (int k = s; k < e; ++k) c.ev_after[k] = e;
+            }
+            s = e - 1;
+            continue;
+        }
+        if (s == n_steps - 1) {
+            float *lvl = c.last_by_slot ? p->buf[bid[s + 1]] : p->final_tmp;      // (in place: the run's own matrix)
+            if (c.need_perm)
+                rc = launch_wide_level(p, s, psi, lvl, kernel);
+            else
+                rc = launch_level(p, main_ctx(p, s), psi, p->result, p->d_shard_rows, p->d_shard_out_rows, static_cast<int>(n_rows), kernel,
+                                  p->shard_groups);
+            if (rc) return rc;
+            if (timing) HIP_TRY(hipEventRecord(p->events[n_steps + 1], p->stream));
+            if (c.need_perm) rc = deliver_proband_order(p, c, lvl);
+        } else {
+            float *out = p->buf[bid[s + 1]];
+            if (st.mode == genphi::kModeWide) {
+                // the first in-place step of a run: the all-zero "none" row P of the run's matrix
+                if (p->stay_active && st.stay && !(s > 0 && pl.steps[s - 1].stay))
+                    HIP_TRY(hipMemsetAsync(out + static_cast<long long>(st.P) * st.ld, 0, static_cast<size_t>(st.ld) * sizeof(float), p->stream));
+                rc = launch_wide_level(p, s, psi, out, kernel);
+            }
+            else if (runs_shard_list(p, s))
+                rc = launch_level(p, main_ctx(p, s), psi, out, p->sh_steps[s].rows, nullptr, p->sh_steps[s].n_rows, kernel,
+                                  p->sh_steps[s].groups);
+            else {
+                rc = ensure_groups(p, s);
+                if (rc == GENPHI_OK)
+                    rc = launch_level(p, main_ctx(p, s), psi, out, p->dsteps[s].work, nullptr, static_cast<int>(st.n), kernel,
+                                      p->dsteps[s].groups);
+            }
+            // the all-zero "none" row of this level (FULL / SPLIT / WIDE launches write it themselves)
+            if (rc == GENPHI_OK && kernel == 1 && st.mode != genphi::kModeWide)
+                HIP_TRY(hipMemsetAsync(out + st.n * st.ld, 0, static_cast<size_t>(st.ld) * sizeof(float), p->stream));
+        }
+        if (rc) return rc;
+        if (timing) HIP_TRY(hipEventRecord(p->events[s + 1], p->stream));
+    }
+    return GENPHI_OK;
+}
+
+// A sweep is 1 + L-1 small launches; deep pedigrees (hundreds of tiny levels) are bound by
+// launch overhead.  After one eager run with the same arguments (which sizes buffers and
+// opts kernels into their LDS), the sweep is captured into a hipGraph and replayed.
+// Timing runs stay eager (they need events between the launches).
+static int run_sweep(genphi_plan *p, SweepCall &c, bool graph_allowed)
+{
+    const int n_steps = p->plan.n_levels - 1;
+    const long long key[5] = {c.kernel, static_cast<long long>(c.r0), static_cast<long long>(c.r0 + c.n_rows),
+                              (c.need_perm ? 1 : 0) | (c.sparse_k >= 0 ? 2 : 0), p->alloc_gen};
+    const bool same_as_eager = p->eager_valid && std::memcmp(key, p->eager_key, sizeof(key)) == 0;
+    const bool use_graph = !c.timing && !p->tun.no_graph && graph_allowed && same_as_eager && n_steps >= 8 && !p->step_hook;
+    if (c.timing) HIP_TRY(hipEventRecord(p->events[0], p->stream));
+    if (!use_graph) {
+        const int rc = enqueue_sweep(p, c);
         if (rc) return rc;
         std::memcpy(p->eager_key, key, sizeof(key));
         p->eager_valid = true;
+        return GENPHI_OK;
     }
-    if (stats) {
-        for (int s = 0; s < n_steps && s < GENPHI_MAX_STAT_LEVELS; ++s) {
-            const LevelStep &st = pl.steps[s];
-            int64_t rows = st.n;
-            if (s == n_steps - 1) rows = need_perm ? st.n : n_rows;
-            else if (st.mode != genphi::kModeWide && p->sh_valid && p->sh_steps[s].rows && s >= prune_min_step) rows = p->sh_steps[s].n_rows;
-            stats->level_rows[s] = rows;
-        }
+    if (!p->graph_exec || std::memcmp(key, p->graph_key, sizeof(key)) != 0) {
+        if (p->graph_exec) { (void)hipGraphExecDestroy(p->graph_exec); p->graph_exec = nullptr; }
+        HIP_TRY(hipStreamBeginCapture(p->stream, hipStreamCaptureModeThreadLocal));
+        const int erc = enqueue_sweep(p, c);
+        hipGraph_t graph = nullptr;
+        const hipError_t ce = hipStreamEndCapture(p->stream, &graph);
+        if (erc != GENPHI_OK) { if (graph) (void)hipGraphDestroy(graph); return erc; }
+        if (ce != hipSuccess) return fail(GENPHI_ERR_DEVICE, std::string("hipStreamEndCapture: ") + hipGetErrorString(ce));
+        const hipError_t ie = hipGraphInstantiate(&p->graph_exec, graph, nullptr, nullptr, 0);
+        (void)hipGraphDestroy(graph);
+        if (ie != hipSuccess) { p->graph_exec = nullptr; return fail(GENPHI_ERR_DEVICE, std::string("hipGraphInstantiate: ") + hipGetErrorString(ie)); }
+        std::memcpy(p->graph_key, key, sizeof(key));
     }
-    if (timing && n_steps == 0) HIP_TRY(hipEventRecord(p->events[1], p->stream));
+    HIP_TRY(hipGraphLaunch(p->graph_exec, p->stream));
+    return GENPHI_OK;
+}
+
+// stats->*_ms from the events of a timed sweep (after its last launch has finished)
+static int read_timing(genphi_plan *p, const SweepCall &c, genphi_stats *stats)
+{
+    const int n_steps = p->plan.n_levels - 1, ne = std::max(n_steps, 1);
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, p->events[0], p->events[ne]));
+    stats->total_ms = ms;
+    for (int s = 0; s < ne; ++s) {
+        const int e0 = s == 0 ? 0 : c.ev_after[s - 1], e1 = c.ev_after[s];
+        ms = 0.f;
+        if (e1 != e0) HIP_TRY(hipEventElapsedTime(&ms, p->events[e0], p->events[e1]));
+        stats->level_ms[s] = ms;
+    }
+    stats->final_ms = stats->level_ms[ne - 1];
+    if (n_steps > 0) {
+        HIP_TRY(hipEventElapsedTime(&ms, p->events[n_steps + 1], p->events[n_steps]));
+        stats->perm_ms = ms;
+    }
+    stats->timed = 1;
+    return GENPHI_OK;
+}
+
+extern "C" {
+
+int genphi_compute_device(genphi_plan *p, const genphi_opts *opts, genphi_stats *stats)
+{
+    if (!p) return fail(GENPHI_ERR_ARG, "plan is NULL");
+    const Plan &pl = p->plan;
+    const unsigned flags = opts ? opts->flags : 0;
+    SweepCall c;
+    bool empty;
+    int rc = begin_call(p, opts, stats, c, &empty);
+    if (rc || empty) return rc;
+
+    PhaseTrace trace;
+    rc = upload_plan(p, opts ? opts->device : -1);
+    if (rc) return rc;
+    trace.mark("upload_plan");
+    p->res_f64 = flags & GENPHI_FLAG_STORAGE_F64;
+    if (p->res_f64) {
+        p->res_ld = pl.ld[pl.n_levels - 1];
+        return compute_f64(p, c.r0, c.r0 + c.n_rows, c.kernel, stats, c.timing, flags & GENPHI_FLAG_NO_SPARSE);
+    }
+    if (p->popt.indices_only) return fail(GENPHI_ERR_ARG, "internal: an indices-only plan serves Float64-storage sweeps only");
+    rc = prepare_buffers(p, c, flags & GENPHI_FLAG_NO_SPARSE, trace);
+    if (rc) return rc;
+    rc = ensure_shard_lists(p, c);
+    if (rc) return rc;
+    trace.mark("shard lists");
+    rc = run_sweep(p, c, !(flags & GENPHI_FLAG_NO_GRAPH));
+    if (rc) return rc;
+    for (int s = 0, n_steps = pl.n_levels - 1; stats && s < n_steps && s < GENPHI_MAX_STAT_LEVELS; ++s)      // the rows every step computed
+        stats->level_rows[s] = s == n_steps - 1 ? (c.need_perm ? pl.steps[s].n : c.n_rows) : runs_shard_list(p, s) ? p->sh_steps[s].n_rows : pl.steps[s].n;
+    if (c.timing && pl.n_levels == 1) HIP_TRY(hipEventRecord(p->events[1], p->stream));
     trace.mark("sweep enqueued");
     HIP_TRY(hipStreamSynchronize(p->stream));
     trace.mark("sweep done");
-    if (sparse_k >= 0 && !genphi::sparse_levels_flags_ok(p->sparse))
+    if (c.sparse_k >= 0 && !genphi::sparse_levels_flags_ok(p->sparse))
         return fail(GENPHI_ERR_DEVICE, "sparse levels: a row list did not have the length the plan recorded (internal error)");
-    if (timing) {
-        const int ne = std::max(n_steps, 1);
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, p->events[0], p->events[ne]));
-        stats->total_ms = ms;
-        for (int s = 0; s < ne; ++s) {
-            const int e0 = s == 0 ? 0 : ev_after[s - 1], e1 = ev_after[s];
-            ms = 0.f;
-            if (e1 != e0) HIP_TRY(hipEventElapsedTime(&ms, p->events[e0], p->events[e1]));
-            stats->level_ms[s] = ms;
-        }
-        stats->final_ms = stats->level_ms[ne - 1];
-        if (n_steps > 0) {
-            HIP_TRY(hipEventElapsedTime(&ms, p->events[n_steps + 1], p->events[n_steps]));
-            stats->perm_ms = ms;
-        }
-        stats->timed = 1;
-    }
-    return GENPHI_OK;
+    return c.timing ? read_timing(p, c, stats) : GENPHI_OK;
 }
 
 #if GENPHI_WG_TIMES

@@ -3,6 +3,7 @@
 // every planner option, under AddressSanitizer + UndefinedBehaviorSanitizer.  Built and run by tests/test_host_sanitizers.py (CPU
 // only; GPU sanitizers are not available on this pool).  Links planner.cpp and loader.cpp directly -- no HIP, no oracle.  Also the host
 // tables of genphi_result_group_sums (group_tables.cpp), over label vectors at every edge of theirs, with their invariants checked.
+// And the work lists of a row shard (shard_lists.cpp), for five shards of every plan, against a per-row backward closure written here.
 //   usage: host_sanitize <genea140.csv> <geneaJi.csv>
 #include <algorithm>
 #include <cstdint>
@@ -14,6 +15,7 @@
 
 #include "../genlib.jl_amd/csrc/group_tables.h"
 #include "../genlib.jl_amd/csrc/planner.h"
+#include "../genlib.jl_amd/csrc/shard_lists.h"
 #include "../include/genphi.h"
 
 static std::string g_err;
@@ -35,6 +37,177 @@ static unsigned long long checksum(const Plan &p)
     for (int32_t v : p.final_members) s += static_cast<unsigned>(v);
     for (int32_t v : p.final_perm) s += static_cast<unsigned>(v);
     return s;
+}
+
+// ---- the work lists of a row shard (shard_lists.h) ------------------------------------------
+static int shard_bad(const char *what, const char *why)
+{
+    std::fprintf(stderr, "shard lists, %s: %s\n", what, why);
+    return 1;
+}
+
+// What the kernels rely on in a hub walk (planner.h: WalkLists) of `rows` of step s
+static int check_walk(const genphi::LevelStep &s, const genphi::WalkLists &w, const std::vector<int> &rows, const int *out_rows, int seg_cap,
+                      const char *what)
+{
+    const int n_rows = static_cast<int>(rows.size()), none = static_cast<int>(s.n_prev);
+    if (w.desc4.size() != 4 * rows.size() || w.row_k.size() != rows.size()) return shard_bad(what, "walk: one descriptor per row");
+    if (w.seg4.size() < 8 || w.seg4.size() % 4 || w.run.size() < 4 || w.run.size() % 4) return shard_bad(what, "walk: list sizes");
+    std::vector<char> seen(rows.size(), 0);
+    for (int q = 0; q < n_rows; ++q) {                     // each row exactly once, with its own output row and rank word
+        const int k = w.row_k[q];
+        if (k < 0 || k >= n_rows || seen[k]) return shard_bad(what, "walk: a row is not listed exactly once");
+        seen[k] = 1;
+        const int i = rows[k];
+        if (w.desc4[4 * q] != i || w.desc4[4 * q + 1] != (out_rows ? out_rows[k] : i) || w.desc4[4 * q + 3] != s.ord[i]) return shard_bad(what, "walk: a descriptor");
+    }
+    const int n_segs = static_cast<int>(w.seg4.size() / 4) - 2, n_runs = static_cast<int>(w.run.size() / 4) - 1;
+    for (int t = n_segs; t < n_segs + 2; ++t)
+        if (w.seg4[4 * t] != n_rows || w.seg4[4 * t + 1] || w.seg4[4 * t + 2] || w.seg4[4 * t + 3]) return shard_bad(what, "walk: segment terminators");
+    if (w.run[4 * n_runs] != n_segs || w.run[4 * n_runs + 1] || w.run[4 * n_runs + 2] != n_rows || w.run[4 * n_runs + 3] != n_rows) return shard_bad(what, "walk: run terminator");
+    if ((n_rows > 0) != (n_segs > 0) || (n_segs > 0) != (n_runs > 0)) return shard_bad(what, "walk: empty lists");
+    int next_run = 0;
+    for (int g = 0; g < n_segs; ++g) {
+        const int b = w.seg4[4 * g], e = w.seg4[4 * g + 4], hub = w.seg4[4 * g + 1], n0 = w.seg4[4 * g + 2], type = w.seg4[4 * g + 3];
+        if (b != (g == 0 ? 0 : w.seg4[4 * g - 4 + 4]) || e <= b || e > n_rows) return shard_bad(what, "walk: a segment's rows");
+        if (n0 < 0 || n0 > 8 || b + n0 > e || e - b - n0 > seg_cap) return shard_bad(what, "walk: a segment's cap");
+        if (hub < 0 || hub > none || type < 0 || type > 2) return shard_bad(what, "walk: a segment's hub or type");
+        for (int q = b; q < e; ++q) {
+            const int i = w.desc4[4 * q], B = w.desc4[4 * q + 2];
+            if (q < b + n0 ? (B != none || s.srcB[i] != none || s.srcA[i] != hub)
+                           : (B == none || !((s.srcA[i] == hub && s.srcB[i] == B) || (s.srcB[i] == hub && s.srcA[i] == B)))) return shard_bad(what, "walk: a row's sources");
+        }
+        if (type == 0) {                                  // a run starts here: its entry repeats the segment
+            if (next_run >= n_runs || w.run[4 * next_run] != g || w.run[4 * next_run + 1] != (hub | n0 << 16) || w.run[4 * next_run + 2] != b ||
+                w.run[4 * next_run + 3] != e) return shard_bad(what, "walk: a run's entry");
+            ++next_run;
+        } else {
+            if (g == 0) return shard_bad(what, "walk: the first segment continues a run");
+            const int prev_hub = w.seg4[4 * g - 3], prev_last_B = w.desc4[4 * (b - 1) + 2];
+            if (type == 2 ? hub != prev_hub : hub != prev_last_B) return shard_bad(what, "walk: a continued segment's hub");
+        }
+    }
+    return next_run == n_runs ? 0 : shard_bad(what, "walk: runs without a first segment");
+}
+
+// The rows of every cut that rows [r0, r1) of the result descend from: a closure over srcA / srcB from each row on its own (a WIDE
+// step reads every row of its source cut, whatever it is asked for); `extra`: one more (cut, member) to start from
+static std::vector<std::vector<char>> shard_ancestry(const Plan &pl, int64_t r0, int64_t r1, int extra_cut, int extra_row)
+{
+    const int n_steps = pl.n_levels - 1;
+    std::vector<std::vector<char>> mark(pl.n_levels);
+    for (int c = 0; c < pl.n_levels; ++c) mark[c].assign(static_cast<size_t>(pl.cut_sizes[c]), 0);
+    std::vector<std::pair<int, int>> stack;
+    auto visit = [&](int c, int i) { if (!mark[c][i]) { mark[c][i] = 1; stack.emplace_back(c, i); } };
+    auto close = [&] {
+        while (!stack.empty()) {
+            const std::pair<int, int> t = stack.back();
+            stack.pop_back();
+            if (t.first == 0) continue;
+            const genphi::LevelStep &s = pl.steps[t.first - 1];
+            if (s.mode == genphi::kModeWide) continue;     // (its whole source cut is a root below)
+            if (s.srcA[t.second] < s.n_prev) visit(t.first - 1, s.srcA[t.second]);
+            if (s.srcB[t.second] < s.n_prev) visit(t.first - 1, s.srcB[t.second]);
+        }
+    };
+    for (int st = 0; st < n_steps; ++st)
+        if (pl.steps[st].mode == genphi::kModeWide) for (int64_t i = 0; i < pl.steps[st].n_prev; ++i) visit(st, static_cast<int>(i));
+    if (extra_cut >= 0) visit(extra_cut, extra_row);
+    close();
+    for (int64_t r = r0; r < r1; ++r) {
+        visit(n_steps, pl.final_perm.empty() ? static_cast<int>(r) : pl.final_perm[r]);
+        close();
+    }
+    return mark;
+}
+
+static int check_shard(const Plan &pl, int64_t r0, int64_t r1, const genphi::ShardOptions &opt, const char *what)
+{
+    genphi::ShardLists sl;
+    genphi::build_shard_lists(pl, r0, r1, opt, sl);
+    const int n_steps = std::max(pl.n_levels - 1, 0);
+    const int64_t n_rows = r1 - r0;
+    // the last step: a permutation of the shard, output row = proband - r0
+    if (static_cast<int64_t>(sl.rows.size()) != n_rows || sl.out_rows.size() != sl.rows.size()) return shard_bad(what, "last step: list lengths");
+    std::vector<char> seen(static_cast<size_t>(n_rows), 0);
+    const bool last_wide = n_steps > 0 && pl.steps[n_steps - 1].mode == genphi::kModeWide;
+    if (last_wide == pl.final_perm.empty() && n_steps > 0) return shard_bad(what, "final_perm and a WIDE last step go together");
+    for (int64_t k = 0; k < n_rows; ++k) {
+        const int o = sl.out_rows[k];
+        if (o < 0 || o >= n_rows || seen[o]) return shard_bad(what, "last step: output rows are not a permutation");
+        seen[o] = 1;
+        if (sl.rows[k] != (pl.final_perm.empty() ? static_cast<int>(r0 + o) : pl.final_perm[r0 + o])) return shard_bad(what, "last step: storage row");
+        if ((last_wide || n_steps == 0) && o != k) return shard_bad(what, "last step: a WIDE step delivers in proband order");
+    }
+    const int cap_of[2] = {std::min(opt.max_group, 4), std::min(opt.max_group, 8)};
+    if (n_steps > 0 && pl.steps[n_steps - 1].mode == genphi::kModeSplit) {
+        const genphi::LevelStep &s = pl.steps[n_steps - 1];
+        if (check_walk(s, sl.last_walk, sl.rows, sl.out_rows.data(), cap_of[s.pos_ord], what)) return 1;
+    } else if (!sl.last_walk.desc4.empty()) return shard_bad(what, "last step: a walk without a SPLIT step");
+    // the upper steps
+    const bool pruned = n_rows < pl.n_pro && n_steps >= 2 && !opt.no_prune;
+    if (sl.pruned != pruned || sl.upper.size() != (pruned ? static_cast<size_t>(n_steps - 1) : 0)) return shard_bad(what, "pruned or not");
+    if (!pruned) return 0;
+    const bool forced = opt.force_step >= 0 && opt.force_step < n_steps - 1 && opt.force_row >= 0 && opt.force_row < pl.cut_sizes[opt.force_step + 1] + 1;
+    const bool force_none = forced && opt.force_row == pl.cut_sizes[opt.force_step + 1];      // (the "none" row: marked, never in a work list)
+    const std::vector<std::vector<char>> mark = shard_ancestry(pl, r0, r1, forced && !force_none ? opt.force_step + 1 : -1, opt.force_row);
+    for (int st = n_steps - 2; st >= 0; --st) {
+        const genphi::LevelStep &s = pl.steps[st];
+        const std::vector<int> &got = sl.upper[st].rows;
+        if (s.mode == genphi::kModeWide) {
+            if (!got.empty() || !sl.upper[st].walk.desc4.empty()) return shard_bad(what, "a WIDE upper step has a list");
+            continue;
+        }
+        size_t at = 0;                                    // a subsequence of the step's work order that holds exactly the needed rows
+        for (int32_t i : s.work) {
+            const bool listed = at < got.size() && got[at] == i;
+            if (listed != (mark[st + 1][i] != 0)) return shard_bad(what, "an upper step's list is not the needed set, in work order");
+            at += listed;
+        }
+        if (at != got.size()) return shard_bad(what, "an upper step lists rows outside its work order");
+        if (pl.steps[st + 1].mode == genphi::kModeWide && (got.size() != s.work.size() || static_cast<int64_t>(got.size()) != s.n))
+            return shard_bad(what, "the step above a WIDE step does not hold every row");
+        if (s.mode == genphi::kModeSplit) {
+            if (check_walk(s, sl.upper[st].walk, got, nullptr, cap_of[s.pos_ord], what)) return 1;
+        } else if (!sl.upper[st].walk.desc4.empty()) return shard_bad(what, "an upper walk without a SPLIT step");
+    }
+    return 0;
+}
+
+// five shards of a plan under two sets of walk options, the pruning switched off, and the force hook
+static int shards_all_ways(const Plan &pl, const char *what)
+{
+    const int64_t n = pl.n_pro;
+    if (n == 0 || pl.n_levels == 0) return 0;
+    const int64_t mid = n / 3 / 4 * 4 + 1;
+    const int64_t shards[5][2] = {{0, n}, {0, 1}, {n - 1, n}, {mid, std::max(mid + 1, (n - n / 5) / 4 * 4 + 3)}, {n / 2, n / 2 + 2}};
+    int bad = 0;
+    for (int v = 0; v < 2 && !bad; ++v) {
+        genphi::ShardOptions o;
+        if (v == 1) { o.max_group = 3; o.max_run = 4; }
+        for (const auto &sh : shards) {
+            if (sh[0] < 0 || sh[1] > n || sh[0] >= sh[1]) continue;
+            bad |= check_shard(pl, sh[0], sh[1], o, what);
+        }
+    }
+    genphi::ShardOptions off;
+    off.no_prune = true;
+    bad |= check_shard(pl, 0, 1, off, what);
+    // the force hook: one more row of an upper step -- the first one the shard does not need --, the "none" row, a row out of range
+    const int n_steps = pl.n_levels - 1;
+    if (n > 1 && n_steps >= 2 && !bad) {
+        const std::vector<std::vector<char>> mark = shard_ancestry(pl, 0, 1, -1, 0);
+        for (int st = n_steps - 2; st >= 0 && st >= n_steps - 4; --st) {
+            genphi::ShardOptions f;
+            f.force_step = st;
+            const std::vector<char> &m = mark[st + 1];
+            f.force_row = static_cast<int>(std::find(m.begin(), m.end(), 0) - m.begin());      // (all needed: the "none" row)
+            bad |= check_shard(pl, 0, 1, f, what);
+            f.force_row = static_cast<int>(m.size()) + 1;
+            bad |= check_shard(pl, 0, 1, f, what);
+        }
+    }
+    return bad;
 }
 
 static int plan_all_ways(const std::vector<int64_t> &ind, const std::vector<int64_t> &fa, const std::vector<int64_t> &mo,
@@ -66,6 +239,7 @@ static int plan_all_ways(const std::vector<int64_t> &ind, const std::vector<int6
             for (int32_t v : w.desc4) sum += static_cast<unsigned>(v);
             for (int32_t v : w.run) sum += static_cast<unsigned>(v);
         }
+        if (!o.indices_only && shards_all_ways(plan, what)) return 1;      // (an indices-only plan has no work order: no Float32 sweep)
         ++n_ok;
     }
     std::printf("%s: %d plans, checksum %llu\n", what, n_ok, sum);

@@ -1,8 +1,8 @@
 """The host code on the gen.phi path that indexes by pedigree data -- the native loader and the planner (levels, cuts, per-step arrays on
 worker threads, hub walks) -- under AddressSanitizer + UndefinedBehaviorSanitizer and under ThreadSanitizer ("use
 -fsanitize=address for the host planner"; GPU sanitizers do not exist on this pool), and with them the host tables of
-genphi_result_group_sums (group_tables.cpp).  tests/host_sanitize.cpp links planner.cpp, loader.cpp and group_tables.cpp directly: no HIP,
-no oracle.  CPU only."""
+genphi_result_group_sums (group_tables.cpp) and the work lists of a row shard (shard_lists.cpp), each checked against what its readers
+rely on.  tests/host_sanitize.cpp links planner.cpp, loader.cpp, group_tables.cpp and shard_lists.cpp directly: no HIP, no oracle.  CPU only."""
 import os
 import shutil
 import subprocess
@@ -22,7 +22,7 @@ def test_planner_and_loader_under_sanitizers(san, tmp_path):
     exe = str(tmp_path / "host_sanitize")
     cmd = [gxx, "-std=c++17", "-O1", "-g", f"-fsanitize={san}", "-fno-omit-frame-pointer", "-pthread",
            os.path.join(ROOT, "tests", "host_sanitize.cpp"), os.path.join(CSRC, "planner.cpp"), os.path.join(CSRC, "loader.cpp"),
-           os.path.join(CSRC, "group_tables.cpp"), "-o", exe]
+           os.path.join(CSRC, "group_tables.cpp"), os.path.join(CSRC, "shard_lists.cpp"), "-o", exe]
     build = subprocess.run(cmd, capture_output=True, text=True)
     if build.returncode != 0 and ("cannot find" in build.stderr or "unrecognized" in build.stderr):
         pytest.skip("this toolchain has no -fsanitize=" + san)
