@@ -934,6 +934,130 @@ def phiNearest(x, k=10, probandIDs=None, device=None):
     return PhiNearest(kk, ids, index, None if ids is None else ids[index], np.take_along_axis(m, index, axis=1))
 
 
+def _resident_query(x, probandIDs, device, query):
+    """(the probands, each once, in order; query(plan)) after gen.phi's sweep of pedigree x through the plan cache."""
+    ids = pro(x) if probandIDs is None else np.ascontiguousarray(probandIDs, dtype=np.int64)
+    x.positions(ids)                                            # KeyError on an unknown ID
+    _, first = np.unique(ids, return_index=True)
+    uniq = ids[np.sort(first)]                                  # duplicates collapse: first occurrences, in order
+    pl, key = _plan_for(x, ids, device)
+    keep = False
+    try:
+        pl.compute_device(device=device)
+        out = query(pl)
+        keep = key is not None and _keep_plan(x, key, pl, ids)
+    finally:
+        if not keep:
+            if key is not None and key in x._plans and x._plans[key][0] is pl:
+                del x._plans[key]
+            pl.close()
+    return uniq, out
+
+
+def _host_matrix(x, probandIDs, who):
+    """(float64 square matrix from a host Float32 kinship matrix, its IDs or None)."""
+    m = np.asarray(x, dtype=np.float32)
+    if m.ndim != 2 or m.shape[0] != m.shape[1]:
+        raise ValueError("%s takes a Pedigree or a square kinship matrix, got shape %s" % (who, m.shape))
+    ids = None if probandIDs is None else np.asarray(probandIDs, dtype=np.int64)
+    if ids is not None and ids.shape != (len(m),):
+        raise ValueError("probandIDs must name the %d rows of the matrix" % len(m))
+    return m.astype(np.float64), ids
+
+
+def phiMatmul(x, X, probandIDs=None, device=None):
+    """The product Phi @ X of the kinship matrix with a vector or a tall, skinny matrix X (one row per proband), float64.  Neither
+    GENLIB nor the reference has this function: it is the primitive under quadratic forms, projections and iterative solvers.
+
+    x a Pedigree: gen.phi's sweep for probandIDs (default gen.pro; duplicates collapse, as gen.phi does), then the product on the
+    device from the resident matrix, which is never copied (genphi_result_matmul).  x a square host matrix: the same
+    product in numpy Float64 (another order of the additions).  A 1-D X gives a 1-D result.  ValueError for a wrong shape, KeyError
+    for an unknown proband ID."""
+    if isinstance(x, Pedigree):
+        return _resident_query(x, probandIDs, device, lambda pl: pl.matmul(X))[1]
+    m, _ = _host_matrix(x, probandIDs, "gen.phiMatmul")
+    X, one = _capi.as_panel(X, len(m), "X")
+    out = m @ X
+    return out[:, 0] if one else out
+
+
+class PhiSolve:
+    """What gen.phiSolve returns: `solution` (float64, the shape of B), per right-hand side `residual` (float64, the true relative
+    residual ||b - (Phi + ridge I) z|| / ||b||), `iterations` (int32, products of the iteration) and `converged` (residual <= tol);
+    `pro` (int64, the N IDs in the order of the rows, None when no IDs were given with a host matrix), `ridge` and `tol`."""
+
+    def __init__(self, solution, residual, iterations, tol, ridge, pro):
+        self.solution, self.residual, self.iterations, self.tol, self.ridge, self.pro = solution, residual, iterations, tol, ridge, pro
+        self.converged = residual <= tol
+
+    def __len__(self):
+        return len(self.solution)
+
+    def __repr__(self):
+        k = len(self.residual)
+        return "PhiSolve: (Phi + %g I) z = b for %d probands, %d right-hand side%s; %d converged to tol = %g; iterations %s, largest residual %.3g" % (
+            self.ridge, len(self), k, "" if k == 1 else "s", int(np.count_nonzero(self.converged)), self.tol,
+            "-" if k == 0 else "%d .. %d" % (self.iterations.min(), self.iterations.max()), self.residual.max() if k else 0.0)
+
+
+def _cg_numpy(a, b, ridge, tol, maxiter):
+    """genphi_result_solve's iteration (include/genphi.h) in numpy Float64 on a host matrix: (z, residual, iterations)."""
+    n, k = b.shape
+    z, res, its = np.zeros((n, k)), np.zeros(k), np.zeros(k, dtype=np.int32)
+    for c in range(k):
+        bc = b[:, c]
+        nb = np.sqrt(bc @ bc)
+        if nb == 0.0:
+            continue
+        zc, r, d = np.zeros(n), bc.copy(), bc.copy()
+        rho = r @ r
+        if not nb <= tol * nb:
+            for _ in range(maxiter):
+                q = a @ d + ridge * d
+                its[c] += 1
+                g = d @ q
+                if not g > 0.0 or not np.isfinite(g):
+                    break
+                alpha = rho / g
+                zc += alpha * d
+                r -= alpha * q
+                rho_new = r @ r
+                if np.sqrt(rho_new) <= tol * nb:
+                    break
+                d = r + (rho_new / rho) * d
+                rho = rho_new
+        z[:, c] = zc
+        e = bc - (a @ zc + ridge * zc)
+        res[c] = np.sqrt(e @ e) / nb
+    return z, res, its
+
+
+def phiSolve(x, B, ridge=0.0, tol=1e-10, maxiter=1000, probandIDs=None, device=None):
+    """Solves (Phi + ridge I) z = B, the system under the animal model, BLUP and heritability: (2 Phi s2g + I s2e)^-1 y with
+    ridge = s2e / (2 s2g).  Returns a PhiSolve.  Neither GENLIB nor the reference has this function.
+
+    x a Pedigree: gen.phi's sweep for probandIDs (default gen.pro; duplicates collapse), then conjugate gradients over the product
+    on the device with the resident matrix, which is never copied (genphi_result_solve): textbook CG from z = 0, every
+    column with its own scalars, stopped when the recurrence residual is <= tol ||b||, when the curvature d.Ad is not positive or not
+    finite, or after maxiter products; the residual reported is the true one, from one more product.  x a square host matrix: the
+    same iteration in numpy Float64.  B is (N,) or (N, k).  ValueError for a wrong shape, a negative or non-finite ridge, a negative
+    or NaN tol, maxiter < 1; KeyError for an unknown proband ID."""
+    ridge, tol, maxiter = float(ridge), float(tol), int(maxiter)
+    if not ridge >= 0.0 or not np.isfinite(ridge):
+        raise ValueError("gen.phiSolve: ridge = %r is negative or not finite" % ridge)
+    if not tol >= 0.0:
+        raise ValueError("gen.phiSolve: tol = %r is negative or NaN" % tol)
+    if not 1 <= maxiter < 2 ** 31:
+        raise ValueError("gen.phiSolve: maxiter = %d, need at least 1" % maxiter)
+    if isinstance(x, Pedigree):
+        ids, (z, res, its) = _resident_query(x, probandIDs, device, lambda pl: pl.solve(B, ridge, tol, maxiter))
+        return PhiSolve(z, res, its, tol, ridge, ids)
+    m, ids = _host_matrix(x, probandIDs, "gen.phiSolve")
+    B, one = _capi.as_panel(B, len(m), "B")
+    z, res, its = _cg_numpy(m, B, ridge, tol, maxiter)
+    return PhiSolve(z[:, 0] if one else z, res, its, tol, ridge, ids)
+
+
 DEFAULT_CI_PROB = (0.025, 0.05, 0.95, 0.975)
 
 

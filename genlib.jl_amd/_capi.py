@@ -25,6 +25,7 @@ GENPHI_FLAG_STORAGE_F64 = 2
 GENPHI_FLAG_NO_SPARSE = 4
 GENPHI_GROUP_SUMS_MAX_GROUPS = 4096
 GENPHI_NEAREST_MAX_K = 64
+GENPHI_MATMUL_MAX_K = 64
 GENPHI_IMPLEX_FLAG_ONLY_NEW = 1
 
 _I64P = C.POINTER(C.c_int64)
@@ -50,7 +51,7 @@ class GenphiStats(C.Structure):
 EXPORTED_SYMBOLS = [
     "genphi_plan_create", "genphi_plan_create_tuned", "genphi_tuning_create", "genphi_tuning_set", "genphi_tuning_destroy", "genphi_plan_levels", "genphi_plan_n_probands", "genphi_plan_step_mode", "genphi_plan_step_info", "genphi_plan_step_slots",
     "genphi_plan_algorithmic_bytes", "genphi_plan_device_bytes", "genphi_plan_device_bytes_needed", "genphi_plan_sparse_levels", "genphi_plan_step_walk", "genphi_plan_set_step_hook", "genphi_compute_device", "genphi_result_device",
-    "genphi_result_to_host", "genphi_result_to_host_f64", "genphi_phi_pairs", "genphi_result_sums", "genphi_result_group_sums", "genphi_result_over", "genphi_result_nearest", "genphi_result_bootstrap", "genphi_bootstrap_counts", "genphi_result_entries",
+    "genphi_result_to_host", "genphi_result_to_host_f64", "genphi_phi_pairs", "genphi_result_sums", "genphi_result_group_sums", "genphi_result_over", "genphi_result_nearest", "genphi_result_matmul", "genphi_result_solve", "genphi_result_bootstrap", "genphi_bootstrap_counts", "genphi_result_entries",
     "genphi_compute_f32",
     "genphi_genealogy_read", "genphi_branching", "genphi_free", "genphi_release_cached", "genphi_cached_bytes", "genphi_plan_release_device", "genphi_plan_destroy",
     "genphi_last_error",
@@ -152,6 +153,11 @@ def lib():
         L.genphi_bootstrap_counts.restype = C.c_int
         L.genphi_result_nearest.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), _F32P]
         L.genphi_result_nearest.restype = C.c_int
+        L.genphi_result_matmul.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.c_int64, C.POINTER(C.c_double), C.c_int64, _I64P]
+        L.genphi_result_matmul.restype = C.c_int
+        L.genphi_result_solve.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.c_int64, C.c_double, C.c_double, C.c_int32,
+                                          C.POINTER(C.c_double), C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_int32)]
+        L.genphi_result_solve.restype = C.c_int
         L.genphi_result_entries.argtypes = [C.c_void_p, C.c_int64, _I64P, _I64P, C.POINTER(C.c_double)]
         L.genphi_result_entries.restype = C.c_int
         L.genphi_branching.argtypes = [C.c_int64, _I64P, _I64P, _I64P, _I64P, C.c_int64, _I64P, C.c_int64, _I64P,
@@ -704,6 +710,47 @@ class PhiPlan:
             _raise(rc)
         return c, v
 
+    def matmul(self, X):
+        """Phi @ X on the RESIDENT rows, float64 (rows, k): X is (N,) or (N, k) and is uploaded, the matrix is not copied
+        (genphi_result_matmul).  Float64 accumulation by fma in an order that depends on N alone: the same call gives
+        the same bits, column c is what the one-column call gives, and the outputs of consecutive row shards stack to the output of
+        the full result.  Any number of columns: more than 64 run as blocks of 64.  A 1-D X gives a 1-D result.  ValueError for a
+        wrong shape or a Float64 result, GenphiDeviceError without a resident result."""
+        X, one = as_panel(X, self.n_probands, "X")
+        k = X.shape[1]
+        rows = 0 if getattr(self, "_f64", False) else self.result_device()[3]      # (a Float64 result: the call below refuses it)
+        out = np.empty((rows, k), dtype=np.float64)
+        dp = C.POINTER(C.c_double)
+        for c0 in range(0, max(k, 1), GENPHI_MATMUL_MAX_K):
+            kk = min(k - c0, GENPHI_MATMUL_MAX_K)
+            if kk <= 0:                                                            # (no column: nothing to ask)
+                break
+            rc = lib().genphi_result_matmul(self._h, kk, X[:, c0:].ctypes.data_as(dp), k, out[:, c0:].ctypes.data_as(dp) if rows else None, k, None)
+            if rc:
+                _raise(rc)
+        return out[:, 0] if one else out
+
+    def solve(self, B, ridge=0.0, tol=1e-10, maxiter=1000):
+        """(z, residual, iterations): (Phi + ridge I) z = B by conjugate gradients over matmul on the FULL resident result
+        (genphi_result_solve).  B is (N,) or (N, k); z has its shape (float64), residual (float64) and iterations (int32)
+        one entry per column: the true relative residual ||b - (Phi + ridge I) z|| / ||b|| and the products the column took part in.
+        Columns beyond 64 run as further calls.  ValueError for a wrong shape, a negative or non-finite ridge, a negative or NaN tol,
+        maxiter < 1, a Float64 result or a row shard; GenphiDeviceError without a resident result."""
+        B, one = as_panel(B, self.n_probands, "B")
+        k = B.shape[1]
+        z, res, its = np.zeros_like(B), np.zeros(k, dtype=np.float64), np.zeros(k, dtype=np.int32)
+        dp = C.POINTER(C.c_double)
+        maxiter = int(maxiter)
+        if not -2 ** 31 <= maxiter < 2 ** 31:
+            raise ValueError("solve: maxiter = %d" % maxiter)
+        for c0 in range(0, k, GENPHI_MATMUL_MAX_K):
+            kk = min(k - c0, GENPHI_MATMUL_MAX_K)
+            rc = lib().genphi_result_solve(self._h, kk, B[:, c0:].ctypes.data_as(dp), k, float(ridge), float(tol), maxiter,
+                                           z[:, c0:].ctypes.data_as(dp), k, res[c0:].ctypes.data_as(dp), its[c0:].ctypes.data_as(C.POINTER(C.c_int32)))
+            if rc:
+                _raise(rc)
+        return (z[:, 0] if one else z), res, its
+
     def bootstrap(self, b, seed, first=0):
         """(quad, self): float64 arrays of b entries, the bootstrap resamples first .. first + b - 1 of the probands on the RESIDENT
         rows (genphi_result_bootstrap; the matrix is not copied).  With c the counts of a resample
@@ -724,6 +771,17 @@ class PhiPlan:
     def compute(self, device=None, kernel=0, rows=None, timing=False, no_sparse=False):
         self.compute_device(device=device, kernel=kernel, rows=rows, timing=timing, no_sparse=no_sparse)
         return self.result_to_host()
+
+
+def as_panel(a, n, what):
+    """A caller's vector or matrix of n rows as (float64 C-contiguous (n, k), was 1-D): the X of matmul, the B of solve."""
+    a = np.asarray(a, dtype=np.float64)
+    one = a.ndim == 1
+    if one:
+        a = a[:, None]
+    if a.ndim != 2 or a.shape[0] != n:
+        raise ValueError("%s must have one row per proband (%d), got shape %s" % (what, n, a.shape))
+    return np.ascontiguousarray(a), one
 
 
 def bootstrap_counts(n, seed, b, first=0):

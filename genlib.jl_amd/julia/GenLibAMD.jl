@@ -309,6 +309,84 @@ function phiCI(pedigree::GenLib.Pedigree, probandIDs::Vector{Int} = GenLib.pro(p
     end
 end
 
+const MATMUL_MAX_K = 64                    # GENPHI_MATMUL_MAX_K
+
+# the sweep of `ordered`, then query(plan) on its resident result
+function with_resident(query, pedigree::GenLib.Pedigree, ordered::Vector{Int}, device::Integer)
+    plan = create_plan(pedigree, ordered, nothing)
+    try
+        opts = Ref(GenphiOpts(Int32(device), 0, 0, 0, 0, 0))
+        check(ccall((:genphi_compute_device, libgenphi), Cint, (Ptr{Cvoid}, Ptr{GenphiOpts}, Ptr{Cvoid}), plan, opts, C_NULL))
+        return query(plan)
+    finally
+        destroy_plan(plan)
+    end
+end
+
+"""
+    phiMatmul(pedigree::GenLib.Pedigree, X::AbstractVecOrMat{<:Real}, probandIDs::Vector{Int} = GenLib.pro(pedigree); device::Integer = -1)
+
+The product `Φ * X` of the kinship matrix of the probands with a vector or a tall, skinny matrix `X` (one row per proband, in the order
+of `unique(probandIDs)`), as `Float64`.  The matrix stays on the GPU: `genphi_result_matmul` uploads `X` and accumulates in `Float64` by
+`fma` in an order that depends on the number of probands alone (`include/genphi.h`), so the same call gives the same bits and a column
+does not depend on its neighbours.  More than 64 columns run as blocks of 64.  The reference has no such function.
+"""
+function phiMatmul(pedigree::GenLib.Pedigree, X::AbstractVecOrMat{<:Real}, probandIDs::Vector{Int} = GenLib.pro(pedigree); device::Integer = -1)
+    ordered = unique(probandIDs)
+    foreach(ID -> pedigree[ID], ordered)                                    # KeyError on unknown ID
+    n = length(ordered)
+    size(X, 1) == n || throw(ArgumentError("X must have one row per proband ($n)"))
+    k = size(X, 2)
+    xt = Matrix{Float64}(permutedims(reshape(Float64.(X), n, k)))           # k x n column-major = n x k row-major, pitch k
+    yt = Matrix{Float64}(undef, k, n)
+    with_resident(pedigree, ordered, device) do plan
+        for c0 in 1:MATMUL_MAX_K:k
+            kk = min(k - c0 + 1, MATMUL_MAX_K)
+            GC.@preserve xt yt check(ccall((:genphi_result_matmul, libgenphi), Cint,
+                (Ptr{Cvoid}, Int32, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Ptr{Int64}),
+                plan, Int32(kk), pointer(xt, c0), Int64(k), pointer(yt, c0), Int64(k), C_NULL))
+        end
+    end
+    Y = permutedims(yt)
+    return X isa AbstractVector ? vec(Y) : Y
+end
+
+"""
+    phiSolve(pedigree::GenLib.Pedigree, B::AbstractVecOrMat{<:Real}, probandIDs::Vector{Int} = GenLib.pro(pedigree);
+             ridge::Real = 0.0, tol::Real = 1e-10, maxiter::Integer = 1000, device::Integer = -1)
+
+Solves `(Φ + ridge * I) z = B`, the system under the animal model, BLUP and heritability, as
+`(solution, residual, iterations, converged, pro)`: conjugate gradients over `genphi_result_matmul` on the resident matrix
+(`genphi_result_solve`; the iteration is written out in `include/genphi.h`).  `residual` is the true relative residual
+`‖b − (Φ + ridge I) z‖ / ‖b‖` per right-hand side, `iterations` the products it took part in, `converged = residual .<= tol`.
+The reference has no such function.
+"""
+function phiSolve(pedigree::GenLib.Pedigree, B::AbstractVecOrMat{<:Real}, probandIDs::Vector{Int} = GenLib.pro(pedigree);
+                  ridge::Real = 0.0, tol::Real = 1e-10, maxiter::Integer = 1000, device::Integer = -1)
+    (ridge >= 0 && isfinite(ridge)) || throw(ArgumentError("ridge must be finite and not negative"))
+    tol >= 0 || throw(ArgumentError("tol must not be negative or NaN"))
+    maxiter >= 1 || throw(ArgumentError("maxiter must be at least 1"))
+    ordered = unique(probandIDs)
+    foreach(ID -> pedigree[ID], ordered)                                    # KeyError on unknown ID
+    n = length(ordered)
+    size(B, 1) == n || throw(ArgumentError("B must have one row per proband ($n)"))
+    k = size(B, 2)
+    bt = Matrix{Float64}(permutedims(reshape(Float64.(B), n, k)))           # k x n column-major = n x k row-major, pitch k
+    zt = zeros(Float64, k, n)
+    residual = zeros(Float64, k); iterations = zeros(Int32, k)
+    with_resident(pedigree, ordered, device) do plan
+        for c0 in 1:MATMUL_MAX_K:k
+            kk = min(k - c0 + 1, MATMUL_MAX_K)
+            GC.@preserve bt zt residual iterations check(ccall((:genphi_result_solve, libgenphi), Cint,
+                (Ptr{Cvoid}, Int32, Ptr{Float64}, Int64, Float64, Float64, Int32, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Int32}),
+                plan, Int32(kk), pointer(bt, c0), Int64(k), Float64(ridge), Float64(tol), Int32(maxiter), pointer(zt, c0), Int64(k),
+                pointer(residual, c0), pointer(iterations, c0)))
+        end
+    end
+    Z = permutedims(zt)
+    return (solution = B isa AbstractVector ? vec(Z) : Z, residual = residual, iterations = Int.(iterations), converged = residual .<= tol, pro = ordered)
+end
+
 """
     fCI(vectF::AbstractVector{<:Real}; prob = [0.025, 0.05, 0.95, 0.975], b::Integer = 5000, seed::Union{Nothing, UInt64} = nothing)
 

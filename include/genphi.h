@@ -283,6 +283,58 @@ int genphi_result_over(genphi_plan *plan, double threshold, int64_t cap, int32_t
 #define GENPHI_NEAREST_MAX_K 64
 int genphi_result_nearest(genphi_plan *plan, int32_t k, int32_t *cols, float *values);
 
+/* The product of the resident result with a caller's tall, skinny panel, without moving the matrix: what quadratic
+ * forms, projections and iterative solvers over the kinship matrix need.  N is the number of probands after duplicates collapse.
+ *   y[r][c]           = sum over j < N of Phi[row_begin + r][j] x[j][c], for the resident rows r and c < k
+ *   x                 host, N x k row-major with pitch ldx >= k (in doubles); y: host, n_rows x k with pitch ldy >= k.  The entries of
+ *                     y between k and ldy are not written.  1 <= k <= GENPHI_MATMUL_MAX_K.  *n_rows (may be NULL): the resident rows.
+ *   arithmetic        Float64 throughout: Phi[i][j] converts exactly, accumulation is by fma, no floating-point atomics.  IEEE
+ *                     semantics: 0 x inf is NaN (as in numpy), an entry of Phi that is zero is multiplied like any other.
+ *   fixed order       with n4 = N rounded up to a multiple of 4 (the row pitch is a multiple of 64, its padding columns are +0, and
+ *                     rows N .. n4 - 1 of the device copy of x are written as +0 on every call): for l = 0 .. 63,
+ *                       s_l = the fma chain, from +0, over the columns j < n4 with (j / 4) % 64 == l, in ascending j:
+ *                             s <- fma((double)Phi[i][j], x[j][c], s);
+ *                     then six rounds t = 32, 16, 8, 4, 2, 1 of s_l <- s_l + s_(l xor t) for all l at once; y = s_0 (every s_l is the
+ *                     same by then).  The order depends on N alone: not on k, ldx, ldy or the other columns of the call, not on the
+ *                     row's place in a block of rows or on which shard is resident, not on the kernel form that k selects.
+ *   consequences      the same call returns the same bits; column c of a k-column call is bit for bit the one-column call on that
+ *                     column; the outputs of consecutive row shards, stacked, are the output of the full result bit for bit.
+ *                     Any order of N fused terms is within (N + 2) 2^-53 (|Phi| |x|)[r][c] of the exact product, and exact where all
+ *                     partial sums are representable (dyadic entries, integer x of moderate size).
+ * An empty shard (no resident row after a genphi_compute_device call) is GENPHI_OK, writes nothing to y and sets *n_rows = 0.
+ * Device memory: 8 n4 k' bytes for the panel (k' = k rounded up to the column tile: 1, 2, 4, 8 or a multiple of 16) and 8 n_rows k for
+ * the product, in the plan's scratch block, kept between calls.  One read of the resident rows for k <= 16, one per 16 columns beyond;
+ * 2 n_rows N k Float64 operations.
+ * GENPHI_ERR_ARG: NULL plan, NULL x, NULL y while rows are resident, k outside [1, GENPHI_MATMUL_MAX_K], ldx < k, ldy < k, a Float64
+ * result (GENPHI_FLAG_STORAGE_F64); GENPHI_ERR_DEVICE: no resident result; GENPHI_ERR_ALLOC: the panel and the product do not fit
+ * (found before any launch).  After any error the plan stays usable, the resident result is untouched, and y and *n_rows are not
+ * written.                                                                                                                          */
+#define GENPHI_MATMUL_MAX_K 64
+int genphi_result_matmul(genphi_plan *plan, int32_t k, const double *x, int64_t ldx, double *y, int64_t ldy, int64_t *n_rows);
+
+/* Solves (Phi + ridge I) z = b for k <= GENPHI_MATMUL_MAX_K right-hand sides by conjugate gradients over genphi_result_matmul on the
+ * FULL resident result: what the animal model, BLUP and heritability ask of a kinship matrix, (2 Phi s2g + I s2e)^-1 y
+ * with ridge = s2e / (2 s2g).  The iteration is a host loop (csrc/result_solve.cpp), one product per iteration for all the columns
+ * that still run; every column has its own scalars, and every dot product is a plain ascending Float64 sum on the host, so the same
+ * call gives the same bits.
+ *   b, z              host, N x k row-major with pitches ldb, ldz >= k; residual (k doubles) and iterations (k) may be NULL
+ *   the iteration     per column, with A = Phi + ridge I:  z = 0, r = b, d = b, rho = r.r, nb = sqrt(b.b).  A column with nb == 0 is
+ *                     done (z = 0, residual 0, 0 iterations), as is one with nb <= tol nb.  Then, while a column runs and fewer than
+ *                     max_iter products were made:  q = Phi d + ridge d;  g = d.q;  if not (g > 0) or g is not finite: the column
+ *                     stops with the z it has (breakdown: A is not positive definite along d, or a NaN / inf came in);
+ *                     alpha = rho / g;  z += alpha d;  r -= alpha q;  rho' = r.r;  if sqrt(rho') <= tol nb: the column stops
+ *                     (converged by the recurrence residual);  d = r + (rho' / rho) d;  rho = rho'.
+ *   iterations[c]     the products of the iteration that column c took part in (the breakdown step included)
+ *   residual[c]       after the iteration one more product, over the columns that are not zero, gives the TRUE relative residual
+ *                     || b - (Phi z + ridge z) ||_2 / || b ||_2; the return value is GENPHI_OK whether or not every column converged:
+ *                     residual says (a column converged when residual[c] <= tol, up to the rounding of the products).
+ * GENPHI_ERR_ARG: NULL plan, NULL b, NULL z, k outside [1, GENPHI_MATMUL_MAX_K], ldb < k, ldz < k, ridge negative or not finite, tol
+ * negative or NaN, max_iter < 1, a Float64 result, fewer than N rows resident (a shard cannot solve; an empty shard too);
+ * GENPHI_ERR_DEVICE: no resident result; GENPHI_ERR_ALLOC as for genphi_result_matmul.  After any error the plan stays usable, the
+ * resident result is untouched, and z, residual and iterations are not written.                                                    */
+int genphi_result_solve(genphi_plan *plan, int32_t k, const double *b, int64_t ldb, double ridge, double tol, int32_t max_iter,
+                        double *z, int64_t ldz, double *residual, int32_t *iterations);
+
 /* GENLIB's gen.phiCI(phiMatrix, prob, b) and gen.fCI(vectF, prob, b): bootstrap confidence intervals of the mean kinship and of the
  * mean inbreeding.  The reference has neither, so this text is the definition.  N is the number of probands after
  * duplicates collapse (genphi_plan_create), N >= 2.
