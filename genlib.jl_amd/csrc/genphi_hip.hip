@@ -56,12 +56,16 @@
 #include "../../include/genphi.h"
 #include "panel_launch.h"
 #include "devcache.h"
+#include "devbuf.h"
+#include "device_sizes.h"
 #include "planner.h"
 #include "shard_lists.h"
 #include "resident.h"
 #include "sparse_levels.h"
 
 using genphi::al256;
+using genphi::DevBuf;
+using genphi::kTailPadFloats;
 using genphi::LevelStep;
 using genphi::Plan;
 
@@ -1926,9 +1930,15 @@ int genphi_set_error(int code, const std::string &msg) { return fail(code, msg);
             return fail(GENPHI_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_));  \
     } while (0)
 
-// level matrices carry a zeroed tail so that the SPLIT kernel's unconditional staging loads
-// (STG * 1024 float4 per row, <= 160 KB) may run past the last row
-constexpr size_t kTailPadFloats = 64 * 1024;
+// As HIP_TRY, for an allocation that went through DevBuf::reserve: `what` is the text the message had when the call was spelled out on
+// the plan's raw pointer (tests/golden/sweep_host_contract.json pins it) -- frozen message text, not code, as in resident.h.
+#define HIP_TRY_AS(what, expr)                                                                  \
+    do {                                                                                        \
+        hipError_t e_ = (expr);                                                                 \
+        if (e_ != hipSuccess)                                                                   \
+            return fail(GENPHI_ERR_DEVICE, std::string(what ": ") + hipGetErrorString(e_));     \
+    } while (0)
+
 // pk / ord are padded so that the unrolled per-thread column loops need no clamp
 constexpr size_t kIdxPad = 32 * 1024;
 // ... which only the SPLIT kernels do (a chunk of up to 24 x 1024 columns whatever the cut's width); the FULL kernel reads whole quads
@@ -2156,87 +2166,86 @@ static void put_groups(const genphi::WalkLists &w, DeviceGroups &d, BlobPacker &
     d.n_runs = static_cast<int>(w.run.size() / 4) - 1;
 }
 
-struct genphi_plan {
-    Plan plan;
-    genphi::PlanOptions popt;
-    Tuning tun;                                  // environment hooks, read once in genphi_plan_create
-    // device state (created lazily by the first compute)
+// What exists only while the plan is uploaded.  free_device assigns a default-constructed one: every block goes back to the cache
+// (devbuf.h) and every pointer, size, flag and cache key is what it is before the first upload -- a member added here is reset with the rest.
+// genphi_plan_device_bytes counts idx_blob, lazy_blobs, d_shard_blob, scratch, buf[], result, final_tmp, psi_p, nn_tmp, d_queues,
+// buf64[], result64 and the sparse levels' own figure.  It does NOT count d_glist, d_small, d_cert_p, d_shard_rows / d_shard_out_rows,
+// sh_blob and d_perm_rows (small next to the rest; tests/golden/sweep_host_contract.json pins the figure as it is).
+struct PlanDevice {
     bool on_device = false;
     int device = -1;
     int n_cus = 256;
     hipStream_t stream = nullptr;
-    char *idx_blob = nullptr;
-    std::vector<char *> lazy_blobs;              // walk lists uploaded after the index blob (ensure_groups)
-    size_t lazy_bytes = 0;
-    size_t idx_blob_bytes = 0, psi_p_floats = 0, nn_tmp_floats = 0;      // (genphi_plan_device_bytes)
+    // The owned blocks, declared in the order in which a release hands them back to the cache (the assignment in free_device goes member
+    // by member): the cache evicts its oldest idle blocks first and breaks ties between equal sizes by age, so the order decides which
+    // blocks the next plan finds.  Everything else in this struct owns no device memory.
+    DevBuf<char> idx_blob;                       // every index array of the upload (BlobPacker); dsteps / nn_dsteps point into it
+    std::vector<DevBuf<char>> lazy_blobs;        // walk lists uploaded after the index blob (ensure_groups)
+    DevBuf<int> d_shard_rows, d_shard_out_rows;
+    DevBuf<char> d_shard_blob;
+    DevBuf<int> d_glist;
+    DevBuf<int> d_queues;           // 16 work-queue counters per slot (a level step or a new x new sub-step), then d_gcnt and d_cert
+    DevBuf<SmallStep> d_small;      // one entry per level step (levels_small_kernel)
+    DevBuf<char> sh_blob;
+    DevBuf<char> scratch;                        // the queries' staging block (resident_scratch: grown on demand)
+    DevBuf<float> buf[2];                        // the two level buffers (sz.buf_of[][c]: which one holds cut c)
+    DevBuf<float> result, final_tmp;
+    DevBuf<float> psi_p;                         // WIDE: compacted parent matrix Psi[parents][parents]
+    DevBuf<int> d_cert_p;                        // certificates of the rows of psi_p ...
+    DevBuf<float> nn_tmp;                        // in-place WIDE steps: the new x new block before it is scattered to the new members' slots
+    // Float64-storage sweeps (gen.f, pairwise phi): own level matrices and result
+    DevBuf<double> buf64[2], result64;
+    DevBuf<int> d_perm_rows;                     // storage member of each resident proband row (f64 sweeps)
+
     std::vector<DeviceStep> dsteps;
     std::vector<const LevelStep *> nn_steps;     // new x new sub-steps of the WIDE steps (owned by the plan's steps)
     std::vector<DeviceStep> nn_dsteps;
-    float *psi_p = nullptr;                      // WIDE: compacted parent matrix Psi[parents][parents]
-    float *nn_tmp = nullptr;                     // in-place WIDE steps: the new x new block before it is scattered to the new members' slots
-    int *d_cert_t = nullptr;                     // ... and its rows' certificate words
-    int *d_cert_p = nullptr;                     // certificates of the rows of psi_p
+    genphi::DeviceSizes sz;                      // buf_of[], cert_cut[], cert_off[] and the buffer sizes of this plan (device_sizes.h)
+    int *d_cert_t = nullptr;                     // (inside d_cert_p's block) certificates of the rows of nn_tmp
     size_t cert_p_words = 0;
-    int *d_final_perm = nullptr;
-    int *d_final_slots = nullptr;                // (the proband cut stayed in place) slot of every proband, result order
-    int *d_shard_rows = nullptr, *d_shard_out_rows = nullptr;
-    int *d_queues = nullptr;        // 16 work-queue counters per slot (a level step or a new x new sub-step)
-    size_t sweep_words = 0;         // ints of the array that holds d_queues, d_gcnt and d_cert (cleared by ONE memset per sweep)
-    size_t n_slots = 0;
-    SmallStep *d_small = nullptr;   // one entry per level step (levels_small_kernel)
+    int *d_final_perm = nullptr;                 // (inside idx_blob)
+    int *d_final_slots = nullptr;                // (the proband cut stayed in place) slot of every proband, result order (inside idx_blob)
+    size_t sweep_words = 0;         // ints of d_queues' block (cleared by ONE memset per sweep)
     hipGraphExec_t graph_exec = nullptr;   // captured sweep (see genphi_compute_device)
     // key = (kernel, r0, r1, need_perm, alloc_gen).  A captured graph bakes raw device pointers into
     // its kernel nodes, so every (re)allocation of a buffer the sweep touches bumps alloc_gen:
     // the stale graph can then never be replayed, and a fresh eager run precedes the next capture.
     long long graph_key[5] = {0, 0, 0, 0, 0}, eager_key[5] = {0, 0, 0, 0, 0};
-    long long alloc_gen = 1;
     bool level_bufs_ready = false;         // buf[] / psi_p exist (ensure_level_buffers)
     int level_bufs_from = 0;               // ... buf[] sized for the dense matrices of cuts >= this one (the cuts before it live as row lists)
-    int alloc_count = 0;                   // device allocations of uploads so far (GENPHI_TEST_FAIL_ALLOC)
-    char *scratch = nullptr;               // the queries' staging block (resident_scratch: grown on demand)
-    size_t scratch_bytes = 0;
     bool eager_valid = false;
     DeviceGroups shard_groups;      // SPLIT lists of the last step restricted to the shard (arrays inside d_shard_blob)
-    char *d_shard_blob = nullptr;
-    size_t shard_blob_bytes = 0;
-    // exactness certificates: one word per row of every level matrix (cert_off[c] = first word of
-    // cut c), the per-launch group flags and [certified, other] group counts per step
-    int *d_cert = nullptr, *d_glist = nullptr, *d_gcnt = nullptr;
-    std::vector<size_t> cert_off;
-    size_t cert_words = 0;
+    // exactness certificates: one word per row of every level matrix (sz.cert_off[c] = first word of
+    // cut c), the per-launch group flags (d_glist) and [certified, other] group counts per step
+    int *d_cert = nullptr, *d_gcnt = nullptr;    // (inside d_queues' block)
     // Row shards: an upper level only needs the rows its shard's last-level rows descend from
     // (~80 % of a cut at 8 shards of cfg4, 55-72 % in the two levels below the last).  Per
-    // intermediate step: restricted work list (+ SPLIT descriptors) of the current shard.
+    // intermediate step: restricted work list (+ SPLIT descriptors) of the current shard (arrays inside sh_blob).
     struct ShardStep { int *rows = nullptr; DeviceGroups groups; int n_rows = 0; };
     std::vector<ShardStep> sh_steps;
-    char *sh_blob = nullptr;
     bool sh_valid = false;
-    int64_t shard_cap = 0, shard_r0 = -1, shard_r1 = -1;
-    float *buf[2] = {nullptr, nullptr};
-    size_t buf_floats[2] = {0, 0};
-    // which of the two level buffers holds cut c: alternating, except that a WIDE step that stays in place (LevelStep::stay)
-    // writes into its source's buffer.  buf_of[0]: with in-place steps (the product sweep), buf_of[1]: plain alternation (the
-    // per-entry kernel = 1 sweep, which knows no slots).  cert_cut[c]: the cut whose certificate words cut c shares in the
-    // product sweep (the entry cut of its in-place run; c itself otherwise).
-    std::vector<int> buf_of[2], cert_cut;
+    int64_t shard_r0 = -1, shard_r1 = -1;
     bool stay_active = false;                    // this sweep keeps WIDE levels in place (set per compute call)
-    genphi_step_fn step_hook = nullptr;          // genphi_plan_set_step_hook: called before every level step of a Float32 sweep
-    void *step_hook_user = nullptr;
-    float *result = nullptr, *final_tmp = nullptr;
-    // Float64-storage sweeps (gen.f, pairwise phi): own level matrices and result
-    double *buf64[2] = {nullptr, nullptr}, *result64 = nullptr;
-    size_t buf64_doubles[2] = {0, 0}, result64_doubles = 0;
-    int *d_perm_rows = nullptr;                  // storage member of each resident proband row (f64 sweeps)
-    size_t perm_rows_cap = 0;
     bool res_f64 = false;                        // the resident result is the Float64 one
-    size_t result_floats = 0, final_tmp_floats = 0;
     int64_t res_ld = 0, res_row_begin = 0, res_n_rows = 0;
     bool res_known = false;                      // a genphi_compute_device call has set the resident row range (it may be empty)
     genphi::OverCache over;                      // genphi_result_over's offsets of the resident result: dropped with it (set_resident_rows)
     // zero-aware leading levels (sparse_levels.h): created and calibrated by the first product sweep of the plan
-    genphi::SparseLevels *sparse = nullptr;
+    genphi::SparseLevels *sparse = nullptr;      // (sparse_levels_destroy; its index arrays live inside idx_blob)
     bool sparse_tried = false;
     std::vector<hipEvent_t> events;
+};
+
+// The plan: what the planner made of the pedigree and what survives a release of the device, then the device state (created lazily
+// by the first compute)
+struct genphi_plan : PlanDevice {
+    Plan plan;
+    genphi::PlanOptions popt;
+    Tuning tun;                                  // environment hooks, read once in genphi_plan_create
+    genphi_step_fn step_hook = nullptr;          // genphi_plan_set_step_hook: called before every level step of a Float32 sweep
+    void *step_hook_user = nullptr;
+    long long alloc_gen = 1;                     // (graph_key; only ever grows: a graph captured before a release is never replayed after it)
+    int alloc_count = 0;                         // device allocations of uploads so far (GENPHI_TEST_FAIL_ALLOC)
 };
 
 // The resident row range changes -- a compute call begins, the device is released -- and what was derived from the previous result goes.
@@ -2254,43 +2263,21 @@ static void drop_graph(genphi_plan *p)
     ++p->alloc_gen;
 }
 
-// Releases everything the plan holds on its device and returns it to the "never uploaded" state:
-// every pointer nulled, every size / capacity / cache key reset, so that a later upload (same or
-// another device) starts from scratch instead of trusting stale pointers.
+// Releases everything the plan holds on its device and returns it to the "never uploaded" state, so that a later upload (same or
+// another device) starts from scratch: what needs a call is destroyed here, the rest goes with the assignment.
 static void free_device(genphi_plan *p)
 {
     if (!p->on_device) return;
     (void)hipSetDevice(p->device);
     if (p->stream) (void)hipStreamSynchronize(p->stream);
     for (hipEvent_t e : p->events) (void)hipEventDestroy(e);
-    p->events.clear();
     drop_graph(p);
-    auto release = [](auto *&ptr) { if (ptr) (void)genphi::cached_free(ptr); ptr = nullptr; };
-    release(p->idx_blob); p->idx_blob_bytes = 0; p->psi_p_floats = p->nn_tmp_floats = 0;
-    for (char *&b : p->lazy_blobs) release(b);
-    p->lazy_blobs.clear(); p->lazy_bytes = 0;
-    release(p->d_shard_rows); release(p->d_shard_out_rows); release(p->d_shard_blob);
-    release(p->d_glist); p->d_cert = p->d_gcnt = nullptr; p->sweep_words = 0;      // (d_cert / d_gcnt live inside d_queues' array)
-    p->shard_groups = DeviceGroups(); p->shard_blob_bytes = 0; p->cert_off.clear(); p->cert_words = 0;
-    release(p->d_queues); release(p->d_small); release(p->sh_blob); release(p->scratch);
-    release(p->buf[0]); release(p->buf[1]); release(p->result); release(p->final_tmp);
-    release(p->psi_p); release(p->d_cert_p); release(p->nn_tmp); p->d_cert_t = nullptr;      // (d_cert_t lives inside d_cert_p's array)
-    release(p->buf64[0]); release(p->buf64[1]); release(p->result64); release(p->d_perm_rows);
-    p->buf64_doubles[0] = p->buf64_doubles[1] = 0; p->result64_doubles = 0; p->perm_rows_cap = 0; p->res_f64 = false;
-    p->nn_steps.clear(); p->nn_dsteps.clear(); p->cert_p_words = 0;
-    genphi::sparse_levels_destroy(p->sparse); p->sparse = nullptr; p->sparse_tried = false;      // (its index arrays live inside idx_blob)
-    p->d_final_perm = nullptr;                       // lived inside idx_blob
-    p->d_final_slots = nullptr;
-    p->dsteps.clear(); p->sh_steps.clear();
-    p->sh_valid = false;
-    p->shard_cap = 0; p->shard_r0 = p->shard_r1 = -1;
-    p->buf_floats[0] = p->buf_floats[1] = 0; p->level_bufs_ready = false;
-    p->result_floats = p->final_tmp_floats = 0; p->scratch_bytes = 0;
-    p->res_ld = 0; set_resident_rows(p, 0, 0, false);
-    genphi::cached_stream_release(p->stream, p->device);
-    p->stream = nullptr;
-    p->on_device = false;
-    p->device = -1;
+    genphi::SparseLevels *const sparse = p->sparse;
+    const hipStream_t stream = p->stream;
+    const int device = p->device;
+    static_cast<PlanDevice &>(*p) = PlanDevice();         // the plan's blocks, in their declaration order ...
+    genphi::sparse_levels_destroy(sparse);                // ... then the sparse levels' ...
+    genphi::cached_stream_release(stream, device);        // ... and the stream last
 }
 
 extern "C" {
@@ -2398,44 +2385,28 @@ double genphi_plan_algorithmic_bytes(const genphi_plan *plan) { return plan ? pl
 int64_t genphi_plan_device_bytes(const genphi_plan *p)
 {
     if (!p || !p->on_device) return 0;
-    const double b = static_cast<double>(p->idx_blob_bytes) + static_cast<double>(p->lazy_bytes) + static_cast<double>(p->shard_blob_bytes) + static_cast<double>(p->scratch_bytes) +
-                     4.0 * (static_cast<double>(p->buf_floats[0]) + static_cast<double>(p->buf_floats[1]) + static_cast<double>(p->result_floats) +
-                            static_cast<double>(p->final_tmp_floats) + static_cast<double>(p->psi_p_floats) + static_cast<double>(p->nn_tmp_floats) +
-                            static_cast<double>(p->sweep_words)) +
-                     8.0 * (static_cast<double>(p->buf64_doubles[0]) + static_cast<double>(p->buf64_doubles[1]) + static_cast<double>(p->result64_doubles)) +
-                     genphi::sparse_levels_device_bytes(p->sparse);
-    return static_cast<int64_t>(b);
+    size_t b = p->idx_blob.bytes() + p->d_shard_blob.bytes() + p->scratch.bytes() + p->buf[0].bytes() + p->buf[1].bytes() + p->result.bytes() +
+               p->final_tmp.bytes() + p->psi_p.bytes() + p->nn_tmp.bytes() + p->d_queues.bytes() + p->buf64[0].bytes() + p->buf64[1].bytes() +
+               p->result64.bytes();
+    for (const DevBuf<char> &lb : p->lazy_blobs) b += lb.bytes();
+    return static_cast<int64_t>(static_cast<double>(b) + genphi::sparse_levels_device_bytes(p->sparse));
 }
 int64_t genphi_plan_device_bytes_needed(const genphi_plan *p)
 {
     if (!p) return 0;
     const Plan &pl = p->plan;
-    const int L = pl.n_levels;
-    if (L == 0) return 0;
+    if (pl.n_levels == 0) return 0;
     // what upload_plan / ensure_level_buffers / genphi_compute_device allocate for a full-result Float32 sweep of this plan
-    double need[2] = {0.0, 0.0}, total = 0.0;
-    int b = 0;
-    for (int c = 0; c + 1 < L; ++c) {                      // (as ensure_level_buffers: each buffer serves the sweep with in-place steps AND
-        if (c >= 1) b = pl.steps[c - 1].stay ? b : 1 - b;  //  the plain alternation of the per-entry sweep)
-        const double rows = static_cast<double>(pl.steps[c].src_slots ? pl.steps[c].P : pl.cut_sizes[c]) + 1.0;
-        const double fl = rows * static_cast<double>(pl.ld[c]) + static_cast<double>(kTailPadFloats);
-        need[b] = std::max(need[b], fl);
-        need[c & 1] = std::max(need[c & 1], fl);
-    }
-    total += need[0] + need[1];
-    const double N = static_cast<double>(pl.n_pro), ldN = static_cast<double>(pl.ld[L - 1]);
-    total += N * ldN;                                      // the result (its pitch is the run's when the proband cut stays in place)
-    if (!pl.final_perm.empty() && pl.final_slots.empty()) total += (N + 1.0) * ldN + static_cast<double>(kTailPadFloats);
-    double psi_p = 0.0, nn_tmp = 0.0, idx = 0.0;
-    for (const LevelStep &st : pl.steps) {
-        if (st.mode == genphi::kModeWide && !st.nn.empty())
-            psi_p = std::max(psi_p, static_cast<double>(st.nn[0].n_prev + 1) * static_cast<double>(st.nn[0].ld_prev) + static_cast<double>(kTailPadFloats));
-        if (st.stay) nn_tmp = std::max(nn_tmp, static_cast<double>(st.npad) * static_cast<double>(st.npad) + static_cast<double>(kTailPadFloats));
+    const genphi::DeviceSizes sz = genphi::device_sizes(pl);
+    size_t need[2];
+    sz.level_buffers(0, need);
+    size_t floats = need[0] + need[1] + genphi::result_floats(pl, pl.n_pro) + sz.psi_p_floats + sz.nn_tmp_floats;
+    if (!pl.final_perm.empty() && pl.final_slots.empty()) floats += sz.final_tmp_floats;
+    double idx = 0.0;                                      // (an estimate: the blob's exact size needs the walk lists, upload_plan_impl)
+    for (const LevelStep &st : pl.steps)
         idx += 5.0 * static_cast<double>(st.n) + 2.0 * static_cast<double>(idx_pad(st)) + (st.mode == genphi::kModeSplit ? 6.0 * static_cast<double>(st.n) : 0.0)
                + (st.mode == genphi::kModeWide ? 12.0 * static_cast<double>(st.n) : 0.0);
-    }
-    total += psi_p + nn_tmp + idx;
-    double bytes = 4.0 * total;
+    double bytes = 4.0 * (static_cast<double>(floats) + idx);
     // the row-list arenas of the sparse leading cuts while they are being calibrated (sparse_levels.hip; shrunk afterwards)
     const int S = (p->tun.sparse_k == -1 || p->popt.indices_only) ? 0 : genphi::sparse_eligible_steps(pl);
     if (S >= 2) {
@@ -2504,10 +2475,11 @@ void genphi_plan_destroy(genphi_plan *plan)
 }  // extern "C"
 
 // Device allocation of an upload; GENPHI_TEST_FAIL_ALLOC = k makes the k-th one of a plan fail (error-path test)
-static hipError_t plan_malloc(genphi_plan *p, void **ptr, size_t bytes)
+template <class T>
+static hipError_t plan_malloc(genphi_plan *p, DevBuf<T> &buf, size_t n)
 {
     if (p->tun.fail_alloc_at > 0 && ++p->alloc_count == p->tun.fail_alloc_at) return hipErrorOutOfMemory;
-    return genphi::cached_malloc(ptr, bytes);
+    return buf.reserve(n);
 }
 
 // upload the flat index arrays once
@@ -2636,8 +2608,7 @@ static int upload_plan_impl(genphi_plan *p, int device)
         bp.put(p->d_final_slots, pl.final_slots.data(), pl.final_slots.size());
     };
     const size_t total = blob_size(layout) + 256;
-    HIP_TRY(plan_malloc(p, reinterpret_cast<void **>(&p->idx_blob), total));
-    p->idx_blob_bytes = total;
+    HIP_TRY_AS("plan_malloc(p, reinterpret_cast<void **>(&p->idx_blob), total)", plan_malloc(p, p->idx_blob, total));
     trace.mark("  upload: hipMalloc index blob");
     std::vector<char> host;
     const int lrc = blob_upload(layout, host, p->idx_blob, total, p->stream);
@@ -2647,38 +2618,21 @@ static int upload_plan_impl(genphi_plan *p, int device)
     trace.mark("  upload: copy to device");
 
     const size_t n_slots = n_all + 1;                    // queue / counter slots: one per (sub-)step
-    p->n_slots = n_slots;
-    {   // certificates: words [cert_off[c], cert_off[c] + n_c] belong to cut c (incl. its "none" row)
-        p->cert_off.assign(pl.n_levels + 1, 0);
-        size_t w = 0;
-        p->cert_cut.assign(pl.n_levels + 1, 0);
-        p->buf_of[0].assign(pl.n_levels, 0); p->buf_of[1].assign(pl.n_levels, 0);
-        for (int c = 0; c < pl.n_levels; ++c) {
-            p->cert_off[c] = w;
-            // (a cut stored by slot -- the source of a step with src_slots -- has one word per slot + the "none" row P)
-            const bool by_slot = c < static_cast<int>(pl.steps.size()) && pl.steps[c].src_slots;
-            w += (by_slot ? static_cast<size_t>(pl.steps[c].P) : static_cast<size_t>(pl.cut_sizes[c])) + 1;
-            const bool stays = c >= 1 && pl.steps[c - 1].stay;
-            p->cert_cut[c] = stays ? p->cert_cut[c - 1] : c;
-            if (c >= 1) { p->buf_of[0][c] = stays ? p->buf_of[0][c - 1] : 1 - p->buf_of[0][c - 1]; p->buf_of[1][c] = c & 1; }
-        }
-        p->cert_cut[pl.n_levels] = pl.n_levels;
-        p->cert_off[pl.n_levels] = w;
-        p->cert_words = w;
-        // ONE array for what every sweep clears first -- the work-queue counters, the group counts, the certificate words -- so that a
-        // sweep starts with one memset instead of three (a deep pedigree's whole sweep is ~190 us)
-        p->sweep_words = n_slots * 16 + n_slots * 4 + std::max<size_t>(w, 1);
-        HIP_TRY(plan_malloc(p, reinterpret_cast<void **>(&p->d_queues), p->sweep_words * sizeof(int)));
-        p->d_gcnt = p->d_queues + n_slots * 16;
-        p->d_cert = p->d_gcnt + n_slots * 4;
-        HIP_TRY(plan_malloc(p, reinterpret_cast<void **>(&p->d_glist), 2 * ((static_cast<size_t>(pl.max_cut) + 64) / 64 * 64) * sizeof(int)));
-    }
+    p->sz = genphi::device_sizes(pl);
+    // ONE array for what every sweep clears first -- the work-queue counters, the group counts, the certificate words -- so that a
+    // sweep starts with one memset instead of three (a deep pedigree's whole sweep is ~190 us)
+    p->sweep_words = n_slots * 16 + n_slots * 4 + std::max<size_t>(p->sz.cert_off.back(), 1);
+    HIP_TRY_AS("plan_malloc(p, reinterpret_cast<void **>(&p->d_queues), p->sweep_words * sizeof(int))", plan_malloc(p, p->d_queues, p->sweep_words));
+    p->d_gcnt = p->d_queues + n_slots * 16;
+    p->d_cert = p->d_gcnt + n_slots * 4;
+    HIP_TRY_AS("plan_malloc(p, reinterpret_cast<void **>(&p->d_glist), 2 * ((static_cast<size_t>(pl.max_cut) + 64) / 64 * 64) * sizeof(int))",
+               plan_malloc(p, p->d_glist, 2 * ((static_cast<size_t>(pl.max_cut) + 64) / 64 * 64)));
     {
         std::vector<SmallStep> sm(pl.steps.size() + 1);
         for (size_t k = 0; k < pl.steps.size(); ++k)
             sm[k] = SmallStep{p->dsteps[k].srcA, p->dsteps[k].srcB, p->dsteps[k].ord,
                               static_cast<int>(pl.steps[k].n_prev), static_cast<int>(pl.steps[k].n)};
-        HIP_TRY(plan_malloc(p, reinterpret_cast<void **>(&p->d_small), sm.size() * sizeof(SmallStep)));
+        HIP_TRY_AS("plan_malloc(p, reinterpret_cast<void **>(&p->d_small), sm.size() * sizeof(SmallStep))", plan_malloc(p, p->d_small, sm.size()));
         HIP_TRY(hipMemcpyAsync(p->d_small, sm.data(), sm.size() * sizeof(SmallStep), hipMemcpyHostToDevice, p->stream));
         HIP_TRY(hipStreamSynchronize(p->stream));
     }
@@ -2689,53 +2643,34 @@ static int upload_plan_impl(genphi_plan *p, int device)
 // the first Float32 sweep, not by the upload -- a Float64-storage sweep (gen.f, pairwise phi) never touches them.
 static int ensure_level_buffers_impl(genphi_plan *p, int first_cut)
 {
-    const Plan &pl = p->plan;
+    const genphi::DeviceSizes &sz = p->sz;
     // ping-pong buffers for the intermediate cuts first_cut..L-2 (the cuts before live as row lists, sparse_levels.hip: genea140's widest
     // cuts -- 13,654 members, 2 x 745 MB of level buffers -- are among them; its first dense cut has 4,8xx: allocating, clearing and
     // giving back the large pair was 0.5 ms of every one-shot call, and released VRAM slows the next copies down, devcache.h)
-    size_t need[2] = {0, 0};
-    for (int c = first_cut; c + 1 < pl.n_levels; ++c) {
-        // a cut stored by slot (the cuts of an in-place run of WIDE steps): P + 1 rows of pitch P = ld[c]
-        const bool by_slot = pl.steps[c].src_slots;
-        const size_t fl = static_cast<size_t>(((by_slot ? static_cast<int64_t>(pl.steps[c].P) : pl.cut_sizes[c]) + 1) * pl.ld[c]) + kTailPadFloats;
-        for (int v = 0; v < 2; ++v) need[p->buf_of[v][c]] = std::max(need[p->buf_of[v][c]], fl);
-    }
+    size_t need[2];
+    sz.level_buffers(first_cut, need);
     for (int b = 0; b < 2; ++b) {
-        if (need[b]) {
-            HIP_TRY(plan_malloc(p, reinterpret_cast<void **>(&p->buf[b]), need[b] * sizeof(float)));
-            // on the plan's own stream: hipMemset on the null stream is asynchronous to the host
-            // and unordered with a non-blocking stream, so it could wipe level results later
-            HIP_TRY(hipMemsetAsync(p->buf[b], 0, need[b] * sizeof(float), p->stream));
-        }
-        p->buf_floats[b] = need[b];
+        if (!need[b]) continue;
+        HIP_TRY_AS("plan_malloc(p, reinterpret_cast<void **>(&p->buf[b]), need[b] * sizeof(float))", plan_malloc(p, p->buf[b], need[b]));
+        // on the plan's own stream: hipMemset on the null stream is asynchronous to the host
+        // and unordered with a non-blocking stream, so it could wipe level results later
+        HIP_TRY(hipMemsetAsync(p->buf[b], 0, p->buf[b].bytes(), p->stream));
     }
     p->level_bufs_from = first_cut;
     if (p->level_bufs_ready) return GENPHI_OK;         // (only the pair was replaced: a sweep that needs earlier cuts densely after all)
-    // WIDE steps: the compacted parent matrix and its rows' certificates
-    {
-        size_t need_p = 0, need_c = 0;
-        for (const LevelStep *nn : p->nn_steps) {
-            need_p = std::max(need_p, static_cast<size_t>((nn->n_prev + 1) * nn->ld_prev) + kTailPadFloats);
-            need_c = std::max(need_c, static_cast<size_t>(nn->n_prev) + 1);
-        }
-        size_t need_t = 0;                                         // in-place steps: npad x npad block + its certificate words
-        for (const LevelStep &st : pl.steps)
-            if (st.stay) need_t = std::max(need_t, static_cast<size_t>(st.npad));
-        if (need_t) {
-            HIP_TRY(plan_malloc(p, reinterpret_cast<void **>(&p->nn_tmp), (need_t * need_t + kTailPadFloats) * sizeof(float)));
-            HIP_TRY(hipMemsetAsync(p->nn_tmp, 0, (need_t * need_t + kTailPadFloats) * sizeof(float), p->stream));
-            p->nn_tmp_floats = need_t * need_t + kTailPadFloats;
-        }
-        if (need_p) {
-            HIP_TRY(plan_malloc(p, reinterpret_cast<void **>(&p->psi_p), need_p * sizeof(float)));
-            HIP_TRY(hipMemsetAsync(p->psi_p, 0, need_p * sizeof(float), p->stream));
-            p->psi_p_floats = need_p;
-        }
-        if (need_p || need_t) {                                    // (one array: an in-place step clears both in one launch)
-            HIP_TRY(plan_malloc(p, reinterpret_cast<void **>(&p->d_cert_p), (need_c + need_t + 1) * sizeof(int)));
-            p->d_cert_t = p->d_cert_p + need_c;
-            p->cert_p_words = need_c + need_t + 1;
-        }
+    // WIDE steps: the compacted parent matrix and its rows' certificates; in-place steps: the new x new block and its certificate words
+    if (sz.nn_tmp_floats) {
+        HIP_TRY_AS("plan_malloc(p, reinterpret_cast<void **>(&p->nn_tmp), (need_t * need_t + kTailPadFloats) * sizeof(float))", plan_malloc(p, p->nn_tmp, sz.nn_tmp_floats));
+        HIP_TRY(hipMemsetAsync(p->nn_tmp, 0, p->nn_tmp.bytes(), p->stream));
+    }
+    if (sz.psi_p_floats) {
+        HIP_TRY_AS("plan_malloc(p, reinterpret_cast<void **>(&p->psi_p), need_p * sizeof(float))", plan_malloc(p, p->psi_p, sz.psi_p_floats));
+        HIP_TRY(hipMemsetAsync(p->psi_p, 0, p->psi_p.bytes(), p->stream));
+    }
+    if (sz.psi_p_floats || sz.nn_pad) {                        // (one array: an in-place step clears both in one launch)
+        p->cert_p_words = sz.psi_p_rows + sz.nn_pad + 1;
+        HIP_TRY_AS("plan_malloc(p, reinterpret_cast<void **>(&p->d_cert_p), (need_c + need_t + 1) * sizeof(int))", plan_malloc(p, p->d_cert_p, p->cert_p_words));
+        p->d_cert_t = p->d_cert_p + sz.psi_p_rows;
     }
     p->level_bufs_ready = true;
     return GENPHI_OK;
@@ -2746,7 +2681,7 @@ static int ensure_level_buffers(genphi_plan *p, int first_cut)
     if (p->level_bufs_ready) {                        // e.g. GENPHI_FLAG_NO_SPARSE on a plan whose sweeps ran their leading cuts on lists
         drop_graph(p);
         (void)hipStreamSynchronize(p->stream);
-        for (int b = 0; b < 2; ++b) { if (p->buf[b]) (void)genphi::cached_free(p->buf[b]); p->buf[b] = nullptr; p->buf_floats[b] = 0; }
+        for (int b = 0; b < 2; ++b) p->buf[b].release();
     }
     const int rc = ensure_level_buffers_impl(p, first_cut);
     if (rc != GENPHI_OK) {                            // same rule as upload_plan: no half-allocated plan survives a failure
@@ -2771,13 +2706,13 @@ static int upload_plan(genphi_plan *p, int device)
     return rc;
 }
 
-static int ensure_floats(genphi_plan *p, float **ptr, size_t *have, size_t need)
+// (Here and at the other grow sites a failing cached_free of the old block is not reported any more -- DevBuf::release drops it, as
+// free_device always did; the allocation that follows is.)
+static int ensure_floats(genphi_plan *p, DevBuf<float> &buf, size_t need)
 {
-    if (*have >= need && *ptr) return GENPHI_OK;
+    if (buf && buf.count() >= need) return GENPHI_OK;
     drop_graph(p);                                   // a captured sweep points at the old buffer
-    if (*ptr) { HIP_TRY(genphi::cached_free(*ptr)); *ptr = nullptr; *have = 0; }
-    HIP_TRY(genphi::cached_malloc(reinterpret_cast<void **>(ptr), std::max<size_t>(need, 1) * sizeof(float)));
-    *have = need;
+    HIP_TRY_AS("genphi::cached_malloc(reinterpret_cast<void **>(ptr), std::max<size_t>(need, 1) * sizeof(float))", buf.reserve(need));
     return GENPHI_OK;
 }
 
@@ -2790,12 +2725,7 @@ genphi::ResidentView genphi::resident_view(const genphi_plan *p)
 int genphi::resident_scratch(genphi_plan *p, size_t bytes, char **scratch)
 {
     *scratch = nullptr;
-    if (p->scratch_bytes < bytes || !p->scratch) {
-        if (p->scratch) { HIP_TRY(genphi::cached_free(p->scratch)); p->scratch = nullptr; p->scratch_bytes = 0; }
-        const size_t want = std::max<size_t>(bytes, size_t(1) << 16);
-        HIP_TRY(genphi::cached_malloc(reinterpret_cast<void **>(&p->scratch), want));
-        p->scratch_bytes = want;
-    }
+    HIP_TRY_AS("genphi::cached_malloc(reinterpret_cast<void **>(&p->scratch), want)", p->scratch.reserve(std::max<size_t>(bytes, size_t(1) << 16)));
     *scratch = p->scratch;
     return GENPHI_OK;
 }
@@ -2947,8 +2877,8 @@ static LevelCtx main_ctx(genphi_plan *p, int step)
     LevelCtx c;
     c.s = &p->plan.steps[step]; c.d = &p->dsteps[step]; c.slot = step;
     // (cuts of an in-place run share the words of the run's entry cut: a member keeps its slot)
-    c.cert_prev = p->d_cert + p->cert_off[p->stay_active ? p->cert_cut[step] : step];
-    c.cert_out = p->d_cert + p->cert_off[p->stay_active ? p->cert_cut[step + 1] : step + 1];      // (the last level's have no reader: harmless)
+    c.cert_prev = p->d_cert + p->sz.cert_off[p->stay_active ? p->sz.cert_cut[step] : step];
+    c.cert_out = p->d_cert + p->sz.cert_off[p->stay_active ? p->sz.cert_cut[step + 1] : step + 1];      // (the last level's have no reader: harmless)
     c.identity = identity_source(step, p->tun);
     c.no_none_row = false;
     c.dbg = (p->tun.dbg_step >= 0 ? p->tun.dbg_step : static_cast<int>(p->plan.steps.size()) - 1) == step;     // default: the last step
@@ -2966,10 +2896,10 @@ static int ensure_groups(genphi_plan *p, int step)
     genphi::walk_lists(s, s.work.data(), nullptr, static_cast<int>(s.work.size()), p->tun.max_group, p->tun.max_run, w);
     auto layout = [&](BlobPacker &bp) { put_groups(w, d.groups, bp); };
     const size_t gb = blob_size(layout);
-    char *blob = nullptr;
-    HIP_TRY(plan_malloc(p, reinterpret_cast<void **>(&blob), gb));
-    p->lazy_blobs.push_back(blob);
-    p->lazy_bytes += gb;
+    DevBuf<char> owned;
+    HIP_TRY_AS("plan_malloc(p, reinterpret_cast<void **>(&blob), gb)", plan_malloc(p, owned, gb));
+    char *blob = owned;
+    p->lazy_blobs.push_back(std::move(owned));
     std::vector<char> img;
     const int rc = blob_upload(layout, img, blob, gb, p->stream);
     if (rc) return rc;
@@ -3390,15 +3320,6 @@ static int ensure_sparse_levels(genphi_plan *p, int kernel, PhaseTrace &trace)
     return GENPHI_OK;
 }
 
-static int ensure_doubles(double **ptr, size_t *have, size_t need)
-{
-    if (*have >= need && *ptr) return GENPHI_OK;
-    if (*ptr) { HIP_TRY(genphi::cached_free(*ptr)); *ptr = nullptr; *have = 0; }
-    HIP_TRY(genphi::cached_malloc(reinterpret_cast<void **>(ptr), std::max<size_t>(need, 1) * sizeof(double)));
-    *have = need;
-    return GENPHI_OK;
-}
-
 // The whole sweep with Float64 level matrices (see level_naive64_kernel): rows [r0, r1) of the
 // proband matrix end up in p->result64 (row pitch = pitch of the last cut).
 static int compute_f64(genphi_plan *p, int64_t r0, int64_t r1, int kernel, genphi_stats *stats, bool timing, bool no_sparse)
@@ -3406,16 +3327,12 @@ static int compute_f64(genphi_plan *p, int64_t r0, int64_t r1, int kernel, genph
     const Plan &pl = p->plan;
     const int L = pl.n_levels, n_steps = L - 1;
     const int64_t N = pl.n_pro, ldN = pl.ld[L - 1], n_rows = r1 - r0;
-    int rc = ensure_doubles(&p->result64, &p->result64_doubles, static_cast<size_t>(n_rows * ldN));
-    if (rc) return rc;
+    HIP_TRY_AS("genphi::cached_malloc(reinterpret_cast<void **>(ptr), std::max<size_t>(need, 1) * sizeof(double))", p->result64.reserve(static_cast<size_t>(n_rows * ldN)));
+    int rc;
     // storage member of each resident row (the last cut may be stored in [dragged, new] order)
     std::vector<int> srow(n_rows), orow(n_rows);
     for (int64_t k = 0; k < n_rows; ++k) { srow[k] = pl.final_perm.empty() ? static_cast<int>(r0 + k) : pl.final_perm[r0 + k]; orow[k] = static_cast<int>(k); }
-    if (static_cast<size_t>(2 * n_rows) > p->perm_rows_cap) {
-        if (p->d_perm_rows) { HIP_TRY(genphi::cached_free(p->d_perm_rows)); p->d_perm_rows = nullptr; }
-        HIP_TRY(genphi::cached_malloc(reinterpret_cast<void **>(&p->d_perm_rows), 2 * n_rows * sizeof(int)));
-        p->perm_rows_cap = static_cast<size_t>(2 * n_rows);
-    }
+    HIP_TRY_AS("genphi::cached_malloc(reinterpret_cast<void **>(&p->d_perm_rows), 2 * n_rows * sizeof(int))", p->d_perm_rows.reserve(static_cast<size_t>(2 * n_rows)));
     HIP_TRY(hipMemcpyAsync(p->d_perm_rows, srow.data(), n_rows * sizeof(int), hipMemcpyHostToDevice, p->stream));
     HIP_TRY(hipMemcpyAsync(p->d_perm_rows + n_rows, orow.data(), n_rows * sizeof(int), hipMemcpyHostToDevice, p->stream));
     HIP_TRY(hipStreamSynchronize(p->stream));           // host vectors go out of scope
@@ -3445,7 +3362,7 @@ static int compute_f64(genphi_plan *p, int64_t r0, int64_t r1, int kernel, genph
         size_t need[2] = {0, 0};
         for (int c = sparse_k + 1; c + 1 < L; ++c) need[c & 1] = std::max(need[c & 1], static_cast<size_t>((pl.cut_sizes[c] + 1) * pl.ld[c]));
         for (int b = 0; b < 2; ++b)
-            if (need[b]) { rc = ensure_doubles(&p->buf64[b], &p->buf64_doubles[b], need[b]); if (rc) return rc; }
+            if (need[b]) HIP_TRY_AS("genphi::cached_malloc(reinterpret_cast<void **>(ptr), std::max<size_t>(need, 1) * sizeof(double))", p->buf64[b].reserve(need[b]));
     }
     const int64_t n0 = pl.cut_sizes[0], ld0 = pl.ld[0];
     // LDS a workgroup may fill with staged Float64 source rows: 160 KB, or the GENPHI_LDS_CAP_FLOATS test budget (4 bytes a
@@ -3595,25 +3512,23 @@ static int prepare_buffers(genphi_plan *p, SweepCall &c, bool no_sparse, PhaseTr
             hipEvent_t e; HIP_TRY(hipEventCreate(&e)); p->events.push_back(e);
         }
     }
-    const int64_t N = pl.n_pro, ldN = pl.ld[L - 1], n_rows = c.n_rows;
-    rc = ensure_floats(p, &p->result, &p->result_floats, static_cast<size_t>(n_rows * ldN));
+    const int64_t ldN = pl.ld[L - 1], n_rows = c.n_rows;
+    rc = ensure_floats(p, p->result, genphi::result_floats(pl, n_rows));
     if (rc) return rc;
     trace.mark("result buffer");
     p->res_ld = ldN;
     c.need_perm = !pl.final_perm.empty();
     c.last_by_slot = c.need_perm && !pl.final_slots.empty() && p->stay_active;
     if (c.need_perm && !c.last_by_slot) {
-        rc = ensure_floats(p, &p->final_tmp, &p->final_tmp_floats, static_cast<size_t>((N + 1) * ldN) + kTailPadFloats);
+        rc = ensure_floats(p, p->final_tmp, p->sz.final_tmp_floats);
         if (rc) return rc;
     }
     // shard row lists for the last step: storage row of proband r, output row r - r0
-    if (n_rows > p->shard_cap) {
+    if (static_cast<size_t>(n_rows) > std::min(p->d_shard_rows.count(), p->d_shard_out_rows.count())) {
         drop_graph(p);
-        if (p->d_shard_rows) { HIP_TRY(genphi::cached_free(p->d_shard_rows)); HIP_TRY(genphi::cached_free(p->d_shard_out_rows)); }
-        p->d_shard_rows = p->d_shard_out_rows = nullptr;
-        HIP_TRY(genphi::cached_malloc(reinterpret_cast<void **>(&p->d_shard_rows), n_rows * sizeof(int)));
-        HIP_TRY(genphi::cached_malloc(reinterpret_cast<void **>(&p->d_shard_out_rows), n_rows * sizeof(int)));
-        p->shard_cap = n_rows; p->shard_r0 = p->shard_r1 = -1;
+        p->shard_r0 = p->shard_r1 = -1;
+        HIP_TRY_AS("genphi::cached_malloc(reinterpret_cast<void **>(&p->d_shard_rows), n_rows * sizeof(int))", p->d_shard_rows.reserve(n_rows));
+        HIP_TRY_AS("genphi::cached_malloc(reinterpret_cast<void **>(&p->d_shard_out_rows), n_rows * sizeof(int))", p->d_shard_out_rows.reserve(n_rows));
     }
     c.ev_after.resize(std::max(n_steps, 1));
     for (int k = 0; k < static_cast<int>(c.ev_after.size()); ++k) c.ev_after[k] = k + 1;
@@ -3638,7 +3553,7 @@ static int ensure_shard_lists(genphi_plan *p, const SweepCall &c)
         HIP_TRY(hipMemcpyAsync(p->d_shard_rows, work, n_rows * sizeof(int), hipMemcpyDeviceToDevice, p->stream));
         HIP_TRY(hipMemcpyAsync(p->d_shard_out_rows, work, n_rows * sizeof(int), hipMemcpyDeviceToDevice, p->stream));      // (output row = storage row)
         p->shard_groups = p->dsteps[n_steps - 1].groups;
-        (void)genphi::cached_free(p->sh_blob); p->sh_blob = nullptr; p->sh_valid = false;
+        p->sh_blob.release(); p->sh_valid = false;
         p->sh_steps.assign(std::max(n_steps, 1), genphi_plan::ShardStep());
         p->shard_r0 = r0; p->shard_r1 = r1;
         return GENPHI_OK;
@@ -3654,11 +3569,7 @@ static int ensure_shard_lists(genphi_plan *p, const SweepCall &c)
     if (n_steps > 0 && pl.steps[n_steps - 1].mode == genphi::kModeSplit) {
         auto layout = [&](BlobPacker &bp) { put_groups(sl.last_walk, p->shard_groups, bp); };
         const size_t gb = blob_size(layout);
-        if (gb > p->shard_blob_bytes) {
-            if (p->d_shard_blob) { HIP_TRY(genphi::cached_free(p->d_shard_blob)); p->d_shard_blob = nullptr; p->shard_blob_bytes = 0; }
-            HIP_TRY(genphi::cached_malloc(reinterpret_cast<void **>(&p->d_shard_blob), gb));
-            p->shard_blob_bytes = gb;
-        }
+        if (gb > p->d_shard_blob.count()) HIP_TRY_AS("genphi::cached_malloc(reinterpret_cast<void **>(&p->d_shard_blob), gb)", p->d_shard_blob.reserve(gb));
         const int rc = blob_upload(layout, img, p->d_shard_blob, gb, p->stream);
         if (rc) return rc;
     }
@@ -3666,7 +3577,7 @@ static int ensure_shard_lists(genphi_plan *p, const SweepCall &c)
     p->shard_r0 = r0; p->shard_r1 = r1;
 
     // the upper levels
-    (void)genphi::cached_free(p->sh_blob); p->sh_blob = nullptr; p->sh_valid = false;
+    p->sh_blob.release(); p->sh_valid = false;
     p->sh_steps.assign(std::max(n_steps, 1), genphi_plan::ShardStep());
     if (!sl.pruned) return GENPHI_OK;
     auto layout = [&](BlobPacker &bp) {
@@ -3678,7 +3589,7 @@ static int ensure_shard_lists(genphi_plan *p, const SweepCall &c)
         }
     };
     const size_t total = blob_size(layout) + 256;
-    HIP_TRY(genphi::cached_malloc(reinterpret_cast<void **>(&p->sh_blob), total));
+    HIP_TRY_AS("genphi::cached_malloc(reinterpret_cast<void **>(&p->sh_blob), total)", p->sh_blob.reserve(total));
     const int rc = blob_upload(layout, img, p->sh_blob, total, p->stream);
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(p->stream));
@@ -3735,7 +3646,7 @@ static int enqueue_sweep(genphi_plan *p, SweepCall &c)
     const int n_steps = pl.n_levels - 1, kernel = c.kernel, sparse_k = c.sparse_k;
     const bool timing = c.timing;
     const int64_t N = pl.n_pro, ldN = pl.ld[pl.n_levels - 1], n_rows = c.n_rows;
-    const std::vector<int> &bid = p->buf_of[p->stay_active ? 0 : 1];       // level buffer of every cut
+    const std::vector<int> &bid = p->sz.buf_of[p->stay_active ? 0 : 1];       // level buffer of every cut
     int rc;
     HIP_TRY(hipMemsetAsync(p->d_queues, 0, p->sweep_words * sizeof(int), p->stream));      // queues, group counts, certificates: one array
     if (n_steps == 0) {
@@ -3784,7 +3695,7 @@ static int enqueue_sweep(genphi_plan *p, SweepCall &c)
             if (p->step_hook) for (int k = s + 1; k < e; ++k) p->step_hook(k, n_steps, p->step_hook_user);
             hipLaunchKernelGGL(levels_small_kernel, dim3(1), dim3(1024), lds, p->stream, p->d_small + s, e - s,
                                psi, static_cast<long long>(pl.ld[s]), s == 0 ? 1 : 0, p->buf[bid[e]],
-                               static_cast<long long>(pl.ld[e]), p->d_cert + p->cert_off[e], cert_threshold(p->tun));
+                               static_cast<long long>(pl.ld[e]), p->d_cert + p->sz.cert_off[e], cert_threshold(p->tun));
             HIP_TRY(hipGetLastError());
             // per-level timing: ONE event for the run, booked on its first step (an event
             // record costs more than a fused level)

@@ -28,6 +28,7 @@
 #include "sparse_levels.h"
 
 #include "devcache.h"
+#include "devbuf.h"
 
 #include <algorithm>
 #include <array>
@@ -452,7 +453,7 @@ struct SparseLevels {
     SparseTuning tun;
     std::vector<int> n_of;           // members of cuts 0..S
     std::vector<SparseStepDev> dev;
-    char *blob = nullptr;            // children and mate lists of the S steps
+    DevBuf<char> blob;               // children and mate lists of the S steps
     std::vector<const int *> ch_off, mt_off;
     std::vector<const unsigned *> ch;
     std::vector<const uint2 *> mt;
@@ -461,30 +462,29 @@ struct SparseLevels {
     std::vector<int> zrow;           // per step: the all-zero "none" row of the matrix it writes
     std::vector<double> dense_ms;    // per step: estimated time of the step as the dense plan would run it (row kernels, block assembly, in place)
     std::vector<double> out_bytes;   // per step: bytes of the dense matrix the sparse -> dense step would write in its place
-    uint2 *ent[2] = {nullptr, nullptr};
-    uint2 *rowd_blob = nullptr;      // row descriptors of cuts 0..S-1, written by the calibration run and kept
+    // the two row-list arenas; ent[b].count() = entries it holds: small at first, enlarged by the calibration run where a cut needs it
+    DevBuf<uint2> ent[2];
+    DevBuf<uint2> rowd_blob;         // row descriptors of cuts 0..S-1, written by the calibration run and kept
     std::vector<uint2 *> rowd;
-    unsigned *fm_blob = nullptr;     // fm[c], c = 0..S-1: one word per member of cut c+1
+    DevBuf<unsigned> fm_blob;        // fm[c], c = 0..S-1: one word per member of cut c+1
     std::vector<unsigned *> fm;
     // rows of a cut by length (calibration): rnz[c][i] = non-zero entries of row i of Psi_c; order[c] = the members of cut c, longest row
     // first; cls[c][j] = first position in order[c] of the rows of class j (0: more than 1024 entries, 1: more than 256, 2: the rest; [3] = n)
-    unsigned *rnz_blob = nullptr;
-    int *order_blob = nullptr;
+    DevBuf<unsigned> rnz_blob;
+    DevBuf<int> order_blob;
     std::vector<unsigned *> rnz;
     std::vector<int *> order;
     std::vector<std::array<int, 4>> cls;
-    size_t ent_cap[2] = {0, 0};      // entries each arena holds: small at first, enlarged by the calibration run where a cut needs it
-    size_t ent_max = 0;              // ... up to this many (a cut that needs more is too dense to stay sparse)
+    size_t ent_max = 0;              // most entries an arena may grow to (a cut that needs more is too dense to stay sparse)
     int n_grown = 0;                 // (trace) how often the calibration run enlarged an arena
     bool lists_fresh = false;        // the calibration run has just written the lists of cut k (its fill launches ARE the list steps of a sweep) and
                                      // nothing has touched them since: the first sweep starts at the step that turns them into a matrix
-    unsigned *stat = nullptr;        // 4 words per cut
+    DevBuf<unsigned> stat;           // 4 words per cut
     unsigned *stat_host = nullptr;   // pinned copy of them, fetched at the end of a sweep
     std::vector<long long> nnz;      // non-zero entries of Psi_c per cut 0..S (-1 unknown)
     std::vector<long long> n_ent;    // entries of Y_c
     std::vector<int> max_row;
     int cap_cal = 0;
-    double bytes = 0.0;
 };
 
 int sparse_eligible_steps(const Plan &plan)
@@ -565,7 +565,7 @@ SparseLevels *sparse_levels_create(const Plan &plan, int S, const std::vector<Sp
     sl->n_ent[0] = sl->n_ch[0];
     trace.mark("  sparse: children, mates (host)");
     auto fail = [&](const std::string &m) { err = m; sparse_levels_destroy(sl); return static_cast<SparseLevels *>(nullptr); };
-    if (cached_malloc(reinterpret_cast<void **>(&sl->blob), total) != hipSuccess) return fail("hipMalloc (children lists) failed");
+    if (sl->blob.reserve(total) != hipSuccess) return fail("hipMalloc (children lists) failed");
     std::vector<char> host(total, 0);
     size_t o = 0;
     sl->ch_off.resize(S); sl->ch.resize(S); sl->mt_off.resize(S); sl->mt.resize(S); sl->slot.assign(S, nullptr); sl->zrow.assign(S, 0);
@@ -616,43 +616,36 @@ SparseLevels *sparse_levels_create(const Plan &plan, int S, const std::vector<Sp
     sl->ent_max = static_cast<size_t>(want);
     const size_t first = std::min(sl->ent_max, std::max<size_t>(static_cast<size_t>(std::max(64, tun.first_entries)), static_cast<size_t>(sl->n_ch[0]) + 64));
     for (int b = 0; b < 2; ++b) {
-        sl->ent_cap[b] = first;
-        if (cached_malloc(reinterpret_cast<void **>(&sl->ent[b]), sl->ent_cap[b] * sizeof(uint2)) != hipSuccess) return fail("hipMalloc (row-list arena) failed");
+        if (sl->ent[b].reserve(first) != hipSuccess) return fail("hipMalloc (row-list arena) failed");
     }
     size_t rowd_total = 0, fm_total = 0;
     auto pad32 = [](int n) { return (static_cast<size_t>(n) + 32) / 32 * 32; };
     for (int c = 0; c < S; ++c) { rowd_total += pad32(sl->n_of[c]); fm_total += pad32(sl->n_of[c + 1]); }
-    if (cached_malloc(reinterpret_cast<void **>(&sl->rowd_blob), rowd_total * sizeof(uint2)) != hipSuccess) return fail("hipMalloc (row descriptors) failed");
-    if (cached_malloc(reinterpret_cast<void **>(&sl->fm_blob), fm_total * sizeof(unsigned)) != hipSuccess) return fail("hipMalloc (parents' kinships) failed");
-    if (cached_malloc(reinterpret_cast<void **>(&sl->rnz_blob), rowd_total * sizeof(unsigned)) != hipSuccess) return fail("hipMalloc (row lengths) failed");
-    if (cached_malloc(reinterpret_cast<void **>(&sl->order_blob), rowd_total * sizeof(int)) != hipSuccess) return fail("hipMalloc (row order) failed");
+    if (sl->rowd_blob.reserve(rowd_total) != hipSuccess) return fail("hipMalloc (row descriptors) failed");
+    if (sl->fm_blob.reserve(fm_total) != hipSuccess) return fail("hipMalloc (parents' kinships) failed");
+    if (sl->rnz_blob.reserve(rowd_total) != hipSuccess) return fail("hipMalloc (row lengths) failed");
+    if (sl->order_blob.reserve(rowd_total) != hipSuccess) return fail("hipMalloc (row order) failed");
     sl->rowd.resize(S); sl->fm.resize(S); sl->rnz.resize(S); sl->order.resize(S); sl->cls.assign(S, std::array<int, 4>{0, 0, 0, 0});
     for (size_t c = 0, at = 0, fat = 0; c < static_cast<size_t>(S); ++c) {
         sl->rowd[c] = sl->rowd_blob + at; sl->rnz[c] = sl->rnz_blob + at; sl->order[c] = sl->order_blob + at; at += pad32(sl->n_of[c]);
         sl->fm[c] = sl->fm_blob + fat; fat += pad32(sl->n_of[c + 1]);
     }
-    if (cached_malloc(reinterpret_cast<void **>(&sl->stat), 4 * (static_cast<size_t>(S) + 1) * sizeof(unsigned)) != hipSuccess) return fail("hipMalloc (counters) failed");
+    if (sl->stat.reserve(4 * (static_cast<size_t>(S) + 1)) != hipSuccess) return fail("hipMalloc (counters) failed");
     if (cached_pinned(reinterpret_cast<void **>(&sl->stat_host), 4 * (static_cast<size_t>(S) + 1) * sizeof(unsigned)) != hipSuccess)
         return fail("hipHostMalloc (counters) failed");
     std::memset(sl->stat_host, 0, 4 * (static_cast<size_t>(S) + 1) * sizeof(unsigned));
-    sl->bytes = static_cast<double>(total) + static_cast<double>((sl->ent_cap[0] + sl->ent_cap[1]) * sizeof(uint2)) +
-                static_cast<double>(rowd_total * sizeof(uint2) + fm_total * sizeof(unsigned));
     sl->cap_cal = std::min(8192, (n_max + 63) / 64 * 64);
     trace.mark("  sparse: arenas");
-    if (static_cast<size_t>(sl->n_ch[0]) > sl->ent_cap[0]) return fail("sparse levels: arena smaller than the first cut");
+    if (static_cast<size_t>(sl->n_ch[0]) > sl->ent[0].count()) return fail("sparse levels: arena smaller than the first cut");
     return sl;
 }
 
 void sparse_levels_destroy(SparseLevels *sl)
 {
     if (!sl) return;
-    if (sl->blob) (void)cached_free(sl->blob);
-    for (int b = 0; b < 2; ++b) if (sl->ent[b]) (void)cached_free(sl->ent[b]);
-    if (sl->rowd_blob) (void)cached_free(sl->rowd_blob);
-    if (sl->fm_blob) (void)cached_free(sl->fm_blob);
-    if (sl->rnz_blob) (void)cached_free(sl->rnz_blob);
-    if (sl->order_blob) (void)cached_free(sl->order_blob);
-    if (sl->stat) (void)cached_free(sl->stat);
+    // (in this order, not the destructors' reverse one: the order in which blocks reach the cache decides which ones the next plan finds)
+    sl->blob.release(); sl->ent[0].release(); sl->ent[1].release(); sl->rowd_blob.release(); sl->fm_blob.release(); sl->rnz_blob.release();
+    sl->order_blob.release(); sl->stat.release();
     cached_pinned_release(sl->stat_host);
     delete sl;
 }
@@ -676,7 +669,7 @@ static SpArgs args_for(const SparseLevels *sl, int s)
         a.rnz_out = sl->rnz[s + 1];
     }
     a.count_only = 0;
-    a.ent_cap = static_cast<unsigned>(std::min<size_t>(sl->ent_cap[(s + 1) & 1], 0xffffffffu));
+    a.ent_cap = static_cast<unsigned>(std::min<size_t>(sl->ent[(s + 1) & 1].count(), 0xffffffffu));
     return a;
 }
 
@@ -731,12 +724,7 @@ static double t_dense_step(const SparseLevels *sl, int s) { return sl->dense_ms[
 static void drop_arenas(SparseLevels *sl, hipStream_t stream)
 {
     (void)hipStreamSynchronize(stream);
-    for (int b = 0; b < 2; ++b) {
-        if (sl->ent[b]) (void)cached_free(sl->ent[b]);
-        sl->ent[b] = nullptr;
-        sl->bytes -= static_cast<double>(sl->ent_cap[b] * sizeof(uint2));
-        sl->ent_cap[b] = 0;
-    }
+    for (int b = 0; b < 2; ++b) sl->ent[b].release();
 }
 
 int sparse_levels_calibrate(SparseLevels *sl, hipStream_t stream, std::string &err)
@@ -776,7 +764,7 @@ int sparse_levels_calibrate(SparseLevels *sl, hipStream_t stream, std::string &e
             if (rc) return rc;
             const unsigned long long stop_entries = sl->tun.force_k >= 0 ? ~0ull : static_cast<unsigned long long>(0.25 * static_cast<double>(n) * static_cast<double>(n));
             hipLaunchKernelGGL(sparse_place_kernel, dim3(1), dim3(1024), 0, stream, sl->rowd[s + 1], n,
-                               static_cast<unsigned>(std::min<size_t>(sl->ent_cap[(s + 1) & 1], 0xffffffffu)), stop_entries, sl->stat + 4 * (s + 1), sl->stat + 3,
+                               static_cast<unsigned>(std::min<size_t>(sl->ent[(s + 1) & 1].count(), 0xffffffffu)), stop_entries, sl->stat + 4 * (s + 1), sl->stat + 3,
                                static_cast<unsigned>(s + 1));
             SP_TRY(hipGetLastError());
             // the writing launches by class of row lengths, as in a sweep (the counting launch has left every row's count on the device;
@@ -844,30 +832,24 @@ int sparse_levels_calibrate(SparseLevels *sl, hipStream_t stream, std::string &e
                 if (!pays) break;
             }
             const size_t cap_b = std::min(sl->ent_max, need + need / 8 + 64);
-            uint2 *larger = nullptr;
-            if (cached_malloc(reinterpret_cast<void **>(&larger), cap_b * sizeof(uint2)) != hipSuccess) {
+            DevBuf<uint2> larger;
+            if (larger.reserve(cap_b) != hipSuccess) {
                 (void)hipGetLastError();                   // (no memory for this cut's lists: the run ends at the cut before it, the sweep goes on densely from there)
                 break;
             }
-            (void)cached_free(sl->ent[b]);                 // (holds cut c-2: dead)
-            sl->ent[b] = larger;
-            sl->bytes += static_cast<double>(cap_b * sizeof(uint2)) - static_cast<double>(sl->ent_cap[b] * sizeof(uint2));
-            sl->ent_cap[b] = cap_b;
+            sl->ent[b] = std::move(larger);                // (the old one held cut c-2: dead)
             if (c < n_cand) {                              // room for the cut behind it in the other arena (lists grow up to ~4 x per cut, less and less)
                 const size_t dense_next = static_cast<size_t>(sl->n_of[c + 1]) * static_cast<size_t>(c + 2 <= sl->S ? sl->n_of[c + 2] : sl->n_of[c + 1]) + 64;
                 const size_t cap_o = std::min(std::min(sl->ent_max, dense_next), 3 * need);
                 // (small lists only: a cut behind this one that needs more than 256 MB is looked at -- does it pay? -- before anything is allocated for it)
-                if (cap_o > sl->ent_cap[b ^ 1] && cap_o * sizeof(uint2) <= (size_t(256) << 20)) {
-                    uint2 *bigger = nullptr;
-                    if (cached_malloc(reinterpret_cast<void **>(&bigger), cap_o * sizeof(uint2)) != hipSuccess) { (void)hipGetLastError(); bigger = nullptr; }
+                if (cap_o > sl->ent[b ^ 1].count() && cap_o * sizeof(uint2) <= (size_t(256) << 20)) {
+                    DevBuf<uint2> bigger;
+                    if (bigger.reserve(cap_o) != hipSuccess) (void)hipGetLastError();
                     const size_t live = static_cast<size_t>(sl->n_ent[c - 1]);       // cut c-1: the source of the leg to come
                     if (bigger) {                            // (room for the next cut is a convenience: without it that cut asks for itself)
                         SP_TRY(hipMemcpyAsync(bigger, sl->ent[b ^ 1], live * sizeof(uint2), hipMemcpyDeviceToDevice, stream));
                         SP_TRY(hipStreamSynchronize(stream));
-                        (void)cached_free(sl->ent[b ^ 1]);
-                        sl->ent[b ^ 1] = bigger;
-                        sl->bytes += static_cast<double>(cap_o * sizeof(uint2)) - static_cast<double>(sl->ent_cap[b ^ 1] * sizeof(uint2));
-                        sl->ent_cap[b ^ 1] = cap_o;
+                        sl->ent[b ^ 1] = std::move(bigger);
                     }
                 }
             }
@@ -878,7 +860,7 @@ int sparse_levels_calibrate(SparseLevels *sl, hipStream_t stream, std::string &e
             from = c;
         }
     }
-    if (trace && sl->n_grown) std::fprintf(stderr, "[genphi trace]   sparse: arenas enlarged %d times (%zu + %zu entries)\n", sl->n_grown, sl->ent_cap[0], sl->ent_cap[1]);
+    if (trace && sl->n_grown) std::fprintf(stderr, "[genphi trace]   sparse: arenas enlarged %d times (%zu + %zu entries)\n", sl->n_grown, sl->ent[0].count(), sl->ent[1].count());
     tr.mark("    calibration: rows sorted by length (host)");
     if (last >= 1) {
         std::vector<int> ord_all(rnz_at[last] + static_cast<size_t>(sl->n_of[last]) - rnz_at[1], 0);
@@ -917,13 +899,13 @@ int sparse_levels_calibrate(SparseLevels *sl, hipStream_t stream, std::string &e
         for (int c = k + 2; c <= n_cand; c += 2)
             if (st[4 * c + 2] == 0u && st[4 * c + 0] != 0u) sl->lists_fresh = false;
         for (int b = 0; b < 2; ++b) {
-            if (need[b] * 2 > sl->ent_cap[b]) continue;    // (not worth a reallocation)
+            if (need[b] * 2 > sl->ent[b].count()) continue;    // (not worth a reallocation)
             if (b == (k & 1)) sl->lists_fresh = false;     // (the lists of cut k go with their arena: the first sweep computes them again)
-            (void)cached_free(sl->ent[b]);
-            sl->ent[b] = nullptr;
-            SP_TRY(cached_malloc(reinterpret_cast<void **>(&sl->ent[b]), need[b] * sizeof(uint2)));
-            sl->bytes += static_cast<double>(need[b] * sizeof(uint2)) - static_cast<double>(sl->ent_cap[b] * sizeof(uint2));
-            sl->ent_cap[b] = need[b];
+            sl->ent[b].release();
+            if (const hipError_t e = sl->ent[b].reserve(need[b]); e != hipSuccess) {      // (the message as it read when the call was spelled out here)
+                err = std::string("cached_malloc(reinterpret_cast<void **>(&sl->ent[b]), need[b] * sizeof(uint2)): ") + hipGetErrorString(e);
+                return GENPHI_ERR_DEVICE;
+            }
         }
     }
     if (trace) std::fprintf(stderr, "[genphi trace]   sparse cuts 0..%d\n", k);
@@ -1004,6 +986,9 @@ int sparse_levels_counts(const SparseLevels *sl, int cap, long long *nnz, long l
     return m;
 }
 
-double sparse_levels_device_bytes(const SparseLevels *sl) { return sl ? sl->bytes : 0.0; }
+double sparse_levels_device_bytes(const SparseLevels *sl)
+{
+    return sl ? static_cast<double>(sl->blob.bytes() + sl->ent[0].bytes() + sl->ent[1].bytes() + sl->rowd_blob.bytes() + sl->fm_blob.bytes()) : 0.0;
+}
 
 }  // namespace genphi

@@ -13,6 +13,7 @@
 #include <string>
 #include <vector>
 
+#include "../genlib.jl_amd/csrc/device_sizes.h"
 #include "../genlib.jl_amd/csrc/group_tables.h"
 #include "../genlib.jl_amd/csrc/planner.h"
 #include "../genlib.jl_amd/csrc/shard_lists.h"
@@ -210,6 +211,55 @@ static int shards_all_ways(const Plan &pl, const char *what)
     return bad;
 }
 
+// device_sizes.h against what its readers rely on: under both alternations every cut's matrix fits in the buffer it is assigned to (rows + 1,
+// or P + 1 when the cut is stored by slot, times the pitch, plus the tail pad) whatever the first dense cut; the certificate offsets increase
+// and end at the word total; a cut shares the words of a cut at or before it; the parent matrix and the new x new block hold every sub-step.
+static int check_sizes(const Plan &pl, const char *what)
+{
+    auto bad = [&](const char *why, long long at) { std::fprintf(stderr, "%s: device sizes: %s (at %lld)\n", what, why, at); return 1; };
+    const genphi::DeviceSizes z = genphi::device_sizes(pl);
+    const int L = pl.n_levels;
+    if (static_cast<int>(z.cert_off.size()) != L + 1 || static_cast<int>(z.cert_cut.size()) != L + 1) return bad("table lengths", L);
+    if (static_cast<int>(z.buf_of[0].size()) != L || static_cast<int>(z.buf_of[1].size()) != L) return bad("buf_of lengths", L);
+    if (L == 0) return (z.cert_off[0] || z.psi_p_floats || z.nn_tmp_floats || z.final_tmp_floats || genphi::result_floats(pl, 0)) ? bad("an empty plan needs memory", 0) : 0;
+    size_t words = 0;
+    std::vector<size_t> fl(L, 0);
+    for (int c = 0; c < L; ++c) {
+        const bool by_slot = c + 1 < L && pl.steps[c].src_slots;
+        const size_t rows = static_cast<size_t>(by_slot ? pl.steps[c].P : pl.cut_sizes[c]) + 1;
+        fl[c] = rows * static_cast<size_t>(pl.ld[c]) + genphi::kTailPadFloats;
+        if (z.cert_off[c] != words) return bad("cert_off is not the running row total", c);
+        if (z.cert_off[c + 1] <= z.cert_off[c]) return bad("cert_off does not increase", c);
+        words += rows;
+        if (z.cert_cut[c] < 0 || z.cert_cut[c] > c) return bad("cert_cut[c] > c", c);
+        // (what main_ctx reads through cert_cut: the shared words hold every row of the cut)
+        if (z.cert_off[z.cert_cut[c] + 1] - z.cert_off[z.cert_cut[c]] < rows && z.cert_cut[c] != c) return bad("a cut has more rows than the certificate words it shares", c);
+        for (int v = 0; v < 2; ++v) if (z.buf_of[v][c] != 0 && z.buf_of[v][c] != 1) return bad("buf_of is not 0 / 1", c);
+        if (c >= 1 && z.buf_of[1][c] == z.buf_of[1][c - 1]) return bad("the plain alternation does not alternate", c);
+        if (c >= 1 && (z.buf_of[0][c] == z.buf_of[0][c - 1]) != pl.steps[c - 1].stay) return bad("a step reads and writes one buffer without staying in place (or the reverse)", c);
+    }
+    if (z.cert_off[L] != words || z.cert_cut[L] != L) return bad("cert_off does not end at the word total", L);
+    for (int first = 0; first < L; ++first) {
+        size_t need[2];
+        z.level_buffers(first, need);
+        for (int c = first; c + 1 < L; ++c)
+            for (int v = 0; v < 2; ++v)
+                if (need[z.buf_of[v][c]] < fl[c]) return bad("a cut does not fit in its level buffer", c);
+        if (first + 1 >= L && (need[0] || need[1])) return bad("level buffers without an intermediate cut", first);
+    }
+    for (const genphi::LevelStep &st : pl.steps) {
+        if (st.mode == genphi::kModeWide && !st.nn.empty()) {
+            if (z.psi_p_floats < static_cast<size_t>((st.nn[0].n_prev + 1) * st.nn[0].ld_prev) + genphi::kTailPadFloats) return bad("psi_p too small", st.nn[0].n_prev);
+            if (z.psi_p_rows < static_cast<size_t>(st.nn[0].n_prev) + 1) return bad("too few certificate words for psi_p", st.nn[0].n_prev);
+        }
+        if (st.stay && (z.nn_pad < static_cast<size_t>(st.npad) || z.nn_tmp_floats < static_cast<size_t>(st.npad) * static_cast<size_t>(st.npad) + genphi::kTailPadFloats))
+            return bad("nn_tmp too small", st.npad);
+    }
+    if (z.final_tmp_floats != static_cast<size_t>((pl.n_pro + 1) * pl.ld[L - 1]) + genphi::kTailPadFloats) return bad("final_tmp", L);
+    if (genphi::result_floats(pl, pl.n_pro) != static_cast<size_t>(pl.n_pro * pl.ld[L - 1]) || genphi::result_floats(pl, 0) != 0) return bad("result", L);
+    return 0;
+}
+
 static int plan_all_ways(const std::vector<int64_t> &ind, const std::vector<int64_t> &fa, const std::vector<int64_t> &mo,
                          const std::vector<int64_t> &pro, const char *what)
 {
@@ -229,6 +279,7 @@ static int plan_all_ways(const std::vector<int64_t> &ind, const std::vector<int6
                                           pro.data(), o, plan, err);
         if (rc != GENPHI_OK) { std::fprintf(stderr, "%s, variant %d: build_plan failed: %s\n", what, variant, err.c_str()); return 1; }
         sum += checksum(plan);
+        if (check_sizes(plan, what)) return 1;
         // the hub walk of every SPLIT step (what the upload builds from the plan)
         for (const genphi::LevelStep &st : plan.steps) {
             if (st.mode != genphi::kModeSplit || st.work.empty()) continue;
@@ -398,6 +449,7 @@ int main(int argc, char **argv)
         if (genphi::build_plan(3, i.data(), fdup.data(), m0.data(), 1, pro_unk.data(), PlanOptions(), plan, err) == GENPHI_OK) { std::fprintf(stderr, "unknown proband accepted\n"); bad = 1; }
         Plan empty;
         if (genphi::build_plan(3, i.data(), fdup.data(), m0.data(), 0, nullptr, PlanOptions(), empty, err) != GENPHI_OK) { std::fprintf(stderr, "no probands: %s\n", err.c_str()); bad = 1; }
+        else bad |= check_sizes(empty, "no probands");
     }
     // random pedigrees: overlapping generations, one-parent individuals, probands at every depth
     std::mt19937_64 rng(20261005);

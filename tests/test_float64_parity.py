@@ -185,6 +185,27 @@ def test_wide_last_step_and_row_shards(gen, oracle):
     pl.close()
 
 
+def test_float64_buffers_grow_and_are_released(gen, oracle):
+    """The Float64 buffers of ONE plan over calls of different sizes and a release (the host contract test makes a single Float64 call):
+    rows (3, 40), (0, 200), (5, 9), release_device(), (3, 40) again -- every result against the oracle's rows; the plan's device bytes
+    never decrease while buffers are only grown, are 0 after the release, and a plan uploaded again holds what it held the first time."""
+    from genlib_jl_amd import synth
+    ind, fa, mo, _, pro = synth.random_mating(8000, 900, 9, skip_permille=40)
+    ped = _ped(gen, ind, fa, mo)
+    want = oracle.Pedigree(ind, fa, mo).phi_rows64(pro, np.arange(200))
+    pl = gen.plan(ped, pro)
+    held = []
+    for r in ((3, 40), (0, 200), (5, 9)):
+        _bits_equal(_sweep64(pl, rows=r), want[r[0]:r[1]], f"rows {r}")
+        held.append(pl.device_bytes)
+    assert 0 < held[0] <= held[1] <= held[2], held
+    pl.release_device()
+    assert pl.device_bytes == 0
+    _bits_equal(_sweep64(pl, rows=(3, 40)), want[3:40], "rows (3, 40) after release_device")
+    assert pl.device_bytes == held[0], (pl.device_bytes, held)
+    pl.close()
+
+
 def test_sparse_leading_cuts_float64(gen, oracle):
     """(f) The sparse leading cuts (csrc/sparse_levels.hip) writing the first dense Float64 matrix, against phi64, with and
     without them: a random pedigree whose calibration keeps at least two cuts as lists.  (genea140: above.)"""
