@@ -61,13 +61,17 @@
 #include "planner.h"
 #include "shard_lists.h"
 #include "resident.h"
+#include "row_geometry.h"
 #include "sparse_levels.h"
+#include "tuning.h"
 
 using genphi::al256;
 using genphi::DevBuf;
 using genphi::kTailPadFloats;
 using genphi::LevelStep;
 using genphi::Plan;
+using genphi::Tuning;          // the hooks of a plan, read once when it is created (tuning.h)
+using genphi::cert_threshold;
 
 // ---------------------------------------------------------------------------------------------
 // device code
@@ -1945,150 +1949,6 @@ constexpr size_t kIdxPad = 32 * 1024;
 // (a deep pedigree of 200 tiny levels carried 52 MB of padding: 11 of the 14 ms of its first call)
 static size_t idx_pad(const LevelStep &s) { return s.mode == genphi::kModeSplit ? kIdxPad : 1024; }
 
-// Tuning, A/B and test hooks.  Every one is an environment variable that is read ONCE, when the plan is
-// created (genphi_plan_create), and kept in the plan: a plan never changes behaviour under the caller's
-// feet, and no launch path calls getenv.  The list (with what each is for) is in README.md,
-// "Environment hooks"; none is needed in production.
-struct Tuning {
-    int lds_cap_floats = 0;        // GENPHI_LDS_CAP_FLOATS   test: LDS budget for staged rows (forces SPLIT / WIDE on small inputs)
-    int full_max_floats = -1;      // GENPHI_FULL_MAX_FLOATS  tuning: FULL vs SPLIT threshold (row length in floats)
-    bool no_stay = false;          // GENPHI_NO_STAY          A/B + test: WIDE levels never stay in place (every level is copied into the other buffer)
-    int stay_max_slots = 0;        // GENPHI_STAY_MAX_SLOTS   test: largest slot capacity of an in-place run (default: planner.h)
-    int stay_headroom = -1;        // GENPHI_STAY_HEADROOM    tuning: extra blocks of free slots per in-place run (longer runs, more memory)
-    int stay_mem_pct = 0;          // GENPHI_STAY_MEM_PCT     test: in-place runs may need this % of the plain buffers' memory (default 120)
-    int stay_min_ratio_pct = -1;   // GENPHI_STAY_MIN_RATIO_PCT tuning: a step stays in place while cut >= this % of its new members (default 200)
-    int stay_slack_pct = -1;       // GENPHI_STAY_SLACK_PCT   tuning: free slots beyond the widest (cut + new members) of an in-place run, in % (default 6)
-    int stay_narrow = -1;          // GENPHI_STAY_NARROW      A/B + test: 0 = only levels whose rows do not fit in LDS stay in place (the round-3 behaviour); 2 = in place wherever the ratio test allows, whatever the cost model says
-    int stay_family = -1;          // GENPHI_STAY_FAMILY      A/B: 0 = new members of a leaving class in rank order instead of by family
-    bool colperm_plain = false;    // GENPHI_COLPERM_PLAIN    A/B + test: the proband-order pass by the one-workgroup-per-row kernel (rounds 1-3)
-    int stay_last = -1;            // GENPHI_STAY_LAST        A/B + test: 0 = the proband cut never stays in place (the step that reads a run's last cut compacts it,
-                                   //                         then the proband-order pass: the form of rounds 3 and early 4)
-    int stay_overhead_k = -1;      // GENPHI_STAY_OVERHEAD_K  tuning + test: fixed cost of a block-assembled step in the planner's cost model, in thousands of
-                                   //                         matrix entries (default 64000; tests that put tiny cuts in place set 0)
-    int stay_narrow_min = -1;      // GENPHI_STAY_NARROW_MIN  tuning + test: narrowest source cut of an in-place step at FULL / SPLIT widths (default 2048)
-    int stay_tile = 0;             // GENPHI_STAY_TILE        tuning: columns per tile of the fused in-place kernel, 256 or 128 (default: by the launch's size)
-    bool stay_scalar_t = false;    // GENPHI_STAY_SCALAR_T    A/B: the fused kernel writes its transposed tile with 4-byte stores (the round-3 form) instead of 16-byte ones
-    bool stay_col_fastest = false; // GENPHI_STAY_COL_FASTEST A/B: fused kernel's workgroups ordered column-fastest instead of granule-fastest (same columns together)
-    bool stay_two_pass = false;    // GENPHI_STAY_TWO_PASS    A/B + test: new x dragged and its transpose as two kernels (rows_avg + transpose_slots) instead of the fused one
-    bool stay_scatter = false;     // GENPHI_STAY_SCATTER     A/B + test: the new x new block of an in-place step always goes through the compact buffer
-    int max_group = 8;             // GENPHI_MAX_GROUP        tuning: children per segment of the SPLIT work lists (<= 8; <= 4 where rank masks are kept)
-    int max_run = 1;               // GENPHI_MAX_RUN          tuning: stages per run of the hub walk.  1 (default): a run is one hub and its children;
-                                   //                         larger: the walk chains from hub to hub (16-20 % fewer staged rows, measured no faster:
-                                   //                         profiles/microbench/out/r03_ab_hub_walk_*.out)
-    int full_bs = 0;               // GENPHI_FULL_BS          tuning: workgroup size of level_full_kernel
-    bool no_identity = false;      // GENPHI_NO_IDENTITY      test: level step 0 on a materialised 1/2 I
-    int cert_min_exp = -27;        // GENPHI_CERT_MIN_EXP     test: certificate threshold 2^e, e in [-27, 0] (always safe)
-    int dbg_step = -1;             // GENPHI_DBG_STEP         GENPHI_WG_TIMES builds: the step whose workgroup timing is recorded
-    bool no_fast = false;          // GENPHI_NO_FAST          test / A-B: grouping-exact SPLIT / FULL bodies only
-    int max_cpt = 0;               // GENPHI_MAX_CPT          test / tuning: columns per thread of a SPLIT chunk
-    int fast_nt = 0;               // GENPHI_FAST_NT          test / tuning: 512- or 1024-thread certified-rows kernel
-    char wide_route = 0;           // GENPHI_WIDE_ROUTE       A-B: 'A' / 'B' route of the WIDE levels (0 = by cost)
-    bool tt_noalign = false;       // GENPHI_TT_NOALIGN       A-B: transpose without line-aligned destination runs
-    bool no_shard_prune = false;   // GENPHI_NO_SHARD_PRUNE   test: a row shard computes every row of the upper levels
-    int shard_force_step = -1, shard_force_row = -1;   // GENPHI_SHARD_FORCE "step:row"  debugging aid
-    int shard_prune_min_step = 0;  // GENPHI_SHARD_PRUNE_MIN_STEP  debugging aid
-    bool no_small = false;         // GENPHI_NO_SMALL         test: no fused small-level runs
-    bool no_graph = false;         // GENPHI_NO_GRAPH         A-B: never replay a captured hipGraph
-    int fail_alloc_at = 0;         // GENPHI_TEST_FAIL_ALLOC  test: the k-th device allocation of an upload fails (error-path test)
-    int sparse_k = -2;             // GENPHI_SPARSE_K         A/B + test: last cut kept as row lists (sparse_levels.h): -1 = none (every level dense), k >= 0 = cuts 0..k
-                                   //                         whatever their density (clamped to the eligible steps); default: by the calibration run's counts
-    int sparse_permille = -1;      // GENPHI_SPARSE_PERMILLE  tuning: a cut stays sparse while at most this share (1/1000) of its entries is non-zero
-    int sparse_min_cut = -1;       // GENPHI_SPARSE_MIN_CUT   tuning + test: ... and only when a cut of the sparse run has this many members
-    int sparse_chunk = 0;          // GENPHI_SPARSE_CHUNK     tuning: columns per workgroup of the sparse -> dense step
-    int sparse_batch = 0;          // GENPHI_SPARSE_BATCH     A/B: list entries in flight per thread of a long row's workgroup, 4 or 8 (default 4; 8 measured slower)
-    int sparse_arena = 0;          // GENPHI_SPARSE_ARENA     test: entries the row-list arenas start with (default 16 Mi; small values exercise their growth)
-    genphi::ResultTuning res;      // the hooks of the resident-result queries (resident.h)
-    int sparse_classes = -1;       // GENPHI_SPARSE_CLASSES   A/B + test: 1 / 0 = a row-list step is always / never one launch per class of row lengths (default: where lengths differ much)
-};
-
-// A set of "GENPHI_NAME" -> value settings handed to genphi_plan_create_tuned (include/genphi.h): the same knobs without the environment.
-struct genphi_tuning {
-    std::map<std::string, std::string> kv;
-};
-
-// every hook name a Tuning understands (genphi_tuning_set refuses anything else)
-static const char *const kTuningNames[] = {
-    "GENPHI_LDS_CAP_FLOATS", "GENPHI_FULL_MAX_FLOATS", "GENPHI_NO_STAY", "GENPHI_STAY_MAX_SLOTS", "GENPHI_STAY_HEADROOM", "GENPHI_STAY_MEM_PCT",
-    "GENPHI_STAY_SCATTER", "GENPHI_STAY_TWO_PASS", "GENPHI_STAY_COL_FASTEST", "GENPHI_STAY_SCALAR_T", "GENPHI_STAY_TILE", "GENPHI_STAY_SLACK_PCT",
-    "GENPHI_STAY_MIN_RATIO_PCT", "GENPHI_STAY_NARROW", "GENPHI_STAY_NARROW_MIN", "GENPHI_STAY_OVERHEAD_K", "GENPHI_STAY_LAST", "GENPHI_COLPERM_PLAIN",
-    "GENPHI_STAY_FAMILY", "GENPHI_MAX_GROUP", "GENPHI_MAX_RUN", "GENPHI_FULL_BS", "GENPHI_NO_IDENTITY", "GENPHI_CERT_MIN_EXP", "GENPHI_DBG_STEP",
-    "GENPHI_NO_FAST", "GENPHI_MAX_CPT", "GENPHI_FAST_NT", "GENPHI_WIDE_ROUTE", "GENPHI_TT_NOALIGN", "GENPHI_NO_SHARD_PRUNE", "GENPHI_SHARD_FORCE",
-    "GENPHI_SHARD_PRUNE_MIN_STEP", "GENPHI_NO_SMALL", "GENPHI_NO_GRAPH", "GENPHI_D2H_THREADS", "GENPHI_D2H_PAGEABLE", "GENPHI_D2H_SYM", "GENPHI_D2H_TILE",
-    "GENPHI_D2H_CHUNK_MB", "GENPHI_TEST_FAIL_ALLOC", "GENPHI_SPARSE_K", "GENPHI_SPARSE_PERMILLE", "GENPHI_SPARSE_MIN_CUT", "GENPHI_SPARSE_CHUNK", "GENPHI_SPARSE_CLASSES", "GENPHI_SPARSE_BATCH", "GENPHI_SPARSE_ARENA", "GENPHI_BOOT_PANEL", "GENPHI_NEAREST_BUF"};
-
-// the settings of a plan: from a genphi_tuning when one is given, else from the environment -- which the library reads only under
-// GENPHI_ENV_HOOKS=1 (planner.h: env_hook)
-static Tuning tuning_from(const genphi_tuning *tu)
-{
-    Tuning t;
-    auto look = [tu](const char *name) -> const char * {
-        if (tu) {
-            auto it = tu->kv.find(name);
-            return it == tu->kv.end() ? nullptr : it->second.c_str();
-        }
-        return genphi::env_hook(name);
-    };
-    auto geti = [&](const char *name, int dflt) { const char *e = look(name); return e ? std::atoi(e) : dflt; };
-    auto has = [&](const char *name) { return look(name) != nullptr; };
-    t.lds_cap_floats = geti("GENPHI_LDS_CAP_FLOATS", 0);
-    t.full_max_floats = geti("GENPHI_FULL_MAX_FLOATS", -1);
-    t.no_stay = geti("GENPHI_NO_STAY", 0) != 0;
-    t.stay_max_slots = geti("GENPHI_STAY_MAX_SLOTS", 0);
-    t.stay_headroom = geti("GENPHI_STAY_HEADROOM", -1);
-    t.stay_mem_pct = geti("GENPHI_STAY_MEM_PCT", 0);
-    t.stay_scatter = geti("GENPHI_STAY_SCATTER", 0) != 0;
-    t.stay_two_pass = geti("GENPHI_STAY_TWO_PASS", 0) != 0;
-    t.stay_col_fastest = geti("GENPHI_STAY_COL_FASTEST", 0) != 0;
-    t.stay_scalar_t = geti("GENPHI_STAY_SCALAR_T", 0) != 0;
-    { const int v = geti("GENPHI_STAY_TILE", 0); t.stay_tile = v == 128 ? 128 : (v == 256 ? 256 : 0); }
-    t.stay_slack_pct = geti("GENPHI_STAY_SLACK_PCT", -1);
-    t.stay_min_ratio_pct = geti("GENPHI_STAY_MIN_RATIO_PCT", -1);
-    t.stay_narrow = geti("GENPHI_STAY_NARROW", -1);
-    t.stay_narrow_min = geti("GENPHI_STAY_NARROW_MIN", -1);
-    t.stay_overhead_k = geti("GENPHI_STAY_OVERHEAD_K", -1);
-    t.stay_last = geti("GENPHI_STAY_LAST", -1);
-    t.colperm_plain = has("GENPHI_COLPERM_PLAIN");
-    t.stay_family = geti("GENPHI_STAY_FAMILY", -1);
-    t.max_group = std::max(1, geti("GENPHI_MAX_GROUP", 8));
-    t.max_run = std::max(1, geti("GENPHI_MAX_RUN", 1));
-    t.full_bs = geti("GENPHI_FULL_BS", 0);
-    t.no_identity = has("GENPHI_NO_IDENTITY");
-    t.cert_min_exp = geti("GENPHI_CERT_MIN_EXP", -27);
-    t.dbg_step = geti("GENPHI_DBG_STEP", -1);
-    t.no_fast = has("GENPHI_NO_FAST");
-    t.max_cpt = geti("GENPHI_MAX_CPT", 0);
-    t.fast_nt = geti("GENPHI_FAST_NT", 0);
-    if (const char *e = look("GENPHI_WIDE_ROUTE")) t.wide_route = (e[0] == 'B' || e[0] == 'b') ? 'B' : 'A';
-    t.tt_noalign = has("GENPHI_TT_NOALIGN");
-    t.no_shard_prune = has("GENPHI_NO_SHARD_PRUNE");
-    if (const char *e = look("GENPHI_SHARD_FORCE")) {
-        int fs = -1, fr = -1;
-        if (std::sscanf(e, "%d:%d", &fs, &fr) == 2) { t.shard_force_step = fs; t.shard_force_row = fr; }
-    }
-    t.shard_prune_min_step = geti("GENPHI_SHARD_PRUNE_MIN_STEP", 0);
-    t.no_small = has("GENPHI_NO_SMALL");
-    t.no_graph = has("GENPHI_NO_GRAPH");
-    t.res.d2h_threads = geti("GENPHI_D2H_THREADS", 0);
-    t.res.d2h_pageable = has("GENPHI_D2H_PAGEABLE");
-    t.res.d2h_sym = geti("GENPHI_D2H_SYM", -1);
-    if (const char *e = look("GENPHI_D2H_TILE")) {
-        int r = 0, c = 0;
-        if (std::sscanf(e, "%dx%d", &r, &c) == 2 && r >= 1 && c >= 1) { t.res.d2h_tile_rows = r; t.res.d2h_tile_cols = c; }
-    }
-    t.fail_alloc_at = geti("GENPHI_TEST_FAIL_ALLOC", 0);
-    t.sparse_k = geti("GENPHI_SPARSE_K", -2);
-    t.sparse_permille = geti("GENPHI_SPARSE_PERMILLE", -1);
-    t.sparse_min_cut = geti("GENPHI_SPARSE_MIN_CUT", -1);
-    t.sparse_chunk = geti("GENPHI_SPARSE_CHUNK", 0);
-    t.sparse_classes = geti("GENPHI_SPARSE_CLASSES", -1);
-    t.res.d2h_chunk_mb = geti("GENPHI_D2H_CHUNK_MB", 0);
-    t.sparse_batch = geti("GENPHI_SPARSE_BATCH", 0);
-    t.sparse_arena = geti("GENPHI_SPARSE_ARENA", 0);
-    t.res.boot_panel = std::max(0, geti("GENPHI_BOOT_PANEL", 0));
-    t.res.nearest_buf = genphi::nearest_buf_entries(geti("GENPHI_NEAREST_BUF", 0));
-    return t;
-}
-
 // Work lists of a SPLIT launch: the hub walk of planner.h (WalkLists) as device arrays.
 //   desc : per work row (storage row, output row, B source, rank word)
 //   seg  : per segment (first work row, hub row, leading rows without B source, type) + terminators
@@ -2294,22 +2154,8 @@ static int plan_create_impl(int64_t n_ind, const int64_t *ind, const int64_t *fa
     *out = nullptr;
     genphi_plan *p = new (std::nothrow) genphi_plan();
     if (!p) return fail(GENPHI_ERR_ALLOC, "out of memory");
-    p->tun = tuning_from(tuning);
-    p->popt.indices_only = indices_only;
-    if (p->tun.lds_cap_floats >= 16) p->popt.lds_cap_floats = p->tun.lds_cap_floats;
-    if (p->tun.full_max_floats >= 0) p->popt.full_max_floats = p->tun.full_max_floats;
-    p->popt.no_stay = p->tun.no_stay;
-    p->popt.stay_scatter = p->tun.stay_scatter;
-    if (p->tun.stay_slack_pct >= 0) p->popt.stay_slack_pct = p->tun.stay_slack_pct;
-    if (p->tun.stay_min_ratio_pct >= 0) p->popt.stay_min_ratio_pct = p->tun.stay_min_ratio_pct;
-    if (p->tun.stay_max_slots > 0) p->popt.stay_max_slots = p->tun.stay_max_slots;
-    if (p->tun.stay_narrow >= 0) { p->popt.stay_narrow = p->tun.stay_narrow != 0; p->popt.stay_narrow_force = p->tun.stay_narrow == 2; }
-    if (p->tun.stay_narrow_min >= 0) p->popt.stay_narrow_min = p->tun.stay_narrow_min;
-    if (p->tun.stay_overhead_k >= 0) p->popt.stay_step_overhead = 1000.0 * p->tun.stay_overhead_k;
-    if (p->tun.stay_last >= 0) p->popt.stay_last = p->tun.stay_last != 0;
-    if (p->tun.stay_family >= 0) p->popt.stay_family_order = p->tun.stay_family != 0;
-    if (p->tun.stay_headroom >= 0) p->popt.stay_headroom = p->tun.stay_headroom;
-    if (p->tun.stay_mem_pct > 0) { p->popt.stay_mem_ratio = p->tun.stay_mem_pct / 100.0; p->popt.stay_mem_floor_bytes = 0.0; }   // (an explicit share is taken literally)
+    p->tun = genphi::tuning_from(tuning);
+    p->popt = genphi::plan_options_from(p->tun, indices_only);
     std::string err;
     int rc;
     try {
@@ -2335,8 +2181,7 @@ int genphi_tuning_set(genphi_tuning *t, const char *name, const char *value)
 {
     if (!t || !name || !value) return fail(GENPHI_ERR_ARG, "genphi_tuning_set: null argument");
     std::string key = std::strncmp(name, "GENPHI_", 7) == 0 ? name : std::string("GENPHI_") + name;
-    for (const char *k : kTuningNames)
-        if (key == k) { t->kv[key] = value; return GENPHI_OK; }
+    if (genphi::tuning_knows(key)) { t->kv[key] = value; return GENPHI_OK; }
     return fail(GENPHI_ERR_ARG, "genphi_tuning_set: unknown setting " + key);
 }
 int genphi_plan_create_tuned(int64_t n_ind, const int64_t *ind, const int64_t *father, const int64_t *mother,
@@ -2770,24 +2615,14 @@ template <bool O>
 static hipError_t launch_split(int cpt, int stg, int grid, size_t lds, hipStream_t stream, const LevelArgs &a,
                                const int4 *desc, const int4 *grp, int *queue)
 {
-#define GENPHI_T(C, S) if (cpt <= C && stg == S) return launch_split_inst<C, S, O>(grid, lds, stream, a, desc, grp, queue)
-#ifdef GENPHI_MIN_INST
-    GENPHI_T(16, 2); GENPHI_T(20, 8);
-#else
-    GENPHI_T(8, 2); GENPHI_T(16, 2); GENPHI_T(24, 2);
-    GENPHI_T(8, 4); GENPHI_T(16, 4); GENPHI_T(24, 4);
-    GENPHI_T(8, 6); GENPHI_T(16, 6); GENPHI_T(20, 6); if constexpr (O) { GENPHI_T(24, 6); }
-    GENPHI_T(8, 7); GENPHI_T(16, 7); GENPHI_T(20, 7); if constexpr (O) { GENPHI_T(24, 7); }
-    GENPHI_T(8, 8); GENPHI_T(16, 8); GENPHI_T(20, 8);
-    GENPHI_T(8, 9); GENPHI_T(16, 9);
-#endif
+    // (the list and its order: row_geometry.h)
+#define GENPHI_T(C, S, ORD_ONLY) \
+    if constexpr (O || !ORD_ONLY) { if (cpt <= C && stg == S) return launch_split_inst<C, S, O>(grid, lds, stream, a, desc, grp, queue); }
+    GENPHI_SPLIT_INSTS(GENPHI_T)
 #undef GENPHI_T
     return hipErrorInvalidValue;
 }
 
-// certified-rows kernel: 1024-thread workgroups (4 waves per SIMD, 128 VGPRs) or 512-thread ones
-// (2 waves per SIMD, 256 VGPRs: the per-thread overhead is paid half as often, so a workgroup
-// holds ~25 % more columns -- 4 column chunks instead of 5 for the 1e5-wide final level of cfg4)
 template <int NT, int C, int S, bool CERT, bool CHAIN>
 static hipError_t launch_fast_inst(int grid, size_t lds, hipStream_t stream, const LevelArgs &a, const int4 *desc,
                                    const int4 *grp, const int4 *run, int *queue)
@@ -2798,67 +2633,19 @@ static hipError_t launch_fast_inst(int grid, size_t lds, hipStream_t stream, con
     return hipGetLastError();
 }
 
-// columns per thread the instantiations of the certified-rows kernel afford without spilling
-// (checked with -Rpass-analysis=kernel-resource-usage: 0 scratch in every one)
-static int fast_max_cpt(int nt, int stg)
-{
-    if (nt == 1024) return stg <= 4 ? 28 : (stg <= 8 ? 24 : 20);
-    return stg <= 12 ? 52 : (stg <= 16 ? 56 : 48);
-}
-
 template <bool CERT, bool CHAIN>
 static hipError_t launch_fast(int nt, int cpt, int stg, int grid, size_t lds, hipStream_t stream, const LevelArgs &a,
                               const int4 *desc, const int4 *grp, const int4 *run, int *queue)
 {
-#define GENPHI_F(N, C, S) if (nt == N && cpt <= C && stg == S) return launch_fast_inst<N, C, S, CERT, CHAIN>(grid, lds, stream, a, desc, grp, run, queue)
-#ifdef GENPHI_MIN_INST
-    GENPHI_F(1024, 16, 2); GENPHI_F(1024, 24, 8); GENPHI_F(512, 56, 16);
-#else
-    GENPHI_F(1024, 8, 2); GENPHI_F(1024, 16, 2); GENPHI_F(1024, 28, 2);
-    GENPHI_F(1024, 8, 4); GENPHI_F(1024, 16, 4); GENPHI_F(1024, 28, 4);
-    GENPHI_F(1024, 8, 6); GENPHI_F(1024, 16, 6); GENPHI_F(1024, 24, 6);
-    GENPHI_F(1024, 8, 7); GENPHI_F(1024, 16, 7); GENPHI_F(1024, 24, 7);
-    GENPHI_F(1024, 8, 8); GENPHI_F(1024, 16, 8); GENPHI_F(1024, 24, 8);
-    GENPHI_F(1024, 8, 9); GENPHI_F(1024, 20, 9);
-    GENPHI_F(512, 32, 12); GENPHI_F(512, 48, 12); GENPHI_F(512, 52, 12);
-    GENPHI_F(512, 32, 14); GENPHI_F(512, 56, 14);
-    GENPHI_F(512, 32, 16); GENPHI_F(512, 52, 16); GENPHI_F(512, 56, 16);
-    GENPHI_F(512, 32, 18); GENPHI_F(512, 48, 18);
-#endif
+#define GENPHI_F(N, C, S) if (nt == N && cpt <= C && stg == S) return launch_fast_inst<N, C, S, CERT, CHAIN>(grid, lds, stream, a, desc, grp, run, queue);
+    GENPHI_FAST_INSTS(GENPHI_F)
 #undef GENPHI_F
     return hipErrorInvalidValue;
-}
-
-static int block_size_for(int64_t n, const Tuning &tun)
-{
-    {
-        const int v = tun.full_bs;
-        if (v == 64 || v == 128 || v == 256 || v == 512 || v == 1024) return v;
-    }
-    if (n <= 512) return 64;
-    if (n <= 2048) return 256;
-    return 512;       // 4 workgroups per CU overlap staging and gathers; 1024 threads measured 20 % slower (cfg3)
 }
 
 // level step 0 reads Psi_1 = 1/2 I: level_identity_kernel computes it from the indices alone
 // (GENPHI_NO_IDENTITY: test hook, the regular kernels on a materialised 1/2 I)
 static bool identity_source(int step, const Tuning &tun) { return step == 0 && !tun.no_identity; }
-
-// item / n_chunks as a multiply-high: exact for item < 2^32 / n_chunks (items are < 2^31 and n_chunks
-// is a handful); n_chunks == 1 has no 32-bit magic number and is flagged by 0
-static unsigned chunk_magic_for(int n_chunks)
-{
-    return n_chunks <= 1 ? 0u : 0xffffffffu / static_cast<unsigned>(n_chunks) + 1u;
-}
-
-// bits(2^-27) - 1: entries below 2^-27 (other than 0) void a row's exactness certificate.  Test hook:
-// GENPHI_CERT_MIN_EXP = e in [-27, 0] raises the bound to 2^e (always safe: fewer rows certified),
-// which makes mixed certified / uncertified levels out of ordinary small pedigrees.
-static unsigned cert_threshold(const Tuning &tun)
-{
-    const int e = std::max(-27, std::min(0, tun.cert_min_exp));
-    return (static_cast<unsigned>(127 + e) << 23) - 1u;
-}
 
 // What a level launch works on: a step of the plan, or the new x new sub-step of a WIDE step.
 struct LevelCtx {
@@ -2922,97 +2709,55 @@ struct LaunchRes {
 static int launch_rows(const LaunchRes &R, LevelArgs a, int mode, bool pos_ord, int64_t src_width, int64_t width, int kernel,
                        const DeviceGroups &dg)
 {
-    const int n_rows = a.n_rows;
-    const int lds_row = static_cast<int>((src_width + 3) / 4 * 4);
     if (mode == genphi::kModeFull) {
-        a.lds_row = lds_row;
-        const size_t lds = 2 * static_cast<size_t>(lds_row) * sizeof(float);
-        const int bs = block_size_for(std::max<int64_t>(a.n, src_width), *R.tun);
+        const genphi::FullGeometry g = genphi::full_geometry(src_width, a.n, a.n_rows, a.zero_row, *R.tun);
+        const size_t lds = g.lds_bytes;
+        a.lds_row = g.lds_row;
         if (pos_ord) {
             HIP_TRY(set_max_lds(reinterpret_cast<const void *>(level_full_kernel<4, true>), lds));
-            hipLaunchKernelGGL((level_full_kernel<4, true>), dim3(n_rows + a.zero_row), dim3(bs), lds, R.stream, a);
+            hipLaunchKernelGGL((level_full_kernel<4, true>), dim3(g.grid), dim3(g.block), lds, R.stream, a);
         } else {
             HIP_TRY(set_max_lds(reinterpret_cast<const void *>(level_full_kernel<4, false>), lds));
-            hipLaunchKernelGGL((level_full_kernel<4, false>), dim3(n_rows + a.zero_row), dim3(bs), lds, R.stream, a);
+            hipLaunchKernelGGL((level_full_kernel<4, false>), dim3(g.grid), dim3(g.block), lds, R.stream, a);
         }
     } else if (mode == genphi::kModeSplit) {
-        a.lds_row = lds_row;
-        const int per_row4 = lds_row / 4;                                // float4 per staged row
-        const int stg1k = (per_row4 + 1023) / 1024;
-        // staging instantiations; the planner keeps lds_row <= 36864 floats (9 * 1024 float4 + the queue slots <= 160 KB)
-        const int stg_inst = stg1k <= 2 ? 2 : (stg1k <= 4 ? 4 : (stg1k <= 6 ? 6 : (stg1k <= 7 ? 7 : (stg1k <= 8 ? 8 : 9))));
-        const bool no_fast = R.tun->no_fast;                                    // test / A-B hook: grouping-exact kernel only
-        const bool certs = !no_fast && kernel == 0;
+        const genphi::SplitGeometry g = genphi::split_geometry(src_width, width, pos_ord, kernel, a.cert_out != nullptr, R.n_cus, dg.n_segs,
+                                                               dg.n_runs, *R.tun, GENPHI_WG_TIMES != 0);
+        auto chunks_of = [](LevelArgs &l, const genphi::ChunkGeometry &c) {
+            l.slot_off = c.slot_off; l.chunk_cols = c.chunk_cols; l.n_chunks = c.n_chunks; l.chunk_magic = c.chunk_magic;
+        };
+        a.lds_row = g.lds_row;
         int *queue = R.queue;                                                 // zeroed at the start of the sweep
         int *gcnt = R.gcnt;
-        // geometry of the grouping-exact kernel (1024 threads)
-        constexpr int nt_s = 1024;
-        // LDS must also absorb the unconditional over-write past the row's end
-        const size_t lds_stage_s = std::max(static_cast<size_t>(lds_row) * sizeof(float), static_cast<size_t>(stg_inst) * nt_s * 16);
-        const size_t lds = lds_stage_s + 32 + (GENPHI_WG_TIMES ? 128 : 0);
-        const int per_thread = static_cast<int>((width + nt_s - 1) / nt_s);     // the padding columns [n, ld) are written too
-        // register budget of the instantiations (all spill-free: a spill stalls the pipeline)
-        int max_cpt;
-        if (pos_ord) max_cpt = stg_inst <= 7 ? 24 : (stg_inst == 8 ? 20 : 16);
-        else           max_cpt = stg_inst <= 4 ? 24 : (stg_inst <= 8 ? 20 : 16);
-        const int env_cpt = R.tun->max_cpt;                                     // tuning hook: smaller chunks
-        if (env_cpt >= 4) max_cpt = std::min(max_cpt, env_cpt / 4 * 4);
-        const int n_chunks = (per_thread + max_cpt - 1) / max_cpt;
-        const int cpt = (per_thread + n_chunks - 1) / n_chunks;
-        const long long n_items = static_cast<long long>(dg.n_segs) * n_chunks;
-        if (certs) {
+        if (g.certs) {
             // ---- certified groups: level_split_fast_kernel ----
-            LevelArgs f = a;
-            int f_nt = 1024, f_chunks = 1 << 30, f_stg = stg_inst;
-            const int force_nt = R.tun->fast_nt;                                // test / tuning hook
-            for (int nt : {1024, 512}) {
-                if (force_nt && nt != force_nt) continue;
-                int stg = (per_row4 + nt - 1) / nt;
-                if (nt == 512) stg = stg <= 12 ? 12 : (stg <= 14 ? 14 : (stg <= 16 ? 16 : 18)); else stg = stg_inst;
-                const int pt = static_cast<int>((width + nt - 1) / nt);
-                int mc = fast_max_cpt(nt, stg);
-                if (env_cpt >= 4) mc = std::min(mc, env_cpt * (1024 / nt) / 4 * 4);
-                const int nch = (pt + mc - 1) / mc;
-                if (nch < f_chunks) { f_chunks = nch; f_nt = nt; f_stg = stg; }
-            }
-            const int f_pt = static_cast<int>((width + f_nt - 1) / f_nt);
-            const int f_cpt = ((f_pt + f_chunks - 1) / f_chunks + 3) / 4 * 4;
-            const long long f_items = static_cast<long long>(dg.n_runs) * f_chunks;
             // certified runs -> glist_f / gcnt[0], the segments of the others -> glist_s / gcnt[1]: decided on the device, per launch
-            int *glist_f = R.glist_f, *glist_s = R.glist_s;
-            int *gcnt_s = gcnt;                                               // [1] = segments of the grouping-exact kernel
             hipLaunchKernelGGL(group_split_kernel, dim3((dg.n_runs + kSplitRuns - 1) / kSplitRuns), dim3(256), 0, R.stream, dg.desc, dg.seg, dg.run, dg.n_runs,
-                               a.cert_prev, glist_f, glist_s, gcnt);
+                               a.cert_prev, R.glist_f, R.glist_s, gcnt);
             HIP_TRY(hipGetLastError());
-            f.glist = glist_f; f.gcnt = gcnt;
-            f.chunk_magic = chunk_magic_for(f_chunks);
-            const size_t f_lds_stage = std::max(static_cast<size_t>(lds_row) * sizeof(float), static_cast<size_t>(f_stg) * f_nt * 16);
-            f.slot_off = static_cast<int>(f_lds_stage / sizeof(float));
-            f.chunk_cols = f_cpt * f_nt;
-            f.n_chunks = f_chunks;
+            const genphi::ChunkGeometry &c = g.fast;
+            LevelArgs f = a;
+            f.glist = R.glist_f; f.gcnt = gcnt;
+            chunks_of(f, c);
             f.n_groups = dg.n_runs;
-            const int f_grid = static_cast<int>(std::min<long long>(R.n_cus, (f_items + 7) / 8 * 8));
-            // (the run lists hold chain steps only under GENPHI_MAX_RUN > 1: the default instantiation carries none of that state)
             hipError_t fe;
-            if (R.tun->max_run > 1)
-                fe = f.cert_out ? launch_fast<true, true>(f_nt, f_cpt, f_stg, f_grid, f_lds_stage + 32, R.stream, f, dg.desc, dg.seg, dg.run, queue)
-                                : launch_fast<false, true>(f_nt, f_cpt, f_stg, f_grid, f_lds_stage + 32, R.stream, f, dg.desc, dg.seg, dg.run, queue);
+            if (g.chain)
+                fe = g.cert ? launch_fast<true, true>(c.nt, c.cpt, c.stg, c.grid, c.lds_bytes, R.stream, f, dg.desc, dg.seg, dg.run, queue)
+                            : launch_fast<false, true>(c.nt, c.cpt, c.stg, c.grid, c.lds_bytes, R.stream, f, dg.desc, dg.seg, dg.run, queue);
             else
-                fe = f.cert_out ? launch_fast<true, false>(f_nt, f_cpt, f_stg, f_grid, f_lds_stage + 32, R.stream, f, dg.desc, dg.seg, dg.run, queue)
-                                : launch_fast<false, false>(f_nt, f_cpt, f_stg, f_grid, f_lds_stage + 32, R.stream, f, dg.desc, dg.seg, dg.run, queue);
+                fe = g.cert ? launch_fast<true, false>(c.nt, c.cpt, c.stg, c.grid, c.lds_bytes, R.stream, f, dg.desc, dg.seg, dg.run, queue)
+                            : launch_fast<false, false>(c.nt, c.cpt, c.stg, c.grid, c.lds_bytes, R.stream, f, dg.desc, dg.seg, dg.run, queue);
             HIP_TRY(fe);
             a.zero_row = 0;                                                   // the fast launch wrote the "none" row
-            a.glist = glist_s; a.gcnt = gcnt_s;
+            a.glist = R.glist_s; a.gcnt = gcnt;                               // [1] = segments of the grouping-exact kernel
         }
         // ---- the other groups (all of them without certificates): level_split_kernel ----
-        a.slot_off = static_cast<int>(lds_stage_s / sizeof(float));
-        a.chunk_cols = (cpt + 3) / 4 * 4 * nt_s;                        // whole quads of columns per thread
-        a.n_chunks = n_chunks;
-        a.chunk_magic = chunk_magic_for(n_chunks);
+        const genphi::ChunkGeometry &c = g.exact;
+        chunks_of(a, c);
         a.n_groups = dg.n_segs;
-        const int grid = static_cast<int>(std::min<long long>(R.n_cus, (n_items + 7) / 8 * 8));   // persistent: one workgroup per CU
-        HIP_TRY(pos_ord ? launch_split<true>(cpt, stg_inst, grid, lds, R.stream, a, dg.desc, dg.seg, queue + 8)
-                          : launch_split<false>(cpt, stg_inst, grid, lds, R.stream, a, dg.desc, dg.seg, queue + 8));
+        HIP_TRY_AS("pos_ord ? launch_split<true>(cpt, stg_inst, grid, lds, R.stream, a, dg.desc, dg.seg, queue + 8) : launch_split<false>(cpt, stg_inst, grid, lds, R.stream, a, dg.desc, dg.seg, queue + 8)",
+                   pos_ord ? launch_split<true>(c.cpt, c.stg, c.grid, c.lds_bytes, R.stream, a, dg.desc, dg.seg, queue + 8)
+                           : launch_split<false>(c.cpt, c.stg, c.grid, c.lds_bytes, R.stream, a, dg.desc, dg.seg, queue + 8));
     } else {
         return fail(GENPHI_ERR_ARG, "internal: launch_rows takes FULL and SPLIT steps");
     }
@@ -3068,28 +2813,10 @@ static int launch_level(genphi_plan *p, const LevelCtx &cx, const float *psi, fl
 }
 
 // ---- column panels (panel_phi.hip): a level step of a rank's panel through the same row kernels -------------
-const void *genphi::panel_tuning_create() { return new (std::nothrow) Tuning(tuning_from(nullptr)); }
-void genphi::panel_tuning_destroy(const void *t) { delete static_cast<const Tuning *>(t); }
-int genphi::panel_tuning_lds_cap(const void *t, int dflt)
-{
-    const Tuning *u = static_cast<const Tuning *>(t);
-    return (u && u->lds_cap_floats >= 16) ? u->lds_cap_floats : dflt;
-}
-int genphi::panel_tuning_full_max(const void *t, int dflt)
-{
-    const Tuning *u = static_cast<const Tuning *>(t);
-    return (u && u->full_max_floats >= 0) ? u->full_max_floats : dflt;
-}
-unsigned genphi::panel_tuning_cert_thresh(const void *t)
-{
-    static const Tuning dflt;
-    return cert_threshold(t ? *static_cast<const Tuning *>(t) : dflt);
-}
-
 int genphi::launch_panel_level(const PanelLaunch &L)
 {
     static const Tuning dflt;
-    const Tuning &tun = L.tuning ? *static_cast<const Tuning *>(L.tuning) : dflt;
+    const Tuning &tun = L.tuning ? *L.tuning : dflt;
     LevelArgs a;
     std::memset(&a, 0, sizeof(a));
     a.psi = L.psi; a.out = L.out; a.ld_prev = L.ld_prev; a.ld = L.ld; a.width = static_cast<int>(L.ld);
@@ -3299,16 +3026,8 @@ static int ensure_sparse_levels(genphi_plan *p, int kernel, PhaseTrace &trace)
         for (int s = 0; s < S; ++s)
             dev[s] = genphi::SparseStepDev{p->dsteps[s].srcA, p->dsteps[s].srcB, p->dsteps[s].ord,
                                            static_cast<int64_t>(pl.steps[s].work.size()) == pl.steps[s].n ? p->dsteps[s].work : nullptr};
-        genphi::SparseTuning stn;
-        stn.force_k = p->tun.sparse_k;
-        if (p->tun.sparse_permille > 0) stn.max_permille = p->tun.sparse_permille;
-        if (p->tun.sparse_min_cut >= 0) stn.min_cut = p->tun.sparse_min_cut;
-        if (p->tun.sparse_chunk > 0) stn.chunk_cols = p->tun.sparse_chunk;
-        stn.classes = p->tun.sparse_classes;
-        if (p->tun.sparse_batch == 4 || p->tun.sparse_batch == 8) stn.long_batch = p->tun.sparse_batch;
-        if (p->tun.sparse_arena > 0) stn.first_entries = p->tun.sparse_arena;
         std::string serr;
-        p->sparse = genphi::sparse_levels_create(pl, S, dev, stn, p->stream, serr);
+        p->sparse = genphi::sparse_levels_create(pl, S, dev, genphi::sparse_tuning_from(p->tun), p->stream, serr);
         if (p->sparse) {
             const int rc = genphi::sparse_levels_calibrate(p->sparse, p->stream, serr);
             if (rc) return fail(rc, "sparse levels: " + serr);

@@ -7,6 +7,8 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "tuning.h"
+
 namespace genphi {
 
 constexpr size_t kPanelIdxPad = 32 * 1024;     // padding entries behind pk_col / ord_col (the row kernels read whole quads past the end)
@@ -16,7 +18,7 @@ constexpr int kPanelSplitMaxFloats = 36864;    // ... up to this: SPLIT (one sou
 struct PanelLaunch {
     hipStream_t stream;
     int n_cus;
-    const void *tuning;          // panel_tuning_create()
+    const Tuning *tuning;        // the handle's hooks (nullptr: the defaults)
     const float *psi;            // extended local panel of the previous cut: (n_prev + 1) rows x ld_prev
     float *out;                  // local panel of this cut: (n_cut + 1) rows x ld
     long long ld_prev, ld;
@@ -41,11 +43,6 @@ struct PanelLaunch {
     int glist_cap;
 };
 
-const void *panel_tuning_create();               // environment hooks, read once per panel handle
-void panel_tuning_destroy(const void *t);
-int panel_tuning_lds_cap(const void *t, int dflt);        // GENPHI_LDS_CAP_FLOATS (>= 16) or dflt
-int panel_tuning_full_max(const void *t, int dflt);       // GENPHI_FULL_MAX_FLOATS (>= 0) or dflt
-unsigned panel_tuning_cert_thresh(const void *t);         // certificate threshold word (GENPHI_CERT_MIN_EXP raises it)
 int launch_panel_level(const PanelLaunch &L);    // GENPHI_OK or an error code (message in genphi_last_error)
 
 }  // namespace genphi

@@ -184,7 +184,7 @@ struct genphi_panel {
     // device
     bool on_device = false;
     int device = -1;
-    int fail_alloc_at = 0, alloc_count = 0;    // GENPHI_TEST_FAIL_ALLOC (read once in genphi_panel_create): the k-th device allocation fails
+    int alloc_count = 0;                       // device allocations so far (Tuning::fail_alloc_at: the k-th fails)
     hipStream_t stream = nullptr;
     float *panel[2] = {nullptr, nullptr};
     size_t panel_floats[2] = {0, 0};
@@ -195,7 +195,7 @@ struct genphi_panel {
     int *d_cert[2] = {nullptr, nullptr};       // exactness certificates of the rows of panel[0] / panel[1]
     int *d_counters = nullptr, *d_glist = nullptr;
     int glist_cap = 0, n_cus = 256;
-    const void *tuning = nullptr;              // environment hooks (panel_tuning_create)
+    genphi::Tuning tuning;                     // environment hooks, read once in genphi_panel_create
     bool naive = false;                        // GENPHI_PANEL_NAIVE: per-entry kernel on every step (A/B, tests)
     std::vector<hipEvent_t> ev;                // two per level step: around the step's kernels (unpack + level) of the last sweep
     hipEvent_t ev_x[2] = {nullptr, nullptr};   // ordering with the caller's stream: [0] packed columns complete, [1] received columns complete
@@ -251,9 +251,8 @@ int genphi_panel_create(int64_t n_ind, const int64_t *ind, const int64_t *father
     } catch (const std::bad_alloc &) { delete p; return genphi_set_error(GENPHI_ERR_ALLOC, "out of memory while planning"); }
     if (rc) { delete p; return genphi_set_error(rc, err); }
     p->rank = rank; p->world = world;
-    if (const char *e = genphi::env_hook("GENPHI_TEST_FAIL_ALLOC")) p->fail_alloc_at = std::atoi(e);
+    p->tuning = genphi::tuning_from(nullptr);
     p->naive = genphi::env_hook("GENPHI_PANEL_NAIVE") != nullptr;
-    p->tuning = genphi::panel_tuning_create();
     const genphi::Plan &pl = p->plan;
     const int L = pl.n_levels;
     const int64_t N = pl.n_pro;
@@ -342,9 +341,9 @@ int genphi_panel_create(int64_t n_ind, const int64_t *ind, const int64_t *father
         }
         // ---- the same step for the row kernels: a source "row" is a row of the extended panel (zcol + 1 floats) ----
         ps.src_width = zcol + 1;
-        // (test hooks, as for plans: read once per handle, in panel_tuning_create)
-        const int lds_cap = genphi::panel_tuning_lds_cap(p->tuning, genphi::kPanelSplitMaxFloats);
-        const int full_max = genphi::panel_tuning_full_max(p->tuning, genphi::kPanelFullMaxFloats);
+        // (test hooks, as for plans: read once per handle)
+        const int lds_cap = p->tuning.lds_cap_floats >= 16 ? p->tuning.lds_cap_floats : genphi::kPanelSplitMaxFloats;
+        const int full_max = p->tuning.full_max_floats >= 0 ? p->tuning.full_max_floats : genphi::kPanelFullMaxFloats;
         const int row4 = (ps.src_width + 3) / 4 * 4;
         ps.mode = p->naive ? 2 : (2 * row4 <= lds_cap && row4 <= full_max ? 0 : (row4 <= lds_cap && zcol < 65536 ? 1 : 2));
         if (ps.mode != 2) {
@@ -463,7 +462,7 @@ static int panel_upload_impl(genphi_panel *p, int device)
     const genphi::Plan &pl = p->plan;
     const int L = pl.n_levels;
     auto pmalloc = [&](void **dst, size_t bytes) -> hipError_t {
-        if (p->fail_alloc_at > 0 && ++p->alloc_count == p->fail_alloc_at) return hipErrorOutOfMemory;
+        if (p->tuning.fail_alloc_at > 0 && ++p->alloc_count == p->tuning.fail_alloc_at) return hipErrorOutOfMemory;
         return hipMalloc(dst, bytes);
     };
     size_t need[2] = {0, 0};
@@ -630,7 +629,7 @@ static int panel_compute_impl(genphi_panel *p, int32_t step, const float *d_recv
         if (!d_recv) return genphi_set_error(GENPHI_ERR_ARG, "genphi_panel_compute: d_recv is NULL");
         dim3 grid(static_cast<unsigned>((ps.n_ext + 63) / 64), static_cast<unsigned>((n_prev + 63) / 64));
         hipLaunchKernelGGL(panel_unpack_kernel, grid, dim3(256), 0, p->stream, psi, ldp, n_prev, n_own, ps.n_ext, d_recv,
-                           p->d_cert[step & 1], genphi::panel_tuning_cert_thresh(p->tuning));
+                           p->d_cert[step & 1], genphi::cert_threshold(p->tuning));
         PN_TRY(hipGetLastError());
     }
     const bool last = step + 1 == static_cast<int32_t>(p->steps.size());
@@ -643,7 +642,7 @@ static int panel_compute_impl(genphi_panel *p, int32_t step, const float *d_recv
         // the FULL / SPLIT row kernels over this rank's local columns (panel_launch.h)
         const DevPanelStep &d = p->d_step[step];
         genphi::PanelLaunch L;
-        L.stream = p->stream; L.n_cus = p->n_cus; L.tuning = p->tuning;
+        L.stream = p->stream; L.n_cus = p->n_cus; L.tuning = &p->tuning;
         L.psi = psi; L.out = out; L.ld_prev = ldp; L.ld = ldo;
         L.n_prev = n_prev; L.n_cut = n; L.n_cols = ps.n_cols; L.src_width = ps.src_width;
         L.srcA = p->d_srcA[step]; L.srcB = p->d_srcB[step]; L.ord = p->d_ord[step];
@@ -717,7 +716,6 @@ void genphi_panel_destroy(genphi_panel *p)
 {
     if (!p) return;
     panel_free_device(p);
-    genphi::panel_tuning_destroy(p->tuning);
     delete p;
 }
 

@@ -9,33 +9,11 @@
 #include <vector>
 
 #include "../../include/genphi.h"
+#include "tuning.h"      // ResultTuning, nearest_buf_entries
 
 int genphi_set_error(int code, const std::string &msg);      // genphi_hip.hip
 
 namespace genphi {
-
-// keys of the LDS buffer of nearest_kernel (GENPHI_NEAREST_BUF): powers of two, >= 2 x GENPHI_NEAREST_MAX_K
-constexpr int kNearBufMin = 128, kNearBufMax = 4096, kNearBufDefault = 1024;
-// the buffer a plan uses: the hook's value clamped to [kNearBufMin, kNearBufMax] and rounded down to a power of two
-inline int nearest_buf_entries(int hook)
-{
-    if (hook <= 0) return kNearBufDefault;
-    int b = kNearBufMin;
-    while (b * 2 <= (hook < kNearBufMax ? hook : kNearBufMax)) b *= 2;
-    return b;
-}
-
-// The hooks the queries read (README.md, "Environment hooks"); tuning_from in genphi_hip.hip fills them when the plan is created.
-struct ResultTuning {
-    int d2h_threads = 0;           // GENPHI_D2H_THREADS      tuning: worker threads of genphi_result_to_host
-    bool d2h_pageable = false;     // GENPHI_D2H_PAGEABLE     A-B: no pinned staging ring
-    int d2h_sym = -1;              // GENPHI_D2H_SYM          opt-in: 1 = a full result crosses the link as upper-triangle tiles + a host mirror pass (default: every entry is copied)
-    int d2h_tile_rows = 0, d2h_tile_cols = 0;   // GENPHI_D2H_TILE "RxC"  test + tuning: tile of the symmetric copy (default 256 x 8192)
-    int d2h_chunk_mb = 0;          // GENPHI_D2H_CHUNK_MB     tuning: size of a pinned staging chunk of genphi_result_to_host (default 16, 4 for results below 2 GB)
-    int boot_panel = 0;            // GENPHI_BOOT_PANEL       tuning + test: resamples per panel of genphi_result_bootstrap, 1 .. 8192 (default: what keeps a panel's counts within 256 MiB)
-    int nearest_buf = kNearBufDefault;   // GENPHI_NEAREST_BUF     tuning + test: keys of the LDS buffer of genphi_result_nearest, a power of two in [128, 4096] (default 1024; the result
-                                   //                         does not depend on it: tests force 128 so that small inputs cut the buffer on every tile)
-};
 
 struct ResidentView {
     int device, n_cus;

@@ -18,7 +18,7 @@ using genphi::al256;
 using genphi::ResidentView;
 using genphi::kGsMaxGroups;
 using genphi::kGsTile;
-using genphi::kNearBufMin;      // (resident.h, with the clamp that tuning_from applies)
+using genphi::kNearBufMin;      // (tuning.h, with the clamp that tuning_from applies)
 
 namespace {
 

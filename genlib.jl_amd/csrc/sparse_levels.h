@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "planner.h"
+#include "tuning.h"      // SparseTuning
 
 namespace genphi {
 
@@ -36,19 +37,6 @@ constexpr int kSparseMaxMembers = 65535;      // columns are kept as 16-bit word
 struct SparseStepDev {                        // device index arrays of level step s (per member of cut s+1)
     const int *srcA, *srcB, *ord;
     const int *work;                          // the planner's row order of the step (rows that share sources adjacent), or nullptr
-};
-
-struct SparseTuning {
-    int max_permille = 200;    // the calibration run stops at the first cut with more than this share (in 1/1000) of non-zero entries; which
-                               // of the cuts before it is the last sparse one is a matter of estimated times (sparse_levels.hip)
-    int force_k = -2;          // test / A-B hook: -2 = by calibration; -1 = never sparse; k >= 0: cuts 0..k sparse whatever the counts say
-                               // (clamped to what is eligible)
-    int min_cut = 1536;        // ... and only when some cut of the sparse run has at least this many members (narrower levels are launch-bound)
-    int chunk_cols = 12288;    // columns per workgroup of the sparse -> dense step (cfg4, same box: 0.62 ms at 8192, 0.56 at 12288, 0.79 at 4096)
-    int long_batch = 4;        // list entries a thread of a four-wavefront row keeps in flight (4; 8 = A/B hook: measured SLOWER -- genea140's
-                               // largest list steps +12..24 %, cfg3s +22 %, cfg4 the same: r05_ab_sparse_list_step_entries_in_flight_4_vs_8_*.out)
-    int first_entries = 1 << 24;   // entries each row-list arena starts with (128 MB: genea140's and cfg3's lists fit, 11 M and 8.5 M entries); the calibration run enlarges them where a cut needs more (test hook: small values)
-    int classes = -1;          // a launch per class of row lengths: -1 = where the rows of a cut differ much in length, 1 / 0 = always / never (A/B hook)
 };
 
 struct SparseLevels;           // opaque (sparse_levels.hip)

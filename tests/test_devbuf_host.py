@@ -67,7 +67,9 @@ def test_devbuf_against_a_host_cache(san, tmp_path):
 
 
 def test_the_owner_has_no_hip_language_in_it():
-    """devbuf.h and device_sizes.h stay host only: that is what lets the stand-alone checkers build them with g++."""
-    for name, banned in (("devbuf.h", ("<hip/hip_runtime.h>", '#include "devcache.h"', "__global__")), ("device_sizes.h", ("#include <hip", '#include "dev'))):
+    """devbuf.h, device_sizes.h, tuning.h and row_geometry.h stay host only: that is what lets the stand-alone checkers build them with g++."""
+    host_only = ("#include <hip", "__global__", '#include "resident.h"', '#include "sparse_levels.h"', '#include "panel_launch.h"')
+    for name, banned in (("devbuf.h", ("<hip/hip_runtime.h>", '#include "devcache.h"', "__global__")), ("device_sizes.h", ("#include <hip", '#include "dev')),
+                         ("tuning.h", host_only), ("row_geometry.h", host_only)):
         text = open(os.path.join(CSRC, name)).read()
         assert not any(b in text for b in banned), name
