@@ -23,6 +23,7 @@ meaning, printed lines and error behaviour as the reference:
     gen.implex(ped)                        # GENLIB's gen.implex: distinct ancestors by generation (csrc/implex.hip)
     gen.simuSample(ped); gen.simuProb(..)  # GENLIB's gene dropping: marked alleles of ancestors in the probands (csrc/simu.hip)
     gen.descendant(ped, 1); gen.children(ped, 1)   # src/identify.jl:203-215, :77-80 (csrc/loader.cpp)
+    gen.phiHist(ped); gen.phiQuantile(ped, 0.5)    # the distribution of the pairwise kinships, on the device (csrc/hist.hip)
 
 All kinship arithmetic runs in hand-written HIP kernels behind the C-ABI in
 include/genphi.h (csrc/genphi_hip.hip); there is no CPU fallback.
@@ -979,6 +980,147 @@ def phiMatmul(x, X, probandIDs=None, device=None):
     X, one = _capi.as_panel(X, len(m), "X")
     out = m @ X
     return out[:, 0] if one else out
+
+
+class PhiHist:
+    """What gen.phiHist returns: `edges` (float64, bins + 1 of them), `counts` (int64: one per bin, or (groups, groups, bins) and
+    symmetric with `groups`), `below` / `above` (the pairs left of the first and right of the last edge: ints, or (groups, groups)),
+    `n_pairs` (the pairs counted) and, with `groups`, `names` (sorted) and `sizes` (probands per group); both None without."""
+
+    def __init__(self, edges, counts, below, above, n_pairs, names=None, sizes=None):
+        self.edges, self.counts, self.below, self.above, self.n_pairs, self.names, self.sizes = edges, counts, below, above, n_pairs, names, sizes
+
+    def __repr__(self):
+        bins = len(self.edges) - 1
+        head = "PhiHist: %d pairs in %d bins over [%g, %g]" % (self.n_pairs, bins, self.edges[0], self.edges[-1])
+        if self.names is None:
+            total = self.counts
+            lines = [head + ", %d below, %d above" % (self.below, self.above)]
+        else:
+            upper = np.triu(np.ones(self.below.shape, dtype=bool))
+            total = self.counts[upper].sum(axis=0)
+            lines = [head + ", %d groups (%s)" % (len(self.names), ", ".join("%s n=%d" % (n, s) for n, s in zip(self.names, self.sizes)))]
+        for b in np.argsort(-total, kind="stable")[:5]:
+            if total[b]:
+                lines.append("[%g, %g%s %d" % (self.edges[b], self.edges[b + 1], "]" if b == bins - 1 else ")", total[b]))
+        return "\n".join(lines)
+
+
+def _hist_numpy(m, edges, labels=None, n_groups=None):
+    """genphi_result_hist's definition (include/genphi.h) on a square host matrix, in numpy: (counts, below, above)."""
+    n, bins = len(m), len(edges) - 1
+    i, j = np.triu_indices(n, 1)
+    x = m[i, j].astype(np.float64)
+    k = np.searchsorted(edges, x, side="right")                 # 0: below; n_edges: at or above the last edge
+    k = np.where((k == bins + 1) & (x == edges[-1]), bins, k)   # the last bin is closed
+    if labels is None:
+        t = np.bincount(k, minlength=bins + 2).astype(np.int64)
+        return t[1:bins + 1], int(t[0]), int(t[bins + 1])
+    g = int(n_groups)
+    a, b = labels[i].astype(np.int64), labels[j].astype(np.int64)
+    keep = (a >= 0) & (b >= 0)
+    a, b, k = a[keep], b[keep], k[keep]
+    t = np.bincount((a * g + b) * (bins + 2) + k, minlength=g * g * (bins + 2)).astype(np.int64).reshape(g, g, bins + 2)
+    t = t + np.transpose(t, (1, 0, 2)) * (1 - np.eye(g, dtype=np.int64))[:, :, None]
+    return np.ascontiguousarray(t[:, :, 1:bins + 1]), np.ascontiguousarray(t[:, :, 0]), np.ascontiguousarray(t[:, :, bins + 1])
+
+
+def _hist_edges(bins, span):
+    if np.ndim(bins) == 0:
+        nb = int(bins)
+        lo, hi = float(span[0]), float(span[1])
+        if nb < 1 or not lo < hi:
+            raise ValueError("gen.phiHist: bins = %d over the range (%r, %r)" % (nb, lo, hi))
+        edges = np.linspace(lo, hi, nb + 1, dtype=np.float64)
+    else:
+        edges = np.ascontiguousarray(bins, dtype=np.float64)
+    if edges.ndim != 1 or not 2 <= len(edges) <= _capi.GENPHI_HIST_MAX_EDGES:
+        raise ValueError("gen.phiHist: %d edges, need 2 .. %d" % (edges.size, _capi.GENPHI_HIST_MAX_EDGES))
+    if np.isnan(edges).any() or not np.all(edges[:-1] < edges[1:]):
+        raise ValueError("gen.phiHist: the edges must be strictly increasing and not NaN")
+    return edges
+
+
+def phiHist(x, bins=64, range=(0.0, 0.5), groups=None, probandIDs=None, device=None):
+    """The distribution of the pairwise kinships: the histogram of Phi[i, j] over all pairs i < j of probands, and with `groups`
+    within and between sub-populations.  Returns a PhiHist.  Neither GENLIB nor the reference has this function.
+
+    bins: a number of uniform bins over `range` (edges = np.linspace(lo, hi, bins + 1), float64), or the edges themselves; bins are
+    numpy.histogram's (edges[b] <= x < edges[b + 1], the last one closed), and the pairs outside the edges are counted in `below` and
+    `above`.  groups: a mapping ID -> group name, as gen._pop returns; probandIDs default to its keys, IDs that are not in it take
+    part in no count (as in gen.phiMeanGroups); counts[a, b] counts the pairs with one member in names[a] and the other in
+    names[b].
+
+    x a Pedigree: gen.phi's sweep for the probands (default gen.pro; duplicates collapse), then the counting on the device from the
+    resident matrix, which is never copied (genphi_result_hist; one read of its upper triangle).  x a square host
+    matrix: the same definition in numpy; with `groups`, probandIDs must name its rows.  ValueError for edges that are not strictly
+    increasing, more than 4,096 bins, more than 256 groups or more than 16,384 groups x bins; KeyError for an unknown proband ID."""
+    edges = _hist_edges(bins, range)
+    if isinstance(x, Pedigree):
+        if groups is None:
+            _, (counts, below, above) = _resident_query(x, probandIDs, device, lambda pl: pl.hist(edges))
+            return PhiHist(edges, counts, below, above, int(counts.sum()) + below + above)
+        names, ids, labels = _group_order(groups, probandIDs)
+        _, (counts, below, above) = _resident_query(x, ids, device, lambda pl: pl.hist(edges, labels, len(names)))
+    else:
+        m, ids = _host_matrix(x, probandIDs, "gen.phiHist")
+        if groups is None:
+            counts, below, above = _hist_numpy(m, edges)
+            return PhiHist(edges, counts, below, above, int(counts.sum()) + below + above)
+        if len(groups) == 0:
+            raise ValueError("groups is empty")
+        if ids is None:
+            raise ValueError("gen.phiHist: groups of a host matrix need probandIDs, the IDs of its rows")
+        names = sorted(set(groups.values()))
+        index = {name: k for k, name in enumerate(names)}
+        labels = np.array([index[groups[i]] if i in groups else -1 for i in ids.tolist()], dtype=np.int32)
+        if len(names) > _capi.GENPHI_HIST_MAX_GROUPS or len(names) * (len(edges) - 1) > _capi.GENPHI_HIST_MAX_CELLS:
+            raise ValueError("gen.phiHist: %d groups x %d bins: at most %d groups and %d cells" % (
+                len(names), len(edges) - 1, _capi.GENPHI_HIST_MAX_GROUPS, _capi.GENPHI_HIST_MAX_CELLS))
+        counts, below, above = _hist_numpy(m, edges, labels, len(names))
+    upper = np.triu(np.ones(below.shape, dtype=bool))
+    sizes = np.bincount(labels[labels >= 0], minlength=len(names)).astype(np.int64)
+    return PhiHist(edges, counts, below, above, int(counts[upper].sum() + below[upper].sum() + above[upper].sum()), names, sizes)
+
+
+def phiQuantile(x, q, probandIDs=None, device=None):
+    """Quantiles of the pairwise kinships Phi[i, j], i < j: a float64 array with one entry per q in [0, 1] (q = 0.5: the median).
+    Neither GENLIB nor the reference has this function; a gen.phiOver threshold is chosen from it.
+
+    With n pairs sorted ascending and h = q (n - 1): lo + (hi - lo) (h - floor(h)) in float64, lo and hi being the entries of rank
+    floor(h) and ceil(h) -- numpy.quantile's "linear" method on the exact order statistics.
+
+    x a Pedigree: gen.phi's sweep for probandIDs (default gen.pro; duplicates collapse), then a radix selection on the device from
+    the resident matrix, which is never copied (genphi_result_select; 8 quantiles per device call, each call four
+    reads of the upper triangle).  x a square host matrix: the same definition by a numpy sort.  ValueError for a q outside [0, 1]
+    or fewer than 2 probands; KeyError for an unknown proband ID."""
+    q = np.atleast_1d(np.asarray(q, dtype=np.float64))
+    if q.ndim != 1 or np.isnan(q).any() or np.any(q < 0) or np.any(q > 1):
+        raise ValueError("gen.phiQuantile: q must be numbers in [0, 1]")
+
+    def ranks_of(n):
+        if n < 1:
+            raise ValueError("gen.phiQuantile: no pair of probands")
+        h = q * (n - 1)
+        lo = np.floor(h)
+        return h - lo, lo.astype(np.int64), np.ceil(h).astype(np.int64)
+
+    if isinstance(x, Pedigree):
+        def query(pl):
+            frac, lo, hi = ranks_of(pl.count_pairs())
+            v_lo, v_hi = np.empty(len(q), dtype=np.float64), np.empty(len(q), dtype=np.float64)
+            for k in np.arange(0, len(q), _capi.GENPHI_SELECT_MAX_RANKS // 2):               # 8 quantiles = 16 ranks per call
+                part = slice(k, k + _capi.GENPHI_SELECT_MAX_RANKS // 2)
+                got = pl.select(np.concatenate([lo[part], hi[part]])).astype(np.float64)
+                v_lo[part], v_hi[part] = got[:len(lo[part])], got[len(lo[part]):]
+            return frac, v_lo, v_hi
+        _, (frac, v_lo, v_hi) = _resident_query(x, probandIDs, device, query)
+    else:
+        m, _ = _host_matrix(x, probandIDs, "gen.phiQuantile")
+        s = np.sort(m[np.triu_indices(len(m), 1)])
+        frac, lo, hi = ranks_of(len(s))
+        v_lo, v_hi = s[lo], s[hi]
+    return v_lo + (v_hi - v_lo) * frac
 
 
 class PhiSolve:

@@ -26,6 +26,10 @@ GENPHI_FLAG_NO_SPARSE = 4
 GENPHI_GROUP_SUMS_MAX_GROUPS = 4096
 GENPHI_NEAREST_MAX_K = 64
 GENPHI_MATMUL_MAX_K = 64
+GENPHI_HIST_MAX_EDGES = 4097
+GENPHI_HIST_MAX_GROUPS = 256
+GENPHI_HIST_MAX_CELLS = 16384
+GENPHI_SELECT_MAX_RANKS = 16
 GENPHI_IMPLEX_FLAG_ONLY_NEW = 1
 
 _I64P = C.POINTER(C.c_int64)
@@ -51,7 +55,7 @@ class GenphiStats(C.Structure):
 EXPORTED_SYMBOLS = [
     "genphi_plan_create", "genphi_plan_create_tuned", "genphi_tuning_create", "genphi_tuning_set", "genphi_tuning_destroy", "genphi_plan_levels", "genphi_plan_n_probands", "genphi_plan_step_mode", "genphi_plan_step_info", "genphi_plan_step_slots",
     "genphi_plan_algorithmic_bytes", "genphi_plan_device_bytes", "genphi_plan_device_bytes_needed", "genphi_plan_sparse_levels", "genphi_plan_step_walk", "genphi_plan_set_step_hook", "genphi_compute_device", "genphi_result_device",
-    "genphi_result_to_host", "genphi_result_to_host_f64", "genphi_phi_pairs", "genphi_result_sums", "genphi_result_group_sums", "genphi_result_over", "genphi_result_nearest", "genphi_result_matmul", "genphi_result_solve", "genphi_result_bootstrap", "genphi_bootstrap_counts", "genphi_result_entries",
+    "genphi_result_to_host", "genphi_result_to_host_f64", "genphi_phi_pairs", "genphi_result_sums", "genphi_result_group_sums", "genphi_result_over", "genphi_result_nearest", "genphi_result_matmul", "genphi_result_solve", "genphi_result_hist", "genphi_result_select", "genphi_result_bootstrap", "genphi_bootstrap_counts", "genphi_result_entries",
     "genphi_compute_f32",
     "genphi_genealogy_read", "genphi_branching", "genphi_free", "genphi_release_cached", "genphi_cached_bytes", "genphi_plan_release_device", "genphi_plan_destroy",
     "genphi_last_error",
@@ -158,6 +162,10 @@ def lib():
         L.genphi_result_solve.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.c_int64, C.c_double, C.c_double, C.c_int32,
                                           C.POINTER(C.c_double), C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_int32)]
         L.genphi_result_solve.restype = C.c_int
+        L.genphi_result_hist.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_int32), _I64P, _I64P, _I64P, _I64P]
+        L.genphi_result_hist.restype = C.c_int
+        L.genphi_result_select.argtypes = [C.c_void_p, C.c_int32, _I64P, _F32P, _I64P]
+        L.genphi_result_select.restype = C.c_int
         L.genphi_result_entries.argtypes = [C.c_void_p, C.c_int64, _I64P, _I64P, C.POINTER(C.c_double)]
         L.genphi_result_entries.restype = C.c_int
         L.genphi_branching.argtypes = [C.c_int64, _I64P, _I64P, _I64P, _I64P, C.c_int64, _I64P, C.c_int64, _I64P,
@@ -750,6 +758,69 @@ class PhiPlan:
             if rc:
                 _raise(rc)
         return (z[:, 0] if one else z), res, its
+
+    def hist(self, edges, labels=None, n_groups=None):
+        """(counts, below, above), int64: the histogram of the pairs i < j of the RESIDENT rows over `edges` (strictly increasing
+        float64, numpy.histogram's bins: the last one closed), counted on the device in one read of the upper triangle
+        (genphi_result_hist); the matrix is not copied.  Without labels counts has one entry per bin and below / above
+        (the pairs left of the first and right of the last edge) are ints.  labels[i] in [0, n_groups) is the group of proband i,
+        -1 = in no group (n_groups defaults to 1 + the largest label): counts is (n_groups, n_groups, bins) and symmetric,
+        counts[a, b] counting the pairs with one member in a and the other in b; below and above are (n_groups, n_groups).  Row
+        shards add their outputs.  ValueError for edges that are not strictly increasing, NaN or too many, for too many groups or
+        cells, a wrong label or a Float64 result; GenphiDeviceError without a resident result."""
+        edges = np.ascontiguousarray(edges, dtype=np.float64)
+        if edges.ndim != 1 or not 2 <= len(edges) <= GENPHI_HIST_MAX_EDGES:
+            raise ValueError("hist: %s edges, need 2 .. %d in one dimension" % (edges.shape, GENPHI_HIST_MAX_EDGES))
+        bins = len(edges) - 1
+        dp = C.POINTER(C.c_double)
+        if labels is None:
+            if n_groups not in (None, 0, 1):
+                raise ValueError("hist: n_groups = %r without labels" % (n_groups,))
+            counts, below, above = np.zeros(bins, dtype=np.int64), C.c_int64(), C.c_int64()
+            rc = lib().genphi_result_hist(self._h, len(edges), edges.ctypes.data_as(dp), 0, None, counts.ctypes.data_as(_I64P), C.byref(below),
+                                          C.byref(above), None)
+            if rc:
+                _raise(rc)
+            return counts, int(below.value), int(above.value)
+        labels = np.ascontiguousarray(labels, dtype=np.int32)
+        if labels.ndim != 1 or len(labels) != self.n_probands:
+            raise ValueError("labels must hold one entry per proband (%d), got shape %s" % (self.n_probands, labels.shape))
+        g = int(n_groups) if n_groups is not None else max(int(labels.max()) + 1 if len(labels) else 0, 1)      # (all -1: one empty group)
+        if not 1 <= g <= GENPHI_HIST_MAX_GROUPS:                       # (checked here too: the outputs are sized by it)
+            raise ValueError("hist: n_groups = %d outside [1, %d]" % (g, GENPHI_HIST_MAX_GROUPS))
+        if g * bins > GENPHI_HIST_MAX_CELLS:
+            raise ValueError("hist: %d groups x %d bins exceed %d cells" % (g, bins, GENPHI_HIST_MAX_CELLS))
+        counts, below, above = np.zeros((g, g, bins), dtype=np.int64), np.zeros((g, g), dtype=np.int64), np.zeros((g, g), dtype=np.int64)
+        rc = lib().genphi_result_hist(self._h, len(edges), edges.ctypes.data_as(dp), g, labels.ctypes.data_as(C.POINTER(C.c_int32)),
+                                      counts.ctypes.data_as(_I64P), below.ctypes.data_as(_I64P), above.ctypes.data_as(_I64P), None)
+        if rc:
+            _raise(rc)
+        return counts, below, above
+
+    def count_pairs(self):
+        """The pairs i < j of the RESIDENT rows: what hist counts without labels and what select ranks."""
+        n = C.c_int64()
+        rc = lib().genphi_result_select(self._h, 0, None, None, C.byref(n))
+        if rc:
+            _raise(rc)
+        return int(n.value)
+
+    def select(self, ranks):
+        """float32 array: values[r] is the entry of 0-based rank ranks[r] among the pairs i < j of the RESIDENT rows sorted
+        ascending, bit for bit an entry of the matrix (genphi_result_select, DESIGN.md 20: radix selection on the device, four reads
+        of the upper triangle per call of up to 16 ranks; more ranks run as further calls).  Ranks may repeat and come in any
+        order.  On a row shard the answer is over that shard's pairs: order statistics of shards do not compose.  ValueError for a
+        rank outside [0, count_pairs()) or a Float64 result, GenphiDeviceError without a resident result."""
+        ranks = _i64(ranks)
+        if ranks.ndim != 1:
+            raise ValueError("ranks must be 1-D, got shape %s" % (ranks.shape,))
+        out = np.empty(len(ranks), dtype=np.float32)
+        for r0 in range(0, len(ranks), GENPHI_SELECT_MAX_RANKS):
+            part = ranks[r0:r0 + GENPHI_SELECT_MAX_RANKS]
+            rc = lib().genphi_result_select(self._h, len(part), part.ctypes.data_as(_I64P), out[r0:].ctypes.data_as(_F32P), None)
+            if rc:
+                _raise(rc)
+        return out
 
     def bootstrap(self, b, seed, first=0):
         """(quad, self): float64 arrays of b entries, the bootstrap resamples first .. first + b - 1 of the probands on the RESIDENT

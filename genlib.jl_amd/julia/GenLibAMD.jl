@@ -274,6 +274,82 @@ function phiOver(pedigree::GenLib.Pedigree, threshold::Real, probandIDs::Vector{
 end
 
 """
+    phiHist(pedigree::GenLib.Pedigree, probandIDs::Vector{Int} = GenLib.pro(pedigree); bins = 64, range = (0.0, 0.5), device::Integer = -1)
+
+The distribution of the pairwise kinships: the histogram of `phi[i, j]` over all pairs `i < j` of `unique(probandIDs)`, as
+`(edges, counts, below, above, n_pairs)`.  `bins` is a number of uniform bins over `range` or a vector of strictly increasing edges;
+a bin holds `edges[b] <= x < edges[b + 1]`, the last one also `x == edges[end]`; `below` and `above` count the pairs outside the edges.
+The matrix stays on the GPU: `genphi_result_hist` counts there in one pass over its upper triangle.  The reference has no `phiHist`;
+the definition is this package's own (`include/genphi.h`).  The labelled form (counts within and between groups) is reached through
+the same entry point with `n_groups` and `group`; this shim does not wrap it.  Uniform edges are computed here as
+`first + b * (last - first) / bins` with the last one set to `last`, the arithmetic of `numpy.linspace`, so that both shims hand the same
+doubles to the library and agree on an entry that ties with an edge.
+"""
+function phiHist(pedigree::GenLib.Pedigree, probandIDs::Vector{Int} = GenLib.pro(pedigree); bins = 64, range = (0.0, 0.5), device::Integer = -1)
+    if bins isa Integer
+        bins >= 1 || throw(ArgumentError("bins must be at least 1"))
+        lo = Float64(range[1]); hi = Float64(range[2]); step = (hi - lo) / bins
+        edges = [lo + b * step for b in 0:bins]
+        edges[end] = hi
+    else
+        edges = Vector{Float64}(bins)
+    end
+    (2 <= length(edges) <= 4097 && !any(isnan, edges) && all(diff(edges) .> 0)) || throw(ArgumentError("the edges must be 2 .. 4097 strictly increasing numbers"))
+    ordered = unique(probandIDs)
+    foreach(ID -> pedigree[ID], ordered)                                    # KeyError on unknown ID
+    plan = create_plan(pedigree, ordered, nothing)
+    try
+        opts = Ref(GenphiOpts(Int32(device), 0, 0, 0, 0, 0))
+        check(ccall((:genphi_compute_device, libgenphi), Cint, (Ptr{Cvoid}, Ptr{GenphiOpts}, Ptr{Cvoid}), plan, opts, C_NULL))
+        counts = Vector{Int64}(undef, length(edges) - 1)
+        below = Ref{Int64}(0); above = Ref{Int64}(0); n = Ref{Int64}(0)
+        GC.@preserve edges counts check(ccall((:genphi_result_hist, libgenphi), Cint,
+            (Ptr{Cvoid}, Int32, Ptr{Float64}, Int32, Ptr{Int32}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}),
+            plan, Int32(length(edges)), edges, Int32(0), C_NULL, counts, below, above, n))
+        return (edges = edges, counts = counts, below = below[], above = above[], n_pairs = n[])
+    finally
+        destroy_plan(plan)
+    end
+end
+
+"""
+    phiQuantile(pedigree::GenLib.Pedigree, q, probandIDs::Vector{Int} = GenLib.pro(pedigree); device::Integer = -1)
+
+Quantiles of the pairwise kinships `phi[i, j]`, `i < j`, one `Float64` per entry of `q` (each in `[0, 1]`): with `n` pairs sorted
+ascending and `h = q (n - 1)`, `lo + (hi - lo) (h - floor(h))` where `lo` and `hi` are the entries of 0-based rank `floor(h)` and
+`ceil(h)` (`Statistics.quantile`'s default).  The matrix stays on the GPU: `genphi_result_select` finds the exact order statistics
+there by radix selection, 16 ranks (8 quantiles) per call, four passes over the upper triangle each.
+"""
+function phiQuantile(pedigree::GenLib.Pedigree, q, probandIDs::Vector{Int} = GenLib.pro(pedigree); device::Integer = -1)
+    qs = Float64.(collect(q))
+    all(p -> 0 <= p <= 1, qs) || throw(ArgumentError("q must lie in [0, 1]"))
+    ordered = unique(probandIDs)
+    foreach(ID -> pedigree[ID], ordered)                                    # KeyError on unknown ID
+    plan = create_plan(pedigree, ordered, nothing)
+    try
+        opts = Ref(GenphiOpts(Int32(device), 0, 0, 0, 0, 0))
+        check(ccall((:genphi_compute_device, libgenphi), Cint, (Ptr{Cvoid}, Ptr{GenphiOpts}, Ptr{Cvoid}), plan, opts, C_NULL))
+        n = Ref{Int64}(0)
+        check(ccall((:genphi_result_select, libgenphi), Cint, (Ptr{Cvoid}, Int32, Ptr{Int64}, Ptr{Float32}, Ptr{Int64}), plan, Int32(0), C_NULL, C_NULL, n))
+        n[] >= 1 || throw(ArgumentError("phiQuantile needs at least 2 probands"))
+        h = qs .* (n[] - 1)
+        out = Vector{Float64}(undef, length(qs))
+        for first in 1:8:length(qs)
+            part = first:min(first + 7, length(qs))
+            ranks = vcat(Int64.(floor.(h[part])), Int64.(ceil.(h[part])))
+            values = Vector{Float32}(undef, length(ranks))
+            GC.@preserve ranks values check(ccall((:genphi_result_select, libgenphi), Cint, (Ptr{Cvoid}, Int32, Ptr{Int64}, Ptr{Float32}, Ptr{Int64}),
+                plan, Int32(length(ranks)), ranks, values, C_NULL))
+            lo = Float64.(values[1:length(part)]); hi = Float64.(values[length(part)+1:end])
+            out[part] = lo .+ (hi .- lo) .* (h[part] .- floor.(h[part]))
+        end
+        return out
+    finally
+        destroy_plan(plan)
+    end
+end
+
+"""
     phiCI(pedigree::GenLib.Pedigree, probandIDs::Vector{Int} = GenLib.pro(pedigree); prob = [0.025, 0.05, 0.95, 0.975],
           b::Integer = 5000, seed::Union{Nothing, UInt64} = nothing, device::Integer = -1)
 

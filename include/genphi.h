@@ -335,6 +335,63 @@ int genphi_result_matmul(genphi_plan *plan, int32_t k, const double *x, int64_t 
 int genphi_result_solve(genphi_plan *plan, int32_t k, const double *b, int64_t ldb, double ridge, double tol, int32_t max_iter,
                         double *z, int64_t ldz, double *residual, int32_t *iterations);
 
+/* The distribution of the pairwise kinships of the resident result, without moving the matrix: the histogram of Phi
+ * over all pairs, within and between groups of probands -- the figure that a mean kinship summarises -- in one read of the upper
+ * triangle.  Neither GENLIB nor the reference has such a function, so this text is the definition.  N is the number of probands
+ * after duplicates collapse (genphi_plan_create).
+ *   the pairs         those of genphi_result_over: (i, j) with i in the resident rows [row_begin, row_begin + n_rows), i < j < N; each
+ *                     unordered pair once, never the diagonal, never a padding column of the row pitch
+ *   edges             n_edges strictly increasing doubles, none NaN; -infinity and +infinity are allowed.  2 <= n_edges <=
+ *                     GENPHI_HIST_MAX_EDGES; n_bins = n_edges - 1
+ *   bins              a pair counts with x = (double)Phi[i][j]: in bin b when edges[b] <= x < edges[b + 1]; the last bin also holds
+ *                     x == edges[n_bins] (numpy.histogram's rule); in `below` when x < edges[0]; in `above` when x > edges[n_bins].
+ *                     (An entry is a Float32, so the library compares it with the smallest Float32 at or above each edge -- above the
+ *                     last one: for every double edge that decides exactly as the Float64 comparison does, csrc/hist_geometry.h.)
+ *   group == NULL     n_groups must be 0 or 1; counts holds n_bins entries, below and above one each
+ *   group != NULL     labels as for genphi_result_group_sums: N entries, 0 .. n_groups - 1, or -1 = in no group; 1 <= n_groups <=
+ *                     GENPHI_HIST_MAX_GROUPS.  counts is n_groups x n_groups x n_bins, row-major, and SYMMETRIC: counts[a][b][.]
+ *                     counts the unordered pairs {i, j}, i resident and i < j, with one member in a and the other in b;
+ *                     counts[a][a][.] are the pairs within a.  below and above are n_groups x n_groups, symmetric too.  A pair with
+ *                     an unlabelled member counts nowhere.
+ *   cells             max(n_groups, 1) x n_bins <= GENPHI_HIST_MAX_CELLS: a workgroup's table of Int32 counters in LDS (64 KB)
+ *   *n_pairs          the pairs counted: the sum of bins + below + above over a <= b
+ * Any output pointer may be NULL.  Counts are integers, accumulated by integer additions only: the answer is a function of the matrix,
+ * the resident rows, the edges and the labels, and the same call gives the same bytes whatever the launch geometry.  The outputs of
+ * row shards add.  An empty shard (no resident row after a genphi_compute_device call), or N < 2, is GENPHI_OK with zeros.
+ * Device memory, in the plan's scratch block, kept between calls: 4 bytes per resident row, 4 per proband when there are labels,
+ * 4 per edge, and 8 max(n_groups, 1)^2 (n_bins + 2) for the table.  The phiOver counts the library keeps (genphi_result_over) are
+ * not touched.
+ * GENPHI_ERR_ARG: NULL plan or edges, n_edges out of range, edges not strictly increasing or NaN, n_groups out of range, too many
+ * cells, a label outside [-1, n_groups), a Float64 result (GENPHI_FLAG_STORAGE_F64); GENPHI_ERR_DEVICE: no resident result;
+ * GENPHI_ERR_ALLOC: the scratch does not fit (found before the launch).  After any error the plan stays usable, the resident
+ * result is untouched and no output is written.                                                                                   */
+#define GENPHI_HIST_MAX_EDGES 4097
+#define GENPHI_HIST_MAX_GROUPS 256
+#define GENPHI_HIST_MAX_CELLS 16384
+int genphi_result_hist(genphi_plan *plan, int32_t n_edges, const double *edges, int32_t n_groups, const int32_t *group,
+                       int64_t *counts, int64_t *below, int64_t *above, int64_t *n_pairs);
+
+/* Exact order statistics of the same pairs: the median and the upper quantiles that a genphi_result_over threshold
+ * is chosen from, in a few reads of the upper triangle.
+ *   values[r]         the entry of 0-based rank ranks[r] among the pairs of the resident rows, sorted ascending: bit for bit an
+ *                     entry of the matrix.  Ranks may repeat and come in any order; each lies in [0, *n_pairs).
+ *   n_ranks           1 .. GENPHI_SELECT_MAX_RANKS; n_ranks == 0 with values == NULL only reports *n_pairs (ranks is not read)
+ *   *n_pairs          the pairs of the resident rows (may be NULL): the sum of N - 1 - i over them
+ *   the method        every entry a sweep produces is finite and >= +0, so its unsigned bit pattern orders like its value.  The
+ *                     selection is a most-significant-digit radix selection on the patterns: each pass is a histogram of one digit
+ *                     of the entries whose higher bits match one of the (distinct) prefixes still alive, and the host narrows
+ *                     every rank between passes.  The answer does not depend on the digit width (8 bits: 4 passes, each one read).
+ *   row shards        on a shard the answer is over that shard's pairs only.  Order statistics of shards do NOT compose: combine
+ *                     the histograms of the shards instead, or select on the full result.
+ * An empty shard or N < 2 has no pair: *n_pairs = 0 and every rank is out of range.  Device memory: 4 bytes per resident row and
+ * 32 KB of digit tables, in the plan's scratch block.  The same call gives the same bytes.
+ * GENPHI_ERR_ARG: NULL plan, n_ranks outside [0, GENPHI_SELECT_MAX_RANKS] or 0 with values given, NULL ranks or NULL values with
+ * n_ranks > 0, a rank outside [0, *n_pairs), a Float64 result; GENPHI_ERR_DEVICE: no resident result; GENPHI_ERR_ALLOC: the scratch
+ * does not fit (found before the first launch).  After any error the plan stays usable, the resident result is untouched and no
+ * output is written.                                                                                                              */
+#define GENPHI_SELECT_MAX_RANKS 16
+int genphi_result_select(genphi_plan *plan, int32_t n_ranks, const int64_t *ranks, float *values, int64_t *n_pairs);
+
 /* GENLIB's gen.phiCI(phiMatrix, prob, b) and gen.fCI(vectF, prob, b): bootstrap confidence intervals of the mean kinship and of the
  * mean inbreeding.  The reference has neither, so this text is the definition.  N is the number of probands after
  * duplicates collapse (genphi_plan_create), N >= 2.
