@@ -1123,6 +1123,77 @@ def phiQuantile(x, q, probandIDs=None, device=None):
     return v_lo + (v_hi - v_lo) * frac
 
 
+class PhiEigen:
+    """What gen.phiEigen returns: `values` (float64 (k,), descending), `vectors` (float64 (N, k): unit columns, the component of largest
+    magnitude positive), `residual` (float64 (k,): the true ||Op v - theta v||_2), `converged` (bool (k,)), `products` (the Lanczos steps
+    taken; 0 by numpy.linalg.eigh), `pro` (int64, the N IDs in the order of the rows; None when no IDs were given with a host matrix),
+    `center`, `tol`, and `coordinates` = vectors * sqrt(max(values, 0)): with center=True the principal coordinates."""
+
+    def __init__(self, values, vectors, residual, converged, products, pro, center, tol):
+        self.values, self.vectors, self.residual, self.converged, self.products = values, vectors, residual, converged, products
+        self.pro, self.center, self.tol = pro, center, tol
+
+    @property
+    def coordinates(self):
+        return self.vectors * np.sqrt(np.maximum(self.values, 0.0))
+
+    def __len__(self):
+        return len(self.vectors)
+
+    def __repr__(self):
+        k = len(self.values)
+        return "PhiEigen: %d largest eigenpair%s of %s for %d probands; %d converged to tol = %g in %d products; values %s; largest residual %.3g" % (
+            k, "" if k == 1 else "s", "J Phi J" if self.center else "Phi", len(self), int(np.count_nonzero(self.converged)), self.tol, self.products,
+            " ".join("%.6g" % v for v in self.values[:4]) + (" .." if k > 4 else ""), float(np.max(self.residual)) if k else 0.0)
+
+
+def _eigen_sign(v):
+    """Each column with its component of largest magnitude (the first among equals) made positive."""
+    big = np.argmax(np.abs(v), axis=0)
+    s = np.where(v[big, np.arange(v.shape[1])] < 0.0, -1.0, 1.0)
+    return v * s
+
+
+def phiEigen(x, k=10, center=False, tol=1e-8, maxiter=300, seed=0, probandIDs=None, device=None):
+    """The k algebraically largest eigenpairs of the kinship matrix Phi: the top of its spectrum and, with center=True (Gower's
+    centring J Phi J, J = I - 11^T / N), the principal coordinates of population structure.  Returns a PhiEigen.  Neither GENLIB nor
+    the reference has this function; include/genphi.h is its definition.
+
+    x a Pedigree: gen.phi's sweep for probandIDs (default gen.pro; duplicates collapse), then Lanczos with full reorthogonalisation on
+    the device with the resident matrix, which is never copied (genphi_result_eigen): the Krylov basis and the Ritz vectors
+    stay on the device, a start vector drawn from `seed`, stopped when the k pairs satisfy beta |s| <= tol theta_1 or after
+    min(maxiter, N) products.  `converged` and the true `residual` say how far each pair got.  x a square host matrix: the same
+    definition by numpy.linalg.eigh on the Float64 matrix (products = 0).
+
+    One Krylov sequence finds one vector per distinct eigenvalue: an eigenvalue that is repeated among the top k is reported ONCE and
+    the list goes on with the next distinct ones (eigh lists every copy); further copies appear only after a breakdown (unrelated
+    founders, Phi = I / 2) or when the iteration runs on far beyond convergence.
+
+    ValueError for k outside [1, min(64, N)], a negative or NaN tol, maxiter outside [k, 4096]; KeyError for an unknown proband ID."""
+    k, tol, maxiter, center = int(k), float(tol), int(maxiter), bool(center)
+    if not tol >= 0.0:
+        raise ValueError("gen.phiEigen: tol = %r is negative or NaN" % tol)
+    if not 1 <= k <= _capi.GENPHI_EIGEN_MAX_K:
+        raise ValueError("gen.phiEigen: k = %d outside [1, %d]" % (k, _capi.GENPHI_EIGEN_MAX_K))
+    if not k <= maxiter <= _capi.GENPHI_EIGEN_MAX_ITER:
+        raise ValueError("gen.phiEigen: maxiter = %d outside [k = %d, %d]" % (maxiter, k, _capi.GENPHI_EIGEN_MAX_ITER))
+    if isinstance(x, Pedigree):
+        ids, (val, vec, res, conv, prod) = _resident_query(x, probandIDs, device, lambda pl: pl.eigen(k, center, tol, maxiter, seed))
+        return PhiEigen(val, vec, res, conv, prod, ids, center, tol)
+    m, ids = _host_matrix(x, probandIDs, "gen.phiEigen")
+    n = len(m)
+    if k > n:
+        raise ValueError("gen.phiEigen: k = %d outside [1, N = %d]" % (k, n))
+    if center:
+        m = m - m.mean(axis=0)[None, :]
+        m = m - m.mean(axis=1)[:, None]
+        m = (m + m.T) / 2
+    lam, vec = np.linalg.eigh(m)
+    val, vec = lam[::-1][:k].copy(), _eigen_sign(np.ascontiguousarray(vec[:, ::-1][:, :k]))
+    res = np.sqrt(((m @ vec - vec * val) ** 2).sum(axis=0))
+    return PhiEigen(val, vec, res, res <= tol * val[0] + (n + 2) * 2.0 ** -53 * abs(val[0]), 0, ids, center, tol)
+
+
 class PhiSolve:
     """What gen.phiSolve returns: `solution` (float64, the shape of B), per right-hand side `residual` (float64, the true relative
     residual ||b - (Phi + ridge I) z|| / ||b||), `iterations` (int32, products of the iteration) and `converged` (residual <= tol);

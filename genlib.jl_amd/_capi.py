@@ -26,6 +26,8 @@ GENPHI_FLAG_NO_SPARSE = 4
 GENPHI_GROUP_SUMS_MAX_GROUPS = 4096
 GENPHI_NEAREST_MAX_K = 64
 GENPHI_MATMUL_MAX_K = 64
+GENPHI_EIGEN_MAX_K = 64
+GENPHI_EIGEN_MAX_ITER = 4096
 GENPHI_HIST_MAX_EDGES = 4097
 GENPHI_HIST_MAX_GROUPS = 256
 GENPHI_HIST_MAX_CELLS = 16384
@@ -55,7 +57,7 @@ class GenphiStats(C.Structure):
 EXPORTED_SYMBOLS = [
     "genphi_plan_create", "genphi_plan_create_tuned", "genphi_tuning_create", "genphi_tuning_set", "genphi_tuning_destroy", "genphi_plan_levels", "genphi_plan_n_probands", "genphi_plan_step_mode", "genphi_plan_step_info", "genphi_plan_step_slots",
     "genphi_plan_algorithmic_bytes", "genphi_plan_device_bytes", "genphi_plan_device_bytes_needed", "genphi_plan_sparse_levels", "genphi_plan_step_walk", "genphi_plan_set_step_hook", "genphi_compute_device", "genphi_result_device",
-    "genphi_result_to_host", "genphi_result_to_host_f64", "genphi_phi_pairs", "genphi_result_sums", "genphi_result_group_sums", "genphi_result_over", "genphi_result_nearest", "genphi_result_matmul", "genphi_result_solve", "genphi_result_hist", "genphi_result_select", "genphi_result_bootstrap", "genphi_bootstrap_counts", "genphi_result_entries",
+    "genphi_result_to_host", "genphi_result_to_host_f64", "genphi_phi_pairs", "genphi_result_sums", "genphi_result_group_sums", "genphi_result_over", "genphi_result_nearest", "genphi_result_matmul", "genphi_result_solve", "genphi_result_eigen", "genphi_result_hist", "genphi_result_select", "genphi_result_bootstrap", "genphi_bootstrap_counts", "genphi_result_entries",
     "genphi_compute_f32",
     "genphi_genealogy_read", "genphi_branching", "genphi_free", "genphi_release_cached", "genphi_cached_bytes", "genphi_plan_release_device", "genphi_plan_destroy",
     "genphi_last_error",
@@ -162,6 +164,9 @@ def lib():
         L.genphi_result_solve.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.c_int64, C.c_double, C.c_double, C.c_int32,
                                           C.POINTER(C.c_double), C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_int32)]
         L.genphi_result_solve.restype = C.c_int
+        L.genphi_result_eigen.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_uint64, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                          C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        L.genphi_result_eigen.restype = C.c_int
         L.genphi_result_hist.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_int32), _I64P, _I64P, _I64P, _I64P]
         L.genphi_result_hist.restype = C.c_int
         L.genphi_result_select.argtypes = [C.c_void_p, C.c_int32, _I64P, _F32P, _I64P]
@@ -758,6 +763,31 @@ class PhiPlan:
             if rc:
                 _raise(rc)
         return (z[:, 0] if one else z), res, its
+
+    def eigen(self, k=10, center=False, tol=1e-8, maxiter=300, seed=0):
+        """(values, vectors, residual, converged, products): the k algebraically largest eigenpairs of the FULL resident result, or
+        with center=True of J Phi J, J = I - 11^T / N, by Lanczos with full reorthogonalisation whose vectors all live on the device
+        (genphi_result_eigen; include/genphi.h writes the iteration out).  values float64 (k,) descending; vectors
+        float64 (N, k), unit columns whose component of largest magnitude is positive; residual float64 (k,), the true
+        ||Op v - theta v||; converged bool (k,), the Lanczos estimate beta |s| <= tol theta_1; products, the Lanczos steps taken.  The
+        same call gives the same bytes.  One Krylov sequence: a repeated eigenvalue is reported once.  ValueError for k outside
+        [1, min(64, N)], a negative or NaN tol, maxiter outside [k, 4096], a Float64 result or a row shard; GenphiDeviceError without
+        a resident result; MemoryError when the basis does not fit."""
+        k, maxiter = int(k), int(maxiter)
+        n = self.n_probands
+        if not 1 <= k <= min(GENPHI_EIGEN_MAX_K, n):                 # (checked here too: the outputs are sized by it)
+            raise ValueError("eigen: k = %d outside [1, %d]" % (k, min(GENPHI_EIGEN_MAX_K, n)))
+        if not -2 ** 31 <= maxiter < 2 ** 31:
+            raise ValueError("eigen: maxiter = %d" % maxiter)
+        values, vectors = np.empty(k, dtype=np.float64), np.empty((n, k), dtype=np.float64)
+        residual, converged, products = np.empty(k, dtype=np.float64), np.zeros(k, dtype=np.int32), C.c_int32()
+        dp = C.POINTER(C.c_double)
+        rc = lib().genphi_result_eigen(self._h, k, 1 if center else 0, float(tol), maxiter, int(seed) & 0xFFFFFFFFFFFFFFFF, values.ctypes.data_as(dp),
+                                       vectors.ctypes.data_as(dp), k, residual.ctypes.data_as(dp), converged.ctypes.data_as(C.POINTER(C.c_int32)),
+                                       C.byref(products))
+        if rc:
+            _raise(rc)
+        return values, vectors, residual, converged.astype(bool), int(products.value)
 
     def hist(self, edges, labels=None, n_groups=None):
         """(counts, below, above), int64: the histogram of the pairs i < j of the RESIDENT rows over `edges` (strictly increasing

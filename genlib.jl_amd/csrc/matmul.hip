@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/genphi.h"
+#include "matmul_device.h"
 #include "resident.h"
 #include "result_solve.h"
 
@@ -114,7 +115,15 @@ inline MmForm matmul_form(int k)
     return {kMmWaves * kMmRowsWide, 16};
 }
 
-void matmul_launch(const ResidentView &v, int n4, int k, const double *xd, double *y)
+}  // namespace
+
+int genphi::matmul_panel_columns(int k)
+{
+    const MmForm f = matmul_form(k);
+    return (k + f.kt - 1) / f.kt * f.kt;
+}
+
+hipError_t genphi::matmul_on_device(const ResidentView &v, int n4, int k, const double *xd, double *y)
 {
     const MmForm f = matmul_form(k);
     const int nr = static_cast<int>(v.n_rows);
@@ -127,7 +136,10 @@ void matmul_launch(const ResidentView &v, int n4, int k, const double *xd, doubl
     case 8: hipLaunchKernelGGL((matmul_kernel<kMmRowsWide, 8, kMmChunkWide8>), grid, dim3(256), 0, v.stream, v.result, ld, n4, nr, k, xd, y); break;
     default: hipLaunchKernelGGL((matmul_kernel<kMmRowsWide, 16, kMmChunkWide16>), grid, dim3(256), 0, v.stream, v.result, ld, n4, nr, k, xd, y); break;
     }
+    return hipGetLastError();
 }
+
+namespace {
 
 // what both entry points check of k and a panel (x of matmul, b of solve)
 int check_panel(const char *name, int32_t k, const char *what, const void *a, int64_t lda)
@@ -175,8 +187,7 @@ int genphi_result_matmul(genphi_plan *p, int32_t k, const double *x, int64_t ldx
     // the device copy of X: tiles of kt columns, each column n4 doubles; rows N .. n4 - 1 and the columns k .. kp - 1 are zero,
     // and all of it is written on every call (the scratch block is reused: nothing stale may meet a padding zero of Phi)
     const int n4 = static_cast<int>((N + 3) / 4 * 4);
-    const MmForm f = matmul_form(k);
-    const int kp = (k + f.kt - 1) / f.kt * f.kt;
+    const int kp = genphi::matmul_panel_columns(k);
     const size_t x_bytes = al256(static_cast<size_t>(kp) * n4 * sizeof(double)), y_bytes = static_cast<size_t>(nr) * k * sizeof(double);
     char *scratch;
     if (genphi::resident_scratch(p, x_bytes + y_bytes, &scratch) != GENPHI_OK)
@@ -192,10 +203,7 @@ int genphi_result_matmul(genphi_plan *p, int32_t k, const double *x, int64_t ldx
         for (int c = 0; c < k; ++c) packed[static_cast<size_t>(c) * n4 + j] = x[j * ldx + c];
     double *d_x = reinterpret_cast<double *>(scratch), *d_y = reinterpret_cast<double *>(scratch + x_bytes);
     hipError_t e = hipMemcpyAsync(d_x, packed.data(), packed.size() * sizeof(double), hipMemcpyHostToDevice, v.stream);
-    if (e == hipSuccess) {
-        matmul_launch(v, n4, k, d_x, d_y);
-        e = hipGetLastError();
-    }
+    if (e == hipSuccess) e = genphi::matmul_on_device(v, n4, k, d_x, d_y);
     if (e == hipSuccess)
         e = hipMemcpy2DAsync(y, static_cast<size_t>(ldy) * sizeof(double), d_y, static_cast<size_t>(k) * sizeof(double), static_cast<size_t>(k) * sizeof(double),
                              static_cast<size_t>(nr), hipMemcpyDeviceToHost, v.stream);

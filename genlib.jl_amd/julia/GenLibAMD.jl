@@ -386,6 +386,7 @@ function phiCI(pedigree::GenLib.Pedigree, probandIDs::Vector{Int} = GenLib.pro(p
 end
 
 const MATMUL_MAX_K = 64                    # GENPHI_MATMUL_MAX_K
+const EIGEN_MAX_K = 64                     # GENPHI_EIGEN_MAX_K
 
 # the sweep of `ordered`, then query(plan) on its resident result
 function with_resident(query, pedigree::GenLib.Pedigree, ordered::Vector{Int}, device::Integer)
@@ -461,6 +462,38 @@ function phiSolve(pedigree::GenLib.Pedigree, B::AbstractVecOrMat{<:Real}, proban
     end
     Z = permutedims(zt)
     return (solution = B isa AbstractVector ? vec(Z) : Z, residual = residual, iterations = Int.(iterations), converged = residual .<= tol, pro = ordered)
+end
+
+"""
+    phiEigen(pedigree::GenLib.Pedigree, probandIDs::Vector{Int} = GenLib.pro(pedigree);
+             k::Integer = 10, center::Bool = false, tol::Real = 1e-8, maxiter::Integer = 300, seed::Integer = 0, device::Integer = -1)
+
+The `k` algebraically largest eigenpairs of the kinship matrix, or with `center = true` of its Gower-centred form `J Φ J`, as
+`(values, vectors, residual, converged, products, coordinates, pro)`: Lanczos with full reorthogonalisation whose vectors all stay on
+the GPU (`genphi_result_eigen`; the iteration is written out in `include/genphi.h`).  `values` descend, `vectors` is N × k with unit
+columns whose component of largest magnitude is positive, `residual` is the true `‖Op v − θ v‖`, `coordinates = vectors .* sqrt.(max.(values, 0))'`
+(with `center = true` the principal coordinates).  One Krylov sequence: an eigenvalue repeated among the top k is reported once.
+The reference has no such function.  Like the other wrappers of this file, this one has never been run.
+"""
+function phiEigen(pedigree::GenLib.Pedigree, probandIDs::Vector{Int} = GenLib.pro(pedigree);
+                  k::Integer = 10, center::Bool = false, tol::Real = 1e-8, maxiter::Integer = 300, seed::Integer = 0, device::Integer = -1)
+    tol >= 0 || throw(ArgumentError("tol must not be negative or NaN"))
+    ordered = unique(probandIDs)
+    foreach(ID -> pedigree[ID], ordered)                                    # KeyError on unknown ID
+    n = length(ordered)
+    1 <= k <= min(EIGEN_MAX_K, n) || throw(ArgumentError("k must lie in [1, $(min(EIGEN_MAX_K, n))]"))
+    k <= maxiter <= 4096 || throw(ArgumentError("maxiter must lie in [k, 4096]"))
+    values = zeros(Float64, k); vt = zeros(Float64, k, n)                   # k x n column-major = n x k row-major, pitch k
+    residual = zeros(Float64, k); converged = zeros(Int32, k); products = Ref{Int32}(0)
+    with_resident(pedigree, ordered, device) do plan
+        GC.@preserve values vt residual converged check(ccall((:genphi_result_eigen, libgenphi), Cint,
+            (Ptr{Cvoid}, Int32, Int32, Float64, Int32, UInt64, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}),
+            plan, Int32(k), Int32(center), Float64(tol), Int32(maxiter), seed % UInt64, pointer(values), pointer(vt), Int64(k),
+            pointer(residual), pointer(converged), products))
+    end
+    V = permutedims(vt)
+    return (values = values, vectors = V, residual = residual, converged = converged .!= 0, products = Int(products[]),
+            coordinates = V .* sqrt.(max.(values, 0.0))', pro = ordered)
 end
 
 """

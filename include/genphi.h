@@ -335,6 +335,62 @@ int genphi_result_matmul(genphi_plan *plan, int32_t k, const double *x, int64_t 
 int genphi_result_solve(genphi_plan *plan, int32_t k, const double *b, int64_t ldb, double ridge, double tol, int32_t max_iter,
                         double *z, int64_t ldz, double *residual, int32_t *iterations);
 
+/* The k algebraically largest eigenpairs of the FULL resident result, or of its Gower-centred form J Phi J, J = I - 1 1^T / N, by
+ * Lanczos with full reorthogonalisation: the principal components / principal coordinates of population structure.
+ * Neither GENLIB nor the reference has such a function, so this text is the definition.  The Krylov basis, the working vector and
+ * the Ritz vectors live on the device from the first step to the last (the plan's scratch block); per step only the projection
+ * coefficients cross the link.  N is the number of probands after duplicates collapse.
+ *   Op                x -> Phi x (genphi_result_matmul's one-column product, its bits), or with center != 0 x -> c(Phi c(x)), c the
+ *                     subtraction of the mean over the N rows
+ *   start vector      a splitmix64 stream on seed (state += 0x9E3779B97F4A7C15; z = state; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;
+ *                     z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^= z >> 31):  u = (z >> 11) 2^-53,  x_e = 2 u - 1, e ascending;
+ *                     centred when center is set, then normalised (plain ascending Float64 sums on the host)
+ *   step m = 1, 2 ..  w = Op v_m;  h = V_m^T w;  w -= V_m h;  h' = V_m^T w;  w -= V_m h'  (classical Gram-Schmidt, twice, against
+ *                     all m basis vectors);  alpha_m = h_m + h'_m;  beta_m = ||w||;  v_(m+1) = w (1 / beta_m).  T_m is the
+ *                     tridiagonal matrix of the alpha (diagonal) and beta (beside it).
+ *   convergence       after every step m >= k: with theta_1 >= theta_2 >= .. the eigenvalues of T_m and s_(m,i) the last components
+ *                     of its unit eigenvectors, pair i has converged when beta_m |s_(m,i)| <= tol theta_1.  (The scale is the
+ *                     largest Ritz value: the zero eigenvalue of a centred matrix needs no special case.)  The iteration stops when
+ *                     the k largest have converged, or after min(max_iter, N) steps.  tol = 0 is allowed.
+ *   breakdown         beta_m <= 2^-40 max over i <= m of (|alpha_i| + beta_i): the Krylov space is invariant.  With m >= k the
+ *                     iteration stops and every pair counts as converged.  With m < k it goes on with the next N draws of the
+ *                     stream as a fresh vector (centred when center is set, normalised), orthogonalised twice against the basis and
+ *                     normalised again, and T holds a 0 at that place; if no more than 2^-40 of the fresh vector is left, it stops.
+ *   non-finite        an alpha or beta that is not finite (it cannot occur on a kinship matrix) stops the iteration: values, vectors
+ *                     and residual are NaN, no flag is set, the return value is GENPHI_OK.  (So does N = 1 with center set: the
+ *                     centred start vector is zero and cannot be normalised.)
+ *   the pairs         the k largest eigenvalues theta_i of the last T_m, descending, and u_i = V_m s_i (centred once more when center
+ *                     is set); the sign of u_i makes its component of largest magnitude, the one of smallest index among equals,
+ *                     positive
+ *   values            k doubles, descending
+ *   vectors           N x k row-major with pitch ldv >= k (in doubles): column i is the unit vector u_i.  Entries between k and ldv
+ *                     are not written.
+ *   residual          k doubles, may be NULL: the TRUE || Op u_i - theta_i u_i ||_2, from one more k-column product on the device
+ *   converged         k flags, may be NULL: the Lanczos estimate above at the last step (all 1 after a breakdown with m >= k)
+ *   products          may be NULL: the Lanczos steps taken (one-column products; the residual's k-column product is not counted)
+ * REPEATED EIGENVALUES: one Krylov sequence finds ONE vector per distinct eigenvalue.  An eigenvalue that is repeated among the top k
+ * is reported once, and the list goes on with the next distinct ones; further copies appear only after a breakdown (Phi = I / 2
+ * returns k copies of 1/2 that way) -- or, in floating point, when the iteration runs on long after that eigenvalue has converged:
+ * every step leaves rounding noise of the order 2^-53 along the other directions of its eigenspace, the iteration amplifies it as
+ * it amplifies any component there, and a copy emerges once the amplification reaches 2^53 (not before the later pairs of the list
+ * have converged to about the square root of that, so not at the default tol on a spectrum as crowded as a kinship matrix's).  A
+ * block method is not provided.
+ * The return value is GENPHI_OK whether or not every pair converged: converged and residual say.
+ * Sums on the device have one order, fixed by n4 = N rounded up to 4 alone: thread t of 256 adds the entry pairs (2p, 2p + 1),
+ * p = t, t + 256, .., by fma in ascending p; six rounds s_l += s_(l xor t), t = 32 .. 1, inside each of the four waves; then
+ * ((s_0 + s_1) + s_2) + s_3.  A combination sum_i c_i v_i is an fma chain in ascending i.  No floating-point atomics: the same call
+ * gives the same bytes, whatever an earlier call left in the scratch block.
+ * Device memory, in the plan's scratch block (one request, before the first launch): 8 n4 (min(max_iter, N) + 3 + k') bytes for the
+ * basis, the two work vectors and the Ritz panel, 8 N k for its product, and 8 (min(max_iter, N) (k + 2)) for coefficients.
+ * Checked in this order -- GENPHI_ERR_ARG: NULL plan; k outside [1, min(GENPHI_EIGEN_MAX_K, N)]; tol negative or NaN; max_iter
+ * outside [k, 4096]; ldv < k; a Float64 result (GENPHI_FLAG_STORAGE_F64).  GENPHI_ERR_DEVICE: no resident result.  GENPHI_ERR_ARG:
+ * fewer than N rows resident (a shard cannot iterate; an empty shard too); NULL values or vectors.  GENPHI_ERR_ALLOC: the scratch
+ * block does not fit (the message states the bytes).  After any error the plan stays usable, the resident result is untouched and
+ * no output is written.  The call adds nothing to genphi_stats.                                                                  */
+#define GENPHI_EIGEN_MAX_K 64
+int genphi_result_eigen(genphi_plan *plan, int32_t k, int32_t center, double tol, int32_t max_iter, uint64_t seed,
+                        double *values, double *vectors, int64_t ldv, double *residual, int32_t *converged, int32_t *products);
+
 /* The distribution of the pairwise kinships of the resident result, without moving the matrix: the histogram of Phi
  * over all pairs, within and between groups of probands -- the figure that a mean kinship summarises -- in one read of the upper
  * triangle.  Neither GENLIB nor the reference has such a function, so this text is the definition.  N is the number of probands
