@@ -18,6 +18,8 @@ meaning, printed lines and error behaviour as the reference:
     gen.occ(ped); gen.rec(ped)             # src/describe.jl:184-238, :133-145: occurrences, coverage (csrc/occ.hip)
     gen.findMRCA(ped, [1, 2, 29])          # src/identify.jl:83-160: MRCAs and meioses; gen.meioses, gen.findDistance,
                                            # gen.findFounders, gen.ancestor (csrc/dist.hip + csrc/loader.cpp)
+    gen.depths(ped)                        # src/describe.jl:241-279 reduced: paths, shortest, longest and mean ascent per pair
+                                           # (csrc/depth.hip); gen.genMin, gen.genMax, gen.genMean: GENLIB's gen.min / gen.max / gen.mean
     gen.completeness(ped); gen.depth(ped)  # src/describe.jl:73-125, :43-66: ascents by generation (csrc/completeness.hip);
                                            # gen.nomen, gen.nowomen, gen.noind, ped.show() (src/describe.jl:6-36, src/create.jl:76-111)
     gen.implex(ped)                        # GENLIB's gen.implex: distinct ancestors by generation (csrc/implex.hip)
@@ -34,7 +36,7 @@ from collections import OrderedDict
 import numpy as np
 
 from . import _capi
-from ._capi import PhiPlan, KinshipMatrix, GCPlan, OccPlan, RecPlan, DistPlan, CompletenessPlan, ImplexPlan, SimuPlan, GenphiDeviceError, GenphiLibraryMissing  # noqa: F401
+from ._capi import PhiPlan, KinshipMatrix, GCPlan, OccPlan, RecPlan, DistPlan, DepthPlan, CompletenessPlan, ImplexPlan, SimuPlan, GenphiDeviceError, GenphiLibraryMissing  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
@@ -402,6 +404,78 @@ def meioses(pedigree, pro=None, ancestors=None, device=None):
         return h.result_to_host()
     finally:
         h.close()
+
+
+class GenDepths:
+    """What gen.depths returns: `pro` and `ancestors` as given, `by`, and the arrays `min`, `max` (int16, -1 = no path), `mean`
+    (float64, NaN = no path) and `paths` (int64), of shape (len(pro), len(ancestors)) for by="pair", (len(pro),) for by="proband"
+    and (len(ancestors),) for by="ancestor"."""
+
+    def __init__(self, pro, ancestors, by, min, max, mean, paths):
+        self.pro, self.ancestors, self.by = pro, ancestors, by
+        self.min, self.max, self.mean, self.paths = min, max, mean, paths
+
+    def __repr__(self):
+        return "GenDepths(by=%r, %d probands, %d ancestors)" % (self.by, len(self.pro), len(self.ancestors))
+
+
+def depths(pedigree, pro=None, ancestors=None, by="pair", device=None):
+    """gen.depths(pedigree; pro = pro(pedigree), ancestors = founder(pedigree), by = "pair"): over ALL ascending paths from each
+    proband (rows) to each ancestor (columns), their number (`paths`), the meioses of the shortest and of the longest (`min`, `max`)
+    and the mean number of meioses (`mean`), as a GenDepths.  The empty path counts where the proband is the ancestor (1, 0, 0, 0.0);
+    where the ancestor is not an ancestor of the proband: paths 0, min = max = -1, mean NaN.
+
+    This is the reference's _findDistance (src/describe.jl:241-279), which returns the length of every ascending path between a
+    descendant and an ancestor, reduced to its count, minimum, maximum and mean -- for every pair at once, by one exact integer
+    recursion over the generation cuts on the GPU (csrc/depth.hip) instead of an enumeration of every path.  `min` equals
+    gen.meioses, `paths` equals gen.occ(...).T without its wrap-around, and mean is the correctly rounded quotient of the exact sum
+    of the lengths and the exact count.  by="proband" reduces over the ancestors on the device (all paths from the proband to any
+    listed ancestor: vectors of len(pro)), by="ancestor" over the probands (vectors of len(ancestors); no pair matrix exists);
+    both combine integers only, and their mean is float(sum of lengths) / float(paths).
+
+    Every listed proband gets its row (with or without children, each time it is listed); under by="pair" and by="ancestor" a
+    duplicated ancestor gives equal entries.  KeyError for an unknown ID.  ValueError for a pedigree of more than 47 generation
+    steps above the probands (the packed count holds 2^47 paths per pair), for a duplicated ancestor under by="proband" (a path
+    would be added twice), for by="ancestor" where len(pro) * steps * 2^steps reaches 2^63 (the sums could exceed Int64), and for
+    another `by`.  Each call plans, sweeps and frees its own handle."""
+    probands = globals()["pro"](pedigree) if pro is None else np.ascontiguousarray(pro, dtype=np.int64)
+    ancestors = founder(pedigree) if ancestors is None else np.ascontiguousarray(ancestors, dtype=np.int64)
+    h = DepthPlan(pedigree.ind, pedigree.father, pedigree.mother, probands, ancestors, by=by)
+    try:
+        h.compute(device=device)
+        lo, hi, paths, mean = h.result_to_host()
+        return GenDepths(probands, ancestors, by, lo, hi, mean, paths)
+    finally:
+        h.close()
+
+
+def _founder_depths(pedigree, individuals, device):
+    individuals = globals()["pro"](pedigree) if individuals is None else _id_list(individuals)
+    return depths(pedigree, individuals, founder(pedigree), by="proband", device=device)
+
+
+def genMin(pedigree, individuals=None, device=None):
+    """GENLIB's gen.min(gen, individuals): for each individual the generations to its NEAREST founder, the shortest of all its
+    ascending paths to any founder (0 for a founder); int16.  gen.depths(..., by="proband").min over all founders.  Not named `min`:
+    a module-level name would shadow the builtin this module itself uses.  The orientation (one entry per listed individual) and
+    the definition are this package's own."""
+    return _founder_depths(pedigree, individuals, device).min
+
+
+def genMax(pedigree, individuals=None, device=None):
+    """GENLIB's gen.max(gen, individuals): for each individual the generations to its FARTHEST founder, the longest of all its
+    ascending paths to any founder (0 for a founder); int16.  gen.depths(..., by="proband").max over all founders.  Not named `max`:
+    a module-level name would shadow the builtin this module itself uses.  The orientation and the definition are this package's
+    own."""
+    return _founder_depths(pedigree, individuals, device).max
+
+
+def genMean(pedigree, individuals=None, device=None):
+    """GENLIB's gen.mean(gen, individuals): for each individual the mean number of generations over ALL its ascending paths to
+    founders (0.0 for a founder), every path with weight one; float64, float(sum of the lengths) / float(number of paths).
+    gen.depths(..., by="proband").mean over all founders.  Not named `mean`, like gen.genMin and gen.genMax beside it (`min` and
+    `max` would shadow builtins the module itself uses).  The orientation and the definition are this package's own."""
+    return _founder_depths(pedigree, individuals, device).mean
 
 
 def completeness(pedigree, pro=None, genNo=None, type="MEAN", device=None):

@@ -71,6 +71,8 @@ EXPORTED_SYMBOLS = [
     "genphi_rec_create", "genphi_rec_compute", "genphi_rec_result", "genphi_rec_stats", "genphi_rec_destroy",
     "genphi_dist_create", "genphi_dist_compute", "genphi_dist_result_device", "genphi_dist_result_to_host", "genphi_dist_stats", "genphi_dist_destroy",
     "genphi_ancestors", "genphi_mrca_filter",
+    "genphi_depth_create", "genphi_depth_compute", "genphi_depth_shape", "genphi_depth_result_device", "genphi_depth_result_to_host", "genphi_depth_stats",
+    "genphi_depth_destroy",
     "genphi_comp_create", "genphi_comp_compute", "genphi_comp_generations", "genphi_comp_result_device", "genphi_comp_result_to_host",
     "genphi_comp_counts_to_host", "genphi_comp_totals", "genphi_comp_stats", "genphi_comp_destroy", "genphi_genealogy_depth",
     "genphi_implex_create", "genphi_implex_compute", "genphi_implex_generations", "genphi_implex_frontier_rows", "genphi_implex_counts",
@@ -261,6 +263,21 @@ def lib():
         L.genphi_dist_result_device.restype = C.c_int
         L.genphi_dist_result_to_host.argtypes = [C.c_void_p, C.POINTER(C.c_int16)]
         L.genphi_dist_result_to_host.restype = C.c_int
+        L.genphi_depth_create.argtypes = [C.c_int64, _I64P, _I64P, _I64P, C.c_int64, _I64P, C.c_int64, _I64P, C.c_int32, C.c_int32, C.c_int32,
+                                          C.POINTER(C.c_void_p)]
+        L.genphi_depth_create.restype = C.c_int
+        L.genphi_depth_compute.argtypes = [C.c_void_p, C.c_int32]
+        L.genphi_depth_compute.restype = C.c_int
+        L.genphi_depth_shape.argtypes = [C.c_void_p, _I64P, _I64P]
+        L.genphi_depth_shape.restype = C.c_int
+        L.genphi_depth_result_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _I64P]
+        L.genphi_depth_result_device.restype = C.c_int
+        L.genphi_depth_result_to_host.argtypes = [C.c_void_p, C.POINTER(C.c_int16), C.POINTER(C.c_int16), _I64P, C.POINTER(C.c_double)]
+        L.genphi_depth_result_to_host.restype = C.c_int
+        L.genphi_depth_stats.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), _I64P, C.POINTER(C.c_int32), _I64P]
+        L.genphi_depth_stats.restype = C.c_int
+        L.genphi_depth_destroy.argtypes = [C.c_void_p]
+        L.genphi_depth_destroy.restype = None
         L.genphi_ancestors.argtypes = [C.c_int64, _I64P, _I64P, _I64P, C.c_int64, _I64P, _I64P, C.POINTER(_I64P)]
         L.genphi_ancestors.restype = C.c_int
         L.genphi_mrca_filter.argtypes = [C.c_int64, _I64P, _I64P, _I64P, C.c_int64, _I64P, _I64P, _I64P]
@@ -1269,6 +1286,55 @@ class DistPlan(_SweepPlan):
     def stats(self):
         """dict(sweep_ms, algorithmic_bytes, peak_slots, panel_cols, row_bits, launches) of the last compute()."""
         return self._sweep_stats()
+
+
+GENPHI_DEPTH_MAX_STEPS = 47
+GENPHI_DEPTH_BY = {"pair": 0, "proband": 1, "ancestor": 2}       # GENPHI_DEPTH_BY_PAIR, _BY_PROBAND, _BY_ANCESTOR
+
+
+class DepthPlan(_SweepPlan):
+    """gen.depths' handle (include/genphi.h, genphi_depth_*): planned on the host at construction (KeyError on an unknown proband or
+    ancestor; ValueError for a sweep deeper than GENPHI_DEPTH_MAX_STEPS, for a duplicated ancestor under by="proband", for sums that
+    could exceed Int64 under by="ancestor" and for another `by`; no GPU needed), swept on the GPU by compute().  by: "pair" (n_pro x
+    n_anc), "proband" (reduced over the ancestors on the device) or "ancestor" (reduced over the probands on the device; an int is
+    passed on as it is).  panel_cols / panels_per_launch: the ancestor columns of a panel / the panels a launch covers, 0 = the
+    default rule (tests, A/B)."""
+
+    _prefix = "depth"
+
+    def __init__(self, ind, father, mother, pro_ids, anc_ids, by="pair", panel_cols=0, panels_per_launch=0):
+        if isinstance(by, str) and by not in GENPHI_DEPTH_BY:
+            raise ValueError('by must be "pair", "proband" or "ancestor", not %r' % (by,))
+        self.by = by
+        ind, father, mother, pro_ids, anc_ids = (_i64(a) for a in (ind, father, mother, pro_ids, anc_ids))
+        h = C.c_void_p()
+        rc = lib().genphi_depth_create(len(ind), ind.ctypes.data_as(_I64P), father.ctypes.data_as(_I64P), mother.ctypes.data_as(_I64P), len(pro_ids),
+                                       pro_ids.ctypes.data_as(_I64P), len(anc_ids), anc_ids.ctypes.data_as(_I64P),
+                                       GENPHI_DEPTH_BY[by] if isinstance(by, str) else int(by), int(panel_cols), int(panels_per_launch), C.byref(h))
+        if rc:
+            _raise(rc)
+        self._h = h
+        rows, cols = C.c_int64(), C.c_int64()
+        self._call("shape", C.byref(rows), C.byref(cols))
+        self.shape = {"pair": (rows.value, cols.value), "proband": (rows.value,), "ancestor": (cols.value,)}.get(by, (rows.value, cols.value))
+
+    def result_device(self):
+        """dict(min, max, paths, mean = device pointers; ld = their row pitch in entries) of the resident result."""
+        ptrs = [C.c_void_p() for _ in range(4)]
+        ld = C.c_int64()
+        self._call("result_device", *[C.byref(p) for p in ptrs], C.byref(ld))
+        return dict(zip(("min", "max", "paths", "mean"), (p.value for p in ptrs)), ld=ld.value)
+
+    def result_to_host(self):
+        """(min int16, max int16, paths int64, mean float64), each of shape self.shape; -1, -1, 0, NaN where there is no path."""
+        out = [np.empty(self.shape, dtype=t) for t in (np.int16, np.int16, np.int64, np.float64)]
+        self._call("result_to_host", out[0].ctypes.data_as(C.POINTER(C.c_int16)), out[1].ctypes.data_as(C.POINTER(C.c_int16)),
+                   out[2].ctypes.data_as(_I64P), out[3].ctypes.data_as(C.POINTER(C.c_double)))
+        return tuple(out)
+
+    def stats(self):
+        """dict(sweep_ms, algorithmic_bytes, peak_slots, panel_cols, launches) of the last compute()."""
+        return self._stats(sweep_ms=C.c_double, algorithmic_bytes=C.c_double, peak_slots=C.c_int64, panel_cols=C.c_int32, launches=C.c_int64)
 
 
 GENPHI_COMP_MAX_GENERATIONS = 62

@@ -798,6 +798,56 @@ function meioses(pedigree::GenLib.Pedigree; pro::Vector{Int} = GenLib.pro(pedigr
     end
 end
 
+const DEPTH_BY = Dict(:pair => Int32(0), :proband => Int32(1), :ancestor => Int32(2))      # GENPHI_DEPTH_BY_* (include/genphi.h)
+
+"""
+    depths(pedigree::GenLib.Pedigree; pro = GenLib.pro(pedigree), ancestors = GenLib.founder(pedigree), by = :pair, device = -1)
+
+Over ALL ascending paths from each of `pro` (rows) to each of `ancestors` (columns): `(min, max, mean, paths)` as a named tuple of
+`Matrix{Int16}`, `Matrix{Int16}`, `Matrix{Float64}` and `Matrix{Int64}`; without a path `-1`, `-1`, `NaN`, `0`.  It is
+`GenLib._findDistance` (src/describe.jl:241-279), the length of every ascending path of a pair, reduced to its minimum, maximum,
+mean and count for every pair at once: one exact integer recursion over the generation cuts on the GPU (csrc/depth.hip) instead of
+an enumeration.  `by = :proband` reduces over the ancestors on the device (vectors of `length(pro)`; no ancestor ID twice),
+`by = :ancestor` over the probands (vectors of `length(ancestors)`).  At most 47 generation steps above the probands.
+"""
+function depths(pedigree::GenLib.Pedigree; pro::Vector{Int} = GenLib.pro(pedigree),
+                ancestors::Vector{Int} = GenLib.founder(pedigree), by::Symbol = :pair, device::Integer = -1)
+    haskey(DEPTH_BY, by) || throw(ArgumentError("by must be :pair, :proband or :ancestor"))
+    ind, father, mother, _ = flatten(pedigree)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve ind father mother pro ancestors check(ccall((:genphi_depth_create, libgenphi), Cint,
+        (Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Int64, Ptr{Int64}, Int64, Ptr{Int64}, Int32, Int32, Int32, Ptr{Ptr{Cvoid}}),
+        length(ind), ind, father, mother, length(pro), pro, length(ancestors), ancestors, DEPTH_BY[by], Int32(0), Int32(0), h))
+    try
+        check(ccall((:genphi_depth_compute, libgenphi), Cint, (Ptr{Cvoid}, Int32), h[], Int32(device)))
+        rows, cols = Ref{Int64}(0), Ref{Int64}(0)
+        check(ccall((:genphi_depth_shape, libgenphi), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}), h[], rows, cols))
+        # the library's arrays are row-major rows x cols: cols x rows in Julia's layout
+        lo, hi = Matrix{Int16}(undef, cols[], rows[]), Matrix{Int16}(undef, cols[], rows[])
+        paths, mean = Matrix{Int64}(undef, cols[], rows[]), Matrix{Float64}(undef, cols[], rows[])
+        GC.@preserve lo hi paths mean check(ccall((:genphi_depth_result_to_host, libgenphi), Cint,
+            (Ptr{Cvoid}, Ptr{Int16}, Ptr{Int16}, Ptr{Int64}, Ptr{Float64}), h[], lo, hi, paths, mean))
+        shape(a) = by == :pair ? permutedims(a) : vec(a)
+        return (min = shape(lo), max = shape(hi), mean = shape(mean), paths = shape(paths))
+    finally
+        ccall((:genphi_depth_destroy, libgenphi), Cvoid, (Ptr{Cvoid},), h[])
+    end
+end
+
+"""
+    genMin(pedigree, individuals) / genMax(pedigree, individuals) / genMean(pedigree, individuals)
+
+GENLIB's `gen.min`, `gen.max` and `gen.mean`: per individual the generations to its nearest founder, to its farthest founder, and
+the mean over all its ascending paths to founders; `depths(...; by = :proband)` over all founders.  Not named `min`, `max` and
+`mean`, which would extend `Base`'s functions of those names.  The orientation and the definition are this package's own.
+"""
+genMin(pedigree::GenLib.Pedigree, individuals::Vector{Int} = GenLib.pro(pedigree); device::Integer = -1) =
+    depths(pedigree; pro = individuals, ancestors = GenLib.founder(pedigree), by = :proband, device = device).min
+genMax(pedigree::GenLib.Pedigree, individuals::Vector{Int} = GenLib.pro(pedigree); device::Integer = -1) =
+    depths(pedigree; pro = individuals, ancestors = GenLib.founder(pedigree), by = :proband, device = device).max
+genMean(pedigree::GenLib.Pedigree, individuals::Vector{Int} = GenLib.pro(pedigree); device::Integer = -1) =
+    depths(pedigree; pro = individuals, ancestors = GenLib.founder(pedigree), by = :proband, device = device).mean
+
 """
     ancestor(pedigree::GenLib.Pedigree, IDs::Vector{Int})
 

@@ -766,6 +766,63 @@ int genphi_ancestors(int64_t n_ind, const int64_t *ind, const int64_t *father, c
 int genphi_mrca_filter(int64_t n_ind, const int64_t *ind, const int64_t *father, const int64_t *mother, int64_t n_common,
                        const int64_t *common, int64_t *n_out, int64_t *out);
 
+/* ---- gen.depths: the number, the shortest, the longest and the mean length of the ascents (csrc/depth.hip) ----------------------
+ * Completes _findDistance (src/describe.jl:241-279), which returns the length of every ascending path between a descendant and an
+ * ancestor; GENLIB's gen.min / gen.max / gen.mean are its reductions over the founders.
+ *
+ * depth.  For pro_ids[i] and anc_ids[j], over all ascending paths from the proband to the ancestor (length = meioses; the empty
+ * path counts where the proband is the ancestor): paths = their number P, min / max = the shortest / longest length, mean = S / P
+ * with S the sum of the lengths.  One exact integer recursion over the generation cuts on the host schedule of gen.gc / gen.occ
+ * (csrc/ancestor_sweep.h), on 16-byte elements (csrc/depth_word.h):
+ *     P[x] = P[f] + P[m],  S[x] = S[f] + S[m] + P[x],  min[x] = min(min[f], min[m]) + 1,  max[x] = max(max[f], max[m]) + 1,
+ * then P = 1, S = 0, min = max = 0 where anc_ids[j] == x.  Without a path: paths 0, mean NaN, min = max = -1.
+ *   by = GENPHI_DEPTH_BY_PAIR      n_pro x n_anc entries, rows in pro_ids order (one row per occurrence), columns in anc_ids order
+ *   by = GENPHI_DEPTH_BY_PROBAND   n_pro entries: over the paths from pro_ids[i] to ANY listed ancestor (paths and S added, min and
+ *                                  max taken over the columns), reduced on the device
+ *   by = GENPHI_DEPTH_BY_ANCESTOR  n_anc entries: over the paths from ANY listed proband (each time it is listed) to anc_ids[j],
+ *                                  reduced on the device; no n_pro x n_anc buffer exists
+ * The reductions add and compare integers only (no floating-point atomics): the same call gives the same bytes whatever the
+ * panels, and mean = double(sum S) / double(sum P).  Rules:
+ *   - every proband gets its row, with or without children; a proband listed again gets the same row again;
+ *   - a proband that is itself a requested ancestor has one path of length 0 to itself (1, 0, 0, 0.0);
+ *   - BY_PAIR, BY_ANCESTOR: a duplicated ancestor gives equal entries.  BY_PROBAND: a duplicated ancestor ID -> GENPHI_ERR_ARG
+ *     (every path then has one end point: over all columns fewer than 2^48 paths, and sum S < 47 * 2^48 fits Int64);
+ *   - an unknown ID in pro_ids or anc_ids -> GENPHI_ERR_UNKNOWN_ID (KeyError); n_pro = 0 or n_anc = 0: nothing is computed (the
+ *     entries of a reduction over an empty list are 0, NaN, -1, -1).
+ * Bounds.  The paths between one pair, as strings of father / mother choices, are prefix-free, so P <= 2^L for a longest ascent L
+ * (Kraft), and L <= the level steps of the sweep.  The packed element holds P in 48 bits: create returns GENPHI_ERR_ARG for a sweep
+ * of more than GENPHI_DEPTH_MAX_STEPS = 47 steps.  Then S <= 47 * 2^47 < 2^53 and the mean of a pair is the correctly rounded
+ * quotient of exact operands.  BY_ANCESTOR: create returns GENPHI_ERR_ARG unless n_pro * max(steps, 1) * 2^steps < 2^63.
+ *   create            host only (no GPU): checks IDs, pedigree order, depth and the bounds above, plans cuts, rows and slots.
+ *                     panel_cols / panels_per_launch: the ancestor columns of a panel / the panels a launch covers; 0 = the default
+ *                     rule (gc's rule on 16-byte elements: one panel's slot rows within about 150 MiB, at least 64 columns and a
+ *                     multiple of 8; one panel per launch), any positive value is honoured (tests, A/B); negative -> GENPHI_ERR_ARG
+ *   compute           the sweep on `device` (-1 = current); the result stays resident; GENPHI_ERR_ALLOC before any launch when the
+ *                     result or the slot rows do not fit
+ *   shape             rows x cols of the result: (n_pro, n_anc), (n_pro, 1) or (1, n_anc)
+ *   result_device     device pointers of the four arrays and their common row pitch in entries (BY_PAIR: n_anc rounded up to a
+ *                     multiple of 8, the entries [n_anc, ld) of a row are undefined; else cols)
+ *   result_to_host    rows x cols entries each, row-major, packed; any of the four pointers may be NULL
+ *   stats             device time of the last sweep (HIP events), its algorithmic bytes (source rows read and rows written at 16
+ *                     bytes per panel column, plus 20 bytes per result entry and 24 per accumulator), the slot rows of one panel,
+ *                     the panel width and the kernel launches of the sweep                                                     */
+#define GENPHI_DEPTH_MAX_STEPS 47
+#define GENPHI_DEPTH_BY_PAIR 0
+#define GENPHI_DEPTH_BY_PROBAND 1
+#define GENPHI_DEPTH_BY_ANCESTOR 2
+typedef struct genphi_depth genphi_depth;
+int genphi_depth_create(int64_t n_ind, const int64_t *ind, const int64_t *father, const int64_t *mother,
+                        int64_t n_pro, const int64_t *pro_ids, int64_t n_anc, const int64_t *anc_ids, int32_t by,
+                        int32_t panel_cols, int32_t panels_per_launch, genphi_depth **out);
+int genphi_depth_compute(genphi_depth *h, int32_t device);
+int genphi_depth_shape(const genphi_depth *h, int64_t *rows, int64_t *cols);
+int genphi_depth_result_device(const genphi_depth *h, const int16_t **d_min, const int16_t **d_max, const int64_t **d_paths,
+                               const double **d_mean, int64_t *ld);
+int genphi_depth_result_to_host(genphi_depth *h, int16_t *min, int16_t *max, int64_t *paths, double *mean);
+int genphi_depth_stats(const genphi_depth *h, double *sweep_ms, double *algorithmic_bytes, int64_t *peak_slots, int32_t *panel_cols,
+                       int64_t *launches);
+void genphi_depth_destroy(genphi_depth *h);
+
 /* ---- gen.completeness and gen.depth: ascents by generation (csrc/completeness.hip, csrc/loader.cpp) ---------------------------
  * Replace completeness(pedigree, pro = pro(pedigree); genNo, type), src/describe.jl:73-125, and depth(pedigree), src/describe.jl:43-66.
  *
