@@ -24,6 +24,7 @@ meaning, printed lines and error behaviour as the reference:
                                            # gen.nomen, gen.nowomen, gen.noind, ped.show() (src/describe.jl:6-36, src/create.jl:76-111)
     gen.implex(ped)                        # GENLIB's gen.implex: distinct ancestors by generation (csrc/implex.hip)
     gen.simuSample(ped); gen.simuProb(..)  # GENLIB's gene dropping: marked alleles of ancestors in the probands (csrc/simu.hip)
+    gen.simuIdentity(ped)                  # Jacquard's nine identity coefficients of every pair by gene dropping (csrc/ident.hip)
     gen.descendant(ped, 1); gen.children(ped, 1)   # src/identify.jl:203-215, :77-80 (csrc/loader.cpp)
     gen.phiHist(ped); gen.phiQuantile(ped, 0.5)    # the distribution of the pairwise kinships, on the device (csrc/hist.hip)
 
@@ -36,7 +37,7 @@ from collections import OrderedDict
 import numpy as np
 
 from . import _capi
-from ._capi import PhiPlan, KinshipMatrix, GCPlan, OccPlan, RecPlan, DistPlan, DepthPlan, CompletenessPlan, ImplexPlan, SimuPlan, GenphiDeviceError, GenphiLibraryMissing  # noqa: F401
+from ._capi import PhiPlan, KinshipMatrix, GCPlan, OccPlan, RecPlan, DistPlan, DepthPlan, CompletenessPlan, ImplexPlan, SimuPlan, IdentityPlan, GenphiDeviceError, GenphiLibraryMissing  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
@@ -647,6 +648,74 @@ def simuProb(pedigree, pro, statePro, ancestors, stateAncestors, simulNo=5000, s
         marginal = h.state_counts()[np.arange(h.n_pro), statePro] / float(S)
         by_number = np.bincount(h.match_counts(statePro), minlength=h.n_pro + 1) / float(S)
         return SimuProb(float(by_number[-1]), marginal, by_number, S, h.seed)
+    finally:
+        h.close()
+
+
+class SimuIdentity:
+    """What gen.simuIdentity returns.  pro: the listed probands; counts: int32 (N, N, 9), the simulations in which the ordered
+    pair (i, j) is in Jacquard's condensed state k + 1; simulNo and the seed used; alleles: int64 (n_labels, 2), the ID and the
+    side (0 = from the father) of every founder allele, in label order; labels: int32 (N, 2, simulNo), the labels of the two
+    sides of every proband, or None.  Every coefficient below is an integer count divided by simulNo once, in Float64."""
+
+    def __init__(self, pro, counts, simulNo, seed, alleles, labels):
+        self.pro, self.counts, self.simulNo, self.seed, self.alleles, self.labels = pro, counts, simulNo, seed, alleles, labels
+
+    def __repr__(self):
+        return "SimuIdentity(%d probands, simulNo=%d, seed=%d)" % (len(self.pro), self.simulNo, self.seed)
+
+    @property
+    def delta(self):
+        """(N, N, 9): the estimates of the identity coefficients D1 .. D9."""
+        return self.counts / float(self.simulNo)
+
+    @property
+    def kinship(self):
+        """(N, N): D1 + (D3 + D5 + D7) / 2 + D8 / 4."""
+        c = self.counts.astype(np.int64)
+        return (4 * c[..., 0] + 2 * (c[..., 2] + c[..., 4] + c[..., 6]) + c[..., 7]) / (4.0 * self.simulNo)
+
+    @property
+    def inbreeding(self):
+        """(N,): the share of the simulations in which the two alleles of proband i are identical by descent."""
+        n = np.arange(len(self.pro))
+        return self.counts[n, n, 0] / float(self.simulNo)
+
+    @property
+    def fraternity(self):
+        """(N, N): D7, the dominance relationship; valid under inbreeding."""
+        return self.counts[..., 6] / float(self.simulNo)
+
+    @property
+    def ibd(self):
+        """(N, N, 3): the shares of the simulations with 0, 1, 2 alleles shared in the non-inbred states 9, 8, 7."""
+        return self.counts[..., [8, 7, 6]] / float(self.simulNo)
+
+    @property
+    def inbred(self):
+        """(N, N): D1 + .. + D6, the share of the simulations in which either of the two is inbred: what ibd leaves out."""
+        return self.counts[..., :6].sum(axis=-1, dtype=np.int64) / float(self.simulNo)
+
+
+def simuIdentity(pedigree, pro=None, simulNo=5000, seed=None, labels=False, device=None):
+    """gen.simuIdentity(pedigree, pro = pro(pedigree), simulNo = 5000): Jacquard's nine condensed identity coefficients of every
+    ordered pair of probands (Chapman & Jacquard 1971 studied them on the bundled geneaJi), estimated by gene dropping: every
+    founder allele is dropped down the pedigree under its own label simulNo times, and the identity state of every pair is read
+    off in every simulation.  Returns a SimuIdentity: counts, and from them delta, kinship, inbreeding, fraternity, ibd, inbred.
+
+    The random bits are those of gen.simuSample (Philox4x32-10 keyed on the seed, the individual's ID, the parental side and the
+    absolute word of 64 simulations): the result is a pure function of the pedigree's relations, the probands, the seed and
+    simulNo (include/genphi.h); a sub-list of probands gives the sub-block and gen.branching(pedigree, pro=..) first changes
+    nothing.  seed=None draws 64 fresh bits; pass a seed to repeat a run.  labels=True also returns the probands' labels.  The
+    sweep and the pair counts run on the GPU (csrc/ident.hip).
+
+    KeyError for an unknown ID; ValueError for simulNo outside 1 .. 2^24, an empty pro, or 2^31 or more ordered pairs.  Each call
+    plans, sweeps and frees its own handle."""
+    probands = globals()["pro"](pedigree) if pro is None else np.ascontiguousarray(pro, dtype=np.int64)
+    h = IdentityPlan(pedigree.ind, pedigree.father, pedigree.mother, probands, simul_no=simulNo, seed=seed, labels=labels)
+    try:
+        h.compute(device=device)
+        return SimuIdentity(probands, h.counts_to_host(), h.simul_no, h.seed, h.alleles(), h.labels_to_host() if labels else None)
     finally:
         h.close()
 

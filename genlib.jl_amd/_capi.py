@@ -79,6 +79,8 @@ EXPORTED_SYMBOLS = [
     "genphi_implex_result_to_host", "genphi_implex_totals", "genphi_implex_stats", "genphi_implex_destroy",
     "genphi_simu_create", "genphi_simu_levels", "genphi_simu_rows", "genphi_simu_compute", "genphi_simu_sample_to_host", "genphi_simu_state_counts",
     "genphi_simu_match_counts", "genphi_simu_stats", "genphi_simu_destroy", "genphi_descendants", "genphi_children",
+    "genphi_ident_create", "genphi_ident_levels", "genphi_ident_alleles", "genphi_ident_compute", "genphi_ident_counts_to_host",
+    "genphi_ident_labels_to_host", "genphi_ident_stats", "genphi_ident_destroy",
 ]
 
 _lib = None
@@ -337,6 +339,24 @@ def lib():
         L.genphi_simu_stats.restype = C.c_int
         L.genphi_simu_destroy.argtypes = [C.c_void_p]
         L.genphi_simu_destroy.restype = None
+        _F64P = C.POINTER(C.c_double)
+        L.genphi_ident_create.argtypes = [C.c_int64, _I64P, _I64P, _I64P, C.c_int64, _I64P, C.c_int64, C.c_uint64, C.c_int32, C.c_int32,
+                                          C.POINTER(C.c_void_p)]
+        L.genphi_ident_create.restype = C.c_int
+        L.genphi_ident_levels.argtypes = [C.c_void_p, _I64P, _I32P, _I64P]
+        L.genphi_ident_levels.restype = C.c_int
+        L.genphi_ident_alleles.argtypes = [C.c_void_p, _I64P, _I32P, _I64P, _I32P]
+        L.genphi_ident_alleles.restype = C.c_int
+        L.genphi_ident_compute.argtypes = [C.c_void_p, C.c_int32]
+        L.genphi_ident_compute.restype = C.c_int
+        L.genphi_ident_counts_to_host.argtypes = [C.c_void_p, _I32P]
+        L.genphi_ident_counts_to_host.restype = C.c_int
+        L.genphi_ident_labels_to_host.argtypes = [C.c_void_p, _I32P]
+        L.genphi_ident_labels_to_host.restype = C.c_int
+        L.genphi_ident_stats.argtypes = [C.c_void_p, _F64P, _F64P, _F64P, _F64P, _I32P, _I32P, _I64P, _I32P, _I32P, _I32P, _I32P]
+        L.genphi_ident_stats.restype = C.c_int
+        L.genphi_ident_destroy.argtypes = [C.c_void_p]
+        L.genphi_ident_destroy.restype = None
         L.genphi_descendants.argtypes = [C.c_int64, _I64P, _I64P, _I64P, C.c_int64, _I64P, _I64P, C.POINTER(_I64P)]
         L.genphi_descendants.restype = C.c_int
         L.genphi_children.argtypes = [C.c_int64, _I64P, _I64P, _I64P, C.c_int64, _I64P, C.POINTER(_I64P)]
@@ -1495,6 +1515,69 @@ class SimuPlan(_SweepPlan):
         """dict(sweep_ms, algorithmic_bytes, levels, panel_cols, panels, lanes_per_row, n_live) of the last compute()."""
         return self._stats(sweep_ms=C.c_double, algorithmic_bytes=C.c_double, levels=C.c_int32, panel_cols=C.c_int32, panels=C.c_int64,
                            lanes_per_row=C.c_int32, n_live=C.c_int64)
+
+
+GENPHI_IDENT_FLAG_LABELS = 1
+GENPHI_IDENT_FLAG_ALL_PAIRS = 2
+
+
+class IdentityPlan(_SweepPlan):
+    """The handle of gen.simuIdentity (include/genphi.h, genphi_ident_*): the nine condensed identity states of every pair of
+    probands by gene dropping.  Planned on the host at construction (KeyError on an unknown proband; ValueError for simul_no
+    outside 1 .. 2^24, no probands, 2^31 or more ordered pairs, a negative panel_cols; no GPU needed), swept on the GPU by
+    compute().  seed=None draws 64 fresh bits; .seed reports the seed used.  labels: keep the probands' labels.  panel_cols: the
+    simulations of a panel (0 = the default).  all_pairs: the pair kernel computes every ordered pair (the same counts; an A/B)."""
+
+    _prefix = "ident"
+
+    def __init__(self, ind, father, mother, pro_ids, simul_no=5000, seed=None, labels=False, panel_cols=0, all_pairs=False):
+        pro_ids = _i64(pro_ids).ravel()
+        if seed is None:
+            import secrets
+            seed = secrets.randbits(64)
+        self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.simul_no = int(simul_no)
+        self.labels = bool(labels)
+        ind, father, mother = _i64(ind), _i64(father), _i64(mother)
+        h = C.c_void_p()
+        flags = (GENPHI_IDENT_FLAG_LABELS if labels else 0) | (GENPHI_IDENT_FLAG_ALL_PAIRS if all_pairs else 0)
+        rc = lib().genphi_ident_create(len(ind), ind.ctypes.data_as(_I64P), father.ctypes.data_as(_I64P), mother.ctypes.data_as(_I64P),
+                                       len(pro_ids), pro_ids.ctypes.data_as(_I64P), self.simul_no, self.seed, int(panel_cols), flags, C.byref(h))
+        if rc:
+            _raise(rc)
+        self._h = h
+        self.n_pro = len(pro_ids)
+        n_live, levels, n_labels, planes = C.c_int64(), C.c_int32(), C.c_int64(), C.c_int32()
+        self._call("levels", C.byref(n_live), C.byref(levels), None)
+        self._call("alleles", C.byref(n_labels), C.byref(planes), None, None)
+        self.n_live, self.levels, self.n_labels, self.planes = int(n_live.value), int(levels.value), int(n_labels.value), int(planes.value)
+
+    def rows_per_level(self):
+        """The live rows of every level (host only)."""
+        out = np.empty(self.levels, dtype=np.int64)
+        self._call("levels", None, None, out.ctypes.data_as(_I64P))
+        return out
+
+    def alleles(self):
+        """The allele table (host only): int64 (n_labels, 2), the ID and the side (0 = from the father) of every label."""
+        ids, sides = np.empty(self.n_labels, np.int64), np.empty(self.n_labels, np.int32)
+        self._call("alleles", None, None, ids.ctypes.data_as(_I64P), sides.ctypes.data_as(C.POINTER(C.c_int32)))
+        return np.stack([ids, sides.astype(np.int64)], axis=1)
+
+    def counts_to_host(self):
+        """The (n_pro, n_pro, 9) int32 counts: the simulations in which the ordered pair (i, j) is in state k + 1."""
+        return self._out("counts_to_host", (self.n_pro, self.n_pro, 9), np.int32, C.c_int32)
+
+    def labels_to_host(self):
+        """The (n_pro, 2, simul_no) int32 labels of the probands' two sides.  ValueError unless created with labels=True."""
+        return self._out("labels_to_host", (self.n_pro, 2, self.simul_no), np.int32, C.c_int32)
+
+    def stats(self):
+        """dict(sweep_ms, pair_ms, algorithmic_bytes, word_ops, levels, panel_cols, panels, planes, tile_rows, tile_cols,
+        lanes_per_row) of the last compute()."""
+        return self._stats(sweep_ms=C.c_double, pair_ms=C.c_double, algorithmic_bytes=C.c_double, word_ops=C.c_double, levels=C.c_int32,
+                           panel_cols=C.c_int32, panels=C.c_int64, planes=C.c_int32, tile_rows=C.c_int32, tile_cols=C.c_int32,
+                           lanes_per_row=C.c_int32)
 
 
 def genealogy_depth(ind, father, mother, leaves_only=False):

@@ -988,6 +988,76 @@ int genphi_simu_stats(const genphi_simu *h, double *sweep_ms, double *algorithmi
                       int64_t *panels, int32_t *lanes_per_row, int64_t *n_live);
 void genphi_simu_destroy(genphi_simu *h);
 
+/* ---- gen.simuIdentity: identity coefficients by gene dropping (csrc/ident.hip, csrc/ident.cpp) ------------------------------------
+ * Jacquard's nine condensed identity states of every pair of probands, counted over S simulations in which every founder allele
+ * is dropped down the pedigree under its own label.  The reference has no form of it, so this text is the definition.
+ * Inputs.  A pedigree.  pro_ids, the listed probands: any individuals, at least one; repeats are allowed and give repeated rows
+ * and columns.  simul_no = S with 1 <= S <= 2^24.  A 64-bit seed.
+ * Live set.  The listed probands and all their ancestors.  level(x) = 0 when neither parent is known, else 1 + the largest level
+ * of the known parents.  Rows are ordered by level, and by rank order within a level.
+ * Founder alleles.  Every live x has two sides: 0 = the copy from the father, 1 = the copy from the mother.  A side whose parent
+ * is unknown carries a founder allele; half-founders have one.  The allele table lists these (ID, side) pairs ascending by ID,
+ * then side.  The label of an allele is its position in the table, n_labels is the table's length, and B = max(1, bit length of
+ * n_labels - 1) planes.  (A live set has an individual without parents, so n_labels >= 2.)
+ * State.  Per live x and simulation s there are two labels, LP_x[s] and LM_x[s].  Simulation s is bit s % 64 of word w = s / 64.
+ * Rule.
+ *   - A side with an unknown parent holds its own label in every simulation.
+ *   - With a known father f: LP_x[s] = bit s of T ? LP_f[s] : LM_f[s], where T = R(seed, ID(x), 0, w).  With a known mother m
+ *     the same from LP_m, LM_m with T = R(seed, ID(x), 1, w).
+ *   - R is the gene-dropping word of this header (above), unchanged: the same Philox4x32-10, key, counter and word selection.
+ *   - Under selfing the two sides draw independent words.  Nothing blocks a path: there are no listed ancestors.
+ * Identity state.  For the ordered pair (i, j) of listed probands in simulation s, take a = LP_i, b = LM_i, c = LP_j, d = LM_j.
+ * Jacquard's condensed states are
+ *   1. a=b, c=d, a=c            4. a=b, c!=d, a not in {c, d}      7. a!=b, c!=d, {a, b} = {c, d}
+ *   2. a=b, c=d, a!=c           5. a!=b, c=d, c in {a, b}          8. a!=b, c!=d, exactly one allele shared
+ *   3. a=b, c!=d, a in {c, d}   6. a!=b, c=d, c not in {a, b}      9. a!=b, c!=d, none shared
+ * The result is counts[i, j, k-1], the number of simulations s < S in state k: an Int32 array of n_pro x n_pro x 9, row-major.
+ * Bits at positions >= S are never counted.
+ * Invariants, all exact.  The nine counts of a pair add up to S.  counts[j, i] is counts[i, j] with the states 3 <-> 5 and
+ * 4 <-> 6 exchanged.  A diagonal pair, or a pair of repeats of one ID, is in state 1 or 7 only.  The result is a pure function of
+ * (pedigree relations, proband IDs, seed, S): it does not depend on the panel width; a sub-list of probands gives the sub-block;
+ * gen.branching(ped, pro=P) first changes nothing; the label rows of S = 64 are the first 64 columns of those of S = 5000.
+ * Cross-check with genphi_simu_*: list some individuals with both parents unknown as its ancestors with states 2 (or 1), under
+ * the same seed; proband i's count in simulation s is then the number of its two labels that belong to those founders (state 1:
+ * to their side-0 alleles).
+ * Errors.  An unknown ID -> GENPHI_ERR_UNKNOWN_ID.  GENPHI_ERR_ARG: S out of range; no probands; n_pro^2 >= 2^31; n_labels >
+ * 2^31 - 1; a negative panel_cols; an unknown flag.  GENPHI_ERR_ALLOC before any launch, when the device memory does not hold all
+ * of the counts (36 n_pro^2 bytes), the optional labels and the rows of even a 128-column panel.
+ * Method.  Plane b of a side is the bit row of bit b of its labels: a meiosis is (T & P_parent[b]) | (~T & M_parent[b]) on all B
+ * planes with one T, one launch per level >= 1 and panel; two labels are equal where ~OR_b (x_b ^ y_b) is set.  The pair kernel
+ * owns tiles of probands x probands and counts the states by popcounts of AND/OR combinations of the six equality words.
+ *   create            host only (no GPU): checks IDs and pedigree order; plans the live set, the levels, the parent rows and the
+ *                     allele table.  panel_cols: the simulations of a panel, 0 = the default (all of S, or the widest that fits
+ *                     the device), else rounded up to a multiple of 128 and cut to S (tests, A/B).  flags: GENPHI_IDENT_FLAG_LABELS
+ *                     keeps the probands' labels; GENPHI_IDENT_FLAG_ALL_PAIRS computes every ordered pair instead of the pairs
+ *                     of tiles on or above the diagonal plus their mirror images (the same result; the A/B of the bench)
+ *   levels            n_live, the number of levels, and the rows of every level (room for that many); host only, any may be NULL
+ *   alleles           n_labels, B, and the table as IDs and sides (room for n_labels each); host only, any may be NULL
+ *   compute           the sweep on `device` (-1 = current); counts (and labels) stay resident
+ *   counts_to_host    out: n_pro x n_pro x 9 Int32, row-major
+ *   labels_to_host    out: n_pro x 2 x S Int32, row-major: LP and LM of proband i; GENPHI_ERR_ARG without GENPHI_IDENT_FLAG_LABELS
+ *   stats             of the last compute, by HIP events: the device time of init and level steps, and of gather and pair kernel,
+ *                     summed over the panels; the algorithmic bytes of the steps (per side with a known parent: two runs of B
+ *                     planes read and one written, 16 bytes per plane and pair of words); the word operations of the pair kernel
+ *                     (ordered pairs computed -- n_pro (n_pro + 1) / 2, or n_pro^2 under ALL_PAIRS -- x words x (12 B + 40));
+ *                     levels; the columns of a panel; the panels; B; the pair kernel's tile rows and columns; the lanes per row
+ *                     of the step kernel                                                                                      */
+#define GENPHI_IDENT_FLAG_LABELS 1
+#define GENPHI_IDENT_FLAG_ALL_PAIRS 2
+typedef struct genphi_ident genphi_ident;
+int genphi_ident_create(int64_t n_ind, const int64_t *ind, const int64_t *father, const int64_t *mother,
+                        int64_t n_pro, const int64_t *pro_ids, int64_t simul_no, uint64_t seed, int32_t panel_cols, int32_t flags,
+                        genphi_ident **out);
+int genphi_ident_levels(const genphi_ident *h, int64_t *n_live, int32_t *levels, int64_t *rows_per_level);
+int genphi_ident_alleles(const genphi_ident *h, int64_t *n_labels, int32_t *planes, int64_t *ids, int32_t *sides);
+int genphi_ident_compute(genphi_ident *h, int32_t device);
+int genphi_ident_counts_to_host(genphi_ident *h, int32_t *out);
+int genphi_ident_labels_to_host(genphi_ident *h, int32_t *out);
+int genphi_ident_stats(const genphi_ident *h, double *sweep_ms, double *pair_ms, double *algorithmic_bytes, double *word_ops,
+                       int32_t *levels, int32_t *panel_cols, int64_t *panels, int32_t *planes, int32_t *tile_rows, int32_t *tile_cols,
+                       int32_t *lanes_per_row);
+void genphi_ident_destroy(genphi_ident *h);
+
 /* gen.descendant and gen.children (src/identify.jl:203-215, :77-80), host only: the strict descendants of ids[0 .. n_ids) (the
  * union over them), and the children of one ID, ascending; *out is allocated by the library (genphi_free).  No order of the
  * pedigree is assumed.  Unknown ID -> GENPHI_ERR_UNKNOWN_ID.                                                                  */
