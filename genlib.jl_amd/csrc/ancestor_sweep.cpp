@@ -8,20 +8,6 @@
 
 namespace genphi {
 
-void Ranks::init(int64_t n, const int64_t *ind)
-{
-    int64_t lo = INT64_MAX, hi = INT64_MIN;
-    for (int64_t i = 0; i < n; ++i) { lo = std::min(lo, ind[i]); hi = std::max(hi, ind[i]); }
-    direct = n > 0 && lo >= 0 && hi < 3 * n + 1024;
-    if (direct) {
-        table.assign(static_cast<size_t>(hi) + 1, -1);
-        for (int64_t i = 0; i < n; ++i) table[ind[i]] = static_cast<int32_t>(i);
-    } else {
-        map.reserve(static_cast<size_t>(n) * 2);
-        for (int64_t i = 0; i < n; ++i) map.emplace(ind[i], static_cast<int32_t>(i));
-    }
-}
-
 int plan_sweep(SweepSchedule &h, int64_t n_ind, const int64_t *ind, const int64_t *father, const int64_t *mother, int64_t n_pro,
                const int64_t *pro_ids, int64_t n_anc, const int64_t *anc_ids, const SweepOptions &sopt, std::string &err)
 {

@@ -20,8 +20,9 @@
 #pragma once
 #include <cstdint>
 #include <string>
-#include <unordered_map>
 #include <vector>
+
+#include "pedigree_index.h"
 
 namespace genphi {
 
@@ -57,20 +58,6 @@ struct SweepSchedule {
     std::vector<int32_t> pro_slots;          // Emit::None: slots of the distinct probands whose row is not zero
     std::vector<char> anc_is_pro;            // per ancestor column: the ancestor is one of the probands
     int32_t n_generations = 0;               // every_member: 1 + the longest ascent of any listed proband (0 without probands)
-};
-
-// ID -> rank (a direct table for dense non-negative IDs, else a hash map)
-struct Ranks {
-    std::vector<int32_t> table;
-    std::unordered_map<int64_t, int32_t> map;
-    bool direct = false;
-    void init(int64_t n, const int64_t *ind);
-    int32_t find(int64_t id) const
-    {
-        if (direct) return (id < 0 || id >= static_cast<int64_t>(table.size())) ? -1 : table[id];
-        auto it = map.find(id);
-        return it == map.end() ? -1 : it->second;
-    }
 };
 
 // Returns 0 or a GENPHI_ERR_* code (include/genphi.h); message in err.  Validates the pedigree (order, duplicates) and the IDs.

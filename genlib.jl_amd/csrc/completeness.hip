@@ -110,12 +110,12 @@ struct genphi_comp : SweepDevice {
     int32_t G = 0, pitch = 0;                // generations (result columns), entries per slot row
     bool totals_only = false;
     genphi::SweepSchedule sched;             // host schedule (ancestor_sweep.h)
-    long long *d_counts = nullptr;           // n_pro x G (not on a totals-only handle)
-    double *d_result = nullptr;              // n_pro x G percentages (not on a totals-only handle)
-    unsigned long long *d_totals = nullptr;  // G totals (a totals-only handle: written by the sweep; else on request)
-    int4 *d_items = nullptr;
+    DevBuf<long long> d_counts;              // n_pro x G (not on a totals-only handle)
+    DevBuf<double> d_result;                 // n_pro x G percentages (not on a totals-only handle)
+    DevBuf<unsigned long long> d_totals;     // G totals (a totals-only handle: written by the sweep; else on request)
+    DevBuf<int4> d_items;
     bool totals_ready = false;
-    genphi_comp() { own(&d_counts, &d_result, &d_totals, &d_items); }
+    genphi_comp() { own(d_counts, d_result, d_totals, d_items); }
     size_t result_entries() const { return static_cast<size_t>(n_pro) * static_cast<size_t>(G); }
     bool empty() const { return n_pro == 0 || G == 0; }
     // a total is at most n_pro 2^(G - 1)
@@ -140,26 +140,28 @@ int compute_impl(genphi_comp *h, int32_t device)
     L.C = G; L.Cp = pitch; L.n_panels = 1; L.per_launch = 1;
     L.stride = static_cast<long long>(L.slots) * pitch;
     L.slot_bytes = static_cast<size_t>(L.stride) * sizeof(long long);
-    if (!h->d_slots) {
+    if (!h->d_slots.get()) {
         double usable = 0.0;
         if (int rc = h->usable_bytes(usable, 0)) return rc;
         const double need = static_cast<double>(L.slot_bytes) + 16.0 * static_cast<double>(n_res) + 16.0 * static_cast<double>(h->sched.items.size()) + (64 << 20);
         if (need > usable)
             return genphi_set_error(GENPHI_ERR_ALLOC, "gen.completeness: " + std::to_string(static_cast<size_t>(need) >> 20) +
                                                           " MiB of slot rows and result do not fit on device " + std::to_string(device));
-        if (int rc = h->reserve_slots(L.slot_bytes)) return rc;
+        GENPHI_HIP_TRY(h->d_slots.reserve(L.slot_bytes));
     }
-    if (!h->d_totals) GENPHI_HIP_TRY(genphi::cached_malloc(reinterpret_cast<void **>(&h->d_totals), static_cast<size_t>(G) * sizeof(unsigned long long)));
-    if (n_res && !h->d_counts) GENPHI_HIP_TRY(genphi::cached_malloc(reinterpret_cast<void **>(&h->d_counts), n_res * sizeof(long long)));
-    if (n_res && !h->d_result) GENPHI_HIP_TRY(genphi::cached_malloc(reinterpret_cast<void **>(&h->d_result), n_res * sizeof(double)));
-    if (int rc = h->upload(&h->d_items, h->sched.items)) return rc;
+    GENPHI_HIP_TRY(h->d_totals.reserve(static_cast<size_t>(G)));
+    if (n_res) {
+        GENPHI_HIP_TRY(h->d_counts.reserve(n_res));
+        GENPHI_HIP_TRY(h->d_result.reserve(n_res));
+    }
+    if (int rc = h->upload(h->d_items, h->sched.items)) return rc;
     const double row_bytes = 8.0 * G;
     SweepRun run;
     if (int rc = run.begin(*h, h->totals_only ? row_bytes : 2.0 * row_bytes * static_cast<double>(h->n_pro))) return rc;
     // (every listed proband is in the last list: each result row is written whole, nothing is pre-filled)
-    if (h->totals_only) GENPHI_HIP_TRY(hipMemsetAsync(h->d_totals, 0, static_cast<size_t>(G) * sizeof(unsigned long long), h->stream));
+    if (h->totals_only) GENPHI_HIP_TRY(hipMemsetAsync(h->d_totals, 0, h->d_totals.bytes(), h->stream));
     const int lpr = lanes_per_row(G);
-    long long *slots = static_cast<long long *>(h->d_slots);
+    long long *slots = h->slots<long long>();
     auto launch = [&](const ListLaunch &l) {
         if (!l.to_result) {
             GENPHI_LPR_SWITCH(lpr, (comp_step_kernel<LPR, false><<<l.grid.x, 256, 0, h->stream>>>(l.items, l.n_items, slots, pitch, G, nullptr, nullptr)));
@@ -219,7 +221,7 @@ int genphi_comp_result_device(const genphi_comp *h, const double **d_ptr, int64_
 {
     if (!h || !h->computed) return genphi_set_error(GENPHI_ERR_ARG, "genphi_comp_result_device: nothing computed");
     if (h->totals_only) return genphi_set_error(GENPHI_ERR_ARG, "genphi_comp_result_device: a totals-only handle has no n_pro x G result");
-    put(d_ptr, h->d_result);
+    put(d_ptr, h->d_result.get());
     put(ld, h->G);
     return GENPHI_OK;
 }
@@ -230,7 +232,7 @@ int genphi_comp_result_to_host(genphi_comp *h, double *out)
     if (h->totals_only) return genphi_set_error(GENPHI_ERR_ARG, "genphi_comp_result_to_host: a totals-only handle has no n_pro x G result");
     if (h->empty()) return GENPHI_OK;
     if (!out) return genphi_set_error(GENPHI_ERR_ARG, "genphi_comp_result_to_host: out is NULL");
-    return h->copy_out(out, h->d_result, h->result_entries() * sizeof(double), "gen.completeness");
+    return h->copy_out(out, h->d_result, h->d_result.bytes(), "gen.completeness");
 }
 
 int genphi_comp_counts_to_host(genphi_comp *h, int64_t *out)
@@ -239,7 +241,7 @@ int genphi_comp_counts_to_host(genphi_comp *h, int64_t *out)
     if (h->totals_only) return genphi_set_error(GENPHI_ERR_ARG, "genphi_comp_counts_to_host: a totals-only handle has no n_pro x G result");
     if (h->empty()) return GENPHI_OK;
     if (!out) return genphi_set_error(GENPHI_ERR_ARG, "genphi_comp_counts_to_host: out is NULL");
-    return h->copy_out(out, h->d_counts, h->result_entries() * sizeof(long long), "gen.completeness");
+    return h->copy_out(out, h->d_counts, h->d_counts.bytes(), "gen.completeness");
 }
 
 int genphi_comp_totals(genphi_comp *h, int64_t *out)

@@ -271,12 +271,12 @@ struct genphi_depth : SweepDevice {
     int64_t n_pro = 0, n_anc = 0, ld = 0;
     genphi::SweepSchedule sched;             // host schedule (ancestor_sweep.h)
     int32_t panel_arg = 0, group_arg = 0;    // create's panel_cols / panels_per_launch (0 = default rule)
-    char *d_result = nullptr;                // the four arrays, one after the other: paths, mean, min, max
-    char *d_acc = nullptr;                   // the reductions' accumulators: paths, sum, close, far
-    int4 *d_items = nullptr;
-    int *d_oh = nullptr;
+    DevBuf<char> d_result;                   // the four arrays, one after the other: paths, mean, min, max
+    DevBuf<char> d_acc;                      // the reductions' accumulators: paths, sum, close, far
+    DevBuf<int4> d_items;
+    DevBuf<int> d_oh;
     int32_t panel_cols = 0;
-    genphi_depth() { own(&d_result, &d_acc, &d_items, &d_oh); }
+    genphi_depth() { own(d_result, d_acc, d_items, d_oh); }
     int64_t rows() const { return by == GENPHI_DEPTH_BY_ANCESTOR ? 1 : n_pro; }
     int64_t cols() const { return by == GENPHI_DEPTH_BY_PROBAND ? 1 : n_anc; }
     size_t entries() const { return static_cast<size_t>(rows()) * static_cast<size_t>(ld); }                 // with the rows' padding
@@ -286,14 +286,16 @@ struct genphi_depth : SweepDevice {
     DepthOut out() const
     {
         const size_t n = entries();
-        return DepthOut{reinterpret_cast<long long *>(d_result), reinterpret_cast<double *>(d_result + 8 * n), reinterpret_cast<short *>(d_result + 16 * n),
-                        reinterpret_cast<short *>(d_result + 18 * n), static_cast<long long>(ld)};
+        char *r = d_result.get();
+        return DepthOut{reinterpret_cast<long long *>(r), reinterpret_cast<double *>(r + 8 * n), reinterpret_cast<short *>(r + 16 * n),
+                        reinterpret_cast<short *>(r + 18 * n), static_cast<long long>(ld)};
     }
     DepthAcc acc() const
     {
         const size_t n = acc_entries();
-        return DepthAcc{reinterpret_cast<unsigned long long *>(d_acc), reinterpret_cast<unsigned long long *>(d_acc + 8 * n),
-                        reinterpret_cast<unsigned *>(d_acc + 16 * n), reinterpret_cast<unsigned *>(d_acc + 20 * n)};
+        char *a = d_acc.get();
+        return DepthAcc{reinterpret_cast<unsigned long long *>(a), reinterpret_cast<unsigned long long *>(a + 8 * n),
+                        reinterpret_cast<unsigned *>(a + 16 * n), reinterpret_cast<unsigned *>(a + 20 * n)};
     }
     bool empty() const { return n_anc == 0 || n_pro == 0; }
 };
@@ -302,7 +304,7 @@ namespace {
 
 void launch_list(genphi_depth *h, int lpr, const ListLaunch &l, const genphi::PanelLayout &L)
 {
-    DepthWord *slots = static_cast<DepthWord *>(h->d_slots);
+    DepthWord *slots = h->slots<DepthWord>();
     const int n_anc = static_cast<int>(h->n_anc), C = static_cast<int>(L.C);
     if (!l.to_result) {
         GENPHI_LPR_SWITCH(lpr, (depth_step_kernel<LPR, false><<<l.grid, 256, 0, h->stream>>>(l.items, h->d_oh, l.n_items, slots, L.stride, L.Cp, C, n_anc,
@@ -326,12 +328,12 @@ int compute_impl(genphi_depth *h, int32_t device)
     if (int rc = h->select(device)) return rc;
     const size_t res_bytes = h->result_bytes(), acc_bytes = h->acc_bytes();
     genphi::PanelLayout L;
-    if (int rc = h->size_panels(L, kDepthPanels, h->sched, h->n_anc, h->panel_arg, h->group_arg, res_bytes + acc_bytes, h->d_result != nullptr, "gen.depths"))
+    if (int rc = h->size_panels(L, kDepthPanels, h->sched, h->n_anc, h->panel_arg, h->group_arg, res_bytes + acc_bytes, h->d_result.get() != nullptr, "gen.depths"))
         return rc;
-    if (!h->d_result) GENPHI_HIP_TRY(genphi::cached_malloc(reinterpret_cast<void **>(&h->d_result), res_bytes));
-    if (acc_bytes && !h->d_acc) GENPHI_HIP_TRY(genphi::cached_malloc(reinterpret_cast<void **>(&h->d_acc), acc_bytes));
-    if (int rc = h->upload(&h->d_items, h->sched.items)) return rc;
-    if (int rc = h->upload(&h->d_oh, h->sched.oh_cols)) return rc;
+    GENPHI_HIP_TRY(h->d_result.reserve(res_bytes));
+    if (acc_bytes) GENPHI_HIP_TRY(h->d_acc.reserve(acc_bytes));
+    if (int rc = h->upload(h->d_items, h->sched.items)) return rc;
+    if (int rc = h->upload(h->d_oh, h->sched.oh_cols)) return rc;
     h->panel_cols = static_cast<int32_t>(L.C);
     SweepRun run;
     if (int rc = run.begin(*h, 20.0 * static_cast<double>(h->rows()) * static_cast<double>(h->cols()))) return rc;
@@ -342,7 +344,7 @@ int compute_impl(genphi_depth *h, int32_t device)
         GENPHI_HIP_TRY(hipMemsetAsync(h->d_result, 0, 8 * n, h->stream));
         GENPHI_HIP_TRY(hipMemsetAsync(h->d_result + 8 * n, 0xFF, 12 * n, h->stream));
     } else {
-        GENPHI_HIP_TRY(hipMemsetAsync(h->d_acc, 0, acc_bytes, h->stream));
+        GENPHI_HIP_TRY(hipMemsetAsync(h->d_acc, 0, h->d_acc.bytes(), h->stream));
     }
     const int lpr = lanes_per_row(L.Cp);
     if (int rc = sweep_lists(run, h->sched, h->d_items, kDepthPanels, L, h->n_anc, 4 * (64 / lpr), h->by == GENPHI_DEPTH_BY_ANCESTOR ? kDepthGroupRows : 1,
@@ -422,7 +424,7 @@ int genphi_depth_result_device(const genphi_depth *h, const int16_t **d_min, con
                                int64_t *ld)
 {
     if (!h || !h->computed) return genphi_set_error(GENPHI_ERR_ARG, "genphi_depth_result_device: nothing computed");
-    const DepthOut o = h->d_result ? h->out() : DepthOut{};
+    const DepthOut o = h->d_result.get() ? h->out() : DepthOut{};
     put(d_min, reinterpret_cast<const int16_t *>(o.min));
     put(d_max, reinterpret_cast<const int16_t *>(o.max));
     put(d_paths, reinterpret_cast<const int64_t *>(o.paths));

@@ -112,11 +112,11 @@ struct genphi_dist : SweepDevice {
     int64_t n_pro = 0, n_anc = 0, ld = 0;
     genphi::SweepSchedule sched;             // host schedule (ancestor_sweep.h)
     int32_t panel_env = 0, group_env = 0;    // GENPHI_DIST_PANEL / GENPHI_DIST_PANELS_PER_LAUNCH (0 = default rule)
-    short *d_result = nullptr;               // n_pro rows of ld entries
-    int4 *d_items = nullptr;
-    int *d_oh = nullptr;
+    DevBuf<short> d_result;                  // n_pro rows of ld entries
+    DevBuf<int4> d_items;
+    DevBuf<int> d_oh;
     int32_t panel_cols = 0;
-    genphi_dist() { own(&d_result, &d_items, &d_oh); }
+    genphi_dist() { own(d_result, d_items, d_oh); }
     size_t result_bytes() const { return static_cast<size_t>(n_pro) * static_cast<size_t>(ld) * sizeof(short); }
     bool empty() const { return n_anc == 0 || n_pro == 0; }
 };
@@ -125,7 +125,7 @@ namespace {
 
 void launch_list(genphi_dist *h, int lpr, const ListLaunch &l, bool aligned, const genphi::PanelLayout &L)
 {
-    unsigned short *slots = static_cast<unsigned short *>(h->d_slots);
+    unsigned short *slots = h->slots<unsigned short>();
     const int n_anc = static_cast<int>(h->n_anc), C = static_cast<int>(L.C);
     if (!l.to_result) {
         GENPHI_LPR_SWITCH(lpr, (dist_step_kernel<LPR, false, false><<<l.grid, 256, 0, h->stream>>>(l.items, h->d_oh, l.n_items, slots, L.stride, L.Cp,
@@ -144,11 +144,11 @@ int compute_impl(genphi_dist *h, int32_t device)
     if (int rc = h->select(device)) return rc;
     const size_t res_bytes = h->result_bytes();
     genphi::PanelLayout L;
-    if (int rc = h->size_panels(L, kDistPanels, h->sched, h->n_anc, h->panel_env, h->group_env, res_bytes, h->d_result != nullptr, "gen.meioses"))
+    if (int rc = h->size_panels(L, kDistPanels, h->sched, h->n_anc, h->panel_env, h->group_env, res_bytes, h->d_result.get() != nullptr, "gen.meioses"))
         return rc;
-    if (!h->d_result) GENPHI_HIP_TRY(genphi::cached_malloc(reinterpret_cast<void **>(&h->d_result), res_bytes));
-    if (int rc = h->upload(&h->d_items, h->sched.items)) return rc;
-    if (int rc = h->upload(&h->d_oh, h->sched.oh_cols)) return rc;
+    GENPHI_HIP_TRY(h->d_result.reserve(res_bytes / sizeof(short)));
+    if (int rc = h->upload(h->d_items, h->sched.items)) return rc;
+    if (int rc = h->upload(h->d_oh, h->sched.oh_cols)) return rc;
     h->panel_cols = static_cast<int32_t>(L.C);
     SweepRun run;
     if (int rc = run.begin(*h, static_cast<double>(h->n_pro) * static_cast<double>(h->n_anc) * sizeof(short))) return rc;
@@ -194,7 +194,7 @@ int genphi_dist_compute(genphi_dist *h, int32_t device) { return compute_entry(h
 int genphi_dist_result_device(const genphi_dist *h, const int16_t **d_ptr, int64_t *ld)
 {
     if (!h || !h->computed) return genphi_set_error(GENPHI_ERR_ARG, "genphi_dist_result_device: nothing computed");
-    put(d_ptr, h->d_result);
+    put(d_ptr, h->d_result.get());
     put(ld, h->ld);
     return GENPHI_OK;
 }

@@ -101,11 +101,11 @@ struct genphi_gc : SweepDevice {
     int64_t n_pro = 0, n_anc = 0;
     genphi::SweepSchedule sched;             // host schedule (ancestor_sweep.h, Emit::LeafFirst)
     int32_t panel_env = 0, group_env = 0;    // GENPHI_GC_PANEL / GENPHI_GC_PANELS_PER_LAUNCH (0 = default rule)
-    float *d_result = nullptr;
-    int4 *d_items = nullptr;
-    int *d_oh = nullptr;
+    DevBuf<float> d_result;
+    DevBuf<int4> d_items;
+    DevBuf<int> d_oh;
     int32_t panel_cols = 0;
-    genphi_gc() { own(&d_result, &d_items, &d_oh); }
+    genphi_gc() { own(d_result, d_items, d_oh); }
     size_t result_bytes() const { return static_cast<size_t>(n_pro) * static_cast<size_t>(n_anc) * sizeof(float); }
     bool empty() const { return n_pro == 0 || n_anc == 0; }
 };
@@ -117,10 +117,10 @@ int compute_impl(genphi_gc *h, int32_t device)
     if (int rc = h->select(device)) return rc;
     const size_t res_bytes = h->result_bytes();
     genphi::PanelLayout L;
-    if (int rc = h->size_panels(L, kGcPanels, h->sched, h->n_anc, h->panel_env, h->group_env, res_bytes, h->d_result != nullptr, "gen.gc")) return rc;
-    if (!h->d_result) GENPHI_HIP_TRY(genphi::cached_malloc(reinterpret_cast<void **>(&h->d_result), res_bytes));
-    if (int rc = h->upload(&h->d_items, h->sched.items)) return rc;
-    if (int rc = h->upload(&h->d_oh, h->sched.oh_cols)) return rc;
+    if (int rc = h->size_panels(L, kGcPanels, h->sched, h->n_anc, h->panel_env, h->group_env, res_bytes, h->d_result.get() != nullptr, "gen.gc")) return rc;
+    GENPHI_HIP_TRY(h->d_result.reserve(res_bytes / sizeof(float)));
+    if (int rc = h->upload(h->d_items, h->sched.items)) return rc;
+    if (int rc = h->upload(h->d_oh, h->sched.oh_cols)) return rc;
     h->panel_cols = static_cast<int32_t>(L.C);
     SweepRun run;
     if (int rc = run.begin(*h, static_cast<double>(res_bytes))) return rc;
@@ -128,10 +128,10 @@ int compute_impl(genphi_gc *h, int32_t device)
     const int lpr = lanes_per_row(L.Cp / 2);
     auto launch = [&](const ListLaunch &l) {
         if (l.to_result)
-            launch_step<true>(lpr, l.grid, h->stream, l.items, h->d_oh, l.n_items, static_cast<double *>(h->d_slots), L.stride, L.Cp,
+            launch_step<true>(lpr, l.grid, h->stream, l.items, h->d_oh, l.n_items, h->slots<double>(), L.stride, L.Cp,
                               static_cast<int>(L.C), static_cast<int>(h->n_anc), l.panel0, h->d_result);
         else
-            launch_step<false>(lpr, l.grid, h->stream, l.items, h->d_oh, l.n_items, static_cast<double *>(h->d_slots), L.stride, L.Cp,
+            launch_step<false>(lpr, l.grid, h->stream, l.items, h->d_oh, l.n_items, h->slots<double>(), L.stride, L.Cp,
                                static_cast<int>(L.C), static_cast<int>(h->n_anc), l.panel0, h->d_result);
     };
     if (int rc = sweep_lists(run, h->sched, h->d_items, kGcPanels, L, h->n_anc, 4 * (64 / lpr), 1, launch)) return rc;
@@ -165,7 +165,7 @@ int genphi_gc_compute(genphi_gc *h, int32_t device) { return compute_entry(h, de
 int genphi_gc_result_device(const genphi_gc *h, const float **d_ptr, int64_t *ld)
 {
     if (!h || !h->computed) return genphi_set_error(GENPHI_ERR_ARG, "genphi_gc_result_device: nothing computed");
-    put(d_ptr, h->d_result);
+    put(d_ptr, h->d_result.get());
     put(ld, h->n_anc);
     return GENPHI_OK;
 }

@@ -14,16 +14,11 @@
 #include <string>
 #include <vector>
 
+#include "drop_plan.h"
+
 namespace genphi {
 
-struct IdentPlan {
-    int64_t n_pro = 0, n_live = 0;
-    int32_t n_levels = 0;
-    std::vector<int64_t> level_rows;         // rows per level
-    std::vector<int64_t> level_begin;        // n_levels + 1: level k owns the rows [level_begin[k], level_begin[k + 1])
-    std::vector<int32_t> fa_row, mo_row;     // per row: the row of the father / mother; an unknown parent: -1 - the side's label
-    std::vector<int64_t> row_id;             // per row: the individual's ID (the key of its random stream)
-    std::vector<int32_t> pro_row;            // per listed proband: its row
+struct IdentPlan : DropRows {                // (drop_plan.h: the rows by level; fa_row / mo_row of an unknown parent: -1 - the side's label)
     std::vector<int64_t> allele_id;          // the allele table: the ID ..
     std::vector<int32_t> allele_side;        // .. and the side (0 = from the father) of every label
     std::vector<int64_t> const_side;         // per label: 2 * row + side of the side that carries it
@@ -35,13 +30,6 @@ struct IdentPlan {
 // as plan_simu does; GENPHI_ERR_ARG for n_labels > 2^31 - 1.  One pass over the pedigree and a sort of the founder sides by ID.
 int plan_ident(IdentPlan &out, int64_t n_ind, const int64_t *ind, const int64_t *father, const int64_t *mother, int64_t n_pro,
                const int64_t *pro_ids, std::string &err);
-
-// The panel width in pairs of words (128 columns): create's panel_cols rounded up to 128 and cut to S; 0 = all of S.
-inline int64_t ident_panel_pairs(int64_t S, int64_t panel_cols)
-{
-    const int64_t total = (S + 127) / 128;
-    return panel_cols > 0 ? std::min(total, (panel_cols + 127) / 128) : total;
-}
 
 // Device bytes of a sweep (ident.hip allocates exactly these; the check before any launch adds them up).
 struct IdentSizes {

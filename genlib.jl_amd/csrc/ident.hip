@@ -25,30 +25,13 @@
 // Everything is integer and keyed on IDs and absolute word indices: the same bytes on every run, with any panel width.
 #include <hip/hip_runtime.h>
 
-#include "bootstrap.h"
-#include "devbuf.h"
+#include "drop_device.h"
 #include "ident.h"
 #include "sweep_device.h"
 
 namespace {
 
-typedef unsigned long long u64;
-using genphi::DevBuf;
-
 constexpr int IDENT_TILE = 32;               // the pair kernel's tile: 32 rows x 32 columns, 2 x 2 pairs per thread
-
-__device__ __forceinline__ ulonglong2 philox_pair(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1)
-{
-    const genphi::PhiloxPair p = genphi::philox_pair(c0, c1, c2, c3, k0, k1);
-    return make_ulonglong2(p.w0, p.w1);
-}
-
-// the columns < S of the absolute word w
-__device__ __forceinline__ u64 column_mask(long long S, long long w)
-{
-    const long long left = S - 64 * w;
-    return left <= 0 ? 0ull : (left >= 64 ? ~0ull : (1ull << left) - 1);
-}
 
 // The constant sides: a thread per (label, pair of words) writes the B planes of the side that carries the label.
 __global__ void __launch_bounds__(256)
@@ -93,7 +76,7 @@ ident_step_kernel(const int *__restrict__ fa_row, const int *__restrict__ mo_row
             ulonglong2 *out = dst + c * B2;
             for (int b = 0; b < B; ++b) {
                 const ulonglong2 p = src[b], q = src[B + b];
-                out[b] = make_ulonglong2((T.x & p.x) | (~T.x & q.x), (T.y & p.y) | (~T.y & q.y));
+                out[b] = meiosis(T, p, q);
             }
         }
         if (m >= 0) {
@@ -102,7 +85,7 @@ ident_step_kernel(const int *__restrict__ fa_row, const int *__restrict__ mo_row
             ulonglong2 *out = dst + c * B2 + B;
             for (int b = 0; b < B; ++b) {
                 const ulonglong2 p = src[b], q = src[B + b];
-                out[b] = make_ulonglong2((T.x & p.x) | (~T.x & q.x), (T.y & p.y) | (~T.y & q.y));
+                out[b] = meiosis(T, p, q);
             }
         }
     }
@@ -259,26 +242,9 @@ struct genphi_ident : SweepDevice {          // d_slots: the rows of one panel (
     int32_t pairs = 0, lanes_per_row = 0;    // pairs of a panel row
     int64_t n_panels = 0;
     double pair_ms = 0.0, word_ops = 0.0;
-    bool lists_up = false;
     bool empty() const { return false; }     // (n_pro >= 1 and S >= 1 always)
+    genphi_ident() { own(d_counts, d_labels, d_fa, d_mo, d_pro_row, d_ids, d_const_side, d_gathered); }
     int64_t total_pairs() const { return (S + 127) / 128; }
-    size_t held_bytes() const
-    {
-        return d_counts.bytes() + d_labels.bytes() + d_fa.bytes() + d_mo.bytes() + d_pro_row.bytes() + d_ids.bytes() + d_const_side.bytes() +
-               d_gathered.bytes();
-    }
-    void release()                           // (shadows SweepDevice::release: the DevBufs go back on the handle's device too)
-    {
-        if (device >= 0) {
-            DeviceGuard keep;
-            (void)hipSetDevice(device);
-            if (stream) (void)hipStreamSynchronize(stream);
-            d_counts.release(); d_labels.release(); d_fa.release(); d_mo.release(); d_pro_row.release(); d_ids.release();
-            d_const_side.release(); d_gathered.release();
-        }
-        lists_up = false;
-        SweepDevice::release();
-    }
 };
 
 namespace {
@@ -295,15 +261,6 @@ struct Events {                              // destroyed on every path
     }
 };
 
-template <typename T, typename V>
-int upload_list(genphi_ident *h, DevBuf<T> &dst, const std::vector<V> &src)
-{
-    static_assert(sizeof(T) == sizeof(V), "uploaded as it is");
-    GENPHI_HIP_TRY(dst.reserve(src.size()));
-    if (!src.empty()) GENPHI_HIP_TRY(hipMemcpyAsync(dst.get(), src.data(), src.size() * sizeof(V), hipMemcpyHostToDevice, h->stream));
-    return GENPHI_OK;
-}
-
 // The panel width, the rows, the results and the lists on the device; GENPHI_ERR_ALLOC before any launch.
 int prepare(genphi_ident *h)
 {
@@ -313,24 +270,20 @@ int prepare(genphi_ident *h)
     if (int rc = h->usable_bytes(usable, h->held_bytes())) return rc;
     const double room = usable - static_cast<double>(z.fixed()) - (64 << 20);
     const double pair_bytes = static_cast<double>(z.panel(1));
-    int64_t Pn = genphi::ident_panel_pairs(h->S, h->panel_arg);
-    if (h->panel_arg <= 0 && pair_bytes * static_cast<double>(Pn) > room) Pn = static_cast<int64_t>(room / pair_bytes);
-    if (Pn < 1 || room < 0.0 || pair_bytes * static_cast<double>(Pn) > room)
+    int64_t Pn;
+    if (!genphi::drop_panel_fits(Pn, h->S, h->panel_arg, room, pair_bytes))
         return genphi_set_error(GENPHI_ERR_ALLOC, "gen.simuIdentity: the counts of " + std::to_string(pl.n_pro) + " probands" +
                                                       (h->want_labels ? ", the labels" : "") + " and " + std::to_string(pl.n_live) + " live rows of " +
                                                       std::to_string(pl.planes) + " planes and " + std::to_string(128 * std::max<int64_t>(Pn, 1)) +
                                                       " simulations do not fit on device " + std::to_string(h->device));
-    if (int rc = h->reserve_slots(z.pair_rows * static_cast<size_t>(Pn))) return rc;
+    GENPHI_HIP_TRY(h->d_slots.reserve(z.pair_rows * static_cast<size_t>(Pn)));
     GENPHI_HIP_TRY(h->d_gathered.reserve(z.pair_gather * static_cast<size_t>(Pn) / sizeof(ulonglong2)));
     GENPHI_HIP_TRY(h->d_counts.reserve(z.counts / 4));
     if (h->want_labels) GENPHI_HIP_TRY(h->d_labels.reserve(z.labels / 4));
-    if (!h->lists_up) {
-        int rc;
-        if ((rc = upload_list(h, h->d_fa, pl.fa_row)) || (rc = upload_list(h, h->d_mo, pl.mo_row)) || (rc = upload_list(h, h->d_pro_row, pl.pro_row)) ||
-            (rc = upload_list(h, h->d_ids, pl.row_id)) || (rc = upload_list(h, h->d_const_side, pl.const_side)))
-            return rc;
-        h->lists_up = true;
-    }
+    int rc;
+    if ((rc = h->upload(h->d_fa, pl.fa_row)) || (rc = h->upload(h->d_mo, pl.mo_row)) || (rc = h->upload(h->d_pro_row, pl.pro_row)) ||
+        (rc = h->upload(h->d_ids, pl.row_id)) || (rc = h->upload(h->d_const_side, pl.const_side)))
+        return rc;
     h->pairs = static_cast<int32_t>(Pn);
     h->lanes_per_row = lanes_per_row(static_cast<int>(Pn));
     h->n_panels = (h->total_pairs() + Pn - 1) / Pn;
@@ -339,15 +292,13 @@ int prepare(genphi_ident *h)
 
 int compute_impl(genphi_ident *h, int32_t device)
 {
-    if (device < 0) GENPHI_HIP_TRY(hipGetDevice(&device));
-    if (h->device >= 0 && h->device != device) h->release();
     if (int rc = h->select(device)) return rc;
     if (int rc = prepare(h)) return rc;
     const genphi::IdentPlan &pl = h->plan;
     const int Pn = h->pairs, lpr = h->lanes_per_row, B = pl.planes, n_pro = static_cast<int>(pl.n_pro);
     const int64_t total = h->total_pairs();
     const unsigned k0 = static_cast<unsigned>(h->seed), k1 = static_cast<unsigned>(h->seed >> 32);
-    ulonglong2 *rows = static_cast<ulonglong2 *>(h->d_slots);
+    ulonglong2 *rows = h->slots<ulonglong2>();
     const int step_rows = 4 * (64 / lpr);
     const unsigned tiles = static_cast<unsigned>((n_pro + IDENT_TILE - 1) / IDENT_TILE);
     const size_t lds = static_cast<size_t>(2 * 2 * 64 * 8) * static_cast<size_t>(B);
@@ -429,7 +380,7 @@ int genphi_ident_create(int64_t n_ind, const int64_t *ind, const int64_t *father
         h->panel_arg = panel_cols;
         std::string err;
         if (const int rc = genphi::plan_ident(h->plan, n_ind, ind, father, mother, n_pro, pro_ids, err)) return genphi_set_error(rc, err);
-        h->pairs = static_cast<int32_t>(genphi::ident_panel_pairs(simul_no, panel_cols));      // (compute may narrow the default to what fits)
+        h->pairs = static_cast<int32_t>(genphi::drop_panel_pairs(simul_no, panel_cols));      // (compute may narrow the default to what fits)
         h->lanes_per_row = lanes_per_row(h->pairs);
         h->n_panels = (h->total_pairs() + h->pairs - 1) / h->pairs;
         return GENPHI_OK;

@@ -4,7 +4,7 @@
 #include <algorithm>
 
 #include "../../include/genphi.h"
-#include "ancestor_sweep.h"
+#include "pedigree_index.h"
 
 namespace genphi {
 
@@ -12,38 +12,17 @@ int plan_implex(ImplexPlan &h, int64_t n_ind, const int64_t *ind, const int64_t 
                 const int64_t *pro_ids, int32_t max_generations, std::string &err)
 {
     h = ImplexPlan();
-    // ---- id -> rank; parents must precede their children, IDs are unique (the planner's rules and messages) ----
-    Ranks ranks;
-    ranks.init(n_ind, ind);
-    std::vector<int32_t> fa(n_ind, -1), mo(n_ind, -1), depth(n_ind, 1);
-    for (int64_t i = 0; i < n_ind; ++i) {
-        if (ranks.find(ind[i]) != i) { err = "duplicate individual ID " + std::to_string(ind[i]); return GENPHI_ERR_DUPLICATE_ID; }
-        if (father[i] != 0) {
-            fa[i] = ranks.find(father[i]);
-            if (fa[i] < 0 || fa[i] >= i) {
-                err = "individual " + std::to_string(ind[i]) + ": father " + std::to_string(father[i]) +
-                      " is unknown or listed after its child (pedigree must be in rank order)";
-                return GENPHI_ERR_ORDER;
-            }
-        }
-        if (mother[i] != 0) {
-            mo[i] = ranks.find(mother[i]);
-            if (mo[i] < 0 || mo[i] >= i) {
-                err = "individual " + std::to_string(ind[i]) + ": mother " + std::to_string(mother[i]) +
-                      " is unknown or listed after its child (pedigree must be in rank order)";
-                return GENPHI_ERR_ORDER;
-            }
-        }
-        depth[i] = 1 + std::max(fa[i] >= 0 ? depth[fa[i]] : 0, mo[i] >= 0 ? depth[mo[i]] : 0);
-    }
+    PedigreeIndex px;
+    if (const int rc = index_pedigree(px, n_ind, ind, father, mother, err)) return rc;
+    const std::vector<int32_t> &fa = px.fa, &mo = px.mo;
+    std::vector<int32_t> depth(n_ind, 1);
+    for (int64_t i = 0; i < n_ind; ++i) depth[i] = 1 + std::max(fa[i] >= 0 ? depth[fa[i]] : 0, mo[i] >= 0 ? depth[mo[i]] : 0);
     // ---- U_0: the distinct probands, with the columns of their listed occurrences ----
     std::vector<int32_t> stamp(n_ind, -1), pos(n_ind, -1), uid(n_ind, -1);
-    std::vector<int32_t> cur, nxt, pro_rank(n_pro);
+    std::vector<int32_t> cur, nxt, pro_rank;
+    if (const int rc = find_probands(pro_rank, px.ranks, n_pro, pro_ids, err)) return rc;
     int32_t G = 0;
-    for (int64_t k = 0; k < n_pro; ++k) {
-        const int32_t r = ranks.find(pro_ids[k]);
-        if (r < 0) { err = "KeyError: proband " + std::to_string(pro_ids[k]) + " not found"; return GENPHI_ERR_UNKNOWN_ID; }
-        pro_rank[k] = r;
+    for (int32_t r : pro_rank) {
         G = std::max(G, depth[r]);
         if (stamp[r] != 0) { stamp[r] = 0; pos[r] = static_cast<int32_t>(cur.size()); cur.push_back(r); }
     }

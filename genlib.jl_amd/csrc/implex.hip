@@ -192,14 +192,14 @@ struct genphi_implex : SweepDevice {         // d_slots: per panel of a launch: 
     genphi::ImplexPlan plan;                 // host plan (implex.h)
     bool only_new = false;
     int32_t panel_env = 0, group_env = 0;    // GENPHI_IMPLEX_PANEL / GENPHI_IMPLEX_PANELS_PER_LAUNCH (0 = default rule)
-    long long *d_counts = nullptr;           // n_pro x G
-    double *d_result = nullptr;              // n_pro x G percentages
-    u64 *d_totals = nullptr;                 // G, on request
-    int *d_occ_start = nullptr, *d_occ_cols = nullptr, *d_estart = nullptr, *d_child = nullptr, *d_seen_row = nullptr;
+    DevBuf<long long> d_counts;              // n_pro x G
+    DevBuf<double> d_result;                 // n_pro x G percentages
+    DevBuf<u64> d_totals;                    // G, on request
+    DevBuf<int> d_occ_start, d_occ_cols, d_estart, d_child, d_seen_row;
     bool totals_ready = false;
     int32_t panel_cols = 0, lanes_per_row = 0;
     int64_t n_panels = 0;
-    genphi_implex() { own(&d_counts, &d_result, &d_totals, &d_occ_start, &d_occ_cols, &d_estart, &d_child, &d_seen_row); }
+    genphi_implex() { own(d_counts, d_result, d_totals, d_occ_start, d_occ_cols, d_estart, d_child, d_seen_row); }
     size_t result_entries() const { return static_cast<size_t>(plan.n_pro) * static_cast<size_t>(plan.G); }
     bool empty() const { return plan.n_pro == 0 || plan.G == 0; }
 };
@@ -215,9 +215,9 @@ int compute_impl(genphi_implex *h, int32_t device)
     const int64_t n_pro = pl.n_pro;
     const size_t n_res = h->result_entries();
     double usable = 0.0;
-    if (int rc = h->usable_bytes(usable, h->d_counts ? 16 * n_res : 0)) return rc;
+    if (int rc = h->usable_bytes(usable, h->d_counts.get() ? 16 * n_res : 0)) return rc;
     const double list_bytes = 4.0 * static_cast<double>(pl.occ_start.size() + pl.occ_cols.size() + pl.edge_start.size() + pl.child.size() + pl.seen_row.size());
-    const double room = usable - 16.0 * static_cast<double>(n_res) - (h->d_child ? 0.0 : list_bytes) - (64 << 20);
+    const double room = usable - 16.0 * static_cast<double>(n_res) - (h->d_child.get() ? 0.0 : list_bytes) - (64 << 20);
     // panels: W words (64 columns each) per row, at a pitch of whole 16-byte pairs
     const int64_t panel_rows = 2 * pl.peak_rows + (h->only_new ? pl.n_union : 0);
     auto panel_bytes = [&](int64_t w) { return 8.0 * static_cast<double>(panel_rows) * static_cast<double>((w + 1) & ~int64_t(1)); };
@@ -244,14 +244,14 @@ int compute_impl(genphi_implex *h, int32_t device)
     const int Wp = static_cast<int>((W + 1) & ~int64_t(1)), P = Wp / 2;
     const long long panel_stride = static_cast<long long>(panel_rows) * Wp;        // words of one panel: buffer 0, buffer 1, seen
     const long long buf_words = static_cast<long long>(pl.peak_rows) * Wp;
-    if (int rc = h->reserve_slots(static_cast<size_t>(group) * static_cast<size_t>(panel_stride) * sizeof(u64))) return rc;
-    if (!h->d_totals) GENPHI_HIP_TRY(genphi::cached_malloc(reinterpret_cast<void **>(&h->d_totals), static_cast<size_t>(G) * sizeof(u64)));
-    if (!h->d_counts) GENPHI_HIP_TRY(genphi::cached_malloc(reinterpret_cast<void **>(&h->d_counts), n_res * sizeof(long long)));
-    if (!h->d_result) GENPHI_HIP_TRY(genphi::cached_malloc(reinterpret_cast<void **>(&h->d_result), n_res * sizeof(double)));
+    GENPHI_HIP_TRY(h->d_slots.reserve(static_cast<size_t>(group) * static_cast<size_t>(panel_stride) * sizeof(u64)));
+    GENPHI_HIP_TRY(h->d_totals.reserve(static_cast<size_t>(G)));
+    GENPHI_HIP_TRY(h->d_counts.reserve(n_res));
+    GENPHI_HIP_TRY(h->d_result.reserve(n_res));
     int rc;
-    if ((rc = h->upload(&h->d_occ_start, pl.occ_start)) || (rc = h->upload(&h->d_occ_cols, pl.occ_cols)) ||
-        (rc = h->upload(&h->d_estart, pl.edge_start)) || (rc = h->upload(&h->d_child, pl.child)) ||
-        (h->only_new && (rc = h->upload(&h->d_seen_row, pl.seen_row))))
+    if ((rc = h->upload(h->d_occ_start, pl.occ_start)) || (rc = h->upload(h->d_occ_cols, pl.occ_cols)) ||
+        (rc = h->upload(h->d_estart, pl.edge_start)) || (rc = h->upload(h->d_child, pl.child)) ||
+        (h->only_new && (rc = h->upload(h->d_seen_row, pl.seen_row))))
         return rc;
     const int lpr = lanes_per_row(P);                         // step: lanes per row, one 16-byte pair each
     const int wpr = lanes_per_row(static_cast<int>(W));       // count: words of a row per group
@@ -260,9 +260,9 @@ int compute_impl(genphi_implex *h, int32_t device)
     h->n_panels = n_panels;
     SweepRun run;
     if ((rc = run.begin(*h, 0.0))) return rc;
-    GENPHI_HIP_TRY(hipMemsetAsync(h->d_counts, 0, n_res * sizeof(long long), h->stream));
+    GENPHI_HIP_TRY(hipMemsetAsync(h->d_counts, 0, h->d_counts.bytes(), h->stream));
     const int step_rows = 4 * (64 / lpr), count_rows = (256 / wpr) * IMPLEX_COUNT_ROWS;
-    u64 *rows = static_cast<u64 *>(h->d_slots);
+    u64 *rows = h->slots<u64>();
     u64 *seen = h->only_new ? rows + 2 * buf_words : nullptr;
     for (int64_t g0 = 0; g0 < n_panels; g0 += group) {
         const unsigned np = static_cast<unsigned>(std::min<int64_t>(group, n_panels - g0));
@@ -292,7 +292,7 @@ int compute_impl(genphi_implex *h, int32_t device)
             const dim3 cgrid(static_cast<unsigned>((n_rows + count_rows - 1) / count_rows), static_cast<unsigned>((W + wpr - 1) / wpr), np);
             GENPHI_LPR_SWITCH(wpr, (implex_count_kernel<LPR><<<cgrid, 256, 0, h->stream>>>(cur, n_rows, panel_stride, Wp, static_cast<int>(C),
                                                                                           static_cast<int>(n_pro), static_cast<int>(g0), G, g,
-                                                                                          reinterpret_cast<u64 *>(h->d_counts))));
+                                                                                          reinterpret_cast<u64 *>(h->d_counts.get()))));
             GENPHI_HIP_TRY(hipGetLastError());
         }
     }
@@ -347,7 +347,7 @@ int genphi_implex_counts(genphi_implex *h, int64_t *out)
     if (!h || !h->computed) return genphi_set_error(GENPHI_ERR_ARG, "genphi_implex_counts: nothing computed");
     if (h->empty()) return GENPHI_OK;
     if (!out) return genphi_set_error(GENPHI_ERR_ARG, "genphi_implex_counts: out is NULL");
-    return h->copy_out(out, h->d_counts, h->result_entries() * sizeof(long long), "gen.implex");
+    return h->copy_out(out, h->d_counts, h->d_counts.bytes(), "gen.implex");
 }
 
 int genphi_implex_result_to_host(genphi_implex *h, double *out)
@@ -355,7 +355,7 @@ int genphi_implex_result_to_host(genphi_implex *h, double *out)
     if (!h || !h->computed) return genphi_set_error(GENPHI_ERR_ARG, "genphi_implex_result_to_host: nothing computed");
     if (h->empty()) return GENPHI_OK;
     if (!out) return genphi_set_error(GENPHI_ERR_ARG, "genphi_implex_result_to_host: out is NULL");
-    return h->copy_out(out, h->d_result, h->result_entries() * sizeof(double), "gen.implex");
+    return h->copy_out(out, h->d_result, h->d_result.bytes(), "gen.implex");
 }
 
 int genphi_implex_totals(genphi_implex *h, int64_t *out)

@@ -238,12 +238,12 @@ struct genphi_anc_sweep : SweepDevice {
     genphi::SweepSchedule sched;             // host schedule (ancestor_sweep.h)
     int32_t panel_env = 0, group_env = 0;    // GENPHI_OCC_PANEL / GENPHI_OCC_PANELS_PER_LAUNCH (0 = default rule)
     int32_t row_bits = 64;                   // occ: 64 or 32; rec: 64 (a word of 64 columns)
-    long long *d_result = nullptr;           // IND: n_pro x n_anc; TOTAL: n_anc totals; rec: n_anc counts
-    unsigned long long *d_colsum = nullptr;  // IND: n_anc totals, on request
-    int4 *d_items = nullptr;
-    int *d_oh = nullptr, *d_rows = nullptr;
+    DevBuf<long long> d_result;              // IND: n_pro x n_anc; TOTAL: n_anc totals; rec: n_anc counts
+    DevBuf<unsigned long long> d_colsum;     // IND: n_anc totals, on request
+    DevBuf<int4> d_items;
+    DevBuf<int> d_oh, d_rows;
     int32_t panel_cols = 0;
-    genphi_anc_sweep() { own(&d_result, &d_colsum, &d_items, &d_oh, &d_rows); }
+    genphi_anc_sweep() { own(d_result, d_colsum, d_items, d_oh, d_rows); }
     size_t result_bytes() const
     {
         return (kind == kOccInd ? static_cast<size_t>(n_pro) : size_t(1)) * static_cast<size_t>(n_anc) * sizeof(long long);
@@ -285,7 +285,7 @@ int create_impl(Sweep *h, int64_t n_ind, const int64_t *ind, const int64_t *fath
 template <typename T, bool BITS>
 void launch_list(Sweep *h, int lpr, const ListLaunch &l, const genphi::PanelLayout &L)
 {
-    T *slots = static_cast<T *>(h->d_slots);
+    T *slots = h->slots<T>();
     const int n_anc = static_cast<int>(h->n_anc), C = static_cast<int>(L.C);
     if (!l.to_result) {
         GENPHI_LPR_SWITCH(lpr, (anc_step_kernel<T, BITS, LPR, false><<<l.grid, 256, 0, h->stream>>>(l.items, h->d_oh, l.n_items, slots, L.stride, L.Cp,
@@ -298,7 +298,7 @@ void launch_list(Sweep *h, int lpr, const ListLaunch &l, const genphi::PanelLayo
                                                                                                        L.Cp, C, n_anc, l.panel0, h->d_result)));
         } else {
             GENPHI_LPR_SWITCH(lpr, (occ_total_kernel<T, LPR><<<l.grid, 256, 0, h->stream>>>(l.items, h->d_oh, l.n_items, slots, L.stride, L.Cp, C, n_anc,
-                                                                                           l.panel0, reinterpret_cast<unsigned long long *>(h->d_result))));
+                                                                                           l.panel0, reinterpret_cast<unsigned long long *>(h->d_result.get()))));
         }
     }
 }
@@ -310,11 +310,11 @@ int compute_impl(Sweep *h, int32_t device)
     const genphi::PanelRule &rule = h->rule();
     const size_t res_bytes = h->result_bytes();
     genphi::PanelLayout L;
-    if (int rc = h->size_panels(L, rule, h->sched, h->n_anc, h->panel_env, h->group_env, res_bytes, h->d_result != nullptr, h->who())) return rc;
-    if (!h->d_result) GENPHI_HIP_TRY(genphi::cached_malloc(reinterpret_cast<void **>(&h->d_result), res_bytes));
-    if (int rc = h->upload(&h->d_items, h->sched.items)) return rc;
-    if (int rc = h->upload(&h->d_oh, h->sched.oh_cols)) return rc;
-    if (int rc = h->upload(&h->d_rows, h->sched.pro_slots)) return rc;
+    if (int rc = h->size_panels(L, rule, h->sched, h->n_anc, h->panel_env, h->group_env, res_bytes, h->d_result.get() != nullptr, h->who())) return rc;
+    GENPHI_HIP_TRY(h->d_result.reserve(res_bytes / sizeof(long long)));
+    if (int rc = h->upload(h->d_items, h->sched.items)) return rc;
+    if (int rc = h->upload(h->d_oh, h->sched.oh_cols)) return rc;
+    if (int rc = h->upload(h->d_rows, h->sched.pro_slots)) return rc;
     h->panel_cols = static_cast<int32_t>(L.C);
     SweepRun run;
     if (int rc = run.begin(*h, static_cast<double>(res_bytes))) return rc;
@@ -332,9 +332,9 @@ int compute_impl(Sweep *h, int32_t device)
         const int nw = static_cast<int>(rule.elems(L.C));
         const dim3 grid(static_cast<unsigned>((nw + 63) / 64), static_cast<unsigned>(std::min(std::max((n_rows + 511) / 512, 1), 1024)),
                         static_cast<unsigned>(g));
-        rec_count_kernel<<<grid, 256, 0, h->stream>>>(h->d_rows, n_rows, static_cast<const unsigned long long *>(h->d_slots), L.stride, L.Cp,
+        rec_count_kernel<<<grid, 256, 0, h->stream>>>(h->d_rows, n_rows, h->slots<const unsigned long long>(), L.stride, L.Cp,
                                                       static_cast<int>(L.C), static_cast<int>(h->n_anc), static_cast<int>(g0),
-                                                      reinterpret_cast<unsigned long long *>(h->d_result));
+                                                      reinterpret_cast<unsigned long long *>(h->d_result.get()));
         GENPHI_HIP_TRY(hipGetLastError());
         run.bytes += row_bytes * static_cast<double>(n_rows);
         ++run.launches;
@@ -388,7 +388,7 @@ int genphi_occ_result_device(const genphi_occ *h, const int64_t **d_ptr, int64_t
 {
     if (!h || !h->computed) return genphi_set_error(GENPHI_ERR_ARG, "genphi_occ_result_device: nothing computed");
     if (h->kind != kOccInd) return genphi_set_error(GENPHI_ERR_ARG, "genphi_occ_result_device: a TOTAL-only handle has no n_pro x n_anc result");
-    put(d_ptr, reinterpret_cast<const int64_t *>(h->d_result));
+    put(d_ptr, reinterpret_cast<const int64_t *>(h->d_result.get()));
     put(ld, h->n_anc);
     return GENPHI_OK;
 }
@@ -412,8 +412,7 @@ int genphi_occ_totals(genphi_occ *h, int64_t *out)
     if (h->kind == kOccTotal) return h->copy_out(out, h->d_result, bytes, "gen.occ");
     // an IND handle: column sums of the resident result
     const int rc = h->on_device("gen.occ totals", [&] {
-        hipError_t e = hipSuccess;
-        if (!h->d_colsum) e = genphi::cached_malloc(reinterpret_cast<void **>(&h->d_colsum), bytes);
+        hipError_t e = h->d_colsum.reserve(static_cast<size_t>(h->n_anc));
         if (e == hipSuccess) e = hipMemsetAsync(h->d_colsum, 0, bytes, h->stream);
         if (e != hipSuccess) return e;
         const dim3 grid(static_cast<unsigned>((h->n_anc + 255) / 256), static_cast<unsigned>((h->n_pro + 255) / 256));

@@ -10,17 +10,12 @@
 #include <string>
 #include <vector>
 
+#include "drop_plan.h"
+
 namespace genphi {
 
-struct SimuPlan {
-    int64_t n_pro = 0, n_live = 0;
-    int32_t n_levels = 0;                    // 0 when nobody is live
-    std::vector<int64_t> level_rows;         // rows per level
-    std::vector<int64_t> level_begin;        // n_levels + 1: level k owns the rows [level_begin[k], level_begin[k + 1])
-    std::vector<int32_t> fa_row, mo_row;     // per row: the row of the father / mother, -1 = a zero row (unknown or not live)
-    std::vector<int64_t> row_id;             // per row: the individual's ID (the key of its random stream)
+struct SimuPlan : DropRows {                 // (drop_plan.h: the rows by level; fa_row / mo_row of level 0 are -1, its own parents are ignored)
     std::vector<int32_t> state0;             // per row of level 0: the state of the listed ancestor (1 or 2)
-    std::vector<int32_t> pro_row;            // per listed proband: its row, -1 = a row of zeros
     std::vector<int64_t> pro_pos;            // per listed proband: its row, -1 = not live, -2 - state = a listed ancestor of that state
 };
 

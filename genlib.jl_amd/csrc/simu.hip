@@ -23,27 +23,11 @@
 // Everything is integer and keyed on IDs and absolute word indices: the same bits on every run, with any panel width.
 #include <hip/hip_runtime.h>
 
-#include "bootstrap.h"
+#include "drop_device.h"
 #include "simu.h"
 #include "sweep_device.h"
 
 namespace {
-
-typedef unsigned long long u64;
-
-// Philox4x32-10: the block of bootstrap.h (shared with gen.phiCI's draws), as the 16-byte pair of words a lane stores
-__device__ __forceinline__ ulonglong2 philox_pair(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1)
-{
-    const genphi::PhiloxPair p = genphi::philox_pair(c0, c1, c2, c3, k0, k1);
-    return make_ulonglong2(p.w0, p.w1);
-}
-
-// the columns < S of the absolute word w
-__device__ __forceinline__ u64 column_mask(long long S, long long w)
-{
-    const long long left = S - 64 * w;
-    return left <= 0 ? 0ull : (left >= 64 ? ~0ull : (1ull << left) - 1);
-}
 
 // Level 0: a thread per (row, pair).  State 1: P = all ones, M = 0; state 2: both all ones (columns >= S are never counted).
 __global__ void __launch_bounds__(256)
@@ -82,14 +66,12 @@ simu_step_kernel(const int *__restrict__ fa_row, const int *__restrict__ mo_row,
         if (f >= 0) {
             const ulonglong2 a = fs[2 * c], b = fs[2 * c + 1];
             const ulonglong2 T = philox_pair(id_lo, id_hi, first_pair + static_cast<unsigned>(c), 0u, k0, k1);
-            px.x = (T.x & a.x) | (~T.x & b.x);
-            px.y = (T.y & a.y) | (~T.y & b.y);
+            px = meiosis(T, a, b);
         }
         if (m >= 0) {
             const ulonglong2 a = ms[2 * c], b = ms[2 * c + 1];
             const ulonglong2 T = philox_pair(id_lo, id_hi, first_pair + static_cast<unsigned>(c), 1u, k0, k1);
-            mx.x = (T.x & a.x) | (~T.x & b.x);
-            mx.y = (T.y & a.y) | (~T.y & b.y);
+            mx = meiosis(T, a, b);
         }
         dst[2 * c] = px;
         dst[2 * c + 1] = mx;
@@ -236,15 +218,15 @@ struct genphi_simu : SweepDevice {           // d_slots: the rows of one panel (
     uint64_t seed = 0;
     bool no_sample = false;
     int32_t panel_env = 0;                   // GENPHI_SIMU_PANEL (0 = default rule)
-    long long *d_counts = nullptr;           // n_pro x 3
-    signed char *d_sample = nullptr;         // n_pro x S, unless no_sample
-    unsigned *d_match = nullptr;             // S
-    int *d_state_pro = nullptr;              // n_pro, the states of the last match_counts
-    int *d_fa = nullptr, *d_mo = nullptr, *d_state0 = nullptr, *d_pro_row = nullptr;
-    long long *d_ids = nullptr;
+    DevBuf<long long> d_counts;              // n_pro x 3
+    DevBuf<signed char> d_sample;            // n_pro x S, unless no_sample
+    DevBuf<unsigned> d_match;                // S
+    DevBuf<int> d_state_pro;                 // n_pro, the states of the last match_counts
+    DevBuf<int> d_fa, d_mo, d_state0, d_pro_row;
+    DevBuf<long long> d_ids;
     int32_t pairs = 0, lanes_per_row = 0;    // pairs of a panel row
     int64_t n_panels = 0;
-    genphi_simu() { own(&d_counts, &d_sample, &d_match, &d_state_pro, &d_fa, &d_mo, &d_state0, &d_pro_row, &d_ids); }
+    genphi_simu() { own(d_counts, d_sample, d_match, d_state_pro, d_fa, d_mo, d_state0, d_pro_row, d_ids); }
     bool empty() const { return false; }     // (n_pro >= 1 and S >= 1 always)
     int64_t total_pairs() const { return (S + 127) / 128; }
     size_t sample_bytes() const { return no_sample ? 0 : static_cast<size_t>(plan.n_pro) * static_cast<size_t>(S); }
@@ -259,30 +241,27 @@ int prepare(genphi_simu *h, int32_t device)
     const size_t n_pro = static_cast<size_t>(pl.n_pro);
     const size_t res_bytes = 24 * n_pro + h->sample_bytes() + 4 * static_cast<size_t>(h->S) + 4 * n_pro;
     double usable = 0.0;
-    if (int rc = h->usable_bytes(usable, h->d_counts ? res_bytes : 0)) return rc;
+    if (int rc = h->usable_bytes(usable, h->d_counts.get() ? res_bytes : 0)) return rc;
     const double list_bytes = 4.0 * static_cast<double>(pl.fa_row.size() + pl.mo_row.size() + pl.state0.size() + pl.pro_row.size()) +
                               8.0 * static_cast<double>(pl.row_id.size());
-    const double room = usable - static_cast<double>(res_bytes) - (h->d_pro_row ? 0.0 : list_bytes) - (64 << 20);
+    const double room = usable - static_cast<double>(res_bytes) - (h->d_pro_row.get() ? 0.0 : list_bytes) - (64 << 20);
     const double pair_bytes = 32.0 * static_cast<double>(pl.n_live);                   // one pair of every row, both sides
-    const int64_t total = h->total_pairs();
-    int64_t Pn = total;
-    if (h->panel_env > 0) Pn = std::min<int64_t>(total, (static_cast<int64_t>(h->panel_env) + 127) / 128);
-    else if (pair_bytes * static_cast<double>(Pn) > room) Pn = static_cast<int64_t>(room / pair_bytes);
-    if (Pn < 1 || room < 0.0 || pair_bytes * static_cast<double>(Pn) > room)
+    int64_t Pn;
+    if (!genphi::drop_panel_fits(Pn, h->S, h->panel_env, room, pair_bytes))
         return genphi_set_error(GENPHI_ERR_ALLOC, "gen.simu: " + std::to_string(pl.n_live) + " live rows of " + std::to_string(128 * std::max<int64_t>(Pn, 1)) +
                                                       " simulations do not fit on device " + std::to_string(device) + " beside the results");
-    if (int rc = h->reserve_slots(static_cast<size_t>(pl.n_live) * static_cast<size_t>(Pn) * 32)) return rc;
-    if (!h->d_counts) GENPHI_HIP_TRY(genphi::cached_malloc(reinterpret_cast<void **>(&h->d_counts), 24 * n_pro));
-    if (!h->d_sample && !h->no_sample) GENPHI_HIP_TRY(genphi::cached_malloc(reinterpret_cast<void **>(&h->d_sample), h->sample_bytes()));
-    if (!h->d_match) GENPHI_HIP_TRY(genphi::cached_malloc(reinterpret_cast<void **>(&h->d_match), 4 * static_cast<size_t>(h->S)));
-    if (!h->d_state_pro) GENPHI_HIP_TRY(genphi::cached_malloc(reinterpret_cast<void **>(&h->d_state_pro), 4 * n_pro));
+    GENPHI_HIP_TRY(h->d_slots.reserve(static_cast<size_t>(pl.n_live) * static_cast<size_t>(Pn) * 32));
+    GENPHI_HIP_TRY(h->d_counts.reserve(3 * n_pro));
+    if (!h->no_sample) GENPHI_HIP_TRY(h->d_sample.reserve(h->sample_bytes()));
+    GENPHI_HIP_TRY(h->d_match.reserve(static_cast<size_t>(h->S)));
+    GENPHI_HIP_TRY(h->d_state_pro.reserve(n_pro));
     int rc;
-    if ((rc = h->upload(&h->d_fa, pl.fa_row)) || (rc = h->upload(&h->d_mo, pl.mo_row)) || (rc = h->upload(&h->d_state0, pl.state0)) ||
-        (rc = h->upload(&h->d_pro_row, pl.pro_row)) || (rc = h->upload(&h->d_ids, pl.row_id)))
+    if ((rc = h->upload(h->d_fa, pl.fa_row)) || (rc = h->upload(h->d_mo, pl.mo_row)) || (rc = h->upload(h->d_state0, pl.state0)) ||
+        (rc = h->upload(h->d_pro_row, pl.pro_row)) || (rc = h->upload(h->d_ids, pl.row_id)))
         return rc;
     h->pairs = static_cast<int32_t>(Pn);
     h->lanes_per_row = lanes_per_row(static_cast<int>(Pn));
-    h->n_panels = (total + Pn - 1) / Pn;
+    h->n_panels = (h->total_pairs() + Pn - 1) / Pn;
     return GENPHI_OK;
 }
 
@@ -294,7 +273,7 @@ int run_panels(genphi_simu *h, bool sweep, bool results, bool match)
     const int Pn = h->pairs, lpr = h->lanes_per_row;
     const int64_t total = h->total_pairs();
     const unsigned k0 = static_cast<unsigned>(h->seed), k1 = static_cast<unsigned>(h->seed >> 32);
-    ulonglong2 *rows = static_cast<ulonglong2 *>(h->d_slots);
+    ulonglong2 *rows = h->slots<ulonglong2>();
     const int step_rows = 4 * (64 / lpr);
     for (int64_t p0 = 0; p0 < total; p0 += Pn) {
         const int Pc = static_cast<int>(std::min<int64_t>(Pn, total - p0)), Wc = 2 * Pc;
@@ -341,7 +320,7 @@ int compute_impl(genphi_simu *h, int32_t device)
     const genphi::SimuPlan &pl = h->plan;
     SweepRun run;
     if (int rc = run.begin(*h, 0.0)) return rc;
-    GENPHI_HIP_TRY(hipMemsetAsync(h->d_counts, 0, 24 * static_cast<size_t>(pl.n_pro), h->stream));
+    GENPHI_HIP_TRY(hipMemsetAsync(h->d_counts, 0, h->d_counts.bytes(), h->stream));
     if (int rc = run_panels(h, true, true, false)) return rc;
     // per non-initial live row: two parent rows read and one written, 32 bytes per pair, over the panels
     const int64_t stepped = pl.n_live - (pl.n_levels ? pl.level_rows[0] : 0);
@@ -406,33 +385,32 @@ int genphi_simu_sample_to_host(genphi_simu *h, int8_t *out)
     if (!h || !h->computed) return genphi_set_error(GENPHI_ERR_ARG, "genphi_simu_sample_to_host: nothing computed");
     if (h->no_sample) return genphi_set_error(GENPHI_ERR_ARG, "genphi_simu_sample_to_host: the handle was created with GENPHI_SIMU_FLAG_NO_SAMPLE");
     if (!out) return genphi_set_error(GENPHI_ERR_ARG, "genphi_simu_sample_to_host: out is NULL");
-    return h->copy_out(out, h->d_sample, h->sample_bytes(), "gen.simu");
+    return h->copy_out(out, h->d_sample, h->d_sample.bytes(), "gen.simu");
 }
 
 int genphi_simu_state_counts(genphi_simu *h, int64_t *out)
 {
     if (!h || !h->computed) return genphi_set_error(GENPHI_ERR_ARG, "genphi_simu_state_counts: nothing computed");
     if (!out) return genphi_set_error(GENPHI_ERR_ARG, "genphi_simu_state_counts: out is NULL");
-    return h->copy_out(out, h->d_counts, 24 * static_cast<size_t>(h->plan.n_pro), "gen.simu");
+    return h->copy_out(out, h->d_counts, h->d_counts.bytes(), "gen.simu");
 }
 
 int genphi_simu_match_counts(genphi_simu *h, const int32_t *state_pro, int32_t *out)
 {
     if (!h || !h->computed) return genphi_set_error(GENPHI_ERR_ARG, "genphi_simu_match_counts: nothing computed");
     if (!state_pro || !out) return genphi_set_error(GENPHI_ERR_ARG, "genphi_simu_match_counts: NULL argument");
-    const size_t n_pro = static_cast<size_t>(h->plan.n_pro);
-    for (size_t i = 0; i < n_pro; ++i)
+    for (size_t i = 0; i < h->d_state_pro.count(); ++i)
         if (state_pro[i] < 0 || state_pro[i] > 2)
             return genphi_set_error(GENPHI_ERR_ARG, "gen.simuProb: state " + std::to_string(state_pro[i]) + " of proband " + std::to_string(i) + " is outside 0..2");
     int rc = GENPHI_OK;
     const int drc = h->on_device("gen.simu match counts", [&] {
-        hipError_t e = hipMemcpyAsync(h->d_state_pro, state_pro, 4 * n_pro, hipMemcpyHostToDevice, h->stream);
+        hipError_t e = hipMemcpyAsync(h->d_state_pro, state_pro, h->d_state_pro.bytes(), hipMemcpyHostToDevice, h->stream);
         if (e != hipSuccess) return e;
-        e = hipMemsetAsync(h->d_match, 0, 4 * static_cast<size_t>(h->S), h->stream);
+        e = hipMemsetAsync(h->d_match, 0, h->d_match.bytes(), h->stream);
         if (e != hipSuccess) return e;
         rc = run_panels(h, h->n_panels > 1, false, true);            // one panel: its rows are resident
         if (rc) return hipSuccess;
-        e = hipMemcpyAsync(out, h->d_match, 4 * static_cast<size_t>(h->S), hipMemcpyDeviceToHost, h->stream);
+        e = hipMemcpyAsync(out, h->d_match, h->d_match.bytes(), hipMemcpyDeviceToHost, h->stream);
         return e == hipSuccess ? hipStreamSynchronize(h->stream) : e;
     });
     return drc ? drc : rc;

@@ -1,4 +1,4 @@
-// sweep_device.h -- the device side of a sweep handle that gc.hip, occ.hip, dist.hip, completeness.hip and implex.hip share:
+// sweep_device.h -- the device side of a sweep handle that the eight sweep files (gc, occ, dist, depth, completeness, implex, simu, ident) share:
 // everything around the kernels that does not depend on the arithmetic.  A sweep's file keeps its kernels, its handle's own
 // fields, its PanelRule, the allocation and pre-fill of its result, its launch callable, its extra passes and its extern "C"
 // functions.  Host functions only; every including file gets its own copy (anonymous namespace).
@@ -14,6 +14,7 @@
 
 #include "../../include/genphi.h"
 #include "ancestor_sweep.h"
+#include "devbuf.h"
 #include "devcache.h"
 #include "planner.h"
 #include "sweep_panels.h"
@@ -71,17 +72,21 @@ struct DeviceGuard {
     DeviceGuard &operator=(const DeviceGuard &) = delete;
 };
 
-// What every sweep handle holds on a device.  The handle registers its cached device blocks once (own); release() frees them.
+using genphi::DevBuf;
+
+// What every sweep handle holds on a device.  Its device blocks are DevBufs (devbuf.h): d_slots here and the handle's own members,
+// which it registers once (own).  release() gives them all back on the handle's device, held_bytes() sums them.
+// A handle is deleted only by destroy_entry, after release(), or by create_entry before anything is allocated: the destructor of a
+// DevBuf never has a block left to free, so it never frees under a current device that is not the block's.
 struct SweepDevice {
     int device = -1;
     hipStream_t stream = nullptr;
-    void *d_slots = nullptr;                 // the slot rows (implex: the frontier rows), grown on demand
-    size_t slot_bytes = 0;
+    DevBuf<char> d_slots;                    // the slot rows (implex: the frontier rows), grown on demand
     bool computed = false;
     double sweep_ms = 0.0, alg_bytes = 0.0;
     int64_t n_launches = 0;
     static constexpr int kMaxBlocks = 12;
-    void **blocks[kMaxBlocks] = {&d_slots};
+    genphi::DevBlock *blocks[kMaxBlocks] = {&d_slots};
     int n_blocks = 1;
 
     SweepDevice() = default;
@@ -89,10 +94,21 @@ struct SweepDevice {
     SweepDevice &operator=(const SweepDevice &) = delete;
 
     template <typename... T>
-    void own(T **...ptrs)
+    void own(DevBuf<T> &...bufs)
     {
         static_assert(sizeof...(T) < kMaxBlocks, "more blocks than the list holds");      // (called once, from the handle's constructor)
-        ((blocks[n_blocks++] = reinterpret_cast<void **>(ptrs)), ...);
+        ((blocks[n_blocks++] = &bufs), ...);
+    }
+
+    template <typename T>
+    T *slots() const { return reinterpret_cast<T *>(d_slots.get()); }
+
+    // the handle's own blocks, beside the slot rows
+    size_t held_bytes() const
+    {
+        size_t sum = 0;
+        for (int i = 1; i < n_blocks; ++i) sum += blocks[i]->bytes();
+        return sum;
     }
 
     void release()
@@ -101,11 +117,7 @@ struct SweepDevice {
         DeviceGuard keep;
         (void)hipSetDevice(device);
         if (stream) (void)hipStreamSynchronize(stream);
-        for (int i = 0; i < n_blocks; ++i) {
-            (void)genphi::cached_free(*blocks[i]);
-            *blocks[i] = nullptr;
-        }
-        slot_bytes = 0;
+        for (int i = 0; i < n_blocks; ++i) blocks[i]->release();
         if (stream) genphi::cached_stream_release(stream, device);
         stream = nullptr;
         device = -1;
@@ -129,17 +141,7 @@ struct SweepDevice {
     {
         size_t free_b = 0, total_b = 0;
         GENPHI_HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-        usable = 0.9 * static_cast<double>(free_b + slot_bytes + held);
-        return GENPHI_OK;
-    }
-
-    int reserve_slots(size_t bytes)
-    {
-        if (bytes <= slot_bytes) return GENPHI_OK;
-        (void)genphi::cached_free(d_slots);
-        d_slots = nullptr; slot_bytes = 0;
-        GENPHI_HIP_TRY(genphi::cached_malloc(&d_slots, bytes));
-        slot_bytes = bytes;
+        usable = 0.9 * static_cast<double>(free_b + d_slots.bytes() + held);
         return GENPHI_OK;
     }
 
@@ -157,17 +159,18 @@ struct SweepDevice {
         if (genphi::plan_panels(L, rule, s.peak_slots, n_cols, panel_env, group_env, slot_room))
             return genphi_set_error(GENPHI_ERR_ALLOC, who + ": " + std::to_string(L.slots) + " slots of " + std::to_string(L.C) +
                                                           " columns do not fit on device " + std::to_string(device) + " beside the result");
-        return reserve_slots(L.slot_bytes);
+        GENPHI_HIP_TRY(d_slots.reserve(L.slot_bytes));
+        return GENPHI_OK;
     }
 
-    // a list of the plan, uploaded once (D and S of one size: int4 for SweepItem)
+    // a list of the plan, uploaded once; an empty list stays a null pointer (D and S of one size: int4 for SweepItem)
     template <typename D, typename S>
-    int upload(D **dst, const std::vector<S> &src)
+    int upload(DevBuf<D> &dst, const std::vector<S> &src)
     {
         static_assert(sizeof(D) == sizeof(S), "uploaded as it is");
-        if (*dst || src.empty()) return GENPHI_OK;
-        GENPHI_HIP_TRY(genphi::cached_malloc(reinterpret_cast<void **>(dst), src.size() * sizeof(S)));
-        GENPHI_HIP_TRY(hipMemcpyAsync(*dst, src.data(), src.size() * sizeof(S), hipMemcpyHostToDevice, stream));
+        if (dst.get() || src.empty()) return GENPHI_OK;
+        GENPHI_HIP_TRY(dst.reserve(src.size()));
+        GENPHI_HIP_TRY(hipMemcpyAsync(dst.get(), src.data(), dst.bytes(), hipMemcpyHostToDevice, stream));
         return GENPHI_OK;
     }
 

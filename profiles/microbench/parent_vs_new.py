@@ -1,7 +1,10 @@
 """A refactor's speed check: the parent commit's build and this tree's, alternately, on one machine.
     parent_vs_new.py run PARENT_TREE FIRST LAST OUT     rounds FIRST..LAST (parent first in rounds 1-3, the new build first afterwards); per build
                                                         and round bench.py --full on cfg4 and call_wall.py on cfg2 (genea140) and cfg3; raw lines to OUT
-    parent_vs_new.py summary OUT [OUT ...]              per figure min..max over the rounds, the median, and where the new median lies
+    parent_vs_new.py run PARENT_TREE FIRST LAST OUT sweeps    the same for the sweep handles: per build and round profiles/simu_bench.py, ident_bench.py,
+                                                        gc_bench.py and implex_bench.py at their defaults (parent first in the first half of FIRST..LAST)
+    parent_vs_new.py summary OUT [OUT ...]              per figure min..max over the rounds, the median, and where the new median lies (of the sweep
+                                                        scripts' lines: every time they print, the keys *_ms and call_ms_*)
 PARENT_TREE is a checkout of the parent commit with its library built.  A command that fails ends the run: nothing more is started."""
 import json
 import os
@@ -13,15 +16,17 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 CMDS = [(300, ["python", "bench.py", "--gpus", "1", "--steps", "10", "--warmup", "2", "--full", "--no-cpu-baseline", "--no-others", "--no-d2h"]),
         (120, ["python", "profiles/microbench/call_wall.py", "cfg2", "cfg3"])]
+SWEEP_CMDS = [(240, ["python", "profiles/%s_bench.py" % s]) for s in ("simu", "ident", "gc", "implex")]
 
 
-def run(parent, first, last, out_path):
+def run(parent, first, last, out_path, sweeps=False):
     trees = {"parent": os.path.abspath(parent), "new": ROOT}
+    parent_first_until = (first + last) // 2 if sweeps else 3
     with open(out_path, "w") as out:
         for r in range(first, last + 1):
-            for which in (("parent", "new") if r <= 3 else ("new", "parent")):
+            for which in (("parent", "new") if r <= parent_first_until else ("new", "parent")):
                 out.write(f"== {which} library, round {r}\n")
-                for limit, cmd in CMDS:
+                for limit, cmd in (SWEEP_CMDS if sweeps else CMDS):
                     p = subprocess.run(["timeout", "-k", "10", str(limit)] + cmd, cwd=trees[which], capture_output=True, text=True)
                     out.write("".join(l + "\n" for l in p.stdout.splitlines() if l.startswith("{") or l.startswith("cfg")))
                     out.flush()
@@ -43,6 +48,11 @@ def summary(paths):
             if m:
                 which = m.group(1)
                 rounds.add(int(m.group(2)))
+            elif line.startswith("{") and "end_to_end" not in line:
+                j = json.loads(line)                                   # a line of a sweep's bench script (gc_bench.py's has no "what")
+                for k, v in j.items():
+                    if k.endswith("_ms") or k.startswith("call_ms_"):
+                        add(f"{j.get('what', 'gc')} {j['workload']} {k}", v)
             elif line.startswith("{"):
                 j = json.loads(line)
                 e = j["end_to_end"]
@@ -57,6 +67,7 @@ def summary(paths):
                     for name, v in zip(("one-shot call wall median", "one-shot call wall min", "first compute", "second compute"), m.groups()[1:]):
                         add(f"{w} {name}", v)
     print(f"parent and new library alternately, rounds {sorted(rounds)}; per figure min..max over the rounds and the median (ms)")
+    width = max(38, max(len(k) for k in fig))
     for k, d in fig.items():
         p, n = d["parent"], d["new"]
         mp, mn = statistics.median(p), statistics.median(n)
@@ -70,11 +81,11 @@ def summary(paths):
             verdict = "within the parent's spread only through the parent's largest round"
         else:
             verdict = "within the parent's spread"
-        print(f"{k:38s} parent {min(p):9.3f}..{max(p):9.3f} med {mp:9.3f} | new {min(n):9.3f}..{max(n):9.3f} med {mn:9.3f} ({mn / mp - 1:+.1%}) | new median {verdict}")
+        print(f"{k:{width}s} parent {min(p):9.3f}..{max(p):9.3f} med {mp:9.3f} | new {min(n):9.3f}..{max(n):9.3f} med {mn:9.3f} ({mn / mp - 1:+.1%}) | new median {verdict}")
 
 
 if __name__ == "__main__":
-    if sys.argv[1:2] == ["run"] and len(sys.argv) == 6:
-        sys.exit(run(sys.argv[2], int(sys.argv[3]), int(sys.argv[4]), sys.argv[5]))
+    if sys.argv[1:2] == ["run"] and (len(sys.argv) == 6 or sys.argv[6:] == ["sweeps"]):
+        sys.exit(run(sys.argv[2], int(sys.argv[3]), int(sys.argv[4]), sys.argv[5], sweeps=len(sys.argv) == 7))
     assert sys.argv[1:2] == ["summary"] and len(sys.argv) > 2, __doc__
     summary(sys.argv[2:])

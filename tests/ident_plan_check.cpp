@@ -1,5 +1,5 @@
 // ident_plan_check.cpp -- the host plan of gen.simuIdentity (csrc/ident.cpp) on random pedigrees, as a stand-alone program: built by
-// tests/test_ident_host.py with g++, plain and under AddressSanitizer + UndefinedBehaviorSanitizer, together with ident.cpp and
+// tests/test_ident_host.py with g++, plain and under AddressSanitizer + UndefinedBehaviorSanitizer, together with ident.cpp, pedigree_index.cpp and
 // ancestor_sweep.cpp.  Every plan is checked against the definition in include/genphi.h, restated here on ranks: the live set by a
 // walk from the probands, the levels, the order of the rows, the parent rows, the allele table and its labels, B, the proband rows,
 // and the device sizes of ident.h.  Prints one summary line; exit status 1 on any violation.
@@ -154,8 +154,8 @@ int main()
             }
         }
     }
-    expect(genphi::ident_panel_pairs(5000, 0) == 40 && genphi::ident_panel_pairs(5000, 1) == 1 && genphi::ident_panel_pairs(5000, 129) == 2 &&
-               genphi::ident_panel_pairs(5000, 1000) == 8 && genphi::ident_panel_pairs(5000, 100000) == 40 && genphi::ident_panel_pairs(1, 0) == 1,
+    expect(genphi::drop_panel_pairs(5000, 0) == 40 && genphi::drop_panel_pairs(5000, 1) == 1 && genphi::drop_panel_pairs(5000, 129) == 2 &&
+               genphi::drop_panel_pairs(5000, 1000) == 8 && genphi::drop_panel_pairs(5000, 100000) == 40 && genphi::drop_panel_pairs(1, 0) == 1,
            "panel pairs", -1);
     std::printf("ident plan check: %ld pedigrees, %ld rows, %ld labels, %ld half-founders, %ld selfings, %ld lists with repeats, %ld refusals, "
                 "most planes %d, most levels %d; %ld violations\n",

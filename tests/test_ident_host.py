@@ -303,7 +303,7 @@ def test_plan_as_a_stand_alone_program(san, tmp_path):
     exe = str(tmp_path / "ident_plan_check")
     flags = ["-O2"] if san is None else ["-O1", "-g", f"-fsanitize={san}", "-fno-omit-frame-pointer"]
     cmd = [gxx, "-std=c++17", "-Wall", "-Wextra", "-pthread"] + flags + [os.path.join(ROOT, "tests", "ident_plan_check.cpp"), os.path.join(CSRC, "ident.cpp"),
-                                                                       os.path.join(CSRC, "ancestor_sweep.cpp"), os.path.join(CSRC, "planner.cpp"), "-o", exe]
+                                                                       os.path.join(CSRC, "ancestor_sweep.cpp"), os.path.join(CSRC, "pedigree_index.cpp"), os.path.join(CSRC, "planner.cpp"), "-o", exe]
     build = subprocess.run(cmd, capture_output=True, text=True)
     if san is not None and build.returncode != 0 and ("cannot find" in build.stderr or "unrecognized" in build.stderr):
         pytest.skip("this toolchain has no -fsanitize=" + san)
