@@ -56,7 +56,7 @@ class GenphiStats(C.Structure):
 # every symbol include/genphi.h declares (tests check that the library exports all of them)
 EXPORTED_SYMBOLS = [
     "genphi_plan_create", "genphi_plan_create_tuned", "genphi_tuning_create", "genphi_tuning_set", "genphi_tuning_destroy", "genphi_plan_levels", "genphi_plan_n_probands", "genphi_plan_step_mode", "genphi_plan_step_info", "genphi_plan_step_slots",
-    "genphi_plan_algorithmic_bytes", "genphi_plan_device_bytes", "genphi_plan_device_bytes_needed", "genphi_plan_sparse_levels", "genphi_plan_step_walk", "genphi_plan_set_step_hook", "genphi_compute_device", "genphi_result_device",
+    "genphi_plan_algorithmic_bytes", "genphi_plan_device_bytes", "genphi_plan_device_bytes_needed", "genphi_plan_sparse_levels", "genphi_plan_cut_formats", "genphi_plan_step_walk", "genphi_plan_set_step_hook", "genphi_compute_device", "genphi_result_device",
     "genphi_result_to_host", "genphi_result_to_host_f64", "genphi_phi_pairs", "genphi_result_sums", "genphi_result_group_sums", "genphi_result_over", "genphi_result_nearest", "genphi_result_matmul", "genphi_result_solve", "genphi_result_eigen", "genphi_result_hist", "genphi_result_select", "genphi_result_bootstrap", "genphi_bootstrap_counts", "genphi_result_entries",
     "genphi_compute_f32",
     "genphi_genealogy_read", "genphi_branching", "genphi_free", "genphi_release_cached", "genphi_cached_bytes", "genphi_plan_release_device", "genphi_plan_destroy",
@@ -138,6 +138,8 @@ def lib():
         L.genphi_cached_bytes.restype = C.c_int64
         L.genphi_plan_sparse_levels.argtypes = [C.c_void_p, C.POINTER(C.c_int32), _I64P, _I64P, C.c_int32]
         L.genphi_plan_sparse_levels.restype = C.c_int
+        L.genphi_plan_cut_formats.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_uint32)]
+        L.genphi_plan_cut_formats.restype = C.c_int
         L.genphi_plan_algorithmic_bytes.argtypes = [C.c_void_p]
         L.genphi_plan_algorithmic_bytes.restype = C.c_double
         L.genphi_compute_device.argtypes = [C.c_void_p, C.POINTER(GenphiOpts), C.POINTER(GenphiStats)]
@@ -593,6 +595,15 @@ class PhiPlan:
         buf = (C.c_int64 * 16)()
         m = lib().genphi_plan_sparse_levels(self._h, C.byref(k), buf, None, 16)
         return int(k.value), [int(buf[c]) for c in range(m)]
+
+    def cut_formats(self):
+        """(formats, guard): the storage format of every cut in the last Float32 sweep (0 Float32, 1 16-bit, 2 24-bit integers of the
+        cut's unit; [] before the first sweep) and the sweep's encode guard (0 = every narrow entry was exact), genphi_plan_cut_formats."""
+        n = len(self.levels()[0])
+        buf = (C.c_int32 * max(n, 1))()
+        guard = C.c_uint32(0)
+        m = lib().genphi_plan_cut_formats(self._h, buf, n, C.byref(guard))
+        return [int(buf[c]) for c in range(m)], int(guard.value)
 
     def sparse_entries(self):
         """List entries ((column, value) pairs, 8 bytes each) every counted cut is stored as; -1 = not counted."""

@@ -61,6 +61,7 @@
 #include "planner.h"
 #include "shard_lists.h"
 #include "resident.h"
+#include "cut_format.h"
 #include "row_geometry.h"
 #include "sparse_levels.h"
 #include "tuning.h"
@@ -159,6 +160,11 @@ struct LevelArgs {
                              // kernels as an argument of its own (const, restrict: scalar loads -- through this struct they are vector loads,
                              // and the wait for one drains vmcnt, i.e. the next row's prefetch, at the start of every stage)
     int zrow;                // index of the all-zero "none" row of `out` (= n unless panel: the cut's size)
+    // Narrow cuts (cut_format.h; the certified-rows SPLIT kernel only): psi / out are then rows of 16-bit integers at the same pitch in
+    // ELEMENTS (ld_prev / ld), in units of unit_prev / 1 / scale_out.  guard: one word, != 0 after an entry that did not encode exactly.
+    int fmt_prev, fmt_out;
+    float unit_prev, scale_out;
+    unsigned *guard;
 };
 
 // ---- shared pieces of the row kernels --------------------------------------------------------
@@ -368,6 +374,79 @@ __device__ __forceinline__ void store_row4(float *row, unsigned row_bytes, unsig
     const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(row, 0, row_bytes, 0x00020000);
     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4_t, v), rsrc, byte_off, 0, GENPHI_STORE_AUX);
 #endif
+}
+
+// ---- narrow cuts (cut_format.h): what the certified-rows kernel needs to read and write a cut kept as 16- or 24-bit integers ----
+// A staged quad of columns is 16 bytes of a Float32 row, 8 bytes of a 16-bit one and 12 bytes of a 24-bit one (entries packed, little
+// endian: a quad is three whole words, so staging loads and row stores stay one aligned access per quad); the LDS copy is Float32.
+typedef unsigned u2_t __attribute__((ext_vector_type(2)));
+typedef genphi::Quad24 u3_t;                // (three words, no 3-element vector type: its loads and stores may be widened to four elements)
+template <int F> struct StageQuad { typedef f4_t type; };
+template <> struct StageQuad<genphi::kFmtU16> { typedef u2_t type; };
+template <> struct StageQuad<genphi::kFmtU24> { typedef u3_t type; };
+template <int F> __device__ __forceinline__ constexpr unsigned quad_bytes() { return F == genphi::kFmtU16 ? 8u : (F == genphi::kFmtU24 ? 12u : 16u); }
+
+// (unpacking, decoding, encoding, packing and the guard are cut_format.h's functions: what tests/cut_format_check.cpp runs on the host)
+__device__ __forceinline__ f4_t decode_quad(f4_t v, float) { return v; }
+__device__ __forceinline__ f4_t decode_words(const unsigned u[4], float unit)
+{
+    const f4_t r = {genphi::decode_entry(u[0], unit), genphi::decode_entry(u[1], unit), genphi::decode_entry(u[2], unit), genphi::decode_entry(u[3], unit)};
+    return r;
+}
+__device__ __forceinline__ f4_t decode_quad(u2_t v, float unit)
+{
+    unsigned u[4];
+    genphi::unpack_quad(genphi::Quad16{v.x, v.y}, u);
+    return decode_words(u, unit);
+}
+__device__ __forceinline__ f4_t decode_quad(const u3_t &v, float unit)
+{
+    unsigned u[4];
+    genphi::unpack_quad(v, u);
+    return decode_words(u, unit);
+}
+
+// Row store of 4 consecutive columns in the row's format (`row`: the row's first byte, col: the quad's first column).  Narrow: the quad
+// encoded by cut_format.h, whose guard bits -- a value that is no integer of the unit, or past the format's range -- collect in `gbad`
+// without a branch per entry.
+template <int F>
+__device__ __forceinline__ void store_quad(char *row, unsigned row_bytes, unsigned col, f4_t v, float scale, unsigned &gbad)
+{
+    if constexpr (F == genphi::kFmtF32) {
+        (void)scale; (void)gbad;
+        store_row4(reinterpret_cast<float *>(row), row_bytes, col * 4u, v);
+    } else if constexpr (F == genphi::kFmtU16) {
+        (void)row_bytes;
+        const genphi::Quad16 q = genphi::encode_quad16(v[0], v[1], v[2], v[3], scale, gbad);
+        const u2_t pk2 = {q.x, q.y};
+        __builtin_nontemporal_store(pk2, reinterpret_cast<u2_t *>(row + col * 2u));
+    } else {
+        (void)row_bytes;
+        const genphi::Quad24 q = genphi::encode_quad24(v[0], v[1], v[2], v[3], scale, gbad);
+        unsigned *dst = reinterpret_cast<unsigned *>(row + col * 3u);      // (three words: the compiler merges them into one 12-byte store)
+        __builtin_nontemporal_store(q.x, dst);
+        __builtin_nontemporal_store(q.y, dst + 1);
+        __builtin_nontemporal_store(q.z, dst + 2);
+    }
+}
+
+// one entry (the diagonal patch)
+template <int F>
+__device__ __forceinline__ void store_entry(char *row, unsigned col, float v, float scale, unsigned &gbad)
+{
+    if constexpr (F == genphi::kFmtF32) {
+        (void)scale; (void)gbad;
+        st_off<float>(row, col * 4u, v);
+    } else {
+        const unsigned u = genphi::encode_one(v, scale, F, gbad);
+        if constexpr (F == genphi::kFmtU16) {
+            st_off<unsigned short>(row, col * 2u, static_cast<unsigned short>(u));
+        } else {
+            st_off<unsigned char>(row, col * 3u, static_cast<unsigned char>(u));
+            st_off<unsigned char>(row, col * 3u + 1u, static_cast<unsigned char>(u >> 8));
+            st_off<unsigned char>(row, col * 3u + 2u, static_cast<unsigned char>(u >> 16));
+        }
+    }
 }
 
 // A work item is (sibling group, column chunk): the rows of a group share source row A, which
@@ -698,7 +777,7 @@ level_split_kernel(const LevelArgs p, const int4 *__restrict__ desc, const int4 
 // Bit-identical to the grouping-exact kernel on certified rows (tests force both on the same input).
 // CHAIN: the run lists may hold chain steps (type-1 segments: GENPHI_MAX_RUN > 1).  The default lists (one hub per run) never do,
 // and their instantiation carries none of that state -- the kernel is at the SGPR limit.
-template <int NTHREADS, int CPT, int STG, bool CERT, bool CHAIN>
+template <int NTHREADS, int CPT, int STG, bool CERT, bool CHAIN, int SF = genphi::kFmtF32, int DF = genphi::kFmtF32>
 __global__ void __launch_bounds__(NTHREADS)
 level_split_fast_kernel(const LevelArgs p, const int4 *__restrict__ desc, const int4 *__restrict__ seg, const int4 *__restrict__ run,
                         const int *__restrict__ glist, const int2 *__restrict__ pdesc, int *queue)
@@ -706,7 +785,18 @@ level_split_fast_kernel(const LevelArgs p, const int4 *__restrict__ desc, const 
     extern __shared__ float lds[];
     constexpr unsigned NT = NTHREADS;
     float *sR = lds;
-    const int n_items = p.gcnt[0] * p.n_chunks;           // certified runs of this launch (group_split_kernel) x column chunks
+    // SF / DF: format of the source / the written cut (cut_format.h).  Every row of a narrow cut is certified (its non-zero entries are
+    // >= its unit >= 2^-23), and so is every row computed from one (cut 12 at the latest: >= 2^-25; the certificate asks for 2^-27): a launch with a narrow source takes ALL runs of the step (no group_split_kernel,
+    // no run list: run rk is item rk), and the narrow forms exist without CERT -- the certificate words stay 0.
+    static_assert((SF == genphi::kFmtF32 && DF == genphi::kFmtF32) || (!CERT && !CHAIN), "narrow forms: CERT = CHAIN = false");
+    static_assert(SF != genphi::kFmtF32 || DF == genphi::kFmtF32, "a narrow run starts at the sparse -> dense step");
+    static_assert(quad_bytes<SF>() % 4u == 0 && quad_bytes<DF>() % 4u == 0, "a quad is whole words");
+    typedef typename StageQuad<SF>::type pre_t;
+    constexpr unsigned SQB = quad_bytes<SF>(), SEB = SQB / 4u, DEB = quad_bytes<DF>() / 4u;       // bytes of a staged quad, of a source / written entry
+    const char *const psi_b = reinterpret_cast<const char *>(p.psi);
+    char *const out_b = reinterpret_cast<char *>(p.out);
+    // certified runs of this launch (group_split_kernel) x column chunks
+    const int n_items = (SF != genphi::kFmtF32 ? p.n_groups : p.gcnt[0]) * p.n_chunks;
     const int xcd = blockIdx.x & 7;
     const int q = n_items >> 3, rem = n_items & 7;
     auto draw = [&]() -> int {                            // next item of a certified run, or n_items
@@ -719,8 +809,8 @@ level_split_fast_kernel(const LevelArgs p, const int4 *__restrict__ desc, const 
         return n_items;
     };
     if (p.zero_row && blockIdx.x == 0) {                  // the all-zero "none" row of this level
-        float *zr = p.out + (long long)p.zrow * p.ld;
-        for (long long j = threadIdx.x; j < p.ld; j += NT) zr[j] = 0.f;
+        unsigned *zr = reinterpret_cast<unsigned *>(out_b + (long long)p.zrow * p.ld * DEB);      // (the pitch is a multiple of 64 entries)
+        for (long long j = threadIdx.x; j < p.ld * DEB / 4; j += NT) zr[j] = 0u;
     }
     if (n_items == 0) return;                             // no certified run in this launch
     int *slot = reinterpret_cast<int *>(lds + p.slot_off);   // queue hand-over slots (thread 0 draws one item ahead)
@@ -736,7 +826,7 @@ level_split_fast_kernel(const LevelArgs p, const int4 *__restrict__ desc, const 
     int kc = 0;
     unsigned tl = threadIdx.x;
 
-    f4_t pre[STG];
+    pre_t pre[STG];
     unsigned pk[CPT];                                     // A_j | B_j << 16 of this thread's columns
     double pab[CPT];                                      // (a + b) / 4 of this thread's columns: the expansion of the current hub row
     static_assert(CPT % 4 == 0, "columns are handled in quads");
@@ -754,8 +844,9 @@ level_split_fast_kernel(const LevelArgs p, const int4 *__restrict__ desc, const 
         const int chunk = cur_l - rk * p.n_chunks;
         // (glist is a kernel argument of its own, const and restrict: its loads are scalar.  Read through the
         // argument struct they were vector loads, and waiting for one drains vmcnt -- row stores included)
-        const int4 rr = run[glist[rk]];                   // (first segment, hub | n0 << 16, its rows [z, w))
-        g = rr.x; g_end = run[glist[rk] + 1].x;
+        const int r0 = SF != genphi::kFmtF32 ? rk : glist[rk];
+        const int4 rr = run[r0];                          // (first segment, hub | n0 << 16, its rows [z, w))
+        g = rr.x; g_end = run[r0 + 1].x;
         wb = rr.z; we = rr.w; n0 = rr.y >> 16; Ai = rr.y & 0xffff;
         cb = (unsigned)chunk * (unsigned)p.chunk_cols;
         ce = min(cb + (unsigned)p.chunk_cols, (unsigned)p.width);
@@ -765,7 +856,7 @@ level_split_fast_kernel(const LevelArgs p, const int4 *__restrict__ desc, const 
     bool have_next = nxt_l < n_items;
 
 #pragma unroll
-    for (int k_ = 0; k_ < STG; ++k_) pre[k_] = ld_off<f4_t>(p.psi + (long long)Ai * p.ld_prev, (tl + k_ * NT) * 16u);
+    for (int k_ = 0; k_ < STG; ++k_) pre[k_] = ld_off<pre_t>(psi_b + (long long)Ai * p.ld_prev * SEB, (tl + k_ * NT) * SQB);
 
     for (;;) {
         asm volatile("" : "+v"(tl));
@@ -803,7 +894,7 @@ level_split_fast_kernel(const LevelArgs p, const int4 *__restrict__ desc, const 
         }
         // the next item's run (a dummy one when nothing is left: an unconditional prefetch keeps `pre` in one set)
         const int rkn = have_next ? (p.chunk_magic ? static_cast<int>(__umulhi(static_cast<unsigned>(nxt_l), p.chunk_magic)) : nxt_l) : 0;
-        const int rn = glist[rkn];
+        const int rn = SF != genphi::kFmtF32 ? rkn : glist[rkn];
         const int4 nrun = run[rn];                        // its first segment: (index, hub row | n0 << 16, rows [z, w)); ONE load chain per
         const int gn_end = run[rn + 1].x;                 // item, issued a stage ahead: nothing is loaded when the item starts
         const int nextAi = nrun.y & 0xffff;
@@ -821,23 +912,24 @@ level_split_fast_kernel(const LevelArgs p, const int4 *__restrict__ desc, const 
         }
         __syncthreads();                                // previous gathers are done with the buffer
         {
-            const float *src = p.psi + (long long)(nextB != p.n_prev ? nextB : nextAi) * p.ld_prev;
+            const char *src = psi_b + (long long)(nextB != p.n_prev ? nextB : nextAi) * p.ld_prev * SEB;
 #pragma unroll
             for (int k_ = 0; k_ < STG; ++k_) {
-                *reinterpret_cast<f4_t *>(reinterpret_cast<char *>(sR) + (tl + k_ * NT) * 16u) = pre[k_];
-                pre[k_] = ld_off<f4_t>(src, (tl + k_ * NT) * 16u);
+                *reinterpret_cast<f4_t *>(reinterpret_cast<char *>(sR) + (tl + k_ * NT) * 16u) = decode_quad(pre[k_], p.unit_prev);
+                pre[k_] = ld_off<pre_t>(src, (tl + k_ * NT) * SQB);
             }
         }
         __syncthreads();
 
         // ---- part 2: gathers from the staged row ----
         int wfin_b = 0, wfin_e = 0;                     // rows without a B source to finish from pab after this stage
+        unsigned gbad = 0u;                             // (narrow destination) the encode guard of this stage's stores
         if (!stage_is_a) {
-            float *orowp = p.out + (long long)orow * p.ld;
+            char *orowp = out_b + (long long)orow * p.ld * DEB;
             // a row with a B source is a new member with both parents: weight 1/2 x 1/2 per column
             const int dcol = pdesc ? pdesc[w].x : ri;           // the member's own column (panel: local column or -1)
             const float diag = static_cast<float>(0.5 + 0.5 * static_cast<double>(sR[pdesc ? pdesc[w].y : Ai]));
-            const unsigned row_bytes = (unsigned)p.ld * 4u;
+            const unsigned row_bytes = (unsigned)p.ld * DEB;
             unsigned ck = 0xffffffffu;
 #pragma unroll
             for (int q = 0; q < NQ; ++q) {
@@ -850,12 +942,12 @@ level_split_fast_kernel(const LevelArgs p, const int4 *__restrict__ desc, const 
                     vq[e] = static_cast<float>(__builtin_fma(cd, 0.25, pab[k]));
                 }
                 if (CERT) { ck = min(ck, min(min(cert_key(vq[0]), cert_key(vq[1])), min(cert_key(vq[2]), cert_key(vq[3])))); asm volatile("" : "+v"(ck)); }
-                if (jq < ce) store_row4(orowp, row_bytes, jq * 4u, vq);
+                if (jq < ce) store_quad<DF>(orowp, row_bytes, jq, vq, p.scale_out, gbad);
             }
             if (dcol >= 0) {
                 const unsigned rr = (unsigned)dcol - cb;
                 if ((unsigned)dcol >= cb && (unsigned)dcol < ce && ((rr >> 2) & (NT - 1)) == tl)
-                    st_off<float>(orowp, (unsigned)dcol * 4u, diag);
+                    store_entry<DF>(orowp, (unsigned)dcol, diag, p.scale_out, gbad);
             }
             if (CERT) { if (ck < p.cert_thresh) p.cert_out[ri] = 1; }     // plain store: the words only ever go 0 -> 1
         }
@@ -884,9 +976,9 @@ level_split_fast_kernel(const LevelArgs p, const int4 *__restrict__ desc, const 
             const int4 df = desc[wf];
             const bool new_f = df.w < 0;
             const unsigned dcol_f = static_cast<unsigned>(pdesc ? pdesc[wf].x : df.x);     // (-1 matches no column)
-            float *orowp = p.out + (long long)df.y * p.ld;
+            char *orowp = out_b + (long long)df.y * p.ld * DEB;
             const double sc = new_f ? 1.0 : 2.0;          // pab carries 1/4; a dragged row weighs 1, not 1/2
-            const unsigned row_bytes = (unsigned)p.ld * 4u;
+            const unsigned row_bytes = (unsigned)p.ld * DEB;
             unsigned ckf = 0xffffffffu;
 #pragma unroll
             for (int q = 0; q < NQ; ++q) {
@@ -898,10 +990,11 @@ level_split_fast_kernel(const LevelArgs p, const int4 *__restrict__ desc, const 
                     vq[e] = (jq + e == dcol_f && new_f) ? 0.5f : v;
                 }
                 if (CERT) { ckf = min(ckf, min(min(cert_key(vq[0]), cert_key(vq[1])), min(cert_key(vq[2]), cert_key(vq[3])))); asm volatile("" : "+v"(ckf)); }
-                if (jq < ce) store_row4(orowp, row_bytes, jq * 4u, vq);
+                if (jq < ce) store_quad<DF>(orowp, row_bytes, jq, vq, p.scale_out, gbad);
             }
             if (CERT) { if (ckf < p.cert_thresh) p.cert_out[df.x] = 1; }
         }
+        if (DF != genphi::kFmtF32) { if (gbad) atomicOr(p.guard, 1u); }      // never taken (cut_format.h): a wrong format rule made loud
 
         // ---- advance the stage state ----
         if (stage_is_a) {
@@ -2026,6 +2119,8 @@ static void put_groups(const genphi::WalkLists &w, DeviceGroups &d, BlobPacker &
     d.n_runs = static_cast<int>(w.run.size() / 4) - 1;
 }
 
+constexpr int kGuardWord = 3;      // d_gcnt[kGuardWord]: the encode guard of a sweep's narrow cuts (group counts use words 0 and 1 of a step's four)
+
 // What exists only while the plan is uploaded.  free_device assigns a default-constructed one: every block goes back to the cache
 // (devbuf.h) and every pointer, size, flag and cache key is what it is before the first upload -- a member added here is reset with the rest.
 // genphi_plan_device_bytes counts idx_blob, lazy_blobs, d_shard_blob, scratch, buf[], result, final_tmp, psi_p, nn_tmp, d_queues,
@@ -2078,6 +2173,11 @@ struct PlanDevice {
     // exactness certificates: one word per row of every level matrix (sz.cert_off[c] = first word of
     // cut c), the per-launch group flags (d_glist) and [certified, other] group counts per step
     int *d_cert = nullptr, *d_gcnt = nullptr;    // (inside d_queues' block)
+    // narrow cuts (cut_format.h): the format of every cut in the sweep being enqueued (empty: all Float32), and the host copy of the
+    // encode guard -- word kGuardWord of d_gcnt, a spare word of step 0's group counts, cleared with the rest at the start of a sweep
+    std::vector<int> cut_fmt;
+    unsigned *guard_host = nullptr;              // (pinned; cached_pinned)
+    bool guard_pending = false;
     // Row shards: an upper level only needs the rows its shard's last-level rows descend from
     // (~80 % of a cut at 8 shards of cfg4, 55-72 % in the two levels below the last).  Per
     // intermediate step: restricted work list (+ SPLIT descriptors) of the current shard (arrays inside sh_blob).
@@ -2133,6 +2233,7 @@ static void free_device(genphi_plan *p)
     for (hipEvent_t e : p->events) (void)hipEventDestroy(e);
     drop_graph(p);
     genphi::SparseLevels *const sparse = p->sparse;
+    if (p->guard_host) genphi::cached_pinned_release(p->guard_host);
     const hipStream_t stream = p->stream;
     const int device = p->device;
     static_cast<PlanDevice &>(*p) = PlanDevice();         // the plan's blocks, in their declaration order ...
@@ -2269,6 +2370,15 @@ int genphi_plan_sparse_levels(const genphi_plan *plan, int32_t *k_out, int64_t *
     std::vector<long long> v(std::max(cap, 0), -1), e(std::max(cap, 0), -1);
     const int m = genphi::sparse_levels_counts(plan->sparse, cap, v.data(), e.data(), nullptr);
     for (int c = 0; c < m; ++c) { if (nnz) nnz[c] = v[c]; if (entries) entries[c] = e[c]; }
+    return m;
+}
+int genphi_plan_cut_formats(const genphi_plan *plan, int32_t *fmt, int32_t cap, uint32_t *guard_out)
+{
+    if (guard_out) *guard_out = 0u;
+    if (!plan || !fmt) return 0;
+    const int m = std::min<int>(std::max(cap, 0), static_cast<int>(plan->cut_fmt.size()));
+    for (int c = 0; c < m; ++c) fmt[c] = plan->cut_fmt[c];
+    if (guard_out && plan->guard_pending && plan->guard_host) *guard_out = *plan->guard_host;
     return m;
 }
 int genphi_plan_set_step_hook(genphi_plan *plan, genphi_step_fn cb, void *user)
@@ -2472,6 +2582,8 @@ static int upload_plan_impl(genphi_plan *p, int device)
     p->d_cert = p->d_gcnt + n_slots * 4;
     HIP_TRY_AS("plan_malloc(p, reinterpret_cast<void **>(&p->d_glist), 2 * ((static_cast<size_t>(pl.max_cut) + 64) / 64 * 64) * sizeof(int))",
                plan_malloc(p, p->d_glist, 2 * ((static_cast<size_t>(pl.max_cut) + 64) / 64 * 64)));
+    HIP_TRY(genphi::cached_pinned(reinterpret_cast<void **>(&p->guard_host), sizeof(unsigned)));
+    *p->guard_host = 0u;
     {
         std::vector<SmallStep> sm(pl.steps.size() + 1);
         for (size_t k = 0; k < pl.steps.size(); ++k)
@@ -2623,21 +2735,23 @@ static hipError_t launch_split(int cpt, int stg, int grid, size_t lds, hipStream
     return hipErrorInvalidValue;
 }
 
-template <int NT, int C, int S, bool CERT, bool CHAIN>
+template <int NT, int C, int S, bool CERT, bool CHAIN, int SF, int DF>
 static hipError_t launch_fast_inst(int grid, size_t lds, hipStream_t stream, const LevelArgs &a, const int4 *desc,
                                    const int4 *grp, const int4 *run, int *queue)
 {
-    hipError_t e = set_max_lds(reinterpret_cast<const void *>(level_split_fast_kernel<NT, C, S, CERT, CHAIN>), lds);
+    hipError_t e = set_max_lds(reinterpret_cast<const void *>(level_split_fast_kernel<NT, C, S, CERT, CHAIN, SF, DF>), lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((level_split_fast_kernel<NT, C, S, CERT, CHAIN>), dim3(grid), dim3(NT), lds, stream, a, desc, grp, run, a.glist, a.pdesc, queue);
+    hipLaunchKernelGGL((level_split_fast_kernel<NT, C, S, CERT, CHAIN, SF, DF>), dim3(grid), dim3(NT), lds, stream, a, desc, grp, run, a.glist, a.pdesc, queue);
     return hipGetLastError();
 }
 
-template <bool CERT, bool CHAIN>
+// (the narrow forms -- SF / DF, cut_format.h -- are the same list, for the (source, destination) pairs of kNarrowPairs only)
+template <bool CERT, bool CHAIN, int SF = genphi::kFmtF32, int DF = genphi::kFmtF32>
 static hipError_t launch_fast(int nt, int cpt, int stg, int grid, size_t lds, hipStream_t stream, const LevelArgs &a,
                               const int4 *desc, const int4 *grp, const int4 *run, int *queue)
 {
-#define GENPHI_F(N, C, S) if (nt == N && cpt <= C && stg == S) return launch_fast_inst<N, C, S, CERT, CHAIN>(grid, lds, stream, a, desc, grp, run, queue);
+#define GENPHI_F(N, C, S) if constexpr (genphi::fast_form_built(SF, N)) { \
+        if (nt == N && cpt <= C && stg == S) return launch_fast_inst<N, C, S, CERT, CHAIN, SF, DF>(grid, lds, stream, a, desc, grp, run, queue); }
     GENPHI_FAST_INSTS(GENPHI_F)
 #undef GENPHI_F
     return hipErrorInvalidValue;
@@ -2657,6 +2771,7 @@ struct LevelCtx {
     bool identity;             // the source matrix is Psi_1 = 1/2 I, never materialised
     bool no_none_row;          // sub-step of a WIDE level: the "none" row belongs to the enclosing level
     bool dbg;                  // GENPHI_WG_TIMES builds: record this launch
+    int fmt_prev = genphi::kFmtF32, fmt_out = genphi::kFmtF32;      // storage format of the cut read / written (cut_format.h; sub-steps: Float32)
 };
 
 static LevelCtx main_ctx(genphi_plan *p, int step)
@@ -2669,6 +2784,7 @@ static LevelCtx main_ctx(genphi_plan *p, int step)
     c.identity = identity_source(step, p->tun);
     c.no_none_row = false;
     c.dbg = (p->tun.dbg_step >= 0 ? p->tun.dbg_step : static_cast<int>(p->plan.steps.size()) - 1) == step;     // default: the last step
+    if (static_cast<size_t>(step) + 1 < p->cut_fmt.size()) { c.fmt_prev = p->cut_fmt[step]; c.fmt_out = p->cut_fmt[step + 1]; }
     return c;
 }
 
@@ -2722,13 +2838,30 @@ static int launch_rows(const LaunchRes &R, LevelArgs a, int mode, bool pos_ord, 
         }
     } else if (mode == genphi::kModeSplit) {
         const genphi::SplitGeometry g = genphi::split_geometry(src_width, width, pos_ord, kernel, a.cert_out != nullptr, R.n_cus, dg.n_segs,
-                                                               dg.n_runs, *R.tun, GENPHI_WG_TIMES != 0);
+                                                               dg.n_runs, *R.tun, GENPHI_WG_TIMES != 0, a.fmt_prev);
         auto chunks_of = [](LevelArgs &l, const genphi::ChunkGeometry &c) {
             l.slot_off = c.slot_off; l.chunk_cols = c.chunk_cols; l.n_chunks = c.n_chunks; l.chunk_magic = c.chunk_magic;
         };
         a.lds_row = g.lds_row;
         int *queue = R.queue;                                                 // zeroed at the start of the sweep
         int *gcnt = R.gcnt;
+        if (a.fmt_prev != genphi::kFmtF32) {
+            // ---- a narrow source cut (cut_format.h): every run is certified -- the certified-rows kernel alone, on the step's own run list ----
+            if (!g.certs || g.chain || genphi::narrow_pair_index(a.fmt_prev, a.fmt_out) < 0)
+                return fail(GENPHI_ERR_ARG, "internal: this step does not read a narrow cut");
+            const genphi::ChunkGeometry &c = g.fast;
+            LevelArgs f = a;
+            chunks_of(f, c);
+            f.n_groups = dg.n_runs;
+            hipError_t ne = hipErrorInvalidValue;
+#define GENPHI_NP(SF, DF) if (a.fmt_prev == genphi::SF && a.fmt_out == genphi::DF) \
+                ne = launch_fast<false, false, genphi::SF, genphi::DF>(c.nt, c.cpt, c.stg, c.grid, c.lds_bytes, R.stream, f, dg.desc, dg.seg, dg.run, queue);
+            GENPHI_NARROW_PAIRS(GENPHI_NP)
+#undef GENPHI_NP
+            HIP_TRY(ne);
+            return GENPHI_OK;
+        }
+        if (a.fmt_out != genphi::kFmtF32) return fail(GENPHI_ERR_ARG, "internal: a narrow run starts at the sparse -> dense step");
         if (g.certs) {
             // ---- certified groups: level_split_fast_kernel ----
             // certified runs -> glist_f / gcnt[0], the segments of the others -> glist_s / gcnt[1]: decided on the device, per launch
@@ -2785,13 +2918,21 @@ static int launch_level(genphi_plan *p, const LevelCtx &cx, const float *psi, fl
     a.cert_thresh = cert_threshold(p->tun);
     a.cert_fast = (kernel == 0 && !p->tun.no_fast && cx.cert_prev != nullptr) ? 1 : 0;
     a.ord_col = d.ord; a.diag_col = nullptr; a.pdesc = nullptr; a.zrow = a.n;
+    // (narrow cuts only occur on a plan's own steps, where the slot is the step: it reads cut `step` and writes cut `step + 1`)
+    a.fmt_prev = cx.fmt_prev; a.fmt_out = cx.fmt_out;
+    a.unit_prev = genphi::cut_unit(step); a.scale_out = genphi::cut_scale(step + 1);
+    a.guard = reinterpret_cast<unsigned *>(p->d_gcnt + kGuardWord);
     if (n_rows <= 0) {
         // nothing to compute (a row shard whose ancestors do not reach this level), but the next level
         // still reads this level's all-zero "none" row for its parentless members
-        if (out_rows == nullptr && !cx.no_none_row)
-            HIP_TRY(hipMemsetAsync(out + s.n * s.ld, 0, static_cast<size_t>(s.ld) * sizeof(float), p->stream));
+        if (out_rows == nullptr && !cx.no_none_row) {
+            const size_t eb = static_cast<size_t>(genphi::format_bytes(a.fmt_out));
+            HIP_TRY(hipMemsetAsync(reinterpret_cast<char *>(out) + static_cast<size_t>(s.n * s.ld) * eb, 0, static_cast<size_t>(s.ld) * eb, p->stream));
+        }
         return GENPHI_OK;
     }
+    if ((a.fmt_prev != genphi::kFmtF32 || a.fmt_out != genphi::kFmtF32) && (kernel != 0 || cx.identity || s.mode != genphi::kModeSplit || out_rows != nullptr))
+        return fail(GENPHI_ERR_ARG, "internal: a narrow cut on a step that keeps Float32");
     if (kernel == 1) {
         dim3 grid(static_cast<unsigned>(n_rows), static_cast<unsigned>((s.ld + 255) / 256));
         hipLaunchKernelGGL(level_naive_kernel, grid, dim3(256), 0, p->stream, a);
@@ -3367,7 +3508,11 @@ static int enqueue_sweep(genphi_plan *p, SweepCall &c)
     const int64_t N = pl.n_pro, ldN = pl.ld[pl.n_levels - 1], n_rows = c.n_rows;
     const std::vector<int> &bid = p->sz.buf_of[p->stay_active ? 0 : 1];       // level buffer of every cut
     int rc;
-    HIP_TRY(hipMemsetAsync(p->d_queues, 0, p->sweep_words * sizeof(int), p->stream));      // queues, group counts, certificates: one array
+    // storage format of every cut (cut_format.h): a pure function of the plan, its hooks and the last list cut
+    p->guard_pending = false;
+    p->cut_fmt = genphi::cut_formats(genphi::sweep_step_kinds(pl, p->tun, kernel, sparse_k, kSmallMax), p->tun.no_narrow ? genphi::kFmtF32 : genphi::kNarrowBuilt);
+    const bool any_narrow = std::any_of(p->cut_fmt.begin(), p->cut_fmt.end(), [](int f) { return f != genphi::kFmtF32; });
+    HIP_TRY(hipMemsetAsync(p->d_queues, 0, p->sweep_words * sizeof(int), p->stream));      // queues, group counts (the encode guard among them), certificates: one array
     if (n_steps == 0) {
         // all probands parentless: result = 1/2 I (src/compute.jl:271-274, loop skipped)
         HIP_TRY(hipMemsetAsync(p->result, 0, static_cast<size_t>(n_rows * ldN) * sizeof(float), p->stream));
@@ -3396,7 +3541,8 @@ static int enqueue_sweep(genphi_plan *p, SweepCall &c)
             // cuts 0..sparse_k are row lists: a list step, or (s == sparse_k) the step that writes cut s+1 as a dense matrix
             std::string serr;
             rc = s < sparse_k ? genphi::sparse_levels_enqueue_step(p->sparse, s, p->stream, serr)
-                              : genphi::sparse_levels_enqueue_dense(p->sparse, p->buf[bid[s + 1]], false, false, st.ld, st.width, p->stream, serr);
+                              : genphi::sparse_levels_enqueue_dense(p->sparse, p->buf[bid[s + 1]], false, false, st.ld, st.width, p->stream, serr,
+                                                                    p->cut_fmt[s + 1], reinterpret_cast<unsigned *>(p->d_gcnt + kGuardWord));
             if (rc == GENPHI_OK && s == sparse_k) rc = genphi::sparse_levels_enqueue_flags(p->sparse, p->stream, serr);
             if (rc) return fail(rc, "sparse levels: " + serr);
             if (timing) HIP_TRY(hipEventRecord(p->events[s + 1], p->stream));
@@ -3458,6 +3604,10 @@ static int enqueue_sweep(genphi_plan *p, SweepCall &c)
         }
         if (rc) return rc;
         if (timing) HIP_TRY(hipEventRecord(p->events[s + 1], p->stream));
+    }
+    if (any_narrow) {      // the encode guard of the narrow cuts: read once the sweep is done (genphi_compute_device)
+        HIP_TRY(hipMemcpyAsync(p->guard_host, p->d_gcnt + kGuardWord, sizeof(unsigned), hipMemcpyDeviceToHost, p->stream));
+        p->guard_pending = true;
     }
     return GENPHI_OK;
 }
@@ -3557,6 +3707,8 @@ int genphi_compute_device(genphi_plan *p, const genphi_opts *opts, genphi_stats 
     trace.mark("sweep done");
     if (c.sparse_k >= 0 && !genphi::sparse_levels_flags_ok(p->sparse))
         return fail(GENPHI_ERR_DEVICE, "sparse levels: a row list did not have the length the plan recorded (internal error)");
+    if (p->guard_pending && *p->guard_host != 0u)
+        return fail(GENPHI_ERR_DEVICE, "narrow cuts: an entry was not an integer of its cut's unit or did not fit its format (internal error)");
     return c.timing ? read_timing(p, c, stats) : GENPHI_OK;
 }
 

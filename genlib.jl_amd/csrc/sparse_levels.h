@@ -59,8 +59,10 @@ int sparse_levels_k(const SparseLevels *sl);                  // last sparse cut
 int sparse_levels_enqueue_step(SparseLevels *sl, int s, hipStream_t stream, std::string &err);
 // ... s == k the step that writes cut k+1 as a dense matrix: out = (n + 1) rows of pitch ld, columns [0, width) written; Float32 or
 // (f64) Float64 entries; compact: rows and columns in the cut's storage order whatever the plan says about slots (the Float64 sweep)
+// fmt = kFmtU16 / kFmtU24 (cut_format.h; Float32 sweeps, compact rows, cut k+1 <= kU16MaxCut / kExactMaxCut): the same matrix as 16- /
+// 24-bit integers in units of 2^-(2(k+1)+1), same pitch in entries; *guard is set != 0 should an entry not fit (it never does)
 int sparse_levels_enqueue_dense(SparseLevels *sl, void *out, bool f64, bool compact, long long ld, long long width, hipStream_t stream,
-                                std::string &err);
+                                std::string &err, int fmt = 0, unsigned *guard = nullptr);
 // ... and after the last sparse step of a sweep: the error flags of the row-list steps are copied to the host (asynchronously); once the
 // stream is synchronised sparse_levels_flags_ok says whether every row had the length the plan recorded for it
 int sparse_levels_enqueue_flags(SparseLevels *sl, hipStream_t stream, std::string &err);

@@ -27,6 +27,7 @@
 // rank words are needed: every grouping of the reference's sum is exact.
 #include "sparse_levels.h"
 
+#include "cut_format.h"
 #include "devcache.h"
 #include "devbuf.h"
 
@@ -82,6 +83,7 @@ struct SpArgs {
     float unit_out;               // 2^-(2s+3): one integer unit of cut s+1
     const int *slot;              // the cut written is stored BY SLOT (a step that stays in place, planner.h: LevelStep::stay): row and column of
     int zrow;                     //   member i = slot[i]; nullptr: compactly (row = column = i).  zrow: the all-zero "none" row (n, or the slot capacity P)
+    unsigned *guard;              // (16-bit output, cut_format.h) one word, set != 0 by an entry past the format's range
 };
 
 // Y_0 = (1/2 I) A^T: row p is the children list of p itself; fm_0[i] = Psi_0[A_i][B_i] = 1/2 only when a member's two parents are
@@ -389,6 +391,28 @@ __device__ __forceinline__ void store4(double *dst, unsigned x, unsigned y, unsi
     __builtin_nontemporal_store(b, reinterpret_cast<d2v_t *>(dst + 2));
 }
 
+// ... and a narrow cut (cut_format.h): the integers themselves, 16 bits each, in the unit of the cut written -- which is the unit they
+// are accumulated in.  Returns whether one of them is past the format's range (the encode guard; it never is where the format rule holds).
+typedef unsigned u2_t __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ bool store4(unsigned short *dst, unsigned x, unsigned y, unsigned z, unsigned w, float)
+{
+    const Quad16 q = pack_quad16(x, y, z, w);             // (cut_format.h: the packing the row kernels unpack)
+    const u2_t v = {q.x, q.y};
+    __builtin_nontemporal_store(v, reinterpret_cast<u2_t *>(dst));
+    return range_bits(x | y | z | w, kFmtU16) != 0u;
+}
+
+struct u24_t { unsigned char b[3]; };      // an entry of a 24-bit cut: packed, little endian; a quad is three whole words
+__device__ __forceinline__ bool store4(u24_t *dst, unsigned x, unsigned y, unsigned z, unsigned w, float)
+{
+    unsigned *d = reinterpret_cast<unsigned *>(dst);
+    const Quad24 q = pack_quad24(x, y, z, w);
+    __builtin_nontemporal_store(q.x, d);
+    __builtin_nontemporal_store(q.y, d + 1);
+    __builtin_nontemporal_store(q.z, d + 2);
+    return range_bits(x | y | z | w, kFmtU24) != 0u;
+}
+
 // ---- rows of Y_k -> the dense matrix of cut k+1: one workgroup per (row, chunk of columns) -------------------------------
 // The chunk's entries are accumulated in LDS (integer units) and leave as whole 16-byte stores, zeros included: the step
 // writes what a FULL / SPLIT row kernel writes (columns [0, width) of every row, the all-zero row n) and reads only lists.
@@ -436,10 +460,13 @@ __global__ void __launch_bounds__(256) sparse_dense_kernel(const SpArgs a)
     if (diag_here && tid == 0) acc[si - c0] = a.half_out + 2u * fm_i;
     __syncthreads();
     OutT *orow = outm + static_cast<long long>(si) * a.ld + c0;
+    bool past = false;
     for (int j = 4 * tid; j < c1 - c0; j += 1024) {
         const uint4 u = *reinterpret_cast<const uint4 *>(acc + j);
-        store4(orow + j, u.x, u.y, u.z, u.w, a.unit_out);
+        if constexpr (sizeof(OutT) < 4) past |= store4(orow + j, u.x, u.y, u.z, u.w, a.unit_out);
+        else store4(orow + j, u.x, u.y, u.z, u.w, a.unit_out);
     }
+    if (past) atomicOr(a.guard, 1u);
 }
 
 inline size_t al256(size_t b) { return (b + 255) / 256 * 256; }
@@ -937,9 +964,17 @@ int sparse_levels_enqueue_step(SparseLevels *sl, int s, hipStream_t stream, std:
     return rc;
 }
 
-int sparse_levels_enqueue_dense(SparseLevels *sl, void *out, bool f64, bool compact, long long ld, long long width, hipStream_t stream, std::string &err)
+int sparse_levels_enqueue_dense(SparseLevels *sl, void *out, bool f64, bool compact, long long ld, long long width, hipStream_t stream, std::string &err,
+                                int fmt, unsigned *guard)
 {
     if (!sl || sl->k < 1) { err = "sparse_levels_enqueue_dense: no sparse cut"; return GENPHI_ERR_ARG; }
+    static_assert(kExactMaxCut == kSparseMaxLevel, "cut_format.h and sparse_levels.h name the same cut");
+    const bool u16 = fmt == kFmtU16, u24 = fmt == kFmtU24;
+    if ((fmt != kFmtF32 && !u16 && !u24) || ((u16 || u24) && (f64 || guard == nullptr || sl->slot[sl->k] != nullptr)) || (u16 && sl->k + 1 > kU16MaxCut) ||
+        (u24 && sl->k + 1 > kExactMaxCut)) {
+        err = "sparse_levels_enqueue_dense: this step does not write that format";
+        return GENPHI_ERR_ARG;
+    }
     sl->lists_fresh = false;                               // (from the next sweep on the list steps run)
     SpArgs a = args_for(sl, sl->k);
     a.out = out; a.ld = ld; a.width = static_cast<int>(width);
@@ -954,7 +989,10 @@ int sparse_levels_enqueue_dense(SparseLevels *sl, void *out, bool f64, bool comp
     a.slot = compact ? nullptr : sl->slot[sl->k];
     a.zrow = compact ? a.n : sl->zrow[sl->k];
     const dim3 grid(static_cast<unsigned>((a.n + 1 + 7) / 8 * 8) * a.n_chunks);
+    a.guard = guard;
     if (f64) hipLaunchKernelGGL(sparse_dense_kernel<double>, grid, dim3(256), lds, stream, a);
+    else if (u16) hipLaunchKernelGGL(sparse_dense_kernel<unsigned short>, grid, dim3(256), lds, stream, a);
+    else if (u24) hipLaunchKernelGGL(sparse_dense_kernel<u24_t>, grid, dim3(256), lds, stream, a);
     else hipLaunchKernelGGL(sparse_dense_kernel<float>, grid, dim3(256), lds, stream, a);
     SP_TRY(hipGetLastError());
     return GENPHI_OK;

@@ -5,8 +5,8 @@
 // genphi_tuning when one is given, else from the environment -- which the library reads only under GENPHI_ENV_HOOKS=1
 // (planner.h: env_hook).  What each is for is also in README.md, "Environment hooks"; none is needed in production.
 //
-// GENPHI_TUNING_HOOKS below is the one place a hook's name is written: the names genphi_tuning_set accepts and the body of
-// tuning_from are expanded from it.
+// GENPHI_TUNING_HOOKS and GENPHI_FORMAT_HOOKS below are the one place a hook's name is written: the names genphi_tuning_set
+// accepts and the body of tuning_from are expanded from them.
 #pragma once
 #include <algorithm>
 #include <climits>
@@ -69,6 +69,7 @@ struct Tuning {
     int sparse_k = -2, sparse_permille = -1, sparse_min_cut = -1, sparse_chunk = 0, sparse_batch = 0, sparse_arena = 0;
     ResultTuning res;
     int sparse_classes = -1;
+    bool no_narrow = false;
 };
 
 // "AxB" / "A:B" hooks: both fields are set when two numbers >= lo are read, neither otherwise
@@ -191,11 +192,19 @@ inline int one_of(int v, int a, int b) { return v == a || v == b ? v : 0; }
        depend on it: tests force 128 so that small inputs cut the buffer on every tile) */                                 \
     X(GENPHI_NEAREST_BUF, t.res.nearest_buf = nearest_buf_entries(std::atoi(e)))
 
+// The hooks of the cuts' storage formats (cut_format.h): same X, same reading, same rules.  They are a list of their own only
+// because tests/tuning_check.cpp pins GENPHI_TUNING_HOOKS at its 50 names ("nothing else") and existing tests are not edited for a new
+// hook; what that test says of "the hooks" now holds for the first list.  tests/cut_format_check.cpp checks this one.
+#define GENPHI_FORMAT_HOOKS(X)                                                                                                           \
+    /* A/B + test: 1 = every dense cut is stored as Float32 (the early exact cuts are 16-bit integers otherwise) */                      \
+    X(GENPHI_NO_NARROW, t.no_narrow = std::atoi(e) != 0)
+
 // is `key` ("GENPHI_NAME") a hook a Tuning understands?  (genphi_tuning_set refuses anything else)
 inline bool tuning_knows(const std::string &key)
 {
 #define GENPHI_X(NAME, SET) if (key == #NAME) return true;
     GENPHI_TUNING_HOOKS(GENPHI_X)
+    GENPHI_FORMAT_HOOKS(GENPHI_X)
 #undef GENPHI_X
     return false;
 }
@@ -213,6 +222,7 @@ inline Tuning tuning_from(const genphi_tuning *tu)
     };
 #define GENPHI_X(NAME, SET) if (const char *e = look(#NAME)) { (void)e; SET; }
     GENPHI_TUNING_HOOKS(GENPHI_X)
+    GENPHI_FORMAT_HOOKS(GENPHI_X)
 #undef GENPHI_X
     return t;
 }

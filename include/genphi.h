@@ -157,6 +157,13 @@ int genphi_plan_set_step_hook(genphi_plan *plan, genphi_step_fn cb, void *user);
  * may be NULL); returns how many were filled.                                                                                   */
 int genphi_plan_sparse_levels(const genphi_plan *plan, int32_t *k_out, int64_t *nnz, int64_t *entries, int32_t cap);
 
+/* Diagnostic: the storage format of every cut in the plan's last Float32 sweep (0 = Float32, 1 = 16-bit integers in units of
+ * 2^-(2c+1), 2 = 24-bit ones): the early dense cuts, whose entries are exactly such integers, are kept narrow between the steps
+ * that carry the format (csrc/cut_format.h).  fmt[c] for c < cap; returns how many were filled (0: no sweep has run yet).
+ * *guard_out (may be NULL) = the sweep's encode guard: 0 unless an entry of a narrow cut was not such an integer, which is an
+ * internal error that genphi_compute_device reports.                                                                          */
+int genphi_plan_cut_formats(const genphi_plan *plan, int32_t *fmt, int32_t cap, uint32_t *guard_out);
+
 /* Device memory the plan holds right now, in bytes (level matrices, row lists of the sparse cuts, the resident result, the index
  * arrays): 0 before the first compute and after genphi_plan_release_device.  What a cache of plans budgets with.             */
 int64_t genphi_plan_device_bytes(const genphi_plan *plan);
