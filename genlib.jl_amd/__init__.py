@@ -25,6 +25,7 @@ meaning, printed lines and error behaviour as the reference:
     gen.implex(ped)                        # GENLIB's gen.implex: distinct ancestors by generation (csrc/implex.hip)
     gen.simuSample(ped); gen.simuProb(..)  # GENLIB's gene dropping: marked alleles of ancestors in the probands (csrc/simu.hip)
     gen.simuIdentity(ped)                  # Jacquard's nine identity coefficients of every pair by gene dropping (csrc/ident.hip)
+    gen.simuSharing(ped, loci=1024)        # linked loci: realised IBD sharing, its variance and the segments (csrc/link.hip)
     gen.descendant(ped, 1); gen.children(ped, 1)   # src/identify.jl:203-215, :77-80 (csrc/loader.cpp)
     gen.phiHist(ped); gen.phiQuantile(ped, 0.5)    # the distribution of the pairwise kinships, on the device (csrc/hist.hip)
 
@@ -37,7 +38,7 @@ from collections import OrderedDict
 import numpy as np
 
 from . import _capi
-from ._capi import PhiPlan, KinshipMatrix, GCPlan, OccPlan, RecPlan, DistPlan, DepthPlan, CompletenessPlan, ImplexPlan, SimuPlan, IdentityPlan, GenphiDeviceError, GenphiLibraryMissing  # noqa: F401
+from ._capi import PhiPlan, KinshipMatrix, GCPlan, OccPlan, RecPlan, DistPlan, DepthPlan, CompletenessPlan, ImplexPlan, SimuPlan, IdentityPlan, SharingPlan, GenphiDeviceError, GenphiLibraryMissing  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
@@ -716,6 +717,121 @@ def simuIdentity(pedigree, pro=None, simulNo=5000, seed=None, labels=False, devi
     try:
         h.compute(device=device)
         return SimuIdentity(probands, h.counts_to_host(), h.simul_no, h.seed, h.alleles(), h.labels_to_host() if labels else None)
+    finally:
+        h.close()
+
+
+class SimuSharing:
+    """What gen.simuSharing returns.  pro: the listed probands; sums: int64 (N, N, 6), the sums over the simulations of m, m^2, n1,
+    n2, g and [n1 > 0] of every pair (include/genphi.h: m = the allele matches summed over the loci, n1 / n2 = the loci with any
+    sharing / with both alleles shared, g = the runs of consecutive loci with any sharing); loci, q and probRecomb = q / 65536, the
+    recombination probability actually used; simulNo and the seed used; alleles: int64 (n_labels, 2), the ID and the side of every
+    founder allele, in label order; labels: int32 (N, 2, simulNo, loci) or None.  Every share below is formed once from the exact
+    integers, in Float64."""
+
+    def __init__(self, pro, sums, loci, q, simulNo, seed, alleles, labels):
+        self.pro, self.sums, self.loci, self.q, self.simulNo, self.seed, self.alleles, self.labels = pro, sums, loci, q, simulNo, seed, alleles, labels
+        self.probRecomb = q / 65536.0
+
+    def __repr__(self):
+        return "SimuSharing(%d probands, loci=%d, probRecomb=%g, simulNo=%d, seed=%d)" % (len(self.pro), self.loci, self.probRecomb, self.simulNo,
+                                                                                         self.seed)
+
+    @property
+    def kinship(self):
+        """(N, N): the mean over the simulations of the realised kinship m_s / (4 loci)."""
+        return self.sums[..., 0] / float(4 * self.simulNo * self.loci)
+
+    @property
+    def kinship_sd(self):
+        """(N, N): the standard deviation over the simulations (divisor simulNo) of the realised kinship m_s / (4 loci):
+        sqrt(S sum m^2 - (sum m)^2) / (4 S loci), the radicand in exact integers."""
+        S = int(self.simulNo)
+        m, m2 = self.sums[..., 0], self.sums[..., 1]
+        den = 4 * S * self.loci
+        if S * int(m2.max(initial=0)) < 2**63:
+            num = S * m2 - m * m
+            return np.sqrt(num.astype(np.float64)) / float(den)
+        num = S * m2.astype(object) - m.astype(object) * m.astype(object)             # Python integers: S sum m^2 may pass 2^63
+        return np.sqrt(np.array([float(v) for v in num.ravel()]).reshape(num.shape)) / float(den)
+
+    @property
+    def ibd1(self):
+        """(N, N): the share of (simulation, locus) at which the pair shares at least one allele identical by descent."""
+        return self.sums[..., 2] / float(self.simulNo * self.loci)
+
+    @property
+    def ibd2(self):
+        """(N, N): the share of (simulation, locus) at which both alleles of the pair are shared."""
+        return self.sums[..., 3] / float(self.simulNo * self.loci)
+
+    @property
+    def segments(self):
+        """(N, N): the mean number of shared segments (runs of consecutive loci with any sharing) per simulation."""
+        return self.sums[..., 4] / float(self.simulNo)
+
+    @property
+    def segment_loci(self):
+        """(N, N): the mean length of a shared segment in loci, sum n1 / sum g; NaN where no segment was seen."""
+        g = self.sums[..., 4]
+        out = np.full(g.shape, np.nan)
+        np.divide(self.sums[..., 2], g, out=out, where=g > 0)
+        return out
+
+    @property
+    def shared(self):
+        """(N, N): the share of the simulations in which the pair shares anything at all."""
+        return self.sums[..., 5] / float(self.simulNo)
+
+    @property
+    def inbreeding(self):
+        """(N,): from the diagonal, (m_ii - 2 S loci) / (2 S loci): the share of (simulation, locus) at which the two alleles of
+        proband i are identical by descent."""
+        n = np.arange(len(self.pro))
+        half = 2 * self.simulNo * self.loci
+        return (self.sums[n, n, 0] - half) / float(half)
+
+
+def sharing_q(loci, length=1.0, probRecomb=None):
+    """q of gen.simuSharing: round(65536 probRecomb), or from Haldane's map over loci - 1 equal intervals of a chromosome of `length`
+    Morgans, r = (1 - exp(-2 length / (loci - 1))) / 2 (one locus: no interval, q = 0).  ValueError outside 0 .. 32768."""
+    if probRecomb is None:
+        loci, length = int(loci), float(length)
+        if not length >= 0.0:
+            raise ValueError("gen.simuSharing: length = %r Morgans" % (length,))
+        r = 0.5 * (1.0 - np.exp(-2.0 * length / (loci - 1))) if loci > 1 else 0.0
+    else:
+        r = float(probRecomb)
+    q = int(round(65536.0 * r)) if np.isfinite(r) else -1
+    if not 0 <= q <= _capi.GENPHI_LINK_MAX_Q:
+        raise ValueError("gen.simuSharing: a recombination probability of %r between neighbouring loci is outside 0 .. 1/2" % (r,))
+    return q
+
+
+def simuSharing(pedigree, pro=None, loci=1024, length=1.0, probRecomb=None, simulNo=1000, seed=None, labels=False, device=None):
+    """gen.simuSharing(pedigree, pro = pro(pedigree), loci = 1024, length = 1.0, simulNo = 1000): gene dropping along a chromosome
+    of `loci` linked loci (GENLIB's gen.simuHaplo is the model): every founder allele is dropped under its own label, a meiosis
+    copies a mosaic of the parent's two chromosomes with crossovers between neighbouring loci, and for every pair of probands the
+    loci shared identical by descent are counted in every simulation.  Returns a SimuSharing: sums, and from them kinship,
+    kinship_sd (how much the realised kinship varies around it), ibd1, ibd2, segments, segment_loci, shared, inbreeding.
+
+    length is the chromosome's length in Morgans: the recombination probability between neighbours comes from Haldane's map over
+    loci - 1 equal intervals; or pass probRecomb itself.  Either is rounded to q / 65536 (sharing_q), and the result reports the
+    probRecomb actually used.  The result is a pure function of the pedigree's relations, the probands, loci, q, the seed and
+    simulNo (include/genphi.h); a sub-list of probands gives the sub-block and gen.branching(pedigree, pro=..) first changes
+    nothing.  seed=None draws 64 fresh bits.  labels=True also returns the probands' labels, (N, 2, simulNo, loci).  The sweep and
+    the pair sums run on the GPU (csrc/link.hip).
+
+    KeyError for an unknown ID; ValueError for loci outside 1 .. 4096, a recombination probability outside 0 .. 1/2, simulNo outside
+    1 .. 2^24, an empty pro, or 2^31 or more ordered pairs.  Each call plans, sweeps and frees its own handle."""
+    probands = globals()["pro"](pedigree) if pro is None else np.ascontiguousarray(pro, dtype=np.int64)
+    if not 1 <= int(loci) <= _capi.GENPHI_LINK_MAX_LOCI:
+        raise ValueError("gen.simuSharing: loci = %r is outside 1 .. 4096" % (loci,))
+    q = sharing_q(loci, length, probRecomb)
+    h = SharingPlan(pedigree.ind, pedigree.father, pedigree.mother, probands, loci=loci, q=q, simul_no=simulNo, seed=seed, labels=labels)
+    try:
+        h.compute(device=device)
+        return SimuSharing(probands, h.sums_to_host(), h.loci, h.q, h.simul_no, h.seed, h.alleles(), h.labels_to_host() if labels else None)
     finally:
         h.close()
 

@@ -81,6 +81,8 @@ EXPORTED_SYMBOLS = [
     "genphi_simu_match_counts", "genphi_simu_stats", "genphi_simu_destroy", "genphi_descendants", "genphi_children",
     "genphi_ident_create", "genphi_ident_levels", "genphi_ident_alleles", "genphi_ident_compute", "genphi_ident_counts_to_host",
     "genphi_ident_labels_to_host", "genphi_ident_stats", "genphi_ident_destroy",
+    "genphi_link_create", "genphi_link_levels", "genphi_link_alleles", "genphi_link_compute", "genphi_link_sums_to_host",
+    "genphi_link_labels_to_host", "genphi_link_stats", "genphi_link_destroy", "genphi_link_words",
 ]
 
 _lib = None
@@ -359,6 +361,25 @@ def lib():
         L.genphi_ident_stats.restype = C.c_int
         L.genphi_ident_destroy.argtypes = [C.c_void_p]
         L.genphi_ident_destroy.restype = None
+        L.genphi_link_create.argtypes = [C.c_int64, _I64P, _I64P, _I64P, C.c_int64, _I64P, C.c_int32, C.c_int32, C.c_int64, C.c_uint64, C.c_int32,
+                                         C.c_int32, C.POINTER(C.c_void_p)]
+        L.genphi_link_create.restype = C.c_int
+        L.genphi_link_levels.argtypes = [C.c_void_p, _I64P, _I32P, _I64P]
+        L.genphi_link_levels.restype = C.c_int
+        L.genphi_link_alleles.argtypes = [C.c_void_p, _I64P, _I32P, _I64P, _I32P]
+        L.genphi_link_alleles.restype = C.c_int
+        L.genphi_link_compute.argtypes = [C.c_void_p, C.c_int32]
+        L.genphi_link_compute.restype = C.c_int
+        L.genphi_link_sums_to_host.argtypes = [C.c_void_p, _I64P]
+        L.genphi_link_sums_to_host.restype = C.c_int
+        L.genphi_link_labels_to_host.argtypes = [C.c_void_p, _I32P]
+        L.genphi_link_labels_to_host.restype = C.c_int
+        L.genphi_link_stats.argtypes = [C.c_void_p, _F64P, _F64P, _F64P, _F64P, _F64P, _I32P, _I32P, _I64P, _I32P, _I32P, _I32P, _I32P]
+        L.genphi_link_stats.restype = C.c_int
+        L.genphi_link_destroy.argtypes = [C.c_void_p]
+        L.genphi_link_destroy.restype = None
+        L.genphi_link_words.argtypes = [C.c_uint64, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.genphi_link_words.restype = C.c_int
         L.genphi_descendants.argtypes = [C.c_int64, _I64P, _I64P, _I64P, C.c_int64, _I64P, _I64P, C.POINTER(_I64P)]
         L.genphi_descendants.restype = C.c_int
         L.genphi_children.argtypes = [C.c_int64, _I64P, _I64P, _I64P, C.c_int64, _I64P, C.POINTER(_I64P)]
@@ -1589,6 +1610,87 @@ class IdentityPlan(_SweepPlan):
         return self._stats(sweep_ms=C.c_double, pair_ms=C.c_double, algorithmic_bytes=C.c_double, word_ops=C.c_double, levels=C.c_int32,
                            panel_cols=C.c_int32, panels=C.c_int64, planes=C.c_int32, tile_rows=C.c_int32, tile_cols=C.c_int32,
                            lanes_per_row=C.c_int32)
+
+
+GENPHI_LINK_FLAG_LABELS = 1
+GENPHI_LINK_FLAG_ALL_PAIRS = 2
+GENPHI_LINK_MAX_LOCI = 4096
+GENPHI_LINK_MAX_Q = 32768
+
+
+class SharingPlan(_SweepPlan):
+    """The handle of gen.simuSharing (include/genphi.h, genphi_link_*): gene dropping along a chromosome of `loci` linked loci with
+    the recombination probability q / 65536 between neighbours, and the sharing of every pair of probands.  Planned on the host at
+    construction (KeyError on an unknown proband; ValueError for loci outside 1 .. 4096, q outside 0 .. 32768, simul_no outside
+    1 .. 2^24, no probands, 2^31 or more ordered pairs, a negative panel_sims; no GPU needed), swept on the GPU by compute().
+    seed=None draws 64 fresh bits; .seed reports the seed used.  labels: keep the probands' labels.  panel_sims: the simulations of
+    a panel (0 = the default).  all_pairs: the pair kernel computes every ordered pair (the same sums; an A/B)."""
+
+    _prefix = "link"
+
+    def __init__(self, ind, father, mother, pro_ids, loci=1024, q=64, simul_no=1000, seed=None, labels=False, panel_sims=0, all_pairs=False):
+        pro_ids = _i64(pro_ids).ravel()
+        if seed is None:
+            import secrets
+            seed = secrets.randbits(64)
+        self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.simul_no, self.loci, self.q = int(simul_no), int(loci), int(q)
+        if not (-2**31 <= self.loci < 2**31 and -2**31 <= self.q < 2**31):
+            raise ValueError("gen.simuSharing: loci = %d or q = %d is not a 32-bit integer" % (self.loci, self.q))
+        self.labels = bool(labels)
+        ind, father, mother = _i64(ind), _i64(father), _i64(mother)
+        h = C.c_void_p()
+        flags = (GENPHI_LINK_FLAG_LABELS if labels else 0) | (GENPHI_LINK_FLAG_ALL_PAIRS if all_pairs else 0)
+        rc = lib().genphi_link_create(len(ind), ind.ctypes.data_as(_I64P), father.ctypes.data_as(_I64P), mother.ctypes.data_as(_I64P),
+                                      len(pro_ids), pro_ids.ctypes.data_as(_I64P), self.loci, self.q, self.simul_no, self.seed, int(panel_sims),
+                                      flags, C.byref(h))
+        if rc:
+            _raise(rc)
+        self._h = h
+        self.n_pro = len(pro_ids)
+        n_live, levels, n_labels, planes = C.c_int64(), C.c_int32(), C.c_int64(), C.c_int32()
+        self._call("levels", C.byref(n_live), C.byref(levels), None)
+        self._call("alleles", C.byref(n_labels), C.byref(planes), None, None)
+        self.n_live, self.levels, self.n_labels, self.planes = int(n_live.value), int(levels.value), int(n_labels.value), int(planes.value)
+
+    def rows_per_level(self):
+        """The live rows of every level (host only)."""
+        out = np.empty(self.levels, dtype=np.int64)
+        self._call("levels", None, None, out.ctypes.data_as(_I64P))
+        return out
+
+    def alleles(self):
+        """The allele table (host only): int64 (n_labels, 2), the ID and the side (0 = from the father) of every label."""
+        ids, sides = np.empty(self.n_labels, np.int64), np.empty(self.n_labels, np.int32)
+        self._call("alleles", None, None, ids.ctypes.data_as(_I64P), sides.ctypes.data_as(C.POINTER(C.c_int32)))
+        return np.stack([ids, sides.astype(np.int64)], axis=1)
+
+    def sums_to_host(self):
+        """The (n_pro, n_pro, 6) int64 sums over the simulations: m, m^2, n1, n2, g and [n1 > 0] (include/genphi.h)."""
+        return self._out("sums_to_host", (self.n_pro, self.n_pro, 6), np.int64, C.c_int64)
+
+    def labels_to_host(self):
+        """The (n_pro, 2, simul_no, loci) int32 labels of the probands' two sides.  ValueError unless created with labels=True."""
+        return self._out("labels_to_host", (self.n_pro, 2, self.simul_no, self.loci), np.int32, C.c_int32)
+
+    def stats(self):
+        """dict(sweep_ms, pair_ms, algorithmic_bytes, word_ops, philox_blocks, levels, panel_sims, panels, planes, tile_rows,
+        tile_cols, lanes_per_sim) of the last compute()."""
+        return self._stats(sweep_ms=C.c_double, pair_ms=C.c_double, algorithmic_bytes=C.c_double, word_ops=C.c_double, philox_blocks=C.c_double,
+                           levels=C.c_int32, panel_sims=C.c_int32, panels=C.c_int64, planes=C.c_int32, tile_rows=C.c_int32, tile_cols=C.c_int32,
+                           lanes_per_sim=C.c_int32)
+
+
+def link_words(seed, ID, side, s, loci, q):
+    """(X, T): the crossover and transmission words, uint64 of length ceil(loci / 64), of (seed, ID, side, simulation s):
+    genphi_link_words, host only -- what the step kernel of gen.simuSharing draws."""
+    W = (max(int(loci), 1) + 63) // 64
+    X, T = np.zeros(W, dtype=np.uint64), np.zeros(W, dtype=np.uint64)
+    u64 = C.POINTER(C.c_uint64)
+    rc = lib().genphi_link_words(int(seed) & 0xFFFFFFFFFFFFFFFF, int(ID), int(side), int(s), int(loci), int(q), X.ctypes.data_as(u64), T.ctypes.data_as(u64))
+    if rc:
+        _raise(rc)
+    return X, T
 
 
 def genealogy_depth(ind, father, mother, leaves_only=False):

@@ -1,5 +1,5 @@
-// drop_device.h -- the device helpers the two gene-dropping sweeps (simu.hip, ident.hip) share: the random word of a meiosis, the
-// meiosis itself and the mask of the simulated columns.  gen.simuIdentity relies on drawing THE word gen.simuSample draws for the same
+// drop_device.h -- the device helpers the gene-dropping sweeps (simu.hip, ident.hip, link.hip) share: the random word of a meiosis, the
+// meiosis itself and the mask of the simulated columns (link.hip: of the loci).  gen.simuIdentity relies on drawing THE word gen.simuSample draws for the same
 // (seed, ID, side, absolute pair index): both take it from here.
 #pragma once
 #include <hip/hip_runtime.h>

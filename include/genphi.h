@@ -1065,6 +1065,85 @@ int genphi_ident_stats(const genphi_ident *h, double *sweep_ms, double *pair_ms,
                        int32_t *lanes_per_row);
 void genphi_ident_destroy(genphi_ident *h);
 
+/* ---- gen.simuSharing: linked-locus gene dropping and IBD segments (csrc/link.hip, csrc/link.cpp) ------------------------------------
+ * gen.simuIdentity above drops every founder allele at ONE locus.  Here a simulation is a chromosome of L linked loci: a meiosis
+ * copies a mosaic of the parent's two chromosomes, and the sharing of a pair of probands is read off locus by locus: how much of the
+ * chromosome they share identical by descent (IBD) in one realisation, how much that varies, and in how many segments it comes.
+ * GENLIB's gen.simuHaplo is the model; the reference has no form of it, so this text is the definition, and it is this package's own.
+ * Inputs.  A pedigree and pro_ids, the listed probands, with the rules of genphi_ident_create.  loci = L with 1 <= L <= 4096;
+ * W = ceil(L / 64) words per chromosome.  q with 0 <= q <= 32768: the recombination probability between neighbouring loci is
+ * r = q / 65536 exactly; q = 32768 gives independent loci, q = 0 no recombination.  simul_no = S with 1 <= S <= 2^24.  A 64-bit
+ * seed.  panel_sims: 0 = the default rule, else the simulations of a panel.  Flags: LABELS and ALL_PAIRS, as for ident.
+ * Live set, levels, rows, allele table, n_labels and B are those of genphi_ident_* for the same pedigree and probands.
+ * Random words.  For individual ID, side (0 = the copy from the father), simulation s and chromosome word w < W, block d is
+ * Philox4x32-10 with the counter (ID low, ID high, s, 0x80000000 | side | w << 1 | d << 8) and the key (seed low, seed high).  Bit 31
+ * of the last counter word keeps these streams disjoint from the gene-dropping word (there the word is 0 or 1) and from the
+ * bootstrap's (2).  U_2d = o0 | o1 << 32 and U_2d+1 = o2 | o3 << 32 of block d, for d = 0 .. 7.
+ * Crossover word.  acc = 0; for t = 0 .. 15, with q_t = bit t of q: acc = q_t ? (acc | U_t) : (acc & U_t); X(w) = acc.  Every bit
+ * of X(w) is set with probability q / 65536 exactly, independently of the others.  Blocks below the lowest set bit of q leave
+ * acc at 0 and may be skipped.  In word 0, bit 0 of X is replaced by bit 0 of U_16 (block d = 8): the strand the copy starts on, a
+ * fair coin.  Bit k of the chromosome is bit k % 64 of word k / 64.
+ * Transmission word.  T is the inclusive prefix XOR of X along the whole chromosome: T[k] = X[0] ^ .. ^ X[k].
+ * Rule.
+ *   - A side with an unknown parent holds its own label at every locus of every simulation.
+ *   - With a known father f: LP_x[s, k] = T[k] ? LP_f[s, k] : LM_f[s, k], with the T of (ID(x), 0, s).  With a known mother m the
+ *     same from LP_m, LM_m with the T of (ID(x), 1, s).
+ *   - Under selfing the two sides draw independent words.
+ * Statistics.  For the pair (i, j) of listed probands in simulation s at locus k < L, take a = LP_i, b = LM_i, c = LP_j, d = LM_j:
+ *   e = [a=c] + [a=d] + [b=c] + [b=d];  any = e > 0;  two = (a=c and b=d) or (a=d and b=c).
+ * Per simulation: m_s = sum_k e; n1_s = sum_k any; n2_s = sum_k two; g_s = the number of maximal runs of consecutive loci with any
+ * (runs do not wrap round, and loci >= L do not exist).  The result is sums[i, j, 0 .. 5], Int64, n_pro x n_pro x 6, row-major:
+ *   0: sum_s m_s    1: sum_s m_s^2    2: sum_s n1_s    3: sum_s n2_s    4: sum_s g_s    5: sum_s [n1_s > 0]
+ * All six are symmetric in (i, j).  m_s <= 4 L <= 2^14, so sum_s m_s^2 <= 2^52.
+ * Labels.  Under GENPHI_LINK_FLAG_LABELS the result also carries the probands' labels, n_pro x 2 x S x L Int32.  They are refused
+ * with GENPHI_ERR_ALLOC before any launch when they do not fit: by compute for the device at hand, and by create already when they
+ * are 2^48 bytes or more.
+ * Invariants, all exact.  The result is a pure function of (pedigree relations, proband IDs, L, q, seed, S): it does not depend
+ * on the panel width or on ALL_PAIRS; a sub-list of probands gives the sub-block; gen.branching(ped, pro=P) first changes nothing;
+ * the labels of S = 3 are the first three simulations of S = 100.  With q = 0 every locus of a simulation carries the same label,
+ * so m_s is L times 0, 1, 2 or 4 and g_s = [n1_s > 0].  A diagonal pair has n1_s = L and g_s = 1.
+ * Errors.  Those of genphi_ident_create; L or q out of range -> GENPHI_ERR_ARG.
+ * Method.  ident's planes, with the column of a panel row running over (simulation, pair of words), the pair fastest.  In the step
+ * kernel the lanes that own the pairs of words of one simulation are neighbours in a wave; each draws and folds its own X words,
+ * and the parity of all earlier words reaches it by a segmented XOR scan over those lanes (wave shuffles); inside a word the prefix
+ * is six shift-and-XOR steps.  The pair kernel has ident's tiles and walks simulation-major: per word the four equality words,
+ * any and two, popcounts, and the runs as popcount(any & ~(any << 1 | carry)) with the carry from the previous word.
+ *   create            host only (no GPU): ident's checks and plan.  A panel is a whole number of simulations: panel_sims of them, cut
+ *                     to S; 0 = all of S, or the most that fit the device
+ *   levels, alleles   as genphi_ident_levels and genphi_ident_alleles
+ *   compute           the sweep on `device` (-1 = current); sums (and labels) stay resident
+ *   sums_to_host      out: n_pro x n_pro x 6 Int64, row-major
+ *   labels_to_host    out: n_pro x 2 x S x L Int32, row-major; GENPHI_ERR_ARG without GENPHI_LINK_FLAG_LABELS
+ *   stats             of the last compute, by HIP events: the device time of init and level steps, and of gather and pair kernel,
+ *                     summed over the panels; the algorithmic bytes of the steps (per side with a known parent and simulation: two
+ *                     runs of B planes read and one written, 16 bytes per plane and pair of words); the word operations of the pair
+ *                     kernel (pairs computed -- n_pro (n_pro + 1) / 2, or n_pro^2 under ALL_PAIRS -- x S x W x (8 B + 32): per plane
+ *                     an XOR and an OR for each of the four equality words, then 8 to negate and mask them, 6 for any and two, 12
+ *                     for the six popcounts and their adds and 6 for the run count and its carry); the Philox blocks drawn (per
+ *                     side with a known parent and simulation: W x (8 - first block drawn) + 1); levels; the simulations of a
+ *                     panel; the panels; B; the pair kernel's tile rows and columns; the lanes per simulation of the step kernel
+ *   words             host only, as genphi_bootstrap_counts is: X[0 .. W) and T[0 .. W) of (seed, ID, side, simulation s) for L loci
+ *                     at q, from the code the step kernel draws with; either may be NULL.  GENPHI_ERR_ARG: L, q, side or s (0 ..
+ *                     2^24 - 1) out of range                                                                                       */
+#define GENPHI_LINK_FLAG_LABELS 1
+#define GENPHI_LINK_FLAG_ALL_PAIRS 2
+#define GENPHI_LINK_MAX_LOCI 4096
+#define GENPHI_LINK_MAX_Q 32768
+typedef struct genphi_link genphi_link;
+int genphi_link_create(int64_t n_ind, const int64_t *ind, const int64_t *father, const int64_t *mother,
+                       int64_t n_pro, const int64_t *pro_ids, int32_t loci, int32_t q, int64_t simul_no, uint64_t seed,
+                       int32_t panel_sims, int32_t flags, genphi_link **out);
+int genphi_link_levels(const genphi_link *h, int64_t *n_live, int32_t *levels, int64_t *rows_per_level);
+int genphi_link_alleles(const genphi_link *h, int64_t *n_labels, int32_t *planes, int64_t *ids, int32_t *sides);
+int genphi_link_compute(genphi_link *h, int32_t device);
+int genphi_link_sums_to_host(genphi_link *h, int64_t *out);
+int genphi_link_labels_to_host(genphi_link *h, int32_t *out);
+int genphi_link_stats(const genphi_link *h, double *sweep_ms, double *pair_ms, double *algorithmic_bytes, double *word_ops,
+                      double *philox_blocks, int32_t *levels, int32_t *panel_sims, int64_t *panels, int32_t *planes,
+                      int32_t *tile_rows, int32_t *tile_cols, int32_t *lanes_per_sim);
+void genphi_link_destroy(genphi_link *h);
+int genphi_link_words(uint64_t seed, int64_t id, int32_t side, int64_t s, int32_t loci, int32_t q, uint64_t *X, uint64_t *T);
+
 /* gen.descendant and gen.children (src/identify.jl:203-215, :77-80), host only: the strict descendants of ids[0 .. n_ids) (the
  * union over them), and the children of one ID, ascending; *out is allocated by the library (genphi_free).  No order of the
  * pedigree is assumed.  Unknown ID -> GENPHI_ERR_UNKNOWN_ID.                                                                  */
