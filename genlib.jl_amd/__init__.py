@@ -25,6 +25,7 @@ meaning, printed lines and error behaviour as the reference:
     gen.implex(ped)                        # GENLIB's gen.implex: distinct ancestors by generation (csrc/implex.hip)
     gen.simuSample(ped); gen.simuProb(..)  # GENLIB's gene dropping: marked alleles of ancestors in the probands (csrc/simu.hip)
     gen.simuIdentity(ped)                  # Jacquard's nine identity coefficients of every pair by gene dropping (csrc/ident.hip)
+    gen.simuRetention(ped)                 # founder allele survival, founder genome equivalents by gene dropping (csrc/retain.hip)
     gen.simuSharing(ped, loci=1024)        # linked loci: realised IBD sharing, its variance and the segments (csrc/link.hip)
     gen.descendant(ped, 1); gen.children(ped, 1)   # src/identify.jl:203-215, :77-80 (csrc/loader.cpp)
     gen.phiHist(ped); gen.phiQuantile(ped, 0.5)    # the distribution of the pairwise kinships, on the device (csrc/hist.hip)
@@ -38,7 +39,7 @@ from collections import OrderedDict
 import numpy as np
 
 from . import _capi
-from ._capi import PhiPlan, KinshipMatrix, GCPlan, OccPlan, RecPlan, DistPlan, DepthPlan, CompletenessPlan, ImplexPlan, SimuPlan, IdentityPlan, SharingPlan, GenphiDeviceError, GenphiLibraryMissing  # noqa: F401
+from ._capi import PhiPlan, KinshipMatrix, GCPlan, OccPlan, RecPlan, DistPlan, DepthPlan, CompletenessPlan, ImplexPlan, SimuPlan, IdentityPlan, RetentionPlan, SharingPlan, GenphiDeviceError, GenphiLibraryMissing  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
@@ -717,6 +718,132 @@ def simuIdentity(pedigree, pro=None, simulNo=5000, seed=None, labels=False, devi
     try:
         h.compute(device=device)
         return SimuIdentity(probands, h.counts_to_host(), h.simul_no, h.seed, h.alleles(), h.labels_to_host() if labels else None)
+    finally:
+        h.close()
+
+
+class SimuRetention:
+    """What gen.simuRetention returns.  pro: the listed probands; alleles: int64 (n_labels, 2), the ID and the side (0 = from the
+    father) of every founder allele, in label order; survived, both: int32 (n_labels,); distinct: int32 (simulNo,) (the definition is
+    the text of genphi_retain_* in include/genphi.h); simulNo and the seed used.  Every share below is formed once from the integers,
+    in Float64.  p: the expected frequency of every founder allele among the proband genes, or None (contributions=False)."""
+
+    def __init__(self, pro, alleles, survived, both, distinct, simulNo, seed, p=None):
+        self.pro, self.alleles, self.survived, self.both, self.distinct = pro, alleles, survived, both, distinct
+        self.simulNo, self.seed, self.p = simulNo, seed, p
+        ids = alleles[:, 0]
+        first = np.ones(len(ids), dtype=bool)
+        first[1:] = ids[1:] != ids[:-1]
+        self._first = np.flatnonzero(first)                        # the label of every founder's first allele
+        self._two = np.diff(np.append(self._first, len(ids))) == 2
+
+    def __repr__(self):
+        return "SimuRetention(%d probands, %d founder alleles, simulNo=%d, seed=%d)" % (len(self.pro), len(self.alleles), self.simulNo, self.seed)
+
+    @property
+    def retention(self):
+        """(n_labels,): the share of the simulations in which the allele survives in at least one proband."""
+        return self.survived / float(self.simulNo)
+
+    @property
+    def founders(self):
+        """The IDs of the allele table, ascending: the founders and half-founders of the live set."""
+        return self.alleles[self._first, 0]
+
+    @property
+    def n_alleles(self):
+        """Per founder: 2, or 1 for a half-founder."""
+        return np.where(self._two, 2, 1)
+
+    def _sums(self):
+        s = self.survived.astype(np.int64)
+        second = np.where(self._two, s[np.minimum(self._first + 1, len(s) - 1)], 0)
+        return s[self._first], second, np.where(self._two, self.both[self._first].astype(np.int64), 0)
+
+    @property
+    def kept(self):
+        """Per founder: the mean retention of its alleles."""
+        a, b, _ = self._sums()
+        return (a + b) / (self.n_alleles * float(self.simulNo))
+
+    @property
+    def lost(self):
+        """Per founder: the share of the simulations in which none of its alleles survives."""
+        a, b, ab = self._sums()
+        return (self.simulNo - (a + b - ab)) / float(self.simulNo)
+
+    @property
+    def whole(self):
+        """Per founder: the share of the simulations in which both of its alleles survive; NaN for a half-founder."""
+        ab = self._sums()[2]
+        return np.where(self._two, ab / float(self.simulNo), np.nan)
+
+    @property
+    def alleles_mean(self):
+        """The mean number of distinct founder alleles left in a simulation."""
+        return int(self.survived.sum(dtype=np.int64)) / float(self.simulNo)
+
+    @property
+    def alleles_sd(self):
+        """The standard deviation (over the simulations, divisor simulNo) of the number of distinct founder alleles left."""
+        d = self.distinct.astype(np.int64)
+        n = self.simulNo
+        return float(np.sqrt(max(n * int((d * d).sum()) - int(d.sum()) ** 2, 0)) / n)
+
+    @property
+    def hist(self):
+        """hist[k]: the simulations with exactly k distinct founder alleles left."""
+        return np.bincount(self.distinct)
+
+    @property
+    def fe(self):
+        """The founder equivalents 1 / (2 sum p^2) (Lacy 1989); None without contributions."""
+        return None if self.p is None else 1.0 / (2.0 * float(np.sum(self.p * self.p)))
+
+    @property
+    def fg_dropped(self):
+        """The alleles with retention 0 that the fg sum leaves out."""
+        return int(np.count_nonzero(self.survived == 0))
+
+    @property
+    def fg(self):
+        """Lacy's founder genome equivalents 1 / (2 sum p^2 / retention) over the alleles with retention > 0; None without
+        contributions."""
+        if self.p is None:
+            return None
+        k = self.survived > 0
+        return 1.0 / (2.0 * float(np.sum(self.p[k] * self.p[k] * (float(self.simulNo) / self.survived[k]))))
+
+
+def simuRetention(pedigree, pro=None, simulNo=5000, seed=None, contributions=True, device=None):
+    """gen.simuRetention(pedigree, pro = pro(pedigree), simulNo = 5000): which founder alleles are still present in the probands,
+    and how many (MacCluer et al. 1986), estimated by gene dropping: every founder allele is dropped down the pedigree under its own
+    label simulNo times (the labels of gen.simuIdentity under the same seed), and in every simulation the labels the probands carry
+    are marked.  Returns a SimuRetention: per founder allele survived and retention; per founder kept, lost and whole; per
+    simulation distinct, with alleles_mean, alleles_sd and hist; and, with contributions=True, p, the exact expected frequency of
+    every founder allele among the 2 n genes of the n different listed probands (sum_i gen.gc(i, founder) / (2 n), with gen.gc's
+    rule that only individuals without children receive contributions; it sums to 1 for such probands), the founder equivalents fe
+    and Lacy's founder genome equivalents fg.
+
+    The result is a pure function of the pedigree's relations, the set of listed probands (order and repeats change nothing), the
+    seed and simulNo (include/genphi.h); gen.branching(pedigree, pro=..) first changes nothing.  seed=None draws 64 fresh bits; pass
+    a seed to repeat a run.  The sweep and the reduction run on the GPU (csrc/retain.hip); only 2 n_labels + simulNo integers come
+    back, and any number of probands is taken.
+
+    KeyError for an unknown ID; ValueError for simulNo outside 1 .. 2^24 or an empty pro.  Each call plans, sweeps and frees its
+    own handles."""
+    probands = globals()["pro"](pedigree) if pro is None else np.ascontiguousarray(pro, dtype=np.int64)
+    h = RetentionPlan(pedigree.ind, pedigree.father, pedigree.mother, probands, simul_no=simulNo, seed=seed)
+    try:
+        h.compute(device=device)
+        alleles = h.alleles()
+        p = None
+        if contributions:
+            listed = np.unique(probands)
+            ids, inverse = np.unique(alleles[:, 0], return_inverse=True)
+            c = gc(pedigree, pro=listed, ancestors=ids, device=device).astype(np.float64).sum(axis=0)
+            p = c[inverse] / (2.0 * len(listed))
+        return SimuRetention(probands, alleles, h.survived_to_host(), h.both_to_host(), h.distinct_to_host(), h.simul_no, h.seed, p)
     finally:
         h.close()
 

@@ -81,6 +81,8 @@ EXPORTED_SYMBOLS = [
     "genphi_simu_match_counts", "genphi_simu_stats", "genphi_simu_destroy", "genphi_descendants", "genphi_children",
     "genphi_ident_create", "genphi_ident_levels", "genphi_ident_alleles", "genphi_ident_compute", "genphi_ident_counts_to_host",
     "genphi_ident_labels_to_host", "genphi_ident_stats", "genphi_ident_destroy",
+    "genphi_retain_create", "genphi_retain_levels", "genphi_retain_alleles", "genphi_retain_compute", "genphi_retain_survived_to_host",
+    "genphi_retain_both_to_host", "genphi_retain_distinct_to_host", "genphi_retain_stats", "genphi_retain_destroy",
     "genphi_link_create", "genphi_link_levels", "genphi_link_alleles", "genphi_link_compute", "genphi_link_sums_to_host",
     "genphi_link_labels_to_host", "genphi_link_stats", "genphi_link_destroy", "genphi_link_words",
 ]
@@ -361,6 +363,23 @@ def lib():
         L.genphi_ident_stats.restype = C.c_int
         L.genphi_ident_destroy.argtypes = [C.c_void_p]
         L.genphi_ident_destroy.restype = None
+        L.genphi_retain_create.argtypes = [C.c_int64, _I64P, _I64P, _I64P, C.c_int64, _I64P, C.c_int64, C.c_uint64, C.c_int32, C.c_int32, C.c_int32,
+                                           C.POINTER(C.c_void_p)]
+        L.genphi_retain_create.restype = C.c_int
+        L.genphi_retain_levels.argtypes = [C.c_void_p, _I64P, _I32P, _I64P]
+        L.genphi_retain_levels.restype = C.c_int
+        L.genphi_retain_alleles.argtypes = [C.c_void_p, _I64P, _I32P, _I64P, _I32P]
+        L.genphi_retain_alleles.restype = C.c_int
+        L.genphi_retain_compute.argtypes = [C.c_void_p, C.c_int32]
+        L.genphi_retain_compute.restype = C.c_int
+        for name in ("survived", "both", "distinct"):
+            fn = getattr(L, "genphi_retain_%s_to_host" % name)
+            fn.argtypes = [C.c_void_p, _I32P]
+            fn.restype = C.c_int
+        L.genphi_retain_stats.argtypes = [C.c_void_p, _F64P, _F64P, _F64P, _F64P, _I32P, _I32P, _I64P, _I32P, _I32P, _I64P, _I32P, _I32P]
+        L.genphi_retain_stats.restype = C.c_int
+        L.genphi_retain_destroy.argtypes = [C.c_void_p]
+        L.genphi_retain_destroy.restype = None
         L.genphi_link_create.argtypes = [C.c_int64, _I64P, _I64P, _I64P, C.c_int64, _I64P, C.c_int32, C.c_int32, C.c_int64, C.c_uint64, C.c_int32,
                                          C.c_int32, C.POINTER(C.c_void_p)]
         L.genphi_link_create.restype = C.c_int
@@ -1610,6 +1629,78 @@ class IdentityPlan(_SweepPlan):
         return self._stats(sweep_ms=C.c_double, pair_ms=C.c_double, algorithmic_bytes=C.c_double, word_ops=C.c_double, levels=C.c_int32,
                            panel_cols=C.c_int32, panels=C.c_int64, planes=C.c_int32, tile_rows=C.c_int32, tile_cols=C.c_int32,
                            lanes_per_row=C.c_int32)
+
+
+GENPHI_RETAIN_FLAG_PLAIN_OR = 1
+GENPHI_RETAIN_FLAG_TEST_FIRST = 2
+
+
+class RetentionPlan(_SweepPlan):
+    """The handle of gen.simuRetention (include/genphi.h, genphi_retain_*): which founder alleles survive in the listed probands, by
+    gene dropping.  Planned on the host at construction (KeyError on an unknown proband; ValueError for simul_no outside 1 .. 2^24,
+    no probands, a negative panel_cols or chunk_labels, an unknown mark; no GPU needed), swept on the GPU by compute().  The plan and
+    the labels are gen.IdentityPlan's for the same arguments, but any number of probands is taken.  seed=None draws 64 fresh bits;
+    .seed reports the seed used.  panel_cols: the simulations of a panel (0 = the default).  chunk_labels: the founder alleles of a
+    chunk of the mark kernel (0 = the default).  mark: None = the form of the mark phase that ships, "or" = an unconditional LDS
+    atomic OR, "test" = read the word first and skip the atomic when the bit is set (the same result; an A/B)."""
+
+    _prefix = "retain"
+    _marks = {None: 0, "or": GENPHI_RETAIN_FLAG_PLAIN_OR, "test": GENPHI_RETAIN_FLAG_TEST_FIRST}
+
+    def __init__(self, ind, father, mother, pro_ids, simul_no=5000, seed=None, panel_cols=0, chunk_labels=0, mark=None):
+        pro_ids = _i64(pro_ids).ravel()
+        if mark not in self._marks:
+            raise ValueError("gen.simuRetention: mark is None, 'or' or 'test', not %r" % (mark,))
+        if seed is None:
+            import secrets
+            seed = secrets.randbits(64)
+        self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.simul_no = int(simul_no)
+        ind, father, mother = _i64(ind), _i64(father), _i64(mother)
+        h = C.c_void_p()
+        rc = lib().genphi_retain_create(len(ind), ind.ctypes.data_as(_I64P), father.ctypes.data_as(_I64P), mother.ctypes.data_as(_I64P),
+                                        len(pro_ids), pro_ids.ctypes.data_as(_I64P), self.simul_no, self.seed, int(panel_cols), int(chunk_labels),
+                                        self._marks[mark], C.byref(h))
+        if rc:
+            _raise(rc)
+        self._h = h
+        self.n_pro = len(pro_ids)
+        n_live, levels, n_labels, planes = C.c_int64(), C.c_int32(), C.c_int64(), C.c_int32()
+        self._call("levels", C.byref(n_live), C.byref(levels), None)
+        self._call("alleles", C.byref(n_labels), C.byref(planes), None, None)
+        self.n_live, self.levels, self.n_labels, self.planes = int(n_live.value), int(levels.value), int(n_labels.value), int(planes.value)
+
+    def rows_per_level(self):
+        """The live rows of every level (host only)."""
+        out = np.empty(self.levels, dtype=np.int64)
+        self._call("levels", None, None, out.ctypes.data_as(_I64P))
+        return out
+
+    def alleles(self):
+        """The allele table (host only): int64 (n_labels, 2), the ID and the side (0 = from the father) of every label."""
+        ids, sides = np.empty(self.n_labels, np.int64), np.empty(self.n_labels, np.int32)
+        self._call("alleles", None, None, ids.ctypes.data_as(_I64P), sides.ctypes.data_as(C.POINTER(C.c_int32)))
+        return np.stack([ids, sides.astype(np.int64)], axis=1)
+
+    def survived_to_host(self):
+        """int32 (n_labels,): the simulations in which some listed proband carries the label."""
+        return self._out("survived_to_host", self.n_labels, np.int32, C.c_int32)
+
+    def both_to_host(self):
+        """int32 (n_labels,): at the side-0 label of a founder with both parents unknown, the simulations in which both of its
+        alleles are present; 0 elsewhere."""
+        return self._out("both_to_host", self.n_labels, np.int32, C.c_int32)
+
+    def distinct_to_host(self):
+        """int32 (simul_no,): the distinct founder alleles present in every simulation."""
+        return self._out("distinct_to_host", self.simul_no, np.int32, C.c_int32)
+
+    def stats(self):
+        """dict(sweep_ms, mark_ms, algorithmic_bytes, mark_bytes, levels, panel_cols, panels, planes, chunk_labels, chunks, lds_bytes,
+        lanes_per_row) of the last compute()."""
+        return self._stats(sweep_ms=C.c_double, mark_ms=C.c_double, algorithmic_bytes=C.c_double, mark_bytes=C.c_double, levels=C.c_int32,
+                           panel_cols=C.c_int32, panels=C.c_int64, planes=C.c_int32, chunk_labels=C.c_int32, chunks=C.c_int64,
+                           lds_bytes=C.c_int32, lanes_per_row=C.c_int32)
 
 
 GENPHI_LINK_FLAG_LABELS = 1

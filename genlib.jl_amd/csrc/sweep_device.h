@@ -1,4 +1,4 @@
-// sweep_device.h -- the device side of a sweep handle that the nine sweep files (gc, occ, dist, depth, completeness, implex, simu, ident, link) share:
+// sweep_device.h -- the device side of a sweep handle that the ten sweep files (gc, occ, dist, depth, completeness, implex, simu, ident, link, retain) share:
 // everything around the kernels that does not depend on the arithmetic.  A sweep's file keeps its kernels, its handle's own
 // fields, its PanelRule, the allocation and pre-fill of its result, its launch callable, its extra passes and its extern "C"
 // functions.  Host functions only; every including file gets its own copy (anonymous namespace).

@@ -760,6 +760,46 @@ function implex(pedigree::GenLib.Pedigree, pro::Vector{Int} = GenLib.pro(pedigre
 end
 
 """
+    simuRetention(pedigree::GenLib.Pedigree, pro = GenLib.pro(pedigree); simulNo = 5000, seed = nothing, device = -1)
+
+Founder allele survival by gene dropping (MacCluer et al. 1986; GenLib.jl has no form of it; the definition is the text of
+`genphi_retain_*` in include/genphi.h): every founder allele is dropped down the pedigree under its own label `simulNo` times, and
+in every simulation the labels the probands carry are marked on the GPU (csrc/retain.hip).  Returns a named tuple: `alleles` (the
+founder alleles as `(ID, side)`, side 0 = from the father, in label order), the Int32 vectors `survived` and `both` (per allele) and
+`distinct` (per simulation), `retention = survived ./ simulNo`, `simulNo` and the `seed` used (`nothing` draws 64 fresh bits).
+Only `2 length(alleles) + simulNo` integers come back, and any number of probands is taken.
+"""
+function simuRetention(pedigree::GenLib.Pedigree, pro::Vector{Int} = GenLib.pro(pedigree);
+                       simulNo::Integer = 5000, seed::Union{Nothing, UInt64} = nothing, device::Integer = -1)
+    isempty(pro) && throw(ArgumentError("gen.simuRetention: no probands"))
+    seed64 = isnothing(seed) ? rand(Random.RandomDevice(), UInt64) : seed
+    ind, father, mother, _ = flatten(pedigree)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve ind father mother pro check(ccall((:genphi_retain_create, libgenphi), Cint,
+        (Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Int64, Ptr{Int64}, Int64, UInt64, Int32, Int32, Int32, Ptr{Ptr{Cvoid}}),
+        length(ind), ind, father, mother, length(pro), pro, Int64(simulNo), seed64, Int32(0), Int32(0), Int32(0), h))
+    try
+        n_labels = Ref{Int64}(0)
+        planes = Ref{Int32}(0)
+        check(ccall((:genphi_retain_alleles, libgenphi), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int32}, Ptr{Int64}, Ptr{Int32}),
+                    h[], n_labels, planes, C_NULL, C_NULL))
+        n = Int(n_labels[])
+        ids = Vector{Int64}(undef, n); sides = Vector{Int32}(undef, n)
+        GC.@preserve ids sides check(ccall((:genphi_retain_alleles, libgenphi), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int32}, Ptr{Int64}, Ptr{Int32}),
+                                           h[], C_NULL, C_NULL, ids, sides))
+        check(ccall((:genphi_retain_compute, libgenphi), Cint, (Ptr{Cvoid}, Int32), h[], Int32(device)))
+        survived = Vector{Int32}(undef, n); both = Vector{Int32}(undef, n); distinct = Vector{Int32}(undef, Int(simulNo))
+        GC.@preserve survived check(ccall((:genphi_retain_survived_to_host, libgenphi), Cint, (Ptr{Cvoid}, Ptr{Int32}), h[], survived))
+        GC.@preserve both check(ccall((:genphi_retain_both_to_host, libgenphi), Cint, (Ptr{Cvoid}, Ptr{Int32}), h[], both))
+        GC.@preserve distinct check(ccall((:genphi_retain_distinct_to_host, libgenphi), Cint, (Ptr{Cvoid}, Ptr{Int32}), h[], distinct))
+        return (alleles = collect(zip(Int.(ids), Int.(sides))), survived = survived, both = both, distinct = distinct,
+                retention = survived ./ Float64(simulNo), simulNo = Int(simulNo), seed = seed64)
+    finally
+        ccall((:genphi_retain_destroy, libgenphi), Cvoid, (Ptr{Cvoid},), h[])
+    end
+end
+
+"""
     depth(pedigree::GenLib.Pedigree)
 
 The number of generations of the pedigree, as `GenLib.depth` (src/describe.jl:43-66): one linear pass on the host

@@ -1065,6 +1065,71 @@ int genphi_ident_stats(const genphi_ident *h, double *sweep_ms, double *pair_ms,
                        int32_t *lanes_per_row);
 void genphi_ident_destroy(genphi_ident *h);
 
+/* ---- gen.simuRetention: founder allele survival by gene dropping (csrc/retain.hip, csrc/retain.h) -----------------------------------
+ * The question gene dropping was made for (MacCluer et al. 1986): which founder alleles are still present in the listed probands,
+ * and how many.  Retention has no closed form on a general pedigree and does not follow from the kinship matrix or from the pair
+ * counts of gen.simuIdentity.  The reference has no form of it, so this text is the definition, and it is this package's own.
+ * Inputs, live set, levels, rows, allele table, labels LP_x[s] / LM_x[s], the rule and the random word R are those of
+ * genphi_ident_* above, word for word: under the same pedigree, probands, seed and S the labels are the same labels.  Repeats in
+ * the proband list are allowed.
+ * present(l, s) holds when some listed proband carries label l on either side in simulation s.  The results:
+ *   survived[l]   Int32 x n_labels: the number of s < S with present(l, s).
+ *   both[l]       Int32 x n_labels.  It applies where labels l and l + 1 belong to the same ID, that is, a founder with both
+ *                 parents unknown, l being its side 0: the number of s < S with present(l, s) and present(l + 1, s), stored at
+ *                 l.  Every other entry is 0.
+ *   distinct[s]   Int32 x S: the number of labels l with present(l, s).
+ * Bits at positions >= S are never counted.
+ * Invariants, all exact.
+ *   1. The sum of distinct over s equals the sum of survived over l.
+ *   2. 1 <= distinct[s] <= min(n_labels, 2 x the number of different listed IDs).
+ *   3. both[l] <= min(survived[l], survived[l + 1]), and survived[l] + survived[l + 1] - both[l] <= S.
+ *   4. The label of a founder side whose carrier is itself listed has survived = S.
+ *   5. The result is a pure function of the pedigree relations, the SET of listed IDs (order and repeats of the list change
+ *      nothing), the seed and S.
+ *   6. The result does not depend on the panel width or on the label chunk.
+ *   7. distinct at S = 64 is the first 64 entries of distinct at S = 5000.
+ *   8. gen.branching(ped, pro=P) first changes nothing.
+ *   9. Matched through (ID, side), survived of a proband set is entrywise <= survived of a superset under the same seed.
+ *  10. The three arrays equal the same reductions of genphi_ident_labels_to_host for the same arguments.
+ * Errors.  Those of genphi_ident_create without the n_pro^2 >= 2^31 refusal (a list that gen.simuIdentity refuses is planned
+ * here), plus a negative chunk_labels and both form flags at once -> GENPHI_ERR_ARG.  GENPHI_ERR_ALLOC from compute before any
+ * launch, when the device does not hold the results (8 n_labels + 4 S bytes), the lists and the rows of even a 128-column panel.
+ * Only 2 n_labels + S integers ever move to the host.
+ * Method.  The label sweep of genphi_ident_* (its init and step kernels, shared), then one mark kernel per panel that reads the
+ * listed probands' rows in place.  A workgroup owns the 64 simulations of a word and a chunk of the labels; it keeps one bitmap per
+ * simulation in LDS, decodes every proband side once, sets bits, and reduces the bitmaps by popcounts and wave ballots into
+ * integer adds (csrc/retain.hip).
+ *   create            host only (no GPU): ident's checks and plan.  panel_cols as for genphi_ident_create.  chunk_labels: the labels
+ *                     of a chunk, 0 = the default (the whole table up to 8,192 labels, else 8,192), else rounded up to a multiple
+ *                     of 32 and cut to n_labels and to 16,384 (tests, A/B).  flags: GENPHI_RETAIN_FLAG_PLAIN_OR marks with an
+ *                     unconditional LDS atomic OR, GENPHI_RETAIN_FLAG_TEST_FIRST reads the word first and skips the atomic when the
+ *                     bit is set already; neither = the form that ships (the same result; the A/B of the bench)
+ *   levels, alleles   as genphi_ident_levels and genphi_ident_alleles
+ *   compute           the sweep on `device` (-1 = current); the three arrays stay resident
+ *   survived_to_host, both_to_host    out: n_labels Int32
+ *   distinct_to_host  out: S Int32
+ *   stats             of the last compute, by HIP events: the device time of init and level steps, and of the mark kernel, summed
+ *                     over the panels; the algorithmic bytes of the steps (as genphi_ident_stats); the bytes of the probands' planes
+ *                     the mark kernel reads (2 n_pro x B x 16 per pair of words and chunk); levels; the columns of a panel; the
+ *                     panels; B; the labels of a chunk; the chunks; the LDS bytes of a workgroup of the mark kernel; the lanes per
+ *                     row of the step kernel                                                                                   */
+#define GENPHI_RETAIN_FLAG_PLAIN_OR 1
+#define GENPHI_RETAIN_FLAG_TEST_FIRST 2
+typedef struct genphi_retain genphi_retain;
+int genphi_retain_create(int64_t n_ind, const int64_t *ind, const int64_t *father, const int64_t *mother,
+                         int64_t n_pro, const int64_t *pro_ids, int64_t simul_no, uint64_t seed, int32_t panel_cols,
+                         int32_t chunk_labels, int32_t flags, genphi_retain **out);
+int genphi_retain_levels(const genphi_retain *h, int64_t *n_live, int32_t *levels, int64_t *rows_per_level);
+int genphi_retain_alleles(const genphi_retain *h, int64_t *n_labels, int32_t *planes, int64_t *ids, int32_t *sides);
+int genphi_retain_compute(genphi_retain *h, int32_t device);
+int genphi_retain_survived_to_host(genphi_retain *h, int32_t *out);
+int genphi_retain_both_to_host(genphi_retain *h, int32_t *out);
+int genphi_retain_distinct_to_host(genphi_retain *h, int32_t *out);
+int genphi_retain_stats(const genphi_retain *h, double *sweep_ms, double *mark_ms, double *algorithmic_bytes, double *mark_bytes,
+                        int32_t *levels, int32_t *panel_cols, int64_t *panels, int32_t *planes, int32_t *chunk_labels,
+                        int64_t *chunks, int32_t *lds_bytes, int32_t *lanes_per_row);
+void genphi_retain_destroy(genphi_retain *h);
+
 /* ---- gen.simuSharing: linked-locus gene dropping and IBD segments (csrc/link.hip, csrc/link.cpp) ------------------------------------
  * gen.simuIdentity above drops every founder allele at ONE locus.  Here a simulation is a chromosome of L linked loci: a meiosis
  * copies a mosaic of the parent's two chromosomes, and the sharing of a pair of probands is read off locus by locus: how much of the
