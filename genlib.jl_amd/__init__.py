@@ -29,6 +29,7 @@ meaning, printed lines and error behaviour as the reference:
     gen.simuSharing(ped, loci=1024)        # linked loci: realised IBD sharing, its variance and the segments (csrc/link.hip)
     gen.descendant(ped, 1); gen.children(ped, 1)   # src/identify.jl:203-215, :77-80 (csrc/loader.cpp)
     gen.phiHist(ped); gen.phiQuantile(ped, 0.5)    # the distribution of the pairwise kinships, on the device (csrc/hist.hip)
+    gen.phiClusters(ped, 1/16); gen.phiUnrelated(ped, 1/16)   # families and a maximal unrelated set at a kinship cutoff (csrc/clusters.hip)
 
 All kinship arithmetic runs in hand-written HIP kernels behind the C-ABI in
 include/genphi.h (csrc/genphi_hip.hip); there is no CPU fallback.
@@ -1242,6 +1243,138 @@ def phiOver(x, threshold, probandIDs=None, device=None):
     row, col = np.nonzero(np.triu(m.astype(np.float64) >= threshold, 1))
     row, col = row.astype(np.int32), col.astype(np.int32)
     return PhiOver(threshold, row, col, None if ids is None else ids[row], None if ids is None else ids[col], m[row, col])
+
+
+class PhiClusters:
+    """What gen.phiClusters returns: the connected components of the graph whose edges are the pairs of probands with kinship >=
+    `threshold`.  `pro` (int64, the N IDs in the order of the rows, None when no IDs were given with a host matrix), `label` (int32
+    (N,), the smallest 0-based position in each proband's cluster), `cluster` (int32 (N,), dense numbers 0 .. K - 1 in the order of
+    each cluster's first member), `sizes` (int64 (K,)) and `n_pairs` (the number of edges)."""
+
+    def __init__(self, threshold, pro, label, n_pairs):
+        self.threshold, self.pro, self.label, self.n_pairs = threshold, pro, label, int(n_pairs)
+        first = np.flatnonzero(label == np.arange(len(label), dtype=np.int64))      # the first member of every cluster, ascending
+        number = np.zeros(len(label), dtype=np.int32)
+        number[first] = np.arange(len(first), dtype=np.int32)
+        self.cluster = number[label] if len(label) else number
+        self.sizes = np.bincount(self.cluster, minlength=len(first)).astype(np.int64)
+
+    def __len__(self):
+        return len(self.sizes)
+
+    def members(self, k):
+        """The probands of cluster k, in order: their IDs, or their positions when there are no IDs."""
+        if not 0 <= int(k) < len(self.sizes):
+            raise IndexError("cluster %d of %d" % (int(k), len(self.sizes)))
+        pos = np.flatnonzero(self.cluster == int(k)).astype(np.int32)
+        return pos if self.pro is None else self.pro[pos]
+
+    def __repr__(self):
+        return "PhiClusters: %d probands in %d clusters at kinship >= %g (%d pairs), the largest of %d" % (
+            len(self.label), len(self.sizes), self.threshold, self.n_pairs, int(self.sizes.max()) if len(self.sizes) else 0)
+
+
+class PhiUnrelated:
+    """What gen.phiUnrelated returns: a maximal set of probands no two of which have kinship >= `threshold`.  `pro` (int64, the N
+    IDs in the order of the rows, None when no IDs were given with a host matrix), `keep` (bool (N,)), `index` (int32, the positions
+    kept, ascending), `kept` (their IDs, None without `pro`), `degree` (int32 (N,), each proband's number of relatives at or above
+    the threshold) and `rounds` (the launches the device took; 0 for a host matrix)."""
+
+    def __init__(self, threshold, pro, keep, degree, rounds):
+        self.threshold, self.pro, self.keep, self.degree, self.rounds = threshold, pro, keep, degree, int(rounds)
+        self.index = np.flatnonzero(keep).astype(np.int32)
+        self.kept = None if pro is None else pro[self.index]
+
+    def __len__(self):
+        return len(self.index)
+
+    def __repr__(self):
+        return "PhiUnrelated: %d of %d probands kept, no two with kinship >= %g (%d rounds)" % (
+            len(self.index), len(self.keep), self.threshold, self.rounds)
+
+
+def _threshold(threshold):
+    threshold = float(threshold)
+    if threshold != threshold:
+        raise ValueError("the threshold is NaN")
+    return threshold
+
+
+def phiClusters(x, threshold, probandIDs=None, device=None):
+    """The families at a kinship cutoff: the connected components of the graph whose edges are the pairs of probands with
+    float64(Phi[i, j]) >= threshold (gen.phiOver's rule; never the diagonal).  Returns a PhiClusters.  Neither GENLIB nor the
+    reference has this function.
+
+    x a Pedigree: gen.phi's sweep for probandIDs (default gen.pro; duplicates collapse, as gen.phi does), then a lock-free
+    union-find on the device over one read of the upper triangle of the resident matrix, which is never copied and whose pairs are
+    never listed (genphi_result_clusters).  x a square host matrix: the same answer in numpy and a plain loop (its
+    upper triangle decides); `pro` comes from probandIDs if given.  ValueError for a NaN threshold, KeyError for an unknown
+    proband ID."""
+    threshold = _threshold(threshold)
+    if isinstance(x, Pedigree):
+        ids, (label, n_pairs) = _resident_query(x, probandIDs, device, lambda pl: pl.clusters(threshold))
+        return PhiClusters(threshold, ids, label, n_pairs)
+    m, ids = _host_matrix(x, probandIDs, "gen.phiClusters")
+    a = np.triu(m >= threshold, 1)
+    n_pairs = int(np.count_nonzero(a))
+    a = a | a.T
+    label = np.full(len(m), -1, dtype=np.int32)
+    for s in range(len(m)):                                     # ascending: the first unlabelled position is its cluster's smallest
+        if label[s] >= 0:
+            continue
+        label[s] = s
+        stack = [s]
+        while stack:
+            fresh = np.flatnonzero(a[stack.pop()] & (label < 0))
+            label[fresh] = s
+            stack.extend(fresh.tolist())
+    return PhiClusters(threshold, ids, label, n_pairs)
+
+
+def phiUnrelated(x, threshold, priority=None, probandIDs=None, device=None):
+    """A maximal set of probands no two of which are related at or above `threshold` -- the "kinship cutoff" of association studies,
+    allele-frequency estimates and founder-population sampling.  Returns a PhiUnrelated.  Neither GENLIB nor the reference has
+    this function.
+
+    Two probands i != j are related when float64(Phi[i, j]) >= threshold (gen.phiOver's rule).  The set is the answer of the
+    sequential greedy rule: visit the probands in ascending order of (priority[i], i) and keep one iff none of its relatives has
+    been kept.  priority: None or "degree" -- the number of relatives, so the fewest relatives first, the usual heuristic for a large
+    set; "position" -- all equal, so earlier probands win; or N integers in the int32 range, smaller is kept first.  The answer is
+    unique given the matrix, the threshold and the priorities.
+
+    x a Pedigree: gen.phi's sweep for probandIDs (default gen.pro; duplicates collapse, as gen.phi does; an array of priorities
+    names the collapsed probands), then rounds over the rows of the resident matrix on the device, which is never copied and whose
+    pairs are never listed (genphi_result_unrelated).  x a square host matrix: the same answer in numpy and a plain
+    loop (its upper triangle decides).  ValueError for a NaN threshold, a priority of the wrong length or not of integers; KeyError
+    for an unknown proband ID."""
+    threshold = _threshold(threshold)
+    if isinstance(priority, str):
+        if priority not in ("degree", "position"):
+            raise ValueError("gen.phiUnrelated: priority %r: \"degree\", \"position\" or one integer per proband" % (priority,))
+    by_degree = priority is None or (isinstance(priority, str) and priority == "degree")
+
+    def priorities(n):
+        if by_degree:
+            return None
+        if isinstance(priority, str):
+            return np.zeros(n, dtype=np.int32)
+        return _capi.as_priority(priority, n)
+
+    if isinstance(x, Pedigree):
+        ids, (keep, degree, rounds) = _resident_query(x, probandIDs, device, lambda pl: pl.unrelated(threshold, priorities(pl.n_probands)))
+        return PhiUnrelated(threshold, ids, keep, degree, rounds)
+    m, ids = _host_matrix(x, probandIDs, "gen.phiUnrelated")
+    n = len(m)
+    pri = priorities(n)
+    a = np.triu(m >= threshold, 1)
+    a = a | a.T
+    degree = a.sum(axis=1).astype(np.int32)
+    keep, barred = np.zeros(n, dtype=bool), np.zeros(n, dtype=bool)
+    for i in np.lexsort((np.arange(n), degree if pri is None else pri)):      # ascending (priority, position)
+        if not barred[i]:
+            keep[i] = True
+            barred |= a[i]
+    return PhiUnrelated(threshold, ids, keep, degree, 0)
 
 
 class PhiNearest:

@@ -57,7 +57,7 @@ class GenphiStats(C.Structure):
 EXPORTED_SYMBOLS = [
     "genphi_plan_create", "genphi_plan_create_tuned", "genphi_tuning_create", "genphi_tuning_set", "genphi_tuning_destroy", "genphi_plan_levels", "genphi_plan_n_probands", "genphi_plan_step_mode", "genphi_plan_step_info", "genphi_plan_step_slots",
     "genphi_plan_algorithmic_bytes", "genphi_plan_device_bytes", "genphi_plan_device_bytes_needed", "genphi_plan_sparse_levels", "genphi_plan_cut_formats", "genphi_plan_step_walk", "genphi_plan_set_step_hook", "genphi_compute_device", "genphi_result_device",
-    "genphi_result_to_host", "genphi_result_to_host_f64", "genphi_phi_pairs", "genphi_result_sums", "genphi_result_group_sums", "genphi_result_over", "genphi_result_nearest", "genphi_result_matmul", "genphi_result_solve", "genphi_result_eigen", "genphi_result_hist", "genphi_result_select", "genphi_result_bootstrap", "genphi_bootstrap_counts", "genphi_result_entries",
+    "genphi_result_to_host", "genphi_result_to_host_f64", "genphi_phi_pairs", "genphi_result_sums", "genphi_result_group_sums", "genphi_result_over", "genphi_result_nearest", "genphi_result_matmul", "genphi_result_solve", "genphi_result_eigen", "genphi_result_hist", "genphi_result_select", "genphi_result_clusters", "genphi_result_unrelated", "genphi_result_bootstrap", "genphi_bootstrap_counts", "genphi_result_entries",
     "genphi_compute_f32",
     "genphi_genealogy_read", "genphi_branching", "genphi_free", "genphi_release_cached", "genphi_cached_bytes", "genphi_plan_release_device", "genphi_plan_destroy",
     "genphi_last_error",
@@ -163,6 +163,11 @@ def lib():
         L.genphi_result_group_sums.restype = C.c_int
         L.genphi_result_over.argtypes = [C.c_void_p, C.c_double, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _F32P, _I64P]
         L.genphi_result_over.restype = C.c_int
+        L.genphi_result_clusters.argtypes = [C.c_void_p, C.c_double, C.POINTER(C.c_int32), _I64P, _I64P]
+        L.genphi_result_clusters.restype = C.c_int
+        L.genphi_result_unrelated.argtypes = [C.c_void_p, C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.POINTER(C.c_int32), _I64P,
+                                              C.POINTER(C.c_int32)]
+        L.genphi_result_unrelated.restype = C.c_int
         L.genphi_result_bootstrap.argtypes = [C.c_void_p, C.c_uint64, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), _I64P]
         L.genphi_result_bootstrap.restype = C.c_int
         L.genphi_bootstrap_counts.argtypes = [C.c_int64, C.c_uint64, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]
@@ -789,6 +794,45 @@ class PhiPlan:
                 raise GenphiDeviceError("genphi_result_over counted %d pairs, then %d" % (n, got.value))
         return rows, cols, vals
 
+    def clusters(self, threshold):
+        """(label int32 (N,), n_pairs): the connected components of the graph whose edges are the pairs with Phi[i, j] >= threshold
+        (genphi_result_over's rule), found on the device in one read of the upper triangle of the FULL resident result
+        (genphi_result_clusters).  label[i] is the smallest position in i's component; n_pairs the number of edges,
+        count_over(threshold).  ValueError for a NaN threshold, a row shard or a Float64 result, GenphiDeviceError without a
+        resident result."""
+        threshold = float(threshold)
+        if threshold != threshold:
+            raise ValueError("clusters: the threshold is NaN")
+        label = np.empty(self.n_probands, dtype=np.int32)
+        k, pairs = C.c_int64(), C.c_int64()
+        rc = lib().genphi_result_clusters(self._h, threshold, label.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(k), C.byref(pairs))
+        if rc:
+            _raise(rc)
+        return label, int(pairs.value)
+
+    def unrelated(self, threshold, priority=None):
+        """(member bool (N,), degree int32 (N,), rounds): a maximal set of probands no two of which have Phi[i, j] >= threshold, from
+        the FULL resident result (genphi_result_unrelated).  degree[i] counts the probands j != i with
+        Phi[i, j] >= threshold.  member is the answer of the sequential greedy rule: visit the probands in ascending order of
+        (priority[i], i) -- priority None: of (degree[i], i) -- and keep one iff none of its relatives has been kept.  priority: N
+        integers in the int32 range.  rounds (the launches it took) is diagnostic.  ValueError for a NaN threshold, a bad
+        priority, a row shard or a Float64 result, GenphiDeviceError without a resident result."""
+        threshold = float(threshold)
+        if threshold != threshold:
+            raise ValueError("unrelated: the threshold is NaN")
+        n = self.n_probands
+        pri = None
+        if priority is not None:
+            pri = as_priority(priority, n)
+        member, degree = np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=np.int32)
+        kept, rounds = C.c_int64(), C.c_int32()
+        i32 = C.POINTER(C.c_int32)
+        rc = lib().genphi_result_unrelated(self._h, threshold, None if pri is None else pri.ctypes.data_as(i32),
+                                           member.ctypes.data_as(C.POINTER(C.c_uint8)), degree.ctypes.data_as(i32), C.byref(kept), C.byref(rounds))
+        if rc:
+            _raise(rc)
+        return member.astype(bool), degree, int(rounds.value)
+
     def nearest(self, k, cols=True, values=True):
         """(cols int32 (rows, k), values float32 (rows, k)): the k closest relatives of every RESIDENT row, selected on the device
         in one pass over the rows (genphi_result_nearest); the matrix is not copied.  The candidates of row i are
@@ -960,6 +1004,18 @@ class PhiPlan:
     def compute(self, device=None, kernel=0, rows=None, timing=False, no_sparse=False):
         self.compute_device(device=device, kernel=kernel, rows=rows, timing=timing, no_sparse=no_sparse)
         return self.result_to_host()
+
+
+def as_priority(priority, n):
+    """N priorities as a contiguous int32 array; ValueError for another length, a non-integer or a value outside the int32 range."""
+    a = np.asarray(priority)
+    if a.shape != (n,):
+        raise ValueError("priority must hold one entry per proband (%d), got shape %s" % (n, a.shape))
+    if a.size and a.dtype.kind not in "iu":
+        raise ValueError("priority must hold integers, got %s" % a.dtype)
+    if n and (int(a.min()) < -2 ** 31 or int(a.max()) > 2 ** 31 - 1):
+        raise ValueError("priority outside the int32 range")
+    return np.ascontiguousarray(a, dtype=np.int32)
 
 
 def as_panel(a, n, what):

@@ -12,12 +12,15 @@
 #include "../../include/genphi.h"
 #include "bootstrap.h"
 #include "group_tables.h"
+#include "over_device.h"
 #include "resident.h"
 
 using genphi::al256;
 using genphi::ResidentView;
 using genphi::kGsMaxGroups;
 using genphi::kGsTile;
+using genphi::kOverTile;
+using genphi::over_hits;
 using genphi::kNearBufMin;      // (tuning.h, with the clamp that tuning_from applies)
 
 namespace {
@@ -66,17 +69,7 @@ __global__ void row_sums_kernel(const float *m, long long ld, int n, int row_beg
 // repeats the walk and gives every hit its place by an exclusive scan over the tile (three ballots over the bits of the
 // per-thread counts 0..4, the four wave totals through LDS): no atomics, so the order is row, column whatever the launch
 // geometry.  Both kernels test the same bits with the same expression, so the second pass finds what the first counted.
-constexpr int kOverTile = 1024;         // columns of a tile: 256 threads x one quad
-
-__device__ __forceinline__ unsigned over_hits(const float4 v, int jq, int i, int n, double t)
-{
-    // bit e = column jq + e is listed: right of the diagonal, left of the padding, at or above the threshold
-    const int lo = min(max(i + 1 - jq, 0), 4), hi = min(max(n - jq, 0), 4);
-    const unsigned valid = (0xFu << lo) & ~(0xFu << hi) & 0xFu;
-    const unsigned h = (static_cast<double>(v.x) >= t ? 1u : 0u) | (static_cast<double>(v.y) >= t ? 2u : 0u) |
-                       (static_cast<double>(v.z) >= t ? 4u : 0u) | (static_cast<double>(v.w) >= t ? 8u : 0u);
-    return h & valid;
-}
+// The tile and the edge test (over_hits) are in over_device.h: the cluster queries (clusters.hip) test the same bits.
 
 __global__ __launch_bounds__(256) void over_count_kernel(const float *__restrict__ m, long long ld, int n, int row_begin, double t,
                                                          long long *__restrict__ row_count)

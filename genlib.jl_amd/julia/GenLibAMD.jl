@@ -274,6 +274,79 @@ function phiOver(pedigree::GenLib.Pedigree, threshold::Real, probandIDs::Vector{
 end
 
 """
+    phiClusters(pedigree::GenLib.Pedigree, threshold::Real, probandIDs::Vector{Int} = GenLib.pro(pedigree); device::Integer = -1)
+
+The families at a kinship cutoff: the connected components of the graph whose edges are the pairs of probands with kinship at or above
+`threshold` (`phiOver`'s rule), as `(pro, label, cluster, sizes, n_pairs)`: `label[i]` is the smallest position (1-based here, in the
+order of `unique(probandIDs)`) in `i`'s component, `cluster[i]` its dense number `1 .. K` in the order of each cluster's first member,
+`sizes` the `K` cluster sizes and `n_pairs` the number of edges.  The matrix stays on the GPU and the pairs are never listed:
+`genphi_result_clusters` runs a lock-free union-find there over one read of its upper triangle.  The reference has no such function;
+the definition is this package's own (`include/genphi.h`).
+"""
+function phiClusters(pedigree::GenLib.Pedigree, threshold::Real, probandIDs::Vector{Int} = GenLib.pro(pedigree); device::Integer = -1)
+    isnan(threshold) && throw(ArgumentError("the threshold is NaN"))
+    ordered = unique(probandIDs)
+    foreach(ID -> pedigree[ID], ordered)                                    # KeyError on unknown ID
+    plan = create_plan(pedigree, ordered, nothing)
+    try
+        opts = Ref(GenphiOpts(Int32(device), 0, 0, 0, 0, 0))
+        check(ccall((:genphi_compute_device, libgenphi), Cint, (Ptr{Cvoid}, Ptr{GenphiOpts}, Ptr{Cvoid}), plan, opts, C_NULL))
+        labels = Vector{Int32}(undef, length(ordered)); k = Ref{Int64}(0); n = Ref{Int64}(0)
+        GC.@preserve labels check(ccall((:genphi_result_clusters, libgenphi), Cint, (Ptr{Cvoid}, Float64, Ptr{Int32}, Ptr{Int64}, Ptr{Int64}),
+            plan, Float64(threshold), labels, k, n))
+        label = Int.(labels) .+ 1
+        firsts = findall(i -> label[i] == i, eachindex(label))              # ascending: the order of each cluster's first member
+        number = zeros(Int, length(label)); number[firsts] = 1:length(firsts)
+        cluster = number[label]
+        sizes = zeros(Int64, length(firsts)); foreach(c -> sizes[c] += 1, cluster)
+        return (pro = ordered, label = label, cluster = cluster, sizes = sizes, n_pairs = n[])
+    finally
+        destroy_plan(plan)
+    end
+end
+
+"""
+    phiUnrelated(pedigree::GenLib.Pedigree, threshold::Real, probandIDs::Vector{Int} = GenLib.pro(pedigree);
+                 priority = :degree, device::Integer = -1)
+
+A maximal set of probands no two of which have kinship at or above `threshold` (the "kinship cutoff" of association studies), as
+`(pro, keep, index, kept, degree, rounds)`.  The set is the answer of the sequential greedy rule: visit the probands in ascending order
+of `(priority[i], i)` and keep one iff none of its relatives has been kept.  `priority`: `:degree` (the number of relatives at or above
+the threshold: the fewest relatives first), `:position` (earlier probands win) or one integer in the `Int32` range per entry of
+`unique(probandIDs)`, smaller kept first.  `degree[i]` is that number of relatives, `rounds` the launches the device took.  The matrix
+stays on the GPU: `genphi_result_unrelated` finds the set there in rounds over the rows.  The reference has no such function; the
+definition is this package's own (`include/genphi.h`).
+"""
+function phiUnrelated(pedigree::GenLib.Pedigree, threshold::Real, probandIDs::Vector{Int} = GenLib.pro(pedigree);
+                      priority = :degree, device::Integer = -1)
+    isnan(threshold) && throw(ArgumentError("the threshold is NaN"))
+    ordered = unique(probandIDs)
+    foreach(ID -> pedigree[ID], ordered)                                    # KeyError on unknown ID
+    if priority isa Symbol
+        priority in (:degree, :position) || throw(ArgumentError("priority: :degree, :position or one integer per proband"))
+        pri = priority == :degree ? nothing : zeros(Int32, length(ordered))
+    else
+        length(priority) == length(ordered) || throw(ArgumentError("priority must hold one entry per proband ($(length(ordered)))"))
+        pri = Vector{Int32}(priority)                                       # InexactError outside the Int32 range or for a non-integer
+    end
+    plan = create_plan(pedigree, ordered, nothing)
+    try
+        opts = Ref(GenphiOpts(Int32(device), 0, 0, 0, 0, 0))
+        check(ccall((:genphi_compute_device, libgenphi), Cint, (Ptr{Cvoid}, Ptr{GenphiOpts}, Ptr{Cvoid}), plan, opts, C_NULL))
+        member = Vector{UInt8}(undef, length(ordered)); degree = Vector{Int32}(undef, length(ordered))
+        kept = Ref{Int64}(0); rounds = Ref{Int32}(0)
+        GC.@preserve pri member degree check(ccall((:genphi_result_unrelated, libgenphi), Cint,
+            (Ptr{Cvoid}, Float64, Ptr{Int32}, Ptr{UInt8}, Ptr{Int32}, Ptr{Int64}, Ptr{Int32}),
+            plan, Float64(threshold), pri === nothing ? C_NULL : pointer(pri), member, degree, kept, rounds))
+        keep = member .== 1
+        index = findall(keep)
+        return (pro = ordered, keep = keep, index = index, kept = ordered[index], degree = Int.(degree), rounds = Int(rounds[]))
+    finally
+        destroy_plan(plan)
+    end
+end
+
+"""
     phiHist(pedigree::GenLib.Pedigree, probandIDs::Vector{Int} = GenLib.pro(pedigree); bins = 64, range = (0.0, 0.5), device::Integer = -1)
 
 The distribution of the pairwise kinships: the histogram of `phi[i, j]` over all pairs `i < j` of `unique(probandIDs)`, as

@@ -455,6 +455,49 @@ int genphi_result_hist(genphi_plan *plan, int32_t n_edges, const double *edges, 
 #define GENPHI_SELECT_MAX_RANKS 16
 int genphi_result_select(genphi_plan *plan, int32_t n_ranks, const int64_t *ranks, float *values, int64_t *n_pairs);
 
+/* Families and unrelated sets: two questions about the graph G_t whose vertices are the probands and whose edges are the
+ * pairs related at or above a threshold t, answered from the resident result in a few passes; the edge list never exists.  Neither
+ * GENLIB nor the reference has such functions, so this text is the definition.  N is the number of probands after duplicates collapse
+ * (genphi_plan_create); positions are 0-based in that order.
+ *   edge rule         positions i != j are joined iff (double)Phi[i][j] >= threshold: the rule of genphi_result_over
+ *   padding           the padding columns j >= N of the row pitch hold zeros and are never edges: a threshold <= 0 does not join them
+ *   diagonal          never an edge
+ *   threshold         any double but NaN; +infinity gives no edge, -infinity joins every pair
+ *   the full result   both calls need the full Float32 result resident (row_begin == 0, n_rows == N): a row shard (an empty one too) is
+ *                     GENPHI_ERR_ARG, a Float64 result (GENPHI_FLAG_STORAGE_F64) is GENPHI_ERR_ARG, a plan without a resident result
+ *                     is GENPHI_ERR_DEVICE.  N = 0 or N = 1 is GENPHI_OK with the trivial answer (checked before the result is).
+ *   after an error    the plan stays usable, the resident result is untouched, and no output is written
+ *
+ * genphi_result_clusters: the connected components of G_t.
+ *   label[i]          the smallest position in i's component: label[i] <= i and label[label[i]] == label[i]
+ *   *n_clusters       the positions with label[i] == i
+ *   *n_pairs          the edges i < j: the count of the count-only call of genphi_result_over at the same threshold
+ * Any output pointer may be NULL.  One read of the upper triangle (2 N^2 bytes) by a lock-free union-find, then a pass over N entries.
+ * The answer is a function of the matrix and the threshold alone, whatever the order in which the device meets the edges.  Device
+ * memory, in the plan's scratch block: 8 N bytes (a parent and a per-row edge count for every proband).
+ *
+ * genphi_result_unrelated: a maximal set of probands no two of which are joined -- the "kinship cutoff" of association studies.
+ *   degree[i]         the edges at i
+ *   the order         vertices are visited in ascending order of the key (priority[i], i); priority == NULL means the key
+ *                     (degree[i], i): the fewest relatives first, the usual heuristic for a large set
+ *   member[i]         1 or 0: the answer of the sequential greedy rule -- visit the vertices in that order and take a vertex iff none
+ *                     of its neighbours has been taken.  The answer is unique: a function of the matrix, the threshold and the
+ *                     priorities alone.  It is a maximal independent set of G_t.
+ *   *n_members        the members
+ *   *rounds           the launches of the round kernel: diagnostic, not part of the answer (it may differ from call to call)
+ * member may not be NULL (GENPHI_ERR_ARG); the other outputs may be.  One full read of the matrix (4 N^2 bytes) for the degrees -- left out
+ * when priorities are given and degree is NULL -- then rounds: a launch reads the rows of the vertices still undecided, 4 N bytes each
+ * (less where a member is met early), and the host reads one 8-byte count after it.  At most N rounds; a graph that is one long path
+ * visited from one end needs about N / 2, each over two rows.  Device memory, in the plan's scratch block: 13 N bytes (a state byte, a
+ * 64-bit key and a degree for every proband).
+ *
+ * The phiOver counts the library keeps (genphi_result_over) are not touched by either call.
+ * GENPHI_ERR_ARG: NULL plan, NaN threshold, NULL member, a Float64 result, a row shard; GENPHI_ERR_DEVICE: no resident result;
+ * GENPHI_ERR_ALLOC: the scratch does not fit (found before the first launch).                                                       */
+int genphi_result_clusters(genphi_plan *plan, double threshold, int32_t *label, int64_t *n_clusters, int64_t *n_pairs);
+int genphi_result_unrelated(genphi_plan *plan, double threshold, const int32_t *priority, uint8_t *member, int32_t *degree,
+                            int64_t *n_members, int32_t *rounds);
+
 /* GENLIB's gen.phiCI(phiMatrix, prob, b) and gen.fCI(vectF, prob, b): bootstrap confidence intervals of the mean kinship and of the
  * mean inbreeding.  The reference has neither, so this text is the definition.  N is the number of probands after
  * duplicates collapse (genphi_plan_create), N >= 2.
