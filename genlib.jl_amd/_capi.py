@@ -1545,7 +1545,47 @@ GENPHI_SIMU_MAX_SIMULATIONS = 1 << 24
 GENPHI_SIMU_FLAG_NO_SAMPLE = 1
 
 
-class SimuPlan(_SweepPlan):
+class _DropPlan(_SweepPlan):
+    """What the handles of the gene-dropping sweeps share: the seed and the levels of the plan."""
+
+    def _set_seed(self, seed):
+        """seed=None draws 64 fresh bits; .seed is the seed used, as 64 unsigned bits."""
+        if seed is None:
+            import secrets
+            seed = secrets.randbits(64)
+        self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+
+    def _read_plan(self):
+        """After create: n_live and levels of the plan."""
+        n_live, levels = C.c_int64(), C.c_int32()
+        self._call("levels", C.byref(n_live), C.byref(levels), None)
+        self.n_live, self.levels = int(n_live.value), int(levels.value)
+
+    def rows_per_level(self):
+        """The live rows of every level (host only)."""
+        out = np.empty(self.levels, dtype=np.int64)
+        self._call("levels", None, None, out.ctypes.data_as(_I64P))
+        return out
+
+
+class _LabelPlan(_DropPlan):
+    """The gene-dropping sweeps that drop every founder allele under its own label: the allele table on top."""
+
+    def _read_plan(self):
+        """After create: n_live, levels, n_labels and planes of the plan."""
+        super()._read_plan()
+        n_labels, planes = C.c_int64(), C.c_int32()
+        self._call("alleles", C.byref(n_labels), C.byref(planes), None, None)
+        self.n_labels, self.planes = int(n_labels.value), int(planes.value)
+
+    def alleles(self):
+        """The allele table (host only): int64 (n_labels, 2), the ID and the side (0 = from the father) of every label."""
+        ids, sides = np.empty(self.n_labels, np.int64), np.empty(self.n_labels, np.int32)
+        self._call("alleles", None, None, ids.ctypes.data_as(_I64P), sides.ctypes.data_as(C.POINTER(C.c_int32)))
+        return np.stack([ids, sides.astype(np.int64)], axis=1)
+
+
+class SimuPlan(_DropPlan):
     """The handle of gen.simuSample / gen.simuProb (include/genphi.h, genphi_simu_*): gene dropping.  Planned on the host at
     construction (KeyError on an unknown proband or ancestor; ValueError for a state outside 0..2, lists of different length, an
     ancestor listed with two states, simul_no outside 1 .. 2^24, no probands or no ancestors; no GPU needed), swept on the GPU by
@@ -1562,10 +1602,7 @@ class SimuPlan(_SweepPlan):
         if len(states) and not np.array_equal(states, states.astype(np.int32)):
             raise ValueError("gen.simu: the states must be the integers 0, 1 or 2")
         states = np.ascontiguousarray(states, dtype=np.int32)
-        if seed is None:
-            import secrets
-            seed = secrets.randbits(64)
-        self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self._set_seed(seed)
         self.simul_no = int(simul_no)
         self.no_sample = bool(no_sample)
         ind, father, mother = _i64(ind), _i64(father), _i64(mother)
@@ -1578,15 +1615,7 @@ class SimuPlan(_SweepPlan):
             _raise(rc)
         self._h = h
         self.n_pro = len(pro_ids)
-        n_live, levels = C.c_int64(), C.c_int32()
-        self._call("levels", C.byref(n_live), C.byref(levels), None)
-        self.n_live, self.levels = int(n_live.value), int(levels.value)
-
-    def rows_per_level(self):
-        """The live rows of every level (host only)."""
-        out = np.empty(self.levels, dtype=np.int64)
-        self._call("levels", None, None, out.ctypes.data_as(_I64P))
-        return out
+        self._read_plan()
 
     def rows(self):
         """dict(ids, father_rows, mother_rows, pro_positions) of the plan (host only): per live row, ordered by level, the ID and the
@@ -1628,7 +1657,7 @@ GENPHI_IDENT_FLAG_LABELS = 1
 GENPHI_IDENT_FLAG_ALL_PAIRS = 2
 
 
-class IdentityPlan(_SweepPlan):
+class IdentityPlan(_LabelPlan):
     """The handle of gen.simuIdentity (include/genphi.h, genphi_ident_*): the nine condensed identity states of every pair of
     probands by gene dropping.  Planned on the host at construction (KeyError on an unknown proband; ValueError for simul_no
     outside 1 .. 2^24, no probands, 2^31 or more ordered pairs, a negative panel_cols; no GPU needed), swept on the GPU by
@@ -1639,10 +1668,7 @@ class IdentityPlan(_SweepPlan):
 
     def __init__(self, ind, father, mother, pro_ids, simul_no=5000, seed=None, labels=False, panel_cols=0, all_pairs=False):
         pro_ids = _i64(pro_ids).ravel()
-        if seed is None:
-            import secrets
-            seed = secrets.randbits(64)
-        self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self._set_seed(seed)
         self.simul_no = int(simul_no)
         self.labels = bool(labels)
         ind, father, mother = _i64(ind), _i64(father), _i64(mother)
@@ -1654,22 +1680,7 @@ class IdentityPlan(_SweepPlan):
             _raise(rc)
         self._h = h
         self.n_pro = len(pro_ids)
-        n_live, levels, n_labels, planes = C.c_int64(), C.c_int32(), C.c_int64(), C.c_int32()
-        self._call("levels", C.byref(n_live), C.byref(levels), None)
-        self._call("alleles", C.byref(n_labels), C.byref(planes), None, None)
-        self.n_live, self.levels, self.n_labels, self.planes = int(n_live.value), int(levels.value), int(n_labels.value), int(planes.value)
-
-    def rows_per_level(self):
-        """The live rows of every level (host only)."""
-        out = np.empty(self.levels, dtype=np.int64)
-        self._call("levels", None, None, out.ctypes.data_as(_I64P))
-        return out
-
-    def alleles(self):
-        """The allele table (host only): int64 (n_labels, 2), the ID and the side (0 = from the father) of every label."""
-        ids, sides = np.empty(self.n_labels, np.int64), np.empty(self.n_labels, np.int32)
-        self._call("alleles", None, None, ids.ctypes.data_as(_I64P), sides.ctypes.data_as(C.POINTER(C.c_int32)))
-        return np.stack([ids, sides.astype(np.int64)], axis=1)
+        self._read_plan()
 
     def counts_to_host(self):
         """The (n_pro, n_pro, 9) int32 counts: the simulations in which the ordered pair (i, j) is in state k + 1."""
@@ -1691,7 +1702,7 @@ GENPHI_RETAIN_FLAG_PLAIN_OR = 1
 GENPHI_RETAIN_FLAG_TEST_FIRST = 2
 
 
-class RetentionPlan(_SweepPlan):
+class RetentionPlan(_LabelPlan):
     """The handle of gen.simuRetention (include/genphi.h, genphi_retain_*): which founder alleles survive in the listed probands, by
     gene dropping.  Planned on the host at construction (KeyError on an unknown proband; ValueError for simul_no outside 1 .. 2^24,
     no probands, a negative panel_cols or chunk_labels, an unknown mark; no GPU needed), swept on the GPU by compute().  The plan and
@@ -1707,10 +1718,7 @@ class RetentionPlan(_SweepPlan):
         pro_ids = _i64(pro_ids).ravel()
         if mark not in self._marks:
             raise ValueError("gen.simuRetention: mark is None, 'or' or 'test', not %r" % (mark,))
-        if seed is None:
-            import secrets
-            seed = secrets.randbits(64)
-        self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self._set_seed(seed)
         self.simul_no = int(simul_no)
         ind, father, mother = _i64(ind), _i64(father), _i64(mother)
         h = C.c_void_p()
@@ -1721,22 +1729,7 @@ class RetentionPlan(_SweepPlan):
             _raise(rc)
         self._h = h
         self.n_pro = len(pro_ids)
-        n_live, levels, n_labels, planes = C.c_int64(), C.c_int32(), C.c_int64(), C.c_int32()
-        self._call("levels", C.byref(n_live), C.byref(levels), None)
-        self._call("alleles", C.byref(n_labels), C.byref(planes), None, None)
-        self.n_live, self.levels, self.n_labels, self.planes = int(n_live.value), int(levels.value), int(n_labels.value), int(planes.value)
-
-    def rows_per_level(self):
-        """The live rows of every level (host only)."""
-        out = np.empty(self.levels, dtype=np.int64)
-        self._call("levels", None, None, out.ctypes.data_as(_I64P))
-        return out
-
-    def alleles(self):
-        """The allele table (host only): int64 (n_labels, 2), the ID and the side (0 = from the father) of every label."""
-        ids, sides = np.empty(self.n_labels, np.int64), np.empty(self.n_labels, np.int32)
-        self._call("alleles", None, None, ids.ctypes.data_as(_I64P), sides.ctypes.data_as(C.POINTER(C.c_int32)))
-        return np.stack([ids, sides.astype(np.int64)], axis=1)
+        self._read_plan()
 
     def survived_to_host(self):
         """int32 (n_labels,): the simulations in which some listed proband carries the label."""
@@ -1765,7 +1758,7 @@ GENPHI_LINK_MAX_LOCI = 4096
 GENPHI_LINK_MAX_Q = 32768
 
 
-class SharingPlan(_SweepPlan):
+class SharingPlan(_LabelPlan):
     """The handle of gen.simuSharing (include/genphi.h, genphi_link_*): gene dropping along a chromosome of `loci` linked loci with
     the recombination probability q / 65536 between neighbours, and the sharing of every pair of probands.  Planned on the host at
     construction (KeyError on an unknown proband; ValueError for loci outside 1 .. 4096, q outside 0 .. 32768, simul_no outside
@@ -1777,10 +1770,7 @@ class SharingPlan(_SweepPlan):
 
     def __init__(self, ind, father, mother, pro_ids, loci=1024, q=64, simul_no=1000, seed=None, labels=False, panel_sims=0, all_pairs=False):
         pro_ids = _i64(pro_ids).ravel()
-        if seed is None:
-            import secrets
-            seed = secrets.randbits(64)
-        self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self._set_seed(seed)
         self.simul_no, self.loci, self.q = int(simul_no), int(loci), int(q)
         if not (-2**31 <= self.loci < 2**31 and -2**31 <= self.q < 2**31):
             raise ValueError("gen.simuSharing: loci = %d or q = %d is not a 32-bit integer" % (self.loci, self.q))
@@ -1795,22 +1785,7 @@ class SharingPlan(_SweepPlan):
             _raise(rc)
         self._h = h
         self.n_pro = len(pro_ids)
-        n_live, levels, n_labels, planes = C.c_int64(), C.c_int32(), C.c_int64(), C.c_int32()
-        self._call("levels", C.byref(n_live), C.byref(levels), None)
-        self._call("alleles", C.byref(n_labels), C.byref(planes), None, None)
-        self.n_live, self.levels, self.n_labels, self.planes = int(n_live.value), int(levels.value), int(n_labels.value), int(planes.value)
-
-    def rows_per_level(self):
-        """The live rows of every level (host only)."""
-        out = np.empty(self.levels, dtype=np.int64)
-        self._call("levels", None, None, out.ctypes.data_as(_I64P))
-        return out
-
-    def alleles(self):
-        """The allele table (host only): int64 (n_labels, 2), the ID and the side (0 = from the father) of every label."""
-        ids, sides = np.empty(self.n_labels, np.int64), np.empty(self.n_labels, np.int32)
-        self._call("alleles", None, None, ids.ctypes.data_as(_I64P), sides.ctypes.data_as(C.POINTER(C.c_int32)))
-        return np.stack([ids, sides.astype(np.int64)], axis=1)
+        self._read_plan()
 
     def sums_to_host(self):
         """The (n_pro, n_pro, 6) int64 sums over the simulations: m, m^2, n1, n2, g and [n1 > 0] (include/genphi.h)."""

@@ -1,6 +1,7 @@
-// drop_device.h -- the device helpers the gene-dropping sweeps (simu.hip, ident.hip, link.hip) share: the random word of a meiosis, the
-// meiosis itself and the mask of the simulated columns (link.hip: of the loci).  gen.simuIdentity relies on drawing THE word gen.simuSample draws for the same
-// (seed, ID, side, absolute pair index): both take it from here.
+// drop_device.h -- the device helpers the four gene-dropping sweeps (simu.hip, ident.hip, retain.hip, link.hip) share: the random word
+// of a meiosis, the meiosis itself and the mask of the simulated columns (link.hip: of the loci).  gen.simuIdentity relies on drawing
+// THE word gen.simuSample draws for the same (seed, ID, side, absolute pair index): both take it from here.  The host side of the four
+// handles is drop_host.h; the label sweep of the last three is label_sweep.h.
 #pragma once
 #include <hip/hip_runtime.h>
 

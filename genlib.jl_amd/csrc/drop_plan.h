@@ -1,5 +1,5 @@
-// drop_plan.h -- what the host plans of the two gene-dropping sweeps (simu.h, ident.h) share: the rows of the live set by level, and
-// the width of a panel of simulations.  Host only, no HIP.
+// drop_plan.h -- what the two host plans of the four gene-dropping sweeps share (simu.h: simu.hip; ident.h: ident.hip, retain.hip,
+// link.hip): the rows of the live set by level, and the width of a panel of simulations.  Host only, no HIP.
 #pragma once
 #include <algorithm>
 #include <cstdint>

@@ -31,6 +31,13 @@ struct IdentPlan : DropRows {                // (drop_plan.h: the rows by level;
 int plan_ident(IdentPlan &out, int64_t n_ind, const int64_t *ind, const int64_t *father, const int64_t *mother, int64_t n_pro,
                const int64_t *pro_ids, std::string &err);
 
+// Device bytes of the lists every label sweep uploads (ident.hip, retain.hip, link.hip): the parent rows, the proband rows, the IDs
+// and the constant sides.
+inline size_t label_list_bytes(const IdentPlan &pl)
+{
+    return 4 * (pl.fa_row.size() + pl.mo_row.size() + pl.pro_row.size()) + 8 * (pl.row_id.size() + pl.const_side.size());
+}
+
 // Device bytes of a sweep (ident.hip allocates exactly these; the check before any launch adds them up).
 struct IdentSizes {
     size_t counts = 0;           // Int32 n_pro x n_pro x 9
@@ -48,7 +55,7 @@ inline IdentSizes ident_sizes(const IdentPlan &pl, int64_t S, bool labels)
     const size_t n_pro = static_cast<size_t>(pl.n_pro), side_bytes = 16 * static_cast<size_t>(pl.planes);
     z.counts = 36 * n_pro * n_pro;
     z.labels = labels ? 8 * n_pro * static_cast<size_t>(S) : 0;
-    z.lists = 4 * (pl.fa_row.size() + pl.mo_row.size() + pl.pro_row.size()) + 8 * (pl.row_id.size() + pl.const_side.size());
+    z.lists = label_list_bytes(pl);
     z.pair_rows = 2 * side_bytes * static_cast<size_t>(pl.n_live);
     z.pair_gather = 2 * side_bytes * n_pro;
     return z;

@@ -6,7 +6,7 @@
 // on (seed, ID, side, absolute pair index).  The host plan (ident.h, no GPU) lists the live set by level and the allele table.
 //   layout  a panel row holds Pn pairs of words; the B planes of one (row, pair, side) are contiguous 16-byte elements and the
 //           two sides of a pair are neighbours: row r, pair j, side s, plane b at ((r * Pn + j) * 2 + s) * B + b (ulonglong2)
-//   (init and step live in ident_device.h: gen.simuRetention, retain.hip, sweeps with them too)
+//   (init, step and gather live in label_sweep.h with the base of the handle: retain.hip and link.hip sweep with them too)
 //   init    the sides with an unknown parent, at any level: plane b of label k is all ones or all zeros.  Only these are ever
 //           initialised: every other side is written whole by the step of its row's level before anything reads it
 //   step    one launch per level >= 1: LPR lanes per row, a lane owns a pair of words: per known side one Philox block and the
@@ -26,27 +26,11 @@
 // Everything is integer and keyed on IDs and absolute word indices: the same bytes on every run, with any panel width.
 #include <hip/hip_runtime.h>
 
-#include "drop_device.h"
-#include "ident.h"
-#include "ident_device.h"
-#include "sweep_device.h"
+#include "label_sweep.h"
 
 namespace {
 
 constexpr int IDENT_TILE = 32;               // the pair kernel's tile: 32 rows x 32 columns, 2 x 2 pairs per thread
-
-// The listed probands' rows, transposed: consecutive threads own consecutive probands of one (pair, side, plane).
-__global__ void __launch_bounds__(256)
-ident_gather_kernel(const ulonglong2 *__restrict__ rows, const int *__restrict__ pro_row, int n_pro, int Pn, int Pc, int B2,
-                    ulonglong2 *__restrict__ gathered)
-{
-    const long long t = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
-    const int i = static_cast<int>(t % n_pro);
-    const long long e = t / n_pro;                       // pair * B2 + (side * B + plane)
-    if (e >= static_cast<long long>(Pc) * B2) return;
-    const long long c = e / B2, q = e % B2;
-    gathered[e * n_pro + i] = rows[(static_cast<long long>(pro_row[i]) * Pn + c) * B2 + q];
-}
 
 // The 32 x 32 tile (blockIdx.y, blockIdx.x) of ordered pairs over the Pc pairs of words of a panel (see the head of the file).
 // tile[]: word w of the pair, side s, plane b, then 64 entries: the tile's 32 rows and its 32 columns.  Thread (ty, tx) owns the
@@ -174,36 +158,16 @@ ident_label_kernel(const ulonglong2 *__restrict__ gathered, int n_pro, int B, in
 
 }  // namespace
 
-struct genphi_ident : SweepDevice {          // d_slots: the rows of one panel (n_live x pairs x 2 sides x B planes x 16 bytes)
-    genphi::IdentPlan plan;                  // host plan (ident.h)
-    int64_t S = 0;
-    uint64_t seed = 0;
+struct genphi_ident : LabelSweep {           // d_slots: the rows of one panel (n_live x pairs x 2 sides x B planes x 16 bytes)
     bool want_labels = false, all_pairs = false;
-    int32_t panel_arg = 0;                   // create's panel_cols (0 = default rule)
-    DevBuf<int> d_counts, d_labels, d_fa, d_mo, d_pro_row;
-    DevBuf<long long> d_ids, d_const_side;
-    DevBuf<ulonglong2> d_gathered;           // the listed probands' rows of one panel, transposed (ident_gather_kernel)
-    int32_t pairs = 0, lanes_per_row = 0;    // pairs of a panel row
-    int64_t n_panels = 0;
+    DevBuf<int> d_counts, d_labels;
+    DevBuf<ulonglong2> d_gathered;           // the listed probands' rows of one panel, transposed (label_gather_kernel)
+    DropPanels panels;
     double pair_ms = 0.0, word_ops = 0.0;
-    bool empty() const { return false; }     // (n_pro >= 1 and S >= 1 always)
-    genphi_ident() { own(d_counts, d_labels, d_fa, d_mo, d_pro_row, d_ids, d_const_side, d_gathered); }
-    int64_t total_pairs() const { return (S + 127) / 128; }
+    genphi_ident() { own(d_counts, d_labels, d_gathered); }
 };
 
 namespace {
-
-struct Events {                              // destroyed on every path
-    hipEvent_t e[3] = {nullptr, nullptr, nullptr};
-    Events() = default;
-    Events(const Events &) = delete;
-    Events &operator=(const Events &) = delete;
-    ~Events()
-    {
-        for (hipEvent_t x : e)
-            if (x) (void)hipEventDestroy(x);
-    }
-};
 
 // The panel width, the rows, the results and the lists on the device; GENPHI_ERR_ALLOC before any launch.
 int prepare(genphi_ident *h)
@@ -224,13 +188,8 @@ int prepare(genphi_ident *h)
     GENPHI_HIP_TRY(h->d_gathered.reserve(z.pair_gather * static_cast<size_t>(Pn) / sizeof(ulonglong2)));
     GENPHI_HIP_TRY(h->d_counts.reserve(z.counts / 4));
     if (h->want_labels) GENPHI_HIP_TRY(h->d_labels.reserve(z.labels / 4));
-    int rc;
-    if ((rc = h->upload(h->d_fa, pl.fa_row)) || (rc = h->upload(h->d_mo, pl.mo_row)) || (rc = h->upload(h->d_pro_row, pl.pro_row)) ||
-        (rc = h->upload(h->d_ids, pl.row_id)) || (rc = h->upload(h->d_const_side, pl.const_side)))
-        return rc;
-    h->pairs = static_cast<int32_t>(Pn);
-    h->lanes_per_row = lanes_per_row(static_cast<int>(Pn));
-    h->n_panels = (h->total_pairs() + Pn - 1) / Pn;
+    if (int rc = h->upload_lists()) return rc;
+    h->panels.set(h->S, Pn);
     return GENPHI_OK;
 }
 
@@ -239,52 +198,30 @@ int compute_impl(genphi_ident *h, int32_t device)
     if (int rc = h->select(device)) return rc;
     if (int rc = prepare(h)) return rc;
     const genphi::IdentPlan &pl = h->plan;
-    const int Pn = h->pairs, lpr = h->lanes_per_row, B = pl.planes, n_pro = static_cast<int>(pl.n_pro);
-    const int64_t total = h->total_pairs();
-    const unsigned k0 = static_cast<unsigned>(h->seed), k1 = static_cast<unsigned>(h->seed >> 32);
-    ulonglong2 *rows = h->slots<ulonglong2>();
-    const int step_rows = 4 * (64 / lpr);
+    const int Pn = h->panels.pairs, B = pl.planes, n_pro = static_cast<int>(pl.n_pro);
+    const int64_t total = h->panels.total;
     const unsigned tiles = static_cast<unsigned>((n_pro + IDENT_TILE - 1) / IDENT_TILE);
     const size_t lds = static_cast<size_t>(2 * 2 * 64 * 8) * static_cast<size_t>(B);
-    Events ev;
-    for (hipEvent_t &x : ev.e) GENPHI_HIP_TRY(hipEventCreate(&x));
+    PhaseTimer timer;
     GENPHI_HIP_TRY(hipMemsetAsync(h->d_counts.get(), 0, h->d_counts.bytes(), h->stream));
     double sweep_ms = 0.0, pair_ms = 0.0;
     int64_t launches = 0;
     for (int64_t p0 = 0; p0 < total; p0 += Pn) {
         const int Pc = static_cast<int>(std::min<int64_t>(Pn, total - p0));
-        const unsigned first_pair = static_cast<unsigned>(p0);
-        GENPHI_HIP_TRY(hipEventRecord(ev.e[0], h->stream));
-        ident_init_kernel<<<static_cast<unsigned>((pl.n_labels * Pc + 255) / 256), 256, 0, h->stream>>>(h->d_const_side.get(), pl.n_labels, rows, Pn, Pc, B);
-        GENPHI_HIP_TRY(hipGetLastError());
-        for (int k = 1; k < pl.n_levels; ++k) {
-            const long long b = pl.level_begin[k];
-            const int n_rows = static_cast<int>(pl.level_rows[k]);
-            const unsigned grid = static_cast<unsigned>((n_rows + step_rows - 1) / step_rows);
-            GENPHI_LPR_SWITCH(lpr, (ident_step_kernel<LPR><<<grid, 256, 0, h->stream>>>(h->d_fa.get() + b, h->d_mo.get() + b, h->d_ids.get() + b, n_rows, b, rows,
-                                                                                     Pn, Pc, B, first_pair, k0, k1)));
-            GENPHI_HIP_TRY(hipGetLastError());
-        }
-        GENPHI_HIP_TRY(hipEventRecord(ev.e[1], h->stream));
-        const long long gather_threads = static_cast<long long>(n_pro) * Pc * 2 * B;
-        ident_gather_kernel<<<static_cast<unsigned>((gather_threads + 255) / 256), 256, 0, h->stream>>>(rows, h->d_pro_row.get(), n_pro, Pn, Pc, 2 * B,
-                                                                                                       h->d_gathered.get());
-        GENPHI_HIP_TRY(hipGetLastError());
+        if (int rc = timer.begin(h->stream)) return rc;
+        if (int rc = label_sweep_panel(h, Pc, static_cast<unsigned>(p0))) return rc;
+        if (int rc = timer.middle(h->stream)) return rc;
+        if (int rc = h->gather_panel(Pn, Pc, h->d_gathered.get())) return rc;
         ident_pair_kernel<<<dim3(tiles, tiles), 256, lds, h->stream>>>(h->d_gathered.get(), n_pro, B, Pc, p0, h->S, h->all_pairs ? 0 : 1, h->d_counts.get());
         GENPHI_HIP_TRY(hipGetLastError());
-        GENPHI_HIP_TRY(hipEventRecord(ev.e[2], h->stream));
+        if (int rc = timer.end(h->stream)) return rc;
         if (h->want_labels) {
             const long long threads = 2ll * n_pro * (2 * Pc) * 64;
             ident_label_kernel<<<static_cast<unsigned>((threads + 255) / 256), 256, 0, h->stream>>>(h->d_gathered.get(), n_pro, B, 2 * Pc, 2 * p0, h->S,
                                                                                                    h->d_labels.get());
             GENPHI_HIP_TRY(hipGetLastError());
         }
-        GENPHI_HIP_TRY(hipEventSynchronize(ev.e[2]));
-        float a = 0.f, b = 0.f;
-        GENPHI_HIP_TRY(hipEventElapsedTime(&a, ev.e[0], ev.e[1]));
-        GENPHI_HIP_TRY(hipEventElapsedTime(&b, ev.e[1], ev.e[2]));
-        sweep_ms += a;
-        pair_ms += b;
+        if (int rc = timer.add(sweep_ms, pair_ms)) return rc;
         launches += pl.n_levels + 2 + (h->want_labels ? 1 : 0);
     }
     GENPHI_HIP_TRY(hipStreamSynchronize(h->stream));
@@ -324,49 +261,31 @@ int genphi_ident_create(int64_t n_ind, const int64_t *ind, const int64_t *father
         h->panel_arg = panel_cols;
         std::string err;
         if (const int rc = genphi::plan_ident(h->plan, n_ind, ind, father, mother, n_pro, pro_ids, err)) return genphi_set_error(rc, err);
-        h->pairs = static_cast<int32_t>(genphi::drop_panel_pairs(simul_no, panel_cols));      // (compute may narrow the default to what fits)
-        h->lanes_per_row = lanes_per_row(h->pairs);
-        h->n_panels = (h->total_pairs() + h->pairs - 1) / h->pairs;
+        h->panels.set(simul_no, genphi::drop_panel_pairs(simul_no, panel_cols));                // (compute may narrow the default to what fits)
         return GENPHI_OK;
     });
 }
 
 int genphi_ident_levels(const genphi_ident *h, int64_t *n_live, int32_t *levels, int64_t *rows_per_level)
 {
-    if (!h) return genphi_set_error(GENPHI_ERR_ARG, "genphi_ident_levels: NULL handle");
-    put(n_live, h->plan.n_live);
-    put(levels, h->plan.n_levels);
-    if (rows_per_level)
-        for (int k = 0; k < h->plan.n_levels; ++k) rows_per_level[k] = h->plan.level_rows[k];
-    return GENPHI_OK;
+    return drop_levels(h, "genphi_ident_levels", n_live, levels, rows_per_level);
 }
 
 int genphi_ident_alleles(const genphi_ident *h, int64_t *n_labels, int32_t *planes, int64_t *ids, int32_t *sides)
 {
-    if (!h) return genphi_set_error(GENPHI_ERR_ARG, "genphi_ident_alleles: NULL handle");
-    put(n_labels, h->plan.n_labels);
-    put(planes, h->plan.planes);
-    if (ids) std::copy(h->plan.allele_id.begin(), h->plan.allele_id.end(), ids);
-    if (sides) std::copy(h->plan.allele_side.begin(), h->plan.allele_side.end(), sides);
-    return GENPHI_OK;
+    return label_alleles(h, "genphi_ident_alleles", n_labels, planes, ids, sides);
 }
 
 int genphi_ident_compute(genphi_ident *h, int32_t device) { return compute_entry(h, device, "genphi_ident_compute", "gen.simuIdentity", compute_impl); }
 
 int genphi_ident_counts_to_host(genphi_ident *h, int32_t *out)
 {
-    if (!h || !h->computed) return genphi_set_error(GENPHI_ERR_ARG, "genphi_ident_counts_to_host: nothing computed");
-    if (!out) return genphi_set_error(GENPHI_ERR_ARG, "genphi_ident_counts_to_host: out is NULL");
-    return h->copy_out(out, h->d_counts.get(), h->d_counts.bytes(), "gen.simuIdentity");
+    return result_to_host(h, out, &genphi_ident::d_counts, "genphi_ident_counts_to_host", "gen.simuIdentity");
 }
 
 int genphi_ident_labels_to_host(genphi_ident *h, int32_t *out)
 {
-    if (!h) return genphi_set_error(GENPHI_ERR_ARG, "genphi_ident_labels_to_host: NULL handle");
-    if (!h->want_labels) return genphi_set_error(GENPHI_ERR_ARG, "genphi_ident_labels_to_host: the handle was created without GENPHI_IDENT_FLAG_LABELS");
-    if (!h->computed) return genphi_set_error(GENPHI_ERR_ARG, "genphi_ident_labels_to_host: nothing computed");
-    if (!out) return genphi_set_error(GENPHI_ERR_ARG, "genphi_ident_labels_to_host: out is NULL");
-    return h->copy_out(out, h->d_labels.get(), h->d_labels.bytes(), "gen.simuIdentity");
+    return labels_to_host(h, out, "genphi_ident_labels_to_host", "GENPHI_IDENT_FLAG_LABELS", "gen.simuIdentity");
 }
 
 int genphi_ident_stats(const genphi_ident *h, double *sweep_ms, double *pair_ms, double *algorithmic_bytes, double *word_ops, int32_t *levels,
@@ -377,12 +296,12 @@ int genphi_ident_stats(const genphi_ident *h, double *sweep_ms, double *pair_ms,
     put(pair_ms, h->pair_ms);
     put(word_ops, h->word_ops);
     put(levels, h->plan.n_levels);
-    put(panel_cols, 128 * h->pairs);
-    put(panels, h->n_panels);
+    put(panel_cols, 128 * h->panels.pairs);
+    put(panels, h->panels.n_panels);
     put(planes, h->plan.planes);
     put(tile_rows, IDENT_TILE);
     put(tile_cols, IDENT_TILE);
-    put(lanes_per_row, h->lanes_per_row);
+    put(lanes_per_row, h->panels.lanes_per_row);
     return GENPHI_OK;
 }
 

@@ -88,7 +88,7 @@ inline LinkSizes link_sizes(const IdentPlan &pl, int64_t S, const LinkShape &sha
     const size_t n_pro = static_cast<size_t>(pl.n_pro), sim_side = 16 * static_cast<size_t>(pl.planes) * static_cast<size_t>(shape.Wp);
     z.sums = 48 * n_pro * n_pro;
     z.labels = labels ? 8 * n_pro * static_cast<size_t>(S) * static_cast<size_t>(shape.L) : 0;
-    z.lists = 4 * (pl.fa_row.size() + pl.mo_row.size() + pl.pro_row.size()) + 8 * (pl.row_id.size() + pl.const_side.size());
+    z.lists = label_list_bytes(pl);
     z.sim_rows = 2 * sim_side * static_cast<size_t>(pl.n_live);
     z.sim_gather = 2 * sim_side * n_pro;
     return z;

@@ -6,6 +6,7 @@
 // prefix XOR of the crossover words X along the chromosome (link.h).  The host plan is ident's (ident.h), unchanged.
 //   layout  ident's, with the column index of a panel row running over (simulation, pair of words), the pair fastest: row r, column
 //           c = s * Wp + p, side, plane b at ((r * Cn + c) * 2 + side) * B + b (ulonglong2: the words 2p and 2p + 1 of the chromosome)
+//   (init and gather live in label_sweep.h with the base of the handle; ident.hip and retain.hip use them too)
 //   init    the sides with an unknown parent, as in ident: plane b of label k is all ones or all zeros
 //   step    one launch per level >= 1 and panel.  LPS = the power of two >= Wp lanes own the pairs of words of one simulation of one
 //           row and are neighbours in a wave (Wp <= 32: a simulation never spans waves).  A lane draws and folds its own two X words
@@ -26,29 +27,12 @@
 // Everything is integer and keyed on IDs and absolute simulation and word indices: the same bytes on every run, with any panel width.
 #include <hip/hip_runtime.h>
 
-#include "drop_device.h"
+#include "label_sweep.h"
 #include "link.h"
-#include "sweep_device.h"
 
 namespace {
 
 constexpr int LINK_TILE = 32;                // the pair kernel's tile: 32 rows x 32 columns, 2 x 2 pairs per thread
-
-// The constant sides: a thread per (label, column) writes the B planes of the side that carries the label.
-__global__ void __launch_bounds__(256)
-link_init_kernel(const long long *__restrict__ const_side, long long n_labels, ulonglong2 *__restrict__ rows, long long Cn, long long Cc, int B)
-{
-    const long long t = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
-    const long long k = t / Cc;
-    if (k >= n_labels) return;
-    const long long c = t % Cc;
-    const long long side = const_side[k];                // 2 * row + side
-    ulonglong2 *dst = rows + ((side >> 1) * Cn + c) * 2 * B + (side & 1) * B;
-    for (int b = 0; b < B; ++b) {
-        const u64 v = (k >> b) & 1 ? ~0ull : 0ull;
-        dst[b] = make_ulonglong2(v, v);
-    }
-}
 
 // One level: the rows row0 .. row0 + n_rows of the panel's Sc simulations from the rows of their parents.  A unit is one simulation of
 // one row; its LPS lanes are neighbours, lane p owns the pair of words p (the lanes p >= Wp only take part in the scan).  No lane
@@ -102,19 +86,6 @@ link_step_kernel(const int *__restrict__ fa_row, const int *__restrict__ mo_row,
                 out[b] = meiosis(T, a, m);
             }
         }
-}
-
-// The listed probands' rows, transposed: consecutive threads own consecutive probands of one (column, side, plane).
-__global__ void __launch_bounds__(256)
-link_gather_kernel(const ulonglong2 *__restrict__ rows, const int *__restrict__ pro_row, int n_pro, long long Cn, long long Cc, int B2,
-                   ulonglong2 *__restrict__ gathered)
-{
-    const long long t = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
-    const int i = static_cast<int>(t % n_pro);
-    const long long e = t / n_pro;                       // column * B2 + (side * B + plane)
-    if (e >= Cc * B2) return;
-    const long long c = e / B2, k = e % B2;
-    gathered[e * n_pro + i] = rows[(static_cast<long long>(pro_row[i]) * Cn + c) * B2 + k];
 }
 
 // The 32 x 32 tile (blockIdx.y, blockIdx.x) of pairs over the Sc simulations of a panel (see the head of the file).  tile[]: word w
@@ -244,36 +215,19 @@ link_label_kernel(const ulonglong2 *__restrict__ gathered, int n_pro, int B, int
 
 }  // namespace
 
-struct genphi_link : SweepDevice {           // d_slots: the rows of one panel (n_live x simulations x Wp pairs x 2 sides x B planes x 16 bytes)
-    genphi::IdentPlan plan;                  // host plan (ident.h)
+struct genphi_link : LabelSweep {            // d_slots: the rows of one panel (n_live x simulations x Wp pairs x 2 sides x B planes x 16 bytes)
     genphi::LinkShape shape;                 // L, q, W, Wp, the lanes per simulation (link.h)
-    int64_t S = 0;
-    uint64_t seed = 0;
     bool want_labels = false, all_pairs = false;
-    int32_t panel_arg = 0;                   // create's panel_sims (0 = default rule)
-    DevBuf<long long> d_sums, d_ids, d_const_side;
-    DevBuf<int> d_labels, d_fa, d_mo, d_pro_row;
-    DevBuf<ulonglong2> d_gathered;           // the listed probands' rows of one panel, transposed (link_gather_kernel)
+    DevBuf<long long> d_sums;
+    DevBuf<int> d_labels;
+    DevBuf<ulonglong2> d_gathered;           // the listed probands' rows of one panel, transposed (label_gather_kernel)
     int64_t sims = 0;                        // simulations of a panel
     int64_t n_panels = 0;
     double pair_ms = 0.0, word_ops = 0.0, philox_blocks = 0.0;
-    bool empty() const { return false; }     // (n_pro >= 1 and S >= 1 always)
-    genphi_link() { own(d_sums, d_ids, d_const_side, d_labels, d_fa, d_mo, d_pro_row, d_gathered); }
+    genphi_link() { own(d_sums, d_labels, d_gathered); }
 };
 
 namespace {
-
-struct Events {                              // destroyed on every path
-    hipEvent_t e[3] = {nullptr, nullptr, nullptr};
-    Events() = default;
-    Events(const Events &) = delete;
-    Events &operator=(const Events &) = delete;
-    ~Events()
-    {
-        for (hipEvent_t x : e)
-            if (x) (void)hipEventDestroy(x);
-    }
-};
 
 // the simulations of a panel: panel_arg cut to S, 0 = all of S (drop_plan.h counts in units of 128 columns: a simulation is one unit)
 int64_t panel_sims(int64_t S, int32_t panel_arg) { return genphi::drop_panel_pairs(128 * S, 128 * static_cast<int64_t>(panel_arg)); }
@@ -297,10 +251,7 @@ int prepare(genphi_link *h)
     GENPHI_HIP_TRY(h->d_gathered.reserve(z.sim_gather * static_cast<size_t>(Sn) / sizeof(ulonglong2)));
     GENPHI_HIP_TRY(h->d_sums.reserve(z.sums / 8));
     if (h->want_labels) GENPHI_HIP_TRY(h->d_labels.reserve(z.labels / 4));
-    int rc;
-    if ((rc = h->upload(h->d_fa, pl.fa_row)) || (rc = h->upload(h->d_mo, pl.mo_row)) || (rc = h->upload(h->d_pro_row, pl.pro_row)) ||
-        (rc = h->upload(h->d_ids, pl.row_id)) || (rc = h->upload(h->d_const_side, pl.const_side)))
-        return rc;
+    if (int rc = h->upload_lists()) return rc;
     h->sims = Sn;
     h->n_panels = (h->S + Sn - 1) / Sn;
     return GENPHI_OK;
@@ -327,17 +278,15 @@ int compute_impl(genphi_link *h, int32_t device)
     const int step_units = 4 * (64 / lps);
     const unsigned tiles = static_cast<unsigned>((n_pro + LINK_TILE - 1) / LINK_TILE);
     const size_t lds = static_cast<size_t>(2 * 2 * 64 * 8) * static_cast<size_t>(B);
-    Events ev;
-    for (hipEvent_t &x : ev.e) GENPHI_HIP_TRY(hipEventCreate(&x));
+    PhaseTimer timer;
     GENPHI_HIP_TRY(hipMemsetAsync(h->d_sums.get(), 0, h->d_sums.bytes(), h->stream));
     double sweep_ms = 0.0, pair_ms = 0.0;
     int64_t launches = 0;
     for (int64_t s0 = 0; s0 < h->S; s0 += Sn) {
         const int Sc = static_cast<int>(std::min<int64_t>(Sn, h->S - s0));
         const long long Cc = static_cast<long long>(Sc) * Wp;
-        GENPHI_HIP_TRY(hipEventRecord(ev.e[0], h->stream));
-        link_init_kernel<<<static_cast<unsigned>((pl.n_labels * Cc + 255) / 256), 256, 0, h->stream>>>(h->d_const_side.get(), pl.n_labels, rows, Cn, Cc, B);
-        GENPHI_HIP_TRY(hipGetLastError());
+        if (int rc = timer.begin(h->stream)) return rc;
+        if (int rc = h->init_panel(Cn, Cc)) return rc;
         for (int k = 1; k < pl.n_levels; ++k) {
             const long long b = pl.level_begin[k];
             const int n_rows = static_cast<int>(pl.level_rows[k]);
@@ -354,26 +303,18 @@ int compute_impl(genphi_link *h, int32_t device)
             }
             GENPHI_HIP_TRY(hipGetLastError());
         }
-        GENPHI_HIP_TRY(hipEventRecord(ev.e[1], h->stream));
-        const long long gather_threads = static_cast<long long>(n_pro) * Cc * 2 * B;
-        link_gather_kernel<<<static_cast<unsigned>((gather_threads + 255) / 256), 256, 0, h->stream>>>(rows, h->d_pro_row.get(), n_pro, Cn, Cc, 2 * B,
-                                                                                                      h->d_gathered.get());
-        GENPHI_HIP_TRY(hipGetLastError());
+        if (int rc = timer.middle(h->stream)) return rc;
+        if (int rc = h->gather_panel(Cn, Cc, h->d_gathered.get())) return rc;
         link_pair_kernel<<<dim3(tiles, tiles), 256, lds, h->stream>>>(h->d_gathered.get(), n_pro, B, Sc, Wp, sh.L, h->all_pairs ? 0 : 1, h->d_sums.get());
         GENPHI_HIP_TRY(hipGetLastError());
-        GENPHI_HIP_TRY(hipEventRecord(ev.e[2], h->stream));
+        if (int rc = timer.end(h->stream)) return rc;
         if (h->want_labels) {
             const long long threads = 2ll * n_pro * Sc * sh.W * 64;
             link_label_kernel<<<static_cast<unsigned>((threads + 255) / 256), 256, 0, h->stream>>>(h->d_gathered.get(), n_pro, B, Sc, sh.W, Wp, sh.L, s0, h->S,
                                                                                                    h->d_labels.get());
             GENPHI_HIP_TRY(hipGetLastError());
         }
-        GENPHI_HIP_TRY(hipEventSynchronize(ev.e[2]));
-        float a = 0.f, b = 0.f;
-        GENPHI_HIP_TRY(hipEventElapsedTime(&a, ev.e[0], ev.e[1]));
-        GENPHI_HIP_TRY(hipEventElapsedTime(&b, ev.e[1], ev.e[2]));
-        sweep_ms += a;
-        pair_ms += b;
+        if (int rc = timer.add(sweep_ms, pair_ms)) return rc;
         launches += pl.n_levels + 2 + (h->want_labels ? 1 : 0);
     }
     GENPHI_HIP_TRY(hipStreamSynchronize(h->stream));
@@ -429,40 +370,24 @@ int genphi_link_create(int64_t n_ind, const int64_t *ind, const int64_t *father,
 
 int genphi_link_levels(const genphi_link *h, int64_t *n_live, int32_t *levels, int64_t *rows_per_level)
 {
-    if (!h) return genphi_set_error(GENPHI_ERR_ARG, "genphi_link_levels: NULL handle");
-    put(n_live, h->plan.n_live);
-    put(levels, h->plan.n_levels);
-    if (rows_per_level)
-        for (int k = 0; k < h->plan.n_levels; ++k) rows_per_level[k] = h->plan.level_rows[k];
-    return GENPHI_OK;
+    return drop_levels(h, "genphi_link_levels", n_live, levels, rows_per_level);
 }
 
 int genphi_link_alleles(const genphi_link *h, int64_t *n_labels, int32_t *planes, int64_t *ids, int32_t *sides)
 {
-    if (!h) return genphi_set_error(GENPHI_ERR_ARG, "genphi_link_alleles: NULL handle");
-    put(n_labels, h->plan.n_labels);
-    put(planes, h->plan.planes);
-    if (ids) std::copy(h->plan.allele_id.begin(), h->plan.allele_id.end(), ids);
-    if (sides) std::copy(h->plan.allele_side.begin(), h->plan.allele_side.end(), sides);
-    return GENPHI_OK;
+    return label_alleles(h, "genphi_link_alleles", n_labels, planes, ids, sides);
 }
 
 int genphi_link_compute(genphi_link *h, int32_t device) { return compute_entry(h, device, "genphi_link_compute", "gen.simuSharing", compute_impl); }
 
 int genphi_link_sums_to_host(genphi_link *h, int64_t *out)
 {
-    if (!h || !h->computed) return genphi_set_error(GENPHI_ERR_ARG, "genphi_link_sums_to_host: nothing computed");
-    if (!out) return genphi_set_error(GENPHI_ERR_ARG, "genphi_link_sums_to_host: out is NULL");
-    return h->copy_out(out, h->d_sums.get(), h->d_sums.bytes(), "gen.simuSharing");
+    return result_to_host(h, out, &genphi_link::d_sums, "genphi_link_sums_to_host", "gen.simuSharing");
 }
 
 int genphi_link_labels_to_host(genphi_link *h, int32_t *out)
 {
-    if (!h) return genphi_set_error(GENPHI_ERR_ARG, "genphi_link_labels_to_host: NULL handle");
-    if (!h->want_labels) return genphi_set_error(GENPHI_ERR_ARG, "genphi_link_labels_to_host: the handle was created without GENPHI_LINK_FLAG_LABELS");
-    if (!h->computed) return genphi_set_error(GENPHI_ERR_ARG, "genphi_link_labels_to_host: nothing computed");
-    if (!out) return genphi_set_error(GENPHI_ERR_ARG, "genphi_link_labels_to_host: out is NULL");
-    return h->copy_out(out, h->d_labels.get(), h->d_labels.bytes(), "gen.simuSharing");
+    return labels_to_host(h, out, "genphi_link_labels_to_host", "GENPHI_LINK_FLAG_LABELS", "gen.simuSharing");
 }
 
 int genphi_link_stats(const genphi_link *h, double *sweep_ms, double *pair_ms, double *algorithmic_bytes, double *word_ops, double *philox_blocks,

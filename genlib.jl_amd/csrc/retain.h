@@ -27,7 +27,7 @@ inline RetainSizes retain_sizes(const IdentPlan &pl, int64_t S)
     RetainSizes z;
     z.survived = z.both = 4 * static_cast<size_t>(pl.n_labels);
     z.distinct = 4 * static_cast<size_t>(S);
-    z.lists = 4 * (pl.fa_row.size() + pl.mo_row.size() + pl.pro_row.size()) + 8 * (pl.row_id.size() + pl.const_side.size());
+    z.lists = label_list_bytes(pl);
     z.pair_rows = 2 * 16 * static_cast<size_t>(pl.planes) * static_cast<size_t>(pl.n_live);
     return z;
 }

@@ -1,6 +1,6 @@
 // retain.hip -- gen.simuRetention: which founder alleles survive in the listed probands, by gene dropping (include/genphi.h,
-// genphi_retain_*).  The label sweep is gen.simuIdentity's (ident_device.h: the init kernel and the step kernel, on ident's row
-// layout: row r, pair j, side s, plane b at ((r * Pn + j) * 2 + s) * B + b, 16-byte elements); the plan is ident's too (ident.h).
+// genphi_retain_*).  The label sweep is the shared one (label_sweep.h: the base of the handle, the init kernel and the step kernel, on
+// ident's columns: row r, pair j, side s, plane b at ((r * Pn + j) * 2 + s) * B + b, 16-byte elements); the plan is ident.h's.
 // Only the reduction is new, and it is the hot path:
 //   mark    one launch per panel after the last level, grid (words of the panel, label chunks), 1,024 threads.  A workgroup owns the
 //           64 simulations of one word and the labels [l0, l0 + LC) of one chunk (retain.h: retain_chunks).  It holds 64 bitmaps in
@@ -21,10 +21,8 @@
 // Everything is integer; the only atomics on global memory are integer adds: the same bytes on every run, with any panel and chunk.
 #include <hip/hip_runtime.h>
 
-#include "drop_device.h"
-#include "ident_device.h"
+#include "label_sweep.h"
 #include "retain.h"
-#include "sweep_device.h"
 
 namespace {
 
@@ -120,36 +118,16 @@ retain_mark_kernel(const ulonglong2 *__restrict__ rows, const int *__restrict__ 
 
 }  // namespace
 
-struct genphi_retain : SweepDevice {         // d_slots: the rows of one panel (n_live x pairs x 2 sides x B planes x 16 bytes)
-    genphi::IdentPlan plan;                  // host plan (ident.h)
+struct genphi_retain : LabelSweep {          // d_slots: the rows of one panel (n_live x pairs x 2 sides x B planes x 16 bytes)
     genphi::RetainChunks chunks;             // the chunk rule (retain.h)
-    int64_t S = 0;
-    uint64_t seed = 0;
     bool test_first = false;                 // the mark phase's form
-    int32_t panel_arg = 0;                   // create's panel_cols (0 = default rule)
-    DevBuf<int> d_survived, d_both, d_distinct, d_fa, d_mo, d_pro_row;
-    DevBuf<long long> d_ids, d_const_side;
-    int32_t pairs = 0, lanes_per_row = 0;    // pairs of a panel row
-    int64_t n_panels = 0;
+    DevBuf<int> d_survived, d_both, d_distinct;
+    DropPanels panels;
     double mark_ms = 0.0, mark_bytes = 0.0;
-    bool empty() const { return false; }     // (n_pro >= 1 and S >= 1 always)
-    genphi_retain() { own(d_survived, d_both, d_distinct, d_fa, d_mo, d_pro_row, d_ids, d_const_side); }
-    int64_t total_pairs() const { return (S + 127) / 128; }
+    genphi_retain() { own(d_survived, d_both, d_distinct); }
 };
 
 namespace {
-
-struct Events {                              // destroyed on every path
-    hipEvent_t e[3] = {nullptr, nullptr, nullptr};
-    Events() = default;
-    Events(const Events &) = delete;
-    Events &operator=(const Events &) = delete;
-    ~Events()
-    {
-        for (hipEvent_t x : e)
-            if (x) (void)hipEventDestroy(x);
-    }
-};
 
 // The panel width, the rows, the results and the lists on the device; GENPHI_ERR_ALLOC before any launch.
 int prepare(genphi_retain *h)
@@ -170,13 +148,8 @@ int prepare(genphi_retain *h)
     GENPHI_HIP_TRY(h->d_survived.reserve(z.survived / 4));
     GENPHI_HIP_TRY(h->d_both.reserve(z.both / 4));
     GENPHI_HIP_TRY(h->d_distinct.reserve(z.distinct / 4));
-    int rc;
-    if ((rc = h->upload(h->d_fa, pl.fa_row)) || (rc = h->upload(h->d_mo, pl.mo_row)) || (rc = h->upload(h->d_pro_row, pl.pro_row)) ||
-        (rc = h->upload(h->d_ids, pl.row_id)) || (rc = h->upload(h->d_const_side, pl.const_side)))
-        return rc;
-    h->pairs = static_cast<int32_t>(Pn);
-    h->lanes_per_row = lanes_per_row(static_cast<int>(Pn));
-    h->n_panels = (h->total_pairs() + Pn - 1) / Pn;
+    if (int rc = h->upload_lists()) return rc;
+    h->panels.set(h->S, Pn);
     return GENPHI_OK;
 }
 
@@ -186,15 +159,13 @@ int compute_impl(genphi_retain *h, int32_t device)
     if (int rc = prepare(h)) return rc;
     const genphi::IdentPlan &pl = h->plan;
     const genphi::RetainChunks &ch = h->chunks;
-    const int Pn = h->pairs, lpr = h->lanes_per_row, B = pl.planes, n_pro = static_cast<int>(pl.n_pro);
-    const int64_t total = h->total_pairs();
-    const unsigned k0 = static_cast<unsigned>(h->seed), k1 = static_cast<unsigned>(h->seed >> 32);
+    const int Pn = h->panels.pairs, B = pl.planes, n_pro = static_cast<int>(pl.n_pro);
+    const int64_t total = h->panels.total;
     ulonglong2 *rows = h->slots<ulonglong2>();
-    const int step_rows = 4 * (64 / lpr);
-    const void *fn = h->test_first ? reinterpret_cast<const void *>(retain_mark_kernel<true>) : reinterpret_cast<const void *>(retain_mark_kernel<false>);
-    if (ch.lds_bytes > 32768) GENPHI_HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(ch.lds_bytes)));
-    Events ev;
-    for (hipEvent_t &x : ev.e) GENPHI_HIP_TRY(hipEventCreate(&x));
+    const auto mark = h->test_first ? retain_mark_kernel<true> : retain_mark_kernel<false>;
+    if (ch.lds_bytes > 32768)
+        GENPHI_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(mark), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(ch.lds_bytes)));
+    PhaseTimer timer;
     GENPHI_HIP_TRY(hipMemsetAsync(h->d_survived.get(), 0, h->d_survived.bytes(), h->stream));
     GENPHI_HIP_TRY(hipMemsetAsync(h->d_both.get(), 0, h->d_both.bytes(), h->stream));
     GENPHI_HIP_TRY(hipMemsetAsync(h->d_distinct.get(), 0, h->d_distinct.bytes(), h->stream));
@@ -202,39 +173,19 @@ int compute_impl(genphi_retain *h, int32_t device)
     int64_t launches = 0;
     for (int64_t p0 = 0; p0 < total; p0 += Pn) {
         const int Pc = static_cast<int>(std::min<int64_t>(Pn, total - p0));
-        const unsigned first_pair = static_cast<unsigned>(p0);
-        GENPHI_HIP_TRY(hipEventRecord(ev.e[0], h->stream));
-        ident_init_kernel<<<static_cast<unsigned>((pl.n_labels * Pc + 255) / 256), 256, 0, h->stream>>>(h->d_const_side.get(), pl.n_labels, rows, Pn, Pc, B);
-        GENPHI_HIP_TRY(hipGetLastError());
-        for (int k = 1; k < pl.n_levels; ++k) {
-            const long long b = pl.level_begin[k];
-            const int n_rows = static_cast<int>(pl.level_rows[k]);
-            const unsigned grid = static_cast<unsigned>((n_rows + step_rows - 1) / step_rows);
-            GENPHI_LPR_SWITCH(lpr, (ident_step_kernel<LPR><<<grid, 256, 0, h->stream>>>(h->d_fa.get() + b, h->d_mo.get() + b, h->d_ids.get() + b, n_rows, b, rows,
-                                                                                     Pn, Pc, B, first_pair, k0, k1)));
-            GENPHI_HIP_TRY(hipGetLastError());
-        }
-        GENPHI_HIP_TRY(hipEventRecord(ev.e[1], h->stream));
+        if (int rc = timer.begin(h->stream)) return rc;
+        if (int rc = label_sweep_panel(h, Pc, static_cast<unsigned>(p0))) return rc;
+        if (int rc = timer.middle(h->stream)) return rc;
         for (int64_t c0 = 0; c0 < ch.chunks; c0 += 65535) {          // (a grid's y extent)
             const dim3 grid(static_cast<unsigned>(2 * Pc), static_cast<unsigned>(std::min<int64_t>(65535, ch.chunks - c0)));
-            if (h->test_first)
-                retain_mark_kernel<true><<<grid, genphi::RETAIN_THREADS, ch.lds_bytes, h->stream>>>(
-                    rows, h->d_pro_row.get(), h->d_const_side.get(), n_pro, pl.n_labels, Pn, B, p0, h->S, c0, static_cast<int>(ch.chunk_labels), ch.stride,
-                    h->d_survived.get(), h->d_both.get(), h->d_distinct.get());
-            else
-                retain_mark_kernel<false><<<grid, genphi::RETAIN_THREADS, ch.lds_bytes, h->stream>>>(
-                    rows, h->d_pro_row.get(), h->d_const_side.get(), n_pro, pl.n_labels, Pn, B, p0, h->S, c0, static_cast<int>(ch.chunk_labels), ch.stride,
-                    h->d_survived.get(), h->d_both.get(), h->d_distinct.get());
+            mark<<<grid, genphi::RETAIN_THREADS, ch.lds_bytes, h->stream>>>(rows, h->d_pro_row.get(), h->d_const_side.get(), n_pro, pl.n_labels, Pn, B, p0, h->S, c0,
+                                                                           static_cast<int>(ch.chunk_labels), ch.stride, h->d_survived.get(), h->d_both.get(),
+                                                                           h->d_distinct.get());
             GENPHI_HIP_TRY(hipGetLastError());
             ++launches;
         }
-        GENPHI_HIP_TRY(hipEventRecord(ev.e[2], h->stream));
-        GENPHI_HIP_TRY(hipEventSynchronize(ev.e[2]));
-        float a = 0.f, b = 0.f;
-        GENPHI_HIP_TRY(hipEventElapsedTime(&a, ev.e[0], ev.e[1]));
-        GENPHI_HIP_TRY(hipEventElapsedTime(&b, ev.e[1], ev.e[2]));
-        sweep_ms += a;
-        mark_ms += b;
+        if (int rc = timer.end(h->stream)) return rc;
+        if (int rc = timer.add(sweep_ms, mark_ms)) return rc;
         launches += pl.n_levels;
     }
     GENPHI_HIP_TRY(hipStreamSynchronize(h->stream));
@@ -247,13 +198,6 @@ int compute_impl(genphi_retain *h, int32_t device)
     h->n_launches = launches;
     h->computed = true;
     return GENPHI_OK;
-}
-
-int to_host(genphi_retain *h, int32_t *out, const DevBuf<int> genphi_retain::*buf, const char *fn)
-{
-    if (!h || !h->computed) return genphi_set_error(GENPHI_ERR_ARG, std::string(fn) + ": nothing computed");
-    if (!out) return genphi_set_error(GENPHI_ERR_ARG, std::string(fn) + ": out is NULL");
-    return h->copy_out(out, (h->*buf).get(), (h->*buf).bytes(), "gen.simuRetention");
 }
 
 }  // namespace
@@ -281,38 +225,37 @@ int genphi_retain_create(int64_t n_ind, const int64_t *ind, const int64_t *fathe
         std::string err;
         if (const int rc = genphi::plan_ident(h->plan, n_ind, ind, father, mother, n_pro, pro_ids, err)) return genphi_set_error(rc, err);
         h->chunks = genphi::retain_chunks(h->plan.n_labels, chunk_labels);
-        h->pairs = static_cast<int32_t>(genphi::drop_panel_pairs(simul_no, panel_cols));      // (compute may narrow the default to what fits)
-        h->lanes_per_row = lanes_per_row(h->pairs);
-        h->n_panels = (h->total_pairs() + h->pairs - 1) / h->pairs;
+        h->panels.set(simul_no, genphi::drop_panel_pairs(simul_no, panel_cols));                // (compute may narrow the default to what fits)
         return GENPHI_OK;
     });
 }
 
 int genphi_retain_levels(const genphi_retain *h, int64_t *n_live, int32_t *levels, int64_t *rows_per_level)
 {
-    if (!h) return genphi_set_error(GENPHI_ERR_ARG, "genphi_retain_levels: NULL handle");
-    put(n_live, h->plan.n_live);
-    put(levels, h->plan.n_levels);
-    if (rows_per_level)
-        for (int k = 0; k < h->plan.n_levels; ++k) rows_per_level[k] = h->plan.level_rows[k];
-    return GENPHI_OK;
+    return drop_levels(h, "genphi_retain_levels", n_live, levels, rows_per_level);
 }
 
 int genphi_retain_alleles(const genphi_retain *h, int64_t *n_labels, int32_t *planes, int64_t *ids, int32_t *sides)
 {
-    if (!h) return genphi_set_error(GENPHI_ERR_ARG, "genphi_retain_alleles: NULL handle");
-    put(n_labels, h->plan.n_labels);
-    put(planes, h->plan.planes);
-    if (ids) std::copy(h->plan.allele_id.begin(), h->plan.allele_id.end(), ids);
-    if (sides) std::copy(h->plan.allele_side.begin(), h->plan.allele_side.end(), sides);
-    return GENPHI_OK;
+    return label_alleles(h, "genphi_retain_alleles", n_labels, planes, ids, sides);
 }
 
 int genphi_retain_compute(genphi_retain *h, int32_t device) { return compute_entry(h, device, "genphi_retain_compute", "gen.simuRetention", compute_impl); }
 
-int genphi_retain_survived_to_host(genphi_retain *h, int32_t *out) { return to_host(h, out, &genphi_retain::d_survived, "genphi_retain_survived_to_host"); }
-int genphi_retain_both_to_host(genphi_retain *h, int32_t *out) { return to_host(h, out, &genphi_retain::d_both, "genphi_retain_both_to_host"); }
-int genphi_retain_distinct_to_host(genphi_retain *h, int32_t *out) { return to_host(h, out, &genphi_retain::d_distinct, "genphi_retain_distinct_to_host"); }
+int genphi_retain_survived_to_host(genphi_retain *h, int32_t *out)
+{
+    return result_to_host(h, out, &genphi_retain::d_survived, "genphi_retain_survived_to_host", "gen.simuRetention");
+}
+
+int genphi_retain_both_to_host(genphi_retain *h, int32_t *out)
+{
+    return result_to_host(h, out, &genphi_retain::d_both, "genphi_retain_both_to_host", "gen.simuRetention");
+}
+
+int genphi_retain_distinct_to_host(genphi_retain *h, int32_t *out)
+{
+    return result_to_host(h, out, &genphi_retain::d_distinct, "genphi_retain_distinct_to_host", "gen.simuRetention");
+}
 
 int genphi_retain_stats(const genphi_retain *h, double *sweep_ms, double *mark_ms, double *algorithmic_bytes, double *mark_bytes, int32_t *levels,
                         int32_t *panel_cols, int64_t *panels, int32_t *planes, int32_t *chunk_labels, int64_t *chunks, int32_t *lds_bytes,
@@ -323,13 +266,13 @@ int genphi_retain_stats(const genphi_retain *h, double *sweep_ms, double *mark_m
     put(mark_ms, h->mark_ms);
     put(mark_bytes, h->mark_bytes);
     put(levels, h->plan.n_levels);
-    put(panel_cols, 128 * h->pairs);
-    put(panels, h->n_panels);
+    put(panel_cols, 128 * h->panels.pairs);
+    put(panels, h->panels.n_panels);
     put(planes, h->plan.planes);
     put(chunk_labels, h->chunks.chunk_labels);
     put(chunks, h->chunks.chunks);
     put(lds_bytes, h->chunks.lds_bytes);
-    put(lanes_per_row, h->lanes_per_row);
+    put(lanes_per_row, h->panels.lanes_per_row);
     return GENPHI_OK;
 }
 

@@ -24,8 +24,8 @@
 #include <hip/hip_runtime.h>
 
 #include "drop_device.h"
+#include "drop_host.h"
 #include "simu.h"
-#include "sweep_device.h"
 
 namespace {
 
@@ -224,11 +224,9 @@ struct genphi_simu : SweepDevice {           // d_slots: the rows of one panel (
     DevBuf<int> d_state_pro;                 // n_pro, the states of the last match_counts
     DevBuf<int> d_fa, d_mo, d_state0, d_pro_row;
     DevBuf<long long> d_ids;
-    int32_t pairs = 0, lanes_per_row = 0;    // pairs of a panel row
-    int64_t n_panels = 0;
+    DropPanels panels;
     genphi_simu() { own(d_counts, d_sample, d_match, d_state_pro, d_fa, d_mo, d_state0, d_pro_row, d_ids); }
     bool empty() const { return false; }     // (n_pro >= 1 and S >= 1 always)
-    int64_t total_pairs() const { return (S + 127) / 128; }
     size_t sample_bytes() const { return no_sample ? 0 : static_cast<size_t>(plan.n_pro) * static_cast<size_t>(S); }
 };
 
@@ -259,9 +257,7 @@ int prepare(genphi_simu *h, int32_t device)
     if ((rc = h->upload(h->d_fa, pl.fa_row)) || (rc = h->upload(h->d_mo, pl.mo_row)) || (rc = h->upload(h->d_state0, pl.state0)) ||
         (rc = h->upload(h->d_pro_row, pl.pro_row)) || (rc = h->upload(h->d_ids, pl.row_id)))
         return rc;
-    h->pairs = static_cast<int32_t>(Pn);
-    h->lanes_per_row = lanes_per_row(static_cast<int>(Pn));
-    h->n_panels = (h->total_pairs() + Pn - 1) / Pn;
+    h->panels.set(h->S, Pn);
     return GENPHI_OK;
 }
 
@@ -270,8 +266,8 @@ int prepare(genphi_simu *h, int32_t device)
 int run_panels(genphi_simu *h, bool sweep, bool results, bool match)
 {
     const genphi::SimuPlan &pl = h->plan;
-    const int Pn = h->pairs, lpr = h->lanes_per_row;
-    const int64_t total = h->total_pairs();
+    const int Pn = h->panels.pairs, lpr = h->panels.lanes_per_row;
+    const int64_t total = h->panels.total;
     const unsigned k0 = static_cast<unsigned>(h->seed), k1 = static_cast<unsigned>(h->seed >> 32);
     ulonglong2 *rows = h->slots<ulonglong2>();
     const int step_rows = 4 * (64 / lpr);
@@ -324,8 +320,8 @@ int compute_impl(genphi_simu *h, int32_t device)
     if (int rc = run_panels(h, true, true, false)) return rc;
     // per non-initial live row: two parent rows read and one written, 32 bytes per pair, over the panels
     const int64_t stepped = pl.n_live - (pl.n_levels ? pl.level_rows[0] : 0);
-    run.bytes = 3.0 * 32.0 * static_cast<double>(stepped) * static_cast<double>(h->total_pairs());
-    run.launches = h->n_panels * (pl.n_levels + 1 + (h->no_sample ? 0 : 1));
+    run.bytes = 3.0 * 32.0 * static_cast<double>(stepped) * static_cast<double>(h->panels.total);
+    run.launches = h->panels.n_panels * (pl.n_levels + 1 + (h->no_sample ? 0 : 1));
     return run.end(*h);
 }
 
@@ -359,12 +355,7 @@ int genphi_simu_create(int64_t n_ind, const int64_t *ind, const int64_t *father,
 
 int genphi_simu_levels(const genphi_simu *h, int64_t *n_live, int32_t *levels, int64_t *rows_per_level)
 {
-    if (!h) return genphi_set_error(GENPHI_ERR_ARG, "genphi_simu_levels: NULL handle");
-    put(n_live, h->plan.n_live);
-    put(levels, h->plan.n_levels);
-    if (rows_per_level)
-        for (int k = 0; k < h->plan.n_levels; ++k) rows_per_level[k] = h->plan.level_rows[k];
-    return GENPHI_OK;
+    return drop_levels(h, "genphi_simu_levels", n_live, levels, rows_per_level);
 }
 
 int genphi_simu_rows(const genphi_simu *h, int64_t *row_ids, int32_t *father_rows, int32_t *mother_rows, int64_t *pro_positions)
@@ -382,17 +373,14 @@ int genphi_simu_compute(genphi_simu *h, int32_t device) { return compute_entry(h
 
 int genphi_simu_sample_to_host(genphi_simu *h, int8_t *out)
 {
-    if (!h || !h->computed) return genphi_set_error(GENPHI_ERR_ARG, "genphi_simu_sample_to_host: nothing computed");
-    if (h->no_sample) return genphi_set_error(GENPHI_ERR_ARG, "genphi_simu_sample_to_host: the handle was created with GENPHI_SIMU_FLAG_NO_SAMPLE");
-    if (!out) return genphi_set_error(GENPHI_ERR_ARG, "genphi_simu_sample_to_host: out is NULL");
-    return h->copy_out(out, h->d_sample, h->d_sample.bytes(), "gen.simu");
+    if (h && h->computed && h->no_sample)    // (nothing computed comes first)
+        return genphi_set_error(GENPHI_ERR_ARG, "genphi_simu_sample_to_host: the handle was created with GENPHI_SIMU_FLAG_NO_SAMPLE");
+    return result_to_host(h, out, &genphi_simu::d_sample, "genphi_simu_sample_to_host", "gen.simu");
 }
 
 int genphi_simu_state_counts(genphi_simu *h, int64_t *out)
 {
-    if (!h || !h->computed) return genphi_set_error(GENPHI_ERR_ARG, "genphi_simu_state_counts: nothing computed");
-    if (!out) return genphi_set_error(GENPHI_ERR_ARG, "genphi_simu_state_counts: out is NULL");
-    return h->copy_out(out, h->d_counts, h->d_counts.bytes(), "gen.simu");
+    return result_to_host(h, out, &genphi_simu::d_counts, "genphi_simu_state_counts", "gen.simu");
 }
 
 int genphi_simu_match_counts(genphi_simu *h, const int32_t *state_pro, int32_t *out)
@@ -408,7 +396,7 @@ int genphi_simu_match_counts(genphi_simu *h, const int32_t *state_pro, int32_t *
         if (e != hipSuccess) return e;
         e = hipMemsetAsync(h->d_match, 0, h->d_match.bytes(), h->stream);
         if (e != hipSuccess) return e;
-        rc = run_panels(h, h->n_panels > 1, false, true);            // one panel: its rows are resident
+        rc = run_panels(h, h->panels.n_panels > 1, false, true);            // one panel: its rows are resident
         if (rc) return hipSuccess;
         e = hipMemcpyAsync(out, h->d_match, h->d_match.bytes(), hipMemcpyDeviceToHost, h->stream);
         return e == hipSuccess ? hipStreamSynchronize(h->stream) : e;
@@ -422,9 +410,9 @@ int genphi_simu_stats(const genphi_simu *h, double *sweep_ms, double *algorithmi
     if (!h) return genphi_set_error(GENPHI_ERR_ARG, "genphi_simu_stats: NULL handle");
     h->stats(sweep_ms, algorithmic_bytes, nullptr);
     put(levels, h->plan.n_levels);
-    put(panel_cols, 128 * h->pairs);
-    put(panels, h->n_panels);
-    put(lanes_per_row, h->lanes_per_row);
+    put(panel_cols, 128 * h->panels.pairs);
+    put(panels, h->panels.n_panels);
+    put(lanes_per_row, h->panels.lanes_per_row);
     put(n_live, h->plan.n_live);
     return GENPHI_OK;
 }

@@ -1,7 +1,8 @@
 // sweep_device.h -- the device side of a sweep handle that the ten sweep files (gc, occ, dist, depth, completeness, implex, simu, ident, link, retain) share:
 // everything around the kernels that does not depend on the arithmetic.  A sweep's file keeps its kernels, its handle's own
 // fields, its PanelRule, the allocation and pre-fill of its result, its launch callable, its extra passes and its extern "C"
-// functions.  Host functions only; every including file gets its own copy (anonymous namespace).
+// functions.  The four gene-dropping sweeps share more on top of this: drop_host.h, and the three label sweeps
+// label_sweep.h.  Host functions only; every including file gets its own copy (anonymous namespace).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -75,7 +76,7 @@ struct DeviceGuard {
 using genphi::DevBuf;
 
 // What every sweep handle holds on a device.  Its device blocks are DevBufs (devbuf.h): d_slots here and the handle's own members,
-// which it registers once (own).  release() gives them all back on the handle's device, held_bytes() sums them.
+// which it registers (own).  release() gives them all back on the handle's device, held_bytes() sums them.
 // A handle is deleted only by destroy_entry, after release(), or by create_entry before anything is allocated: the destructor of a
 // DevBuf never has a block left to free, so it never frees under a current device that is not the block's.
 struct SweepDevice {
@@ -93,10 +94,13 @@ struct SweepDevice {
     SweepDevice(const SweepDevice &) = delete;
     SweepDevice &operator=(const SweepDevice &) = delete;
 
+    // Called from the handle's constructor, and from that of a base handle that has blocks of its own (label_sweep.h): a call is bounded
+    // when it is compiled, the calls together when the first handle of the type is created.
     template <typename... T>
     void own(DevBuf<T> &...bufs)
     {
-        static_assert(sizeof...(T) < kMaxBlocks, "more blocks than the list holds");      // (called once, from the handle's constructor)
+        static_assert(sizeof...(T) < kMaxBlocks, "more blocks than the list holds");
+        if (n_blocks + static_cast<int>(sizeof...(T)) > kMaxBlocks) std::abort();
         ((blocks[n_blocks++] = &bufs), ...);
     }
 

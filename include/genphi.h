@@ -1038,7 +1038,7 @@ int genphi_simu_stats(const genphi_simu *h, double *sweep_ms, double *algorithmi
                       int64_t *panels, int32_t *lanes_per_row, int64_t *n_live);
 void genphi_simu_destroy(genphi_simu *h);
 
-/* ---- gen.simuIdentity: identity coefficients by gene dropping (csrc/ident.hip, csrc/ident.cpp) ------------------------------------
+/* ---- gen.simuIdentity: identity coefficients by gene dropping (csrc/ident.hip, csrc/ident.cpp, csrc/label_sweep.h) ---------------
  * Jacquard's nine condensed identity states of every pair of probands, counted over S simulations in which every founder allele
  * is dropped down the pedigree under its own label.  The reference has no form of it, so this text is the definition.
  * Inputs.  A pedigree.  pro_ids, the listed probands: any individuals, at least one; repeats are allowed and give repeated rows
@@ -1108,7 +1108,7 @@ int genphi_ident_stats(const genphi_ident *h, double *sweep_ms, double *pair_ms,
                        int32_t *lanes_per_row);
 void genphi_ident_destroy(genphi_ident *h);
 
-/* ---- gen.simuRetention: founder allele survival by gene dropping (csrc/retain.hip, csrc/retain.h) -----------------------------------
+/* ---- gen.simuRetention: founder allele survival by gene dropping (csrc/retain.hip, csrc/retain.h, csrc/label_sweep.h) --------------
  * The question gene dropping was made for (MacCluer et al. 1986): which founder alleles are still present in the listed probands,
  * and how many.  Retention has no closed form on a general pedigree and does not follow from the kinship matrix or from the pair
  * counts of gen.simuIdentity.  The reference has no form of it, so this text is the definition, and it is this package's own.
@@ -1173,7 +1173,7 @@ int genphi_retain_stats(const genphi_retain *h, double *sweep_ms, double *mark_m
                         int64_t *chunks, int32_t *lds_bytes, int32_t *lanes_per_row);
 void genphi_retain_destroy(genphi_retain *h);
 
-/* ---- gen.simuSharing: linked-locus gene dropping and IBD segments (csrc/link.hip, csrc/link.cpp) ------------------------------------
+/* ---- gen.simuSharing: linked-locus gene dropping and IBD segments (csrc/link.hip, csrc/link.cpp, csrc/label_sweep.h) ---------------
  * gen.simuIdentity above drops every founder allele at ONE locus.  Here a simulation is a chromosome of L linked loci: a meiosis
  * copies a mosaic of the parent's two chromosomes, and the sharing of a pair of probands is read off locus by locus: how much of the
  * chromosome they share identical by descent (IBD) in one realisation, how much that varies, and in how many segments it comes.
