@@ -27,6 +27,7 @@ meaning, printed lines and error behaviour as the reference:
     gen.simuIdentity(ped)                  # Jacquard's nine identity coefficients of every pair by gene dropping (csrc/ident.hip)
     gen.simuRetention(ped)                 # founder allele survival, founder genome equivalents by gene dropping (csrc/retain.hip)
     gen.simuSharing(ped, loci=1024)        # linked loci: realised IBD sharing, its variance and the segments (csrc/link.hip)
+    gen.simuSegments(ped, loci=1024)       # the lengths of those segments: histogram, within and between groups, per pair
     gen.descendant(ped, 1); gen.children(ped, 1)   # src/identify.jl:203-215, :77-80 (csrc/loader.cpp)
     gen.phiHist(ped); gen.phiQuantile(ped, 0.5)    # the distribution of the pairwise kinships, on the device (csrc/hist.hip)
     gen.phiClusters(ped, 1/16); gen.phiUnrelated(ped, 1/16)   # families and a maximal unrelated set at a kinship cutoff (csrc/clusters.hip)
@@ -960,6 +961,127 @@ def simuSharing(pedigree, pro=None, loci=1024, length=1.0, probRecomb=None, simu
     try:
         h.compute(device=device)
         return SimuSharing(probands, h.sums_to_host(), h.loci, h.q, h.simul_no, h.seed, h.alleles(), h.labels_to_host() if labels else None)
+    finally:
+        h.close()
+
+
+class SimuSegments:
+    """What gen.simuSegments returns.  pro: the listed probands; edges: int32, the bin edges in loci (a segment of len loci is in
+    bin b when edges[b] <= len < edges[b + 1]); minLoci; counts, loci_in, censored: int64 (n_bins,), or (G, G, n_bins) and symmetric
+    with groups -- the segments of every bin over the pairs i < j of list positions and all simulations, the loci in them, and those
+    of them that the end of the chromosome cut short (they hold locus 0 or the last locus); below, above: the same three integers
+    (segments, loci, censored) for the lengths under edges[0] and at or above edges[-1], int64 (3,) or (G, G, 3); names (sorted) and
+    sizes (list positions per group) with groups, else None; pairs: int64 (N, N, 3), per pair the sums over the simulations of the
+    segments of at least minLoci loci, of the loci in them, and of the longest segment; sharing: the SimuSharing of the same run.
+    Every property is formed once from the exact integers, in Float64."""
+
+    def __init__(self, pro, edges, minLoci, hist, pairs, sharing, names=None, sizes=None):
+        self.pro, self.edges, self.minLoci, self.pairs, self.sharing, self.names, self.sizes = pro, edges, minLoci, pairs, sharing, names, sizes
+        table = hist if names is not None else hist[0, 0]
+        self.counts = np.ascontiguousarray(table[..., 1:-1, 0])
+        self.loci_in = np.ascontiguousarray(table[..., 1:-1, 1])
+        self.censored = np.ascontiguousarray(table[..., 1:-1, 2])
+        self.below = np.ascontiguousarray(table[..., 0, :])
+        self.above = np.ascontiguousarray(table[..., -1, :])
+
+    def __repr__(self):
+        upper = np.triu(np.ones(self.counts.shape[:2], dtype=bool)) if self.names is not None else None
+        total = int(self.counts.sum() + self.below[..., 0].sum() + self.above[..., 0].sum()) if upper is None else int(
+            self.counts[upper].sum() + self.below[upper][:, 0].sum() + self.above[upper][:, 0].sum())
+        return "SimuSegments(%d probands, loci=%d, simulNo=%d, %d bins over [%d, %d), %d segments%s)" % (
+            len(self.pro), self.sharing.loci, self.sharing.simulNo, len(self.edges) - 1, self.edges[0], self.edges[-1], total,
+            "" if self.names is None else ", %d groups" % len(self.names))
+
+    @property
+    def mean_length(self):
+        """Per bin: the mean length in loci of its segments, loci_in / counts; NaN where the bin is empty."""
+        out = np.full(self.counts.shape, np.nan)
+        np.divide(self.loci_in, self.counts, out=out, where=self.counts > 0)
+        return out
+
+    @property
+    def segments_over(self):
+        """(N, N): the mean number per simulation of the pair's segments of at least minLoci loci."""
+        return self.pairs[..., 0] / float(self.sharing.simulNo)
+
+    @property
+    def loci_over(self):
+        """(N, N): the mean number per simulation of the pair's loci in segments of at least minLoci loci."""
+        return self.pairs[..., 1] / float(self.sharing.simulNo)
+
+    @property
+    def longest(self):
+        """(N, N): the mean over the simulations of the pair's longest segment in loci (0 in a simulation without sharing)."""
+        return self.pairs[..., 2] / float(self.sharing.simulNo)
+
+    @property
+    def locus_cM(self):
+        """The genetic length of the interval between neighbouring loci in centimorgans, -50 ln(1 - 2 q / 65536): Haldane's map
+        read backwards from the recombination probability actually used; infinite for independent loci (q = 32768)."""
+        with np.errstate(divide="ignore"):
+            return float(-50.0 * np.log(np.float64(1.0 - 2.0 * self.sharing.q / 65536.0)))
+
+
+def _segment_edges(bins, loci):
+    if bins is None:
+        top = 1
+        while top <= loci:
+            top *= 2
+        edges = [1]
+        while edges[-1] < top:
+            edges.append(edges[-1] * 2)                  # 1, 2, 4, .. up to and including the first power of two above loci
+        edges[-1] = min(edges[-1], _capi.GENPHI_SEG_MAX_EDGE)     # loci = 4096: 8192 is no edge; the last bin is [4096, 4097)
+        return np.array(edges, dtype=np.int32)
+    return _capi._i32_list(bins, "bins")
+
+
+def simuSegments(pedigree, pro=None, loci=1024, length=1.0, probRecomb=None, simulNo=1000, seed=None, bins=None, minLoci=1, groups=None,
+                 device=None):
+    """gen.simuSegments(pedigree, pro = pro(pedigree), loci = 1024, length = 1.0, simulNo = 1000): the length spectrum of the
+    segments that pairs of probands share identical by descent, by gen.simuSharing's gene dropping along a chromosome of `loci`
+    linked loci.  A segment is a maximal run of consecutive loci at which the pair shares an allele (what SimuSharing.segments
+    counts); its length is a number of loci, locus_cM centimorgans each.  Returns a SimuSegments: the histogram of the lengths over
+    all pairs i < j and all simulations (counts, loci_in, censored per bin, below and above), with `groups` within and between
+    sub-populations, and per pair the segments of at least minLoci loci (segments_over, loci_over) and the longest (longest).
+    Neither GENLIB nor the reference has this function.
+
+    pedigree, pro, loci, length, probRecomb, simulNo and seed are gen.simuSharing's, and .sharing is the SimuSharing of the same
+    run.  bins: None = the edges 1, 2, 4, .. up to and including the first power of two above loci (at loci = 4096 that would be
+    8192, past the largest edge: the list ends 2048, 4096, 4097, so the last bin holds the whole chromosome and `above` stays
+    empty, as for every other loci); or the edges themselves, 2 ..
+    257 strictly increasing integers in 1 .. 4097.  minLoci: 1 .. 4097.  groups: a mapping ID -> group name, as gen._pop returns
+    and gen.phiHist takes; probands that are not in it take part in no count of the histogram (they keep their per-pair sums); at
+    most 32 groups and G (G + 1) / 2 x (bins + 2) <= 2,048.  The result is integers added by integer additions: a pure function of
+    the pedigree's relations, the probands, loci, q, the seed, simulNo, the edges, minLoci and the groups.  The sweep, the pair sums
+    and the segment walk run on the GPU (csrc/link.hip).
+
+    KeyError and ValueError as gen.simuSharing; ValueError for edges, minLoci or groups outside the limits."""
+    probands = globals()["pro"](pedigree) if pro is None else np.ascontiguousarray(pro, dtype=np.int64)
+    if not 1 <= int(loci) <= _capi.GENPHI_LINK_MAX_LOCI:
+        raise ValueError("gen.simuSegments: loci = %r is outside 1 .. 4096" % (loci,))
+    q = sharing_q(loci, length, probRecomb)
+    edges = _segment_edges(bins, int(loci))
+    names = labels = sizes = None
+    if groups is not None:
+        if len(groups) == 0:
+            raise ValueError("groups is empty")
+        names = sorted(set(groups.values()))
+        index = {name: k for k, name in enumerate(names)}
+        labels = np.array([index[groups[i]] if i in groups else -1 for i in probands.tolist()], dtype=np.int32)
+        if len(names) > _capi.GENPHI_SEG_MAX_GROUPS:
+            raise ValueError("gen.simuSegments: %d groups: at most %d" % (len(names), _capi.GENPHI_SEG_MAX_GROUPS))
+        sizes = np.bincount(labels[labels >= 0], minlength=len(names)).astype(np.int64)
+    h = SharingPlan(pedigree.ind, pedigree.father, pedigree.mother, probands, loci=loci, q=q, simul_no=simulNo, seed=seed)
+    try:
+        h.request_segments(edges, min_loci=minLoci, groups=labels)
+        h.compute(device=device)
+        hist, pairs = h.segments_to_host()
+        if names is not None and hist.shape[0] < len(names):                              # the last names have no listed proband
+            full = np.zeros((len(names), len(names)) + hist.shape[2:], dtype=np.int64)
+            full[:hist.shape[0], :hist.shape[0]] = hist
+            hist = full
+        sharing = SimuSharing(probands, h.sums_to_host(), h.loci, h.q, h.simul_no, h.seed, h.alleles(), None)
+        return SimuSegments(probands, edges, int(minLoci), hist, pairs, sharing, names, sizes)
     finally:
         h.close()
 

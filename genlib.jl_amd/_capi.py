@@ -85,6 +85,7 @@ EXPORTED_SYMBOLS = [
     "genphi_retain_both_to_host", "genphi_retain_distinct_to_host", "genphi_retain_stats", "genphi_retain_destroy",
     "genphi_link_create", "genphi_link_levels", "genphi_link_alleles", "genphi_link_compute", "genphi_link_sums_to_host",
     "genphi_link_labels_to_host", "genphi_link_stats", "genphi_link_destroy", "genphi_link_words",
+    "genphi_seg_request", "genphi_seg_to_host", "genphi_seg_stats", "genphi_seg_host",
 ]
 
 _lib = None
@@ -404,6 +405,14 @@ def lib():
         L.genphi_link_destroy.restype = None
         L.genphi_link_words.argtypes = [C.c_uint64, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.genphi_link_words.restype = C.c_int
+        L.genphi_seg_request.argtypes = [C.c_void_p, C.c_int32, _I32P, C.c_int32, C.c_int32, _I32P]
+        L.genphi_seg_request.restype = C.c_int
+        L.genphi_seg_to_host.argtypes = [C.c_void_p, _I64P, _I64P]
+        L.genphi_seg_to_host.restype = C.c_int
+        L.genphi_seg_stats.argtypes = [C.c_void_p, _F64P, _F64P, _I64P, _I32P, _I64P]
+        L.genphi_seg_stats.restype = C.c_int
+        L.genphi_seg_host.argtypes = [C.c_int32, C.POINTER(C.c_uint64), C.c_int32, _I32P, C.c_int32, _I64P, _I64P]
+        L.genphi_seg_host.restype = C.c_int
         L.genphi_descendants.argtypes = [C.c_int64, _I64P, _I64P, _I64P, C.c_int64, _I64P, _I64P, C.POINTER(_I64P)]
         L.genphi_descendants.restype = C.c_int
         L.genphi_children.argtypes = [C.c_int64, _I64P, _I64P, _I64P, C.c_int64, _I64P, C.POINTER(_I64P)]
@@ -1756,6 +1765,18 @@ GENPHI_LINK_FLAG_LABELS = 1
 GENPHI_LINK_FLAG_ALL_PAIRS = 2
 GENPHI_LINK_MAX_LOCI = 4096
 GENPHI_LINK_MAX_Q = 32768
+GENPHI_SEG_MAX_EDGES = 257
+GENPHI_SEG_MAX_EDGE = 4097
+GENPHI_SEG_MAX_GROUPS = 32
+GENPHI_SEG_MAX_CELLS = 2048
+
+
+def _i32_list(values, what):
+    """A contiguous int32 vector of integers that fit, or ValueError."""
+    a = np.asarray(values)
+    if a.ndim != 1 or (a.size and not np.issubdtype(a.dtype, np.integer)) or (a.size and (a.min() < -2**31 or a.max() >= 2**31)):
+        raise ValueError("gen.simuSegments: %s must be a vector of 32-bit integers" % what)
+    return np.ascontiguousarray(a, dtype=np.int32)
 
 
 class SharingPlan(_LabelPlan):
@@ -1801,6 +1822,80 @@ class SharingPlan(_LabelPlan):
         return self._stats(sweep_ms=C.c_double, pair_ms=C.c_double, algorithmic_bytes=C.c_double, word_ops=C.c_double, philox_blocks=C.c_double,
                            levels=C.c_int32, panel_sims=C.c_int32, panels=C.c_int64, planes=C.c_int32, tile_rows=C.c_int32, tile_cols=C.c_int32,
                            lanes_per_sim=C.c_int32)
+
+    def request_segments(self, edges, min_loci=1, groups=None):
+        """Ask the next compute() for the lengths of the shared segments too (include/genphi.h, genphi_seg_*).  edges: 2 .. 257
+        strictly increasing integers in 1 .. 4097; a segment of len loci is in bin b when edges[b] <= len < edges[b + 1].  min_loci
+        (1 .. 4097): the per-pair sums count the segments of at least that many loci.  groups: None, or a label per list position,
+        0 .. max, or -1 for "counts nowhere"; the number of groups is max + 1, at most 32, and groups (groups + 1) / 2 x
+        (bins + 2) is at most 2,048.  edges=None withdraws the request.  ValueError names the offending value; the handle, an
+        earlier request and earlier results stay as they were."""
+        i32 = C.POINTER(C.c_int32)
+        if edges is None:
+            self._call_seg("request", 0, None, 1, 0, None)
+            self._seg_shape = None
+            return
+        edges = _i32_list(edges, "edges")
+        if len(edges) == 0:                              # (the C call reads 0 edges as a withdrawal; here that is edges=None)
+            raise ValueError("gen.simuSegments: 0 edges: need 2 .. 257 (edges=None withdraws the request)")
+        n_groups, labels = 0, None
+        if groups is not None:
+            labels = _i32_list(groups, "groups")
+            if len(labels) != self.n_pro:
+                raise ValueError("gen.simuSegments: %d labels for %d probands" % (len(labels), self.n_pro))
+            n_groups = max(int(labels.max(initial=-1)) + 1, 1)
+        if not -2**31 <= int(min_loci) < 2**31:
+            raise ValueError("gen.simuSegments: min_loci = %d is outside 1 .. 4097" % min_loci)
+        self._call_seg("request", len(edges), edges.ctypes.data_as(i32), int(min_loci), n_groups, None if labels is None else labels.ctypes.data_as(i32))
+        self._seg_shape = (max(n_groups, 1), len(edges) + 1)
+
+    def compute(self, device=None):
+        super().compute(device)
+        self._seg_ran = self._seg_shape
+
+    _seg_shape = _seg_ran = None                 # (groups, columns) of the request standing / answered by the last compute
+
+    def segments_to_host(self):
+        """(hist, pairs) of the last compute(): int64 (G, G, n_bins + 2, 3), G = max(groups, 1) -- segments, loci and censored
+        segments of `below`, the bins and `above`, over the pairs i < j -- and int64 (n_pro, n_pro, 3): the sums over the simulations
+        of the segments of at least min_loci loci, the loci in them, and the longest segment.  ValueError unless that compute ran with
+        a request."""
+        if self._seg_ran is None:
+            self._call_seg("to_host", None, None)                                         # raises: nothing computed, or no request
+            raise ValueError("gen.simuSegments: the last compute ran without a request")
+        G, columns = self._seg_ran
+        hist = np.zeros((G, G, columns, 3), dtype=np.int64)
+        pairs = np.zeros((self.n_pro, self.n_pro, 3), dtype=np.int64)
+        self._call_seg("to_host", hist.ctypes.data_as(_I64P), pairs.ctypes.data_as(_I64P))
+        return hist, pairs
+
+    def _call_seg(self, name, *args):
+        rc = getattr(lib(), "genphi_seg_" + name)(self._h, *args)
+        if rc:
+            _raise(rc)
+
+    def segment_stats(self):
+        """dict(segment_ms, word_ops, segments, cells, lds_bytes) of the last compute(); zeros when it ran without a request."""
+        fields = dict(segment_ms=C.c_double, word_ops=C.c_double, segments=C.c_int64, cells=C.c_int32, lds_bytes=C.c_int64)
+        vals = [t() for t in fields.values()]
+        self._call_seg("stats", *[C.byref(v) for v in vals])
+        return {k: v.value for k, v in zip(fields, vals)}
+
+
+def seg_host(loci, any_words, edges, min_loci=1):
+    """(hist, pair) of one pair in one simulation whose `any` is given as ceil(loci / 64) uint64 words: int64 (n_bins + 2, 3) --
+    segments, loci, censored segments in `below`, the bins and `above` -- and int64 (3,): the segments of at least min_loci loci, the
+    loci in them, the longest segment.  genphi_seg_host, host only -- the walk that the segment kernel of gen.simuSegments runs."""
+    words = np.ascontiguousarray(any_words, dtype=np.uint64).ravel()
+    if len(words) != (max(int(loci), 1) + 63) // 64:
+        raise ValueError("gen.simuSegments: %d words for %d loci" % (len(words), loci))
+    edges = _i32_list(edges, "edges")
+    hist, pair = np.zeros((len(edges) + 1, 3), dtype=np.int64), np.zeros(3, dtype=np.int64)
+    rc = lib().genphi_seg_host(int(loci), words.ctypes.data_as(C.POINTER(C.c_uint64)), len(edges), edges.ctypes.data_as(C.POINTER(C.c_int32)),
+                               int(min_loci), hist.ctypes.data_as(_I64P), pair.ctypes.data_as(_I64P))
+    if rc:
+        _raise(rc)
+    return hist, pair
 
 
 def link_words(seed, ID, side, s, loci, q):

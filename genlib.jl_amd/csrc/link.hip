@@ -24,11 +24,16 @@
 //           its sums to the mirrored pairs (all six are symmetric).  GENPHI_LINK_FLAG_ALL_PAIRS computes every tile instead.  A pair
 //           has one owner per panel and panels run one after the other on one stream: plain Int64 adds, no atomics
 //   labels  under GENPHI_LINK_FLAG_LABELS: a lane per locus of a word expands the planes of the listed probands into Int32
+//   segment under a request (genphi_seg_*, gen.simuSegments): after the pair kernel, on its tile and staging, the lengths of the runs of
+//           `any`: a state carried from word to word (link_segments.h), a table of 64-bit counters in LDS, Int64 per pair
 // Everything is integer and keyed on IDs and absolute simulation and word indices: the same bytes on every run, with any panel width.
 #include <hip/hip_runtime.h>
 
+#include <vector>
+
 #include "label_sweep.h"
 #include "link.h"
+#include "link_segments.h"
 
 namespace {
 
@@ -190,6 +195,135 @@ link_pair_kernel(const ulonglong2 *__restrict__ gathered, int n_pro, int B, int 
         }
 }
 
+// gen.simuSegments (include/genphi.h, genphi_seg_*): the lengths of the runs of `any`, on the tile, the staging and the ownership of
+// link_pair_kernel, over the tiles with tile row <= tile column always.  Dynamic LDS: the tile (2048 * B bytes), then the workgroup's
+// table (cells x 3 u64), then the edges.  Per word only the four inequality words, the masks and `any`; the walk (link_segments.h)
+// carries a pair's open run from word to word of a simulation.  A closed run goes to the pair's counts of the simulation and, for
+// i < j with both labels >= 0, to the table in LDS by 64-bit adds; the table goes to the global one once, its non-zero cells only, by
+// 64-bit integer atomics (integer sums: the same bytes in any order).  pairs[(i * n_pro + j) * 3 + k]: one owner per pair and panel.
+__global__ void __launch_bounds__(256)
+link_segment_kernel(const ulonglong2 *__restrict__ gathered, int n_pro, int B, int Sc, int Wp, int L, const int *__restrict__ edges_in, int n_edges,
+                    int min_loci, const int *__restrict__ group, int G, int cells, u64 *__restrict__ table_out, long long *__restrict__ pairs)
+{
+    extern __shared__ u64 tile[];
+    const int tr = blockIdx.y, tc = blockIdx.x;
+    if (tr > tc) return;
+    const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
+    const int B2 = 2 * B, W = (L + 63) >> 6;
+    u64 *table = tile + 2 * B2 * 64;
+    int *edges = reinterpret_cast<int *>(table + 3 * cells);
+    for (int e = t; e < 3 * cells; e += 256) table[e] = 0;
+    for (int e = t; e < n_edges; e += 256) edges[e] = edges_in[e];
+    int cell0[2][2];                                     // the pair's first cell of the table, -1: the pair counts in no cell
+    long long acc[2][2][3];
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const int i = tr * LINK_TILE + ty + 16 * r, j = tc * LINK_TILE + tx + 16 * k;
+            cell0[r][k] = -1;
+            if (i < j && j < n_pro) {
+                const int a = group[i], b = group[j];
+                if (a >= 0 && b >= 0) cell0[r][k] = genphi::seg_group_pair(a, b, G) * (n_edges + 1);
+            }
+#pragma unroll
+            for (int v = 0; v < 3; ++v) acc[r][k][v] = 0;
+        }
+    for (int s = 0; s < Sc; ++s) {
+        genphi::SegState st[2][2];
+        int over[2][2] = {{0, 0}, {0, 0}}, over_loci[2][2] = {{0, 0}, {0, 0}};
+        for (int p = 0; p < Wp; ++p) {
+            const long long col = static_cast<long long>(s) * Wp + p;
+            __syncthreads();                             // the previous pair of words has been read (first: the table is zero)
+            for (int e = t; e < B2 * 64; e += 256) {
+                const int idx = e & 63, k = e >> 6;
+                const int gi = idx < LINK_TILE ? tr * LINK_TILE + idx : tc * LINK_TILE + idx - LINK_TILE;
+                ulonglong2 v = make_ulonglong2(0, 0);
+                if (gi < n_pro) v = gathered[(col * B2 + k) * n_pro + gi];
+                tile[k * 64 + idx] = v.x;
+                tile[(B2 + k) * 64 + idx] = v.y;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int w = 0; w < 2; ++w) {
+                const u64 mask = column_mask(L, 2 * p + w);
+                if (mask == 0) continue;                 // (uniform) an odd W leaves the second word of the last pair empty
+                const int valid = min(64, L - 64 * (2 * p + w));
+                const bool last = 2 * p + w == W - 1;
+                const u64 *P = tile + w * B2 * 64, *M = P + B * 64;
+                u64 nac[2][2] = {{0, 0}, {0, 0}}, nad[2][2] = {{0, 0}, {0, 0}}, nbc[2][2] = {{0, 0}, {0, 0}}, nbd[2][2] = {{0, 0}, {0, 0}};
+                for (int b = 0; b < B; ++b) {
+                    u64 a[2], bb[2], c[2], d[2];
+#pragma unroll
+                    for (int r = 0; r < 2; ++r) {
+                        a[r] = P[b * 64 + ty + 16 * r];
+                        bb[r] = M[b * 64 + ty + 16 * r];
+                        c[r] = P[b * 64 + LINK_TILE + tx + 16 * r];
+                        d[r] = M[b * 64 + LINK_TILE + tx + 16 * r];
+                    }
+#pragma unroll
+                    for (int r = 0; r < 2; ++r)
+#pragma unroll
+                        for (int k = 0; k < 2; ++k) {
+                            nac[r][k] |= a[r] ^ c[k];
+                            nad[r][k] |= a[r] ^ d[k];
+                            nbc[r][k] |= bb[r] ^ c[k];
+                            nbd[r][k] |= bb[r] ^ d[k];
+                        }
+                }
+#pragma unroll
+                for (int r = 0; r < 2; ++r)
+#pragma unroll
+                    for (int k = 0; k < 2; ++k) {
+                        const u64 any = ~(nac[r][k] & nad[r][k] & nbc[r][k] & nbd[r][k]) & mask;
+                        const int c0 = cell0[r][k];
+                        int &n_over = over[r][k], &n_loci = over_loci[r][k];
+                        genphi::seg_walk_word(any, valid, last, st[r][k], [&](int len, bool censored) {
+                            if (len >= min_loci) {
+                                n_over += 1;
+                                n_loci += len;
+                            }
+                            if (c0 >= 0) {
+                                u64 *cell = table + 3 * (c0 + genphi::seg_bin(edges, n_edges, len));
+                                atomicAdd(cell, 1ull);
+                                atomicAdd(cell + 1, static_cast<u64>(len));
+                                if (censored) atomicAdd(cell + 2, 1ull);
+                            }
+                        });
+                    }
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < 2; ++r)
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                acc[r][k][0] += over[r][k];
+                acc[r][k][1] += over_loci[r][k];
+                acc[r][k][2] += st[r][k].longest;
+            }
+    }
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const int i = tr * LINK_TILE + ty + 16 * r, j = tc * LINK_TILE + tx + 16 * k;
+            if (i >= n_pro || j >= n_pro) continue;
+            long long *o = pairs + (static_cast<long long>(i) * n_pro + j) * 3;
+#pragma unroll
+            for (int v = 0; v < 3; ++v) o[v] += acc[r][k][v];
+            if (tr != tc) {                              // (j, i): all three sums are symmetric
+                long long *o2 = pairs + (static_cast<long long>(j) * n_pro + i) * 3;
+#pragma unroll
+                for (int v = 0; v < 3; ++v) o2[v] += acc[r][k][v];
+            }
+        }
+    __syncthreads();                                     // every run of the workgroup is in the table
+    for (int e = t; e < 3 * cells; e += 256) {
+        const u64 v = table[e];
+        if (v) atomicAdd(table_out + e, v);
+    }
+}
+
 // labels[i][side][simulation][locus]: a lane per locus of a word, a wave per (proband, side, simulation, word); loci >= L are dropped.
 __global__ void __launch_bounds__(256)
 link_label_kernel(const ulonglong2 *__restrict__ gathered, int n_pro, int B, int Sc, int W, int Wp, int L, long long first_sim, long long S,
@@ -224,7 +358,19 @@ struct genphi_link : LabelSweep {            // d_slots: the rows of one panel (
     int64_t sims = 0;                        // simulations of a panel
     int64_t n_panels = 0;
     double pair_ms = 0.0, word_ops = 0.0, philox_blocks = 0.0;
-    genphi_link() { own(d_sums, d_labels, d_gathered); }
+    // gen.simuSegments (genphi_seg_*): the request that the next compute answers, and the one that the last compute answered
+    struct SegRequest {
+        std::vector<int32_t> edges, group;   // no edges: no request; group: a label per list position (zeros without groups)
+        int32_t min_loci = 1, n_groups = 0;
+        int32_t n_edges() const { return static_cast<int32_t>(edges.size()); }
+        int32_t G() const { return n_groups > 1 ? n_groups : 1; }
+    } seg_next, seg_ran;
+    DevBuf<u64> d_seg_table;                 // cells x 3, the pairs of groups a <= b (link_segments.h)
+    DevBuf<long long> d_seg_pairs;           // n_pro x n_pro x 3
+    DevBuf<int> d_seg_lists;                 // the edges, then the labels
+    double seg_ms = 0.0, seg_word_ops = 0.0;
+    int64_t seg_lds = 0, seg_closed = 0;     // the segments closed: the sum of the table's first counters
+    genphi_link() { own(d_sums, d_labels, d_gathered, d_seg_table, d_seg_pairs, d_seg_lists); }
 };
 
 namespace {
@@ -239,18 +385,24 @@ int prepare(genphi_link *h)
     const genphi::LinkSizes z = genphi::link_sizes(pl, h->S, h->shape, h->want_labels);
     double usable = 0.0;
     if (int rc = h->usable_bytes(usable, h->held_bytes())) return rc;
-    const double room = usable - static_cast<double>(z.fixed()) - (64 << 20);
+    const genphi::SegSizes zs = genphi::seg_sizes(pl.n_pro, h->seg_next.n_edges(), h->seg_next.n_groups);
+    const double room = usable - static_cast<double>(z.fixed()) - static_cast<double>(zs.fixed()) - (64 << 20);
     const double sim_bytes = static_cast<double>(z.panel(1));
     int64_t Sn;
     if (!genphi::drop_panel_fits(Sn, 128 * h->S, 128 * static_cast<int64_t>(h->panel_arg), room, sim_bytes))
         return genphi_set_error(GENPHI_ERR_ALLOC, "gen.simuSharing: the sums of " + std::to_string(pl.n_pro) + " probands" +
-                                                      (h->want_labels ? ", the labels" : "") + " and " + std::to_string(pl.n_live) + " live rows of " +
+                                                      (h->want_labels ? ", the labels" : "") + (zs.fixed() ? ", the segment tables" : "") + " and " + std::to_string(pl.n_live) + " live rows of " +
                                                       std::to_string(pl.planes) + " planes, " + std::to_string(h->shape.L) + " loci and " +
                                                       std::to_string(std::max<int64_t>(Sn, 1)) + " simulations do not fit on device " + std::to_string(h->device));
     GENPHI_HIP_TRY(h->d_slots.reserve(z.sim_rows * static_cast<size_t>(Sn)));
     GENPHI_HIP_TRY(h->d_gathered.reserve(z.sim_gather * static_cast<size_t>(Sn) / sizeof(ulonglong2)));
     GENPHI_HIP_TRY(h->d_sums.reserve(z.sums / 8));
     if (h->want_labels) GENPHI_HIP_TRY(h->d_labels.reserve(z.labels / 4));
+    if (zs.fixed()) {
+        GENPHI_HIP_TRY(h->d_seg_table.reserve(zs.table / 8));
+        GENPHI_HIP_TRY(h->d_seg_pairs.reserve(zs.pairs / 8));
+        GENPHI_HIP_TRY(h->d_seg_lists.reserve((zs.edges + zs.labels) / 4));
+    }
     if (int rc = h->upload_lists()) return rc;
     h->sims = Sn;
     h->n_panels = (h->S + Sn - 1) / Sn;
@@ -266,7 +418,8 @@ int prepare(genphi_link *h)
 
 int compute_impl(genphi_link *h, int32_t device)
 {
-    if (int rc = h->select(device)) return rc;
+    if (int rc = h->select(device)) return rc;           // (computed = false: a compute that fails leaves no result, segments included)
+    h->seg_ran = genphi_link::SegRequest();              // before prepare() may replace the blocks of the request answered last
     if (int rc = prepare(h)) return rc;
     const genphi::IdentPlan &pl = h->plan;
     const genphi::LinkShape &sh = h->shape;
@@ -278,8 +431,22 @@ int compute_impl(genphi_link *h, int32_t device)
     const int step_units = 4 * (64 / lps);
     const unsigned tiles = static_cast<unsigned>((n_pro + LINK_TILE - 1) / LINK_TILE);
     const size_t lds = static_cast<size_t>(2 * 2 * 64 * 8) * static_cast<size_t>(B);
-    PhaseTimer timer;
+    PhaseTimer timer, seg_timer;
     GENPHI_HIP_TRY(hipMemsetAsync(h->d_sums.get(), 0, h->d_sums.bytes(), h->stream));
+    // gen.simuSegments: the request as it stands now is the one this compute answers
+    const genphi_link::SegRequest &rq = h->seg_next;
+    const genphi::SegSizes zs = genphi::seg_sizes(n_pro, rq.n_edges(), rq.n_groups);
+    const int seg_cells = rq.n_edges() ? static_cast<int>(genphi::seg_cells(rq.n_edges(), rq.n_groups)) : 0;
+    const size_t seg_lds = rq.n_edges() ? genphi::seg_lds_bytes(B, rq.n_edges(), rq.n_groups) : 0;
+    if (rq.n_edges()) {
+        GENPHI_HIP_TRY(hipMemsetAsync(h->d_seg_table.get(), 0, zs.table, h->stream));
+        GENPHI_HIP_TRY(hipMemsetAsync(h->d_seg_pairs.get(), 0, zs.pairs, h->stream));
+        GENPHI_HIP_TRY(hipMemcpyAsync(h->d_seg_lists.get(), rq.edges.data(), zs.edges, hipMemcpyHostToDevice, h->stream));
+        GENPHI_HIP_TRY(hipMemcpyAsync(h->d_seg_lists.get() + rq.n_edges(), rq.group.data(), zs.labels, hipMemcpyHostToDevice, h->stream));
+        GENPHI_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(link_segment_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           static_cast<int>(seg_lds)));
+    }
+    double seg_ms = 0.0, seg_idle = 0.0;                 // seg_idle: the empty first phase of seg_timer, never reported
     double sweep_ms = 0.0, pair_ms = 0.0;
     int64_t launches = 0;
     for (int64_t s0 = 0; s0 < h->S; s0 += Sn) {
@@ -308,6 +475,16 @@ int compute_impl(genphi_link *h, int32_t device)
         link_pair_kernel<<<dim3(tiles, tiles), 256, lds, h->stream>>>(h->d_gathered.get(), n_pro, B, Sc, Wp, sh.L, h->all_pairs ? 0 : 1, h->d_sums.get());
         GENPHI_HIP_TRY(hipGetLastError());
         if (int rc = timer.end(h->stream)) return rc;
+        if (rq.n_edges()) {
+            // the kernel alone between two events: PhaseTimer's first phase (begin .. middle) is empty here, its second is segment_ms
+            if (int rc = seg_timer.begin(h->stream)) return rc;
+            if (int rc = seg_timer.middle(h->stream)) return rc;
+            link_segment_kernel<<<dim3(tiles, tiles), 256, seg_lds, h->stream>>>(h->d_gathered.get(), n_pro, B, Sc, Wp, sh.L, h->d_seg_lists.get(), rq.n_edges(),
+                                                                                 rq.min_loci, h->d_seg_lists.get() + rq.n_edges(), rq.G(), seg_cells,
+                                                                                 h->d_seg_table.get(), h->d_seg_pairs.get());
+            GENPHI_HIP_TRY(hipGetLastError());
+            if (int rc = seg_timer.end(h->stream)) return rc;
+        }
         if (h->want_labels) {
             const long long threads = 2ll * n_pro * Sc * sh.W * 64;
             link_label_kernel<<<static_cast<unsigned>((threads + 255) / 256), 256, 0, h->stream>>>(h->d_gathered.get(), n_pro, B, Sc, sh.W, Wp, sh.L, s0, h->S,
@@ -315,7 +492,9 @@ int compute_impl(genphi_link *h, int32_t device)
             GENPHI_HIP_TRY(hipGetLastError());
         }
         if (int rc = timer.add(sweep_ms, pair_ms)) return rc;
-        launches += pl.n_levels + 2 + (h->want_labels ? 1 : 0);
+        if (rq.n_edges())
+            if (int rc = seg_timer.add(seg_idle, seg_ms)) return rc;
+        launches += pl.n_levels + 2 + (h->want_labels ? 1 : 0) + (rq.n_edges() ? 1 : 0);
     }
     GENPHI_HIP_TRY(hipStreamSynchronize(h->stream));
     // per side with a known parent and simulation: two runs of B planes read and one written, 16 bytes per plane and pair of words
@@ -327,6 +506,16 @@ int compute_impl(genphi_link *h, int32_t device)
     h->word_ops = (h->all_pairs ? n * n : n * (n + 1.0) / 2.0) * S * sh.W * (8.0 * B + 32.0);
     h->philox_blocks = known_sides * S * static_cast<double>(genphi::link_blocks_per_side(sh));
     h->n_launches = launches;
+    h->seg_closed = 0;
+    if (rq.n_edges()) {                                  // the segments closed, read from the table (at most 48 KB)
+        std::vector<int64_t> upper(zs.table / 8);
+        if (int rc = h->copy_out(upper.data(), h->d_seg_table.get(), zs.table, "gen.simuSegments")) return rc;
+        for (size_t c = 0; c < upper.size(); c += 3) h->seg_closed += upper[c];
+    }
+    h->seg_ran = rq;
+    h->seg_ms = seg_ms;
+    h->seg_word_ops = rq.n_edges() ? n * (n + 1.0) / 2.0 * S * sh.W * (8.0 * B + 10.0) : 0.0;
+    h->seg_lds = static_cast<int64_t>(seg_lds);
     h->computed = true;
     return GENPHI_OK;
 }
@@ -410,5 +599,63 @@ int genphi_link_stats(const genphi_link *h, double *sweep_ms, double *pair_ms, d
 }
 
 void genphi_link_destroy(genphi_link *h) { destroy_entry(h); }
+
+int genphi_seg_request(genphi_link *h, int32_t n_edges, const int32_t *edges, int32_t min_loci, int32_t n_groups, const int32_t *group)
+{
+    if (!h) return genphi_set_error(GENPHI_ERR_ARG, "genphi_seg_request: NULL handle");
+    if (n_edges == 0) {
+        h->seg_next = genphi_link::SegRequest();
+        return GENPHI_OK;
+    }
+    const int64_t n_pro = h->plan.n_pro;
+    const std::string err = genphi::seg_check_request(n_edges, edges, min_loci, n_groups, group, n_pro);
+    if (!err.empty()) return genphi_set_error(GENPHI_ERR_ARG, "gen.simuSegments: " + err);
+    try {
+        genphi_link::SegRequest rq;
+        rq.edges.assign(edges, edges + n_edges);
+        if (n_groups > 0) rq.group.assign(group, group + n_pro);
+        else rq.group.assign(static_cast<size_t>(n_pro), 0);
+        rq.min_loci = min_loci;
+        rq.n_groups = n_groups;
+        h->seg_next = std::move(rq);
+    } catch (const std::bad_alloc &) { return genphi_set_error(GENPHI_ERR_ALLOC, "out of host memory in gen.simuSegments"); }
+    return GENPHI_OK;
+}
+
+int genphi_seg_to_host(genphi_link *h, int64_t *hist, int64_t *pairs)
+{
+    if (!h || !h->computed) return genphi_set_error(GENPHI_ERR_ARG, "genphi_seg_to_host: nothing computed");
+    const genphi_link::SegRequest &rq = h->seg_ran;
+    if (!rq.n_edges()) return genphi_set_error(GENPHI_ERR_ARG, "genphi_seg_to_host: the last compute ran without a request (genphi_seg_request)");
+    const genphi::SegSizes zs = genphi::seg_sizes(h->plan.n_pro, rq.n_edges(), rq.n_groups);
+    if (pairs)
+        if (int rc = h->copy_out(pairs, h->d_seg_pairs.get(), zs.pairs, "gen.simuSegments")) return rc;
+    if (hist) {
+        try {
+            std::vector<int64_t> upper(zs.table / 8);
+            if (int rc = h->copy_out(upper.data(), h->d_seg_table.get(), zs.table, "gen.simuSegments")) return rc;
+            const int32_t G = rq.G();
+            const size_t row = 3 * static_cast<size_t>(rq.n_edges() + 1);                // the Int64 of one pair of groups
+            for (int32_t a = 0; a < G; ++a)
+                for (int32_t b = 0; b < G; ++b)
+                    std::copy_n(upper.data() + row * static_cast<size_t>(genphi::seg_group_pair(a, b, G)), row, hist + row * (static_cast<size_t>(a) * G + b));
+        } catch (const std::bad_alloc &) { return genphi_set_error(GENPHI_ERR_ALLOC, "out of host memory in gen.simuSegments"); }
+    }
+    return GENPHI_OK;
+}
+
+int genphi_seg_stats(const genphi_link *h, double *segment_ms, double *word_ops, int64_t *segments, int32_t *cells, int64_t *lds_bytes)
+{
+    if (!h) return genphi_set_error(GENPHI_ERR_ARG, "genphi_seg_stats: NULL handle");
+    const genphi_link::SegRequest &rq = h->seg_ran;
+    const bool ran = h->computed && rq.n_edges();
+    const int64_t n_cells = ran ? genphi::seg_cells(rq.n_edges(), rq.n_groups) : 0;
+    put(segment_ms, ran ? h->seg_ms : 0.0);
+    put(word_ops, ran ? h->seg_word_ops : 0.0);
+    put(segments, ran ? h->seg_closed : int64_t(0));
+    put(cells, n_cells);
+    put(lds_bytes, ran ? h->seg_lds : int64_t(0));
+    return GENPHI_OK;
+}
 
 }  // extern "C"

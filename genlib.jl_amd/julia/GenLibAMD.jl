@@ -873,6 +873,66 @@ function simuRetention(pedigree::GenLib.Pedigree, pro::Vector{Int} = GenLib.pro(
 end
 
 """
+    simuSegments(pedigree::GenLib.Pedigree, pro = GenLib.pro(pedigree); loci = 1024, length = 1.0, probRecomb = nothing,
+                 simulNo = 1000, seed = nothing, bins = nothing, minLoci = 1, groups = nothing, device = -1)
+
+The length spectrum of the segments that pairs of probands share identical by descent, by gene dropping along a chromosome of
+`loci` linked loci on the GPU (csrc/link.hip; GenLib.jl has no form of it; the definition is the text of `genphi_link_*` and
+`genphi_seg_*` in include/genphi.h).  `bins`: `nothing` = the edges 1, 2, 4, .. (the last one capped at 4097, which matters at `loci = 4096` only) up to and including the first power of two above
+`loci`, or the edges in loci; `groups`: a `Dict` ID => group name.  Returns a named tuple: `edges`, `hist` (Int64,
+`3 x (bins + 2) x G x G`: segments, loci and censored segments of `below`, the bins and `above`, over the pairs `i < j`; the
+library's row-major `G x G x (bins + 2) x 3` is the memory of that array, and the table is symmetric in the groups), `pairs`
+(Int64 `3 x N x N`: per pair the segments of at least `minLoci` loci, their loci and the longest segment, summed over the
+simulations), `sums` (Int64 `6 x N x N`, the sums of the sharing of the same run), `names`, `locus_cM`, `q`, `simulNo`, `seed`.
+"""
+function simuSegments(pedigree::GenLib.Pedigree, pro::Vector{Int} = GenLib.pro(pedigree);
+                      loci::Integer = 1024, length::Real = 1.0, probRecomb::Union{Nothing, Real} = nothing, simulNo::Integer = 1000,
+                      seed::Union{Nothing, UInt64} = nothing, bins::Union{Nothing, Vector{<:Integer}} = nothing, minLoci::Integer = 1,
+                      groups::Union{Nothing, AbstractDict} = nothing, device::Integer = -1)
+    isempty(pro) && throw(ArgumentError("gen.simuSegments: no probands"))
+    1 <= loci <= 4096 || throw(ArgumentError("gen.simuSegments: loci = $loci is outside 1 .. 4096"))
+    r = isnothing(probRecomb) ? (loci > 1 ? 0.5 * (1.0 - exp(-2.0 * Float64(length) / (loci - 1))) : 0.0) : Float64(probRecomb)
+    (isfinite(r) && 0 <= round(Int, 65536.0 * r) <= 32768) ||
+        throw(ArgumentError("gen.simuSegments: a recombination probability of $r between neighbouring loci is outside 0 .. 1/2"))
+    q = round(Int, 65536.0 * r)
+    edges = Int32[]
+    if isnothing(bins)
+        push!(edges, 1)
+        while edges[end] <= loci
+            push!(edges, 2 * edges[end])
+        end
+        edges[end] = min(edges[end], Int32(4097))       # loci = 4096: 8192 is no edge; the last bin is [4096, 4097)
+    else
+        edges = Int32.(bins)
+    end
+    names = isnothing(groups) ? nothing : sort(unique(collect(values(groups))))
+    labels = isnothing(groups) ? Int32[] : Int32[haskey(groups, i) ? findfirst(==(groups[i]), names) - 1 : -1 for i in pro]
+    G = isnothing(groups) ? 0 : Base.length(names)
+    seed64 = isnothing(seed) ? rand(Random.RandomDevice(), UInt64) : seed
+    ind, father, mother, _ = flatten(pedigree)
+    n = Base.length(pro)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve ind father mother pro check(ccall((:genphi_link_create, libgenphi), Cint,
+        (Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Int64, Ptr{Int64}, Int32, Int32, Int64, UInt64, Int32, Int32, Ptr{Ptr{Cvoid}}),
+        Base.length(ind), ind, father, mother, n, pro, Int32(loci), Int32(q), Int64(simulNo), seed64, Int32(0), Int32(0), h))
+    try
+        GC.@preserve edges labels check(ccall((:genphi_seg_request, libgenphi), Cint, (Ptr{Cvoid}, Int32, Ptr{Int32}, Int32, Int32, Ptr{Int32}),
+                                              h[], Int32(Base.length(edges)), edges, Int32(minLoci), Int32(G), G > 0 ? pointer(labels) : C_NULL))
+        check(ccall((:genphi_link_compute, libgenphi), Cint, (Ptr{Cvoid}, Int32), h[], Int32(device)))
+        Gt = max(G, 1)
+        hist = Array{Int64}(undef, 3, Base.length(edges) + 1, Gt, Gt)
+        pairs = Array{Int64}(undef, 3, n, n)
+        sums = Array{Int64}(undef, 6, n, n)
+        GC.@preserve hist pairs check(ccall((:genphi_seg_to_host, libgenphi), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}), h[], hist, pairs))
+        GC.@preserve sums check(ccall((:genphi_link_sums_to_host, libgenphi), Cint, (Ptr{Cvoid}, Ptr{Int64}), h[], sums))
+        return (edges = Int.(edges), hist = hist, pairs = pairs, sums = sums, names = names, locus_cM = -50.0 * log(1.0 - 2.0 * q / 65536.0),
+                q = q, simulNo = Int(simulNo), seed = seed64)
+    finally
+        ccall((:genphi_link_destroy, libgenphi), Cvoid, (Ptr{Cvoid},), h[])
+    end
+end
+
+"""
     depth(pedigree::GenLib.Pedigree)
 
 The number of generations of the pedigree, as `GenLib.depth` (src/describe.jl:43-66): one linear pass on the host

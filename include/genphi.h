@@ -1252,6 +1252,59 @@ int genphi_link_stats(const genphi_link *h, double *sweep_ms, double *pair_ms, d
 void genphi_link_destroy(genphi_link *h);
 int genphi_link_words(uint64_t seed, int64_t id, int32_t side, int64_t s, int32_t loci, int32_t q, uint64_t *X, uint64_t *T);
 
+/* ---- gen.simuSegments: the lengths of the IBD segments of gen.simuSharing (csrc/link.hip, csrc/link.cpp, csrc/link_segments.h) ------
+ * gen.simuSharing reduces the word `any` of a pair to the number of its runs (sums[.., 4]) and of its loci (sums[.., 2]); the lengths
+ * of the runs are what a genealogy is compared with the segments that detection software reports, and they are kept here.  The
+ * functions work on a genphi_link handle: a request is answered by the next genphi_link_compute, beside the sums.
+ * Segment.  For a pair of list positions (i, j) in one simulation: a maximal run of consecutive loci with `any` set, the run that
+ * g_s counts.  Its length is a number of loci, 1 .. L.
+ * Censored.  A segment that contains locus 0 or locus L - 1: the chromosome cut it short.  A segment of length L is censored.
+ * Edges.  n_edges strictly increasing Int32 with 1 <= edges[0], edges[n_edges - 1] <= 4097 and 2 <= n_edges <= 257; n_bins =
+ * n_edges - 1.  A length len is in bin b when edges[b] <= len < edges[b + 1], in `below` when len < edges[0] and in `above` when
+ * len >= edges[n_bins].  Lengths are integers: the last bin has no rule of its own.  (gen.simuSegments' default edges are 1, 2, 4, ..
+ * up to and including the first power of two above L, the last one capped at 4097: at L = 4096 they end 2048, 4096, 4097.)
+ * Histogram.  Over the unordered pairs i < j of list positions, never the diagonal.  hist[a][b][k][3], Int64, row-major: k = 0 is
+ * `below`, k = 1 .. n_bins the bins, k = n_bins + 1 `above`; the three numbers of a cell are the segments, the loci in them and the
+ * censored segments.  Without groups a = b = 0.  With groups, group[i] is the label of list position i, 0 .. n_groups - 1, or -1 for
+ * "counts nowhere" (as in genphi_result_hist): a segment of the pair (i, j) counts in hist[group[i]][group[j]] and in its mirror;
+ * the table is symmetric and hist[a][a] holds the pairs within group a.  n_groups <= 32, and with G = max(n_groups, 1) the cells
+ * G (G + 1) / 2 x (n_bins + 2) are at most 2048.
+ * Per pair.  pairs[i][j][3], Int64, n_pro x n_pro x 3, symmetric, the diagonal included: the sums over the simulations of the
+ * segments with len >= min_loci, of the loci in those segments, and of the longest segment of the simulation (0 when it has none,
+ * whatever min_loci is).  1 <= min_loci <= 4097.
+ * Invariants, all exact.  Everything is an integer and is added by integer additions only: the result is a function of the pedigree's
+ * relations, the list, L, q, the seed, S, the edges, min_loci and the labels, and does not depend on the panel width, the order of
+ * the tiles or ALL_PAIRS.  Over i < j: the segments of all cells add up to sum g and their loci to sum n1.  With min_loci = 1,
+ * pairs[.., 0] = sums[.., 4] and pairs[.., 1] = sums[.., 2].
+ * Method.  A second kernel after the pair kernel, on the same gathered rows, with the pair kernel's tile and staging; it forms the
+ * four equality words and `any`, and walks the runs of `any` with a state carried from word to word of a simulation (the length of
+ * the open run, whether it began at locus 0, the longest so far): a zero word with nothing open and a full word are one step, else
+ * the runs are peeled with count-trailing-zeros on the word and its complement.  A closed run goes to the thread's Int64 of the pair
+ * and, for i < j, to the workgroup's table in LDS (64-bit counters), which is added to the global table once at the end by 64-bit
+ * integer atomics.
+ *   request      takes effect at the next genphi_link_compute; n_edges = 0 withdraws the request.  Everything is checked on the host:
+ *                GENPHI_ERR_ARG with a message that names the offending value; the handle, an earlier request and earlier results
+ *                stay as they were.  group is read only with n_groups > 0: n_pro labels
+ *   to_host      hist: G x G x (n_bins + 2) x 3 Int64, mirrored here; pairs: n_pro x n_pro x 3 Int64; either may be NULL.
+ *                GENPHI_ERR_ARG unless the last compute succeeded and ran with a request (a compute that fails leaves no result,
+ *                the segments included)
+ *   stats        of the last compute: the device time of the segment kernel by HIP events, summed over the panels; its word
+ *                operations (pairs walked x S x W x (8 B + 10): the equality words as in the pair kernel, 8 to negate and mask, 3
+ *                for any, and the two tests of the walk's common words; the peeled runs are not counted); the segments closed,
+ *                summed from the table; the cells of the request; the dynamic LDS of a workgroup in bytes
+ *   host         host only, in the role of genphi_link_words: one pair and one simulation, the chromosome's `any` given as
+ *                ceil(loci / 64) words (bits at and above loci are ignored), reduced by the code the kernel walks with.  hist_out:
+ *                (n_bins + 2) x 3, pair_out: 3; both are added to, either may be NULL                                            */
+#define GENPHI_SEG_MAX_EDGES 257
+#define GENPHI_SEG_MAX_EDGE 4097
+#define GENPHI_SEG_MAX_GROUPS 32
+#define GENPHI_SEG_MAX_CELLS 2048
+int genphi_seg_request(genphi_link *h, int32_t n_edges, const int32_t *edges, int32_t min_loci, int32_t n_groups, const int32_t *group);
+int genphi_seg_to_host(genphi_link *h, int64_t *hist, int64_t *pairs);
+int genphi_seg_stats(const genphi_link *h, double *segment_ms, double *word_ops, int64_t *segments, int32_t *cells, int64_t *lds_bytes);
+int genphi_seg_host(int32_t loci, const uint64_t *any_words, int32_t n_edges, const int32_t *edges, int32_t min_loci, int64_t *hist_out,
+                    int64_t *pair_out);
+
 /* gen.descendant and gen.children (src/identify.jl:203-215, :77-80), host only: the strict descendants of ids[0 .. n_ids) (the
  * union over them), and the children of one ID, ascending; *out is allocated by the library (genphi_free).  No order of the
  * pedigree is assumed.  Unknown ID -> GENPHI_ERR_UNKNOWN_ID.                                                                  */
