@@ -10,8 +10,7 @@
 
 #include "../../include/genphi.h"
 #include "bootstrap.h"
-
-int genphi_set_error(int code, const std::string &msg);      // genphi_hip.hip
+#include "error.h"
 
 extern "C" int genphi_bootstrap_counts(int64_t n, uint64_t seed, int32_t first, int32_t n_boot, int32_t *counts)
 {

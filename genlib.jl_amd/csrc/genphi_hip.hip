@@ -39,7 +39,8 @@
 //   No MFMA anywhere: this is a gather-average, HBM-bound.
 //
 // Only the sweep lives here.  What reads the finished resident result (genphi_result_*) is in result_queries.hip and
-// result_to_host.cpp, which see the plan through resident.h.
+// result_to_host.cpp, which see the plan through resident.h.  The Float64-storage kernels, their buffers and launches are
+// sweep_f64.hip; the plan's state (plan_device.h) is what the two units share.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -58,6 +59,7 @@
 #include "devcache.h"
 #include "devbuf.h"
 #include "device_sizes.h"
+#include "plan_device.h"
 #include "planner.h"
 #include "shard_lists.h"
 #include "resident.h"
@@ -67,11 +69,7 @@
 #include "tuning.h"
 
 using genphi::al256;
-using genphi::DevBuf;
 using genphi::kTailPadFloats;
-using genphi::LevelStep;
-using genphi::Plan;
-using genphi::Tuning;          // the hooks of a plan, read once when it is created (tuning.h)
 using genphi::cert_threshold;
 
 // ---------------------------------------------------------------------------------------------
@@ -79,7 +77,7 @@ using genphi::cert_threshold;
 // ---------------------------------------------------------------------------------------------
 namespace {
 
-constexpr int kOrdMask = 0x7fffffff;
+using genphi::kOrdMask;      // (planner.h)
 
 typedef float f4_t __attribute__((ext_vector_type(4)));
 typedef unsigned u4_t __attribute__((ext_vector_type(4)));
@@ -1502,262 +1500,6 @@ __global__ void level_naive_kernel(const LevelArgs p)
     p.out[orow * p.ld + j] = v;
 }
 
-// ---- Float64 storage (opts flag GENPHI_FLAG_STORAGE_F64) -----------------------------------------
-// The pairwise recursion of the reference, phi(i::Individual, j::Individual) (src/compute.jl:66-95),
-// and gen.f built on it (:500-511) work in Float64 throughout and never round to Float32 between
-// generations.  The same level sweep with Float64 level matrices reproduces them: every kinship
-// is a dyadic rational, exactly representable in Float64 while the pedigree is less than ~26
-// generations deep (then the sweep and the recursion are bit-identical whatever their order of
-// operations).  Beyond, the four terms are grouped as the recursion groups them and scaled once
-// (exact for normal doubles): bit-identical to the recursion memoised level by level (the oracle's
-// Float64 sweep) wherever the result is normal, within 2 L 2^-53 relative of the exact kinship
-// after L level steps; subnormal results are kept (no flush), within 4 x 2^-1074.  One thread per entry, four global gathers;
-// meant for the small proband sets of gen.f / pairwise queries, not for throughput.
-//   colmap: member index of output column j (the last level is delivered in proband order), or nullptr
-__global__ void level_naive64_kernel(const double *__restrict__ psi, long long ld_prev, int n_prev, double *__restrict__ out,
-                                     long long ld, int n, const int *__restrict__ srcA, const int *__restrict__ srcB,
-                                     const int *__restrict__ ord, const int *__restrict__ rows, const int *__restrict__ out_rows,
-                                     const int *__restrict__ colmap, int n_cols)
-{
-    const int w = blockIdx.x;
-    const long long j = (long long)blockIdx.y * blockDim.x + threadIdx.x;
-    if (j >= ld) return;
-    const int i = rows ? rows[w] : w;
-    const long long orow = out_rows ? out_rows[w] : i;
-    double v = 0.0;
-    if (j < n_cols) {
-        const int jm = colmap ? colmap[j] : static_cast<int>(j);
-        const int Ai = srcA[i], Bi = srcB[i], oi = ord[i];
-        const int Aj = srcA[jm], Bj = srcB[jm], oj = ord[jm];
-        const double *rowA = psi + (long long)Ai * ld_prev;
-        const double *rowB = psi + (long long)Bi * ld_prev;
-        if (jm == i && oi < 0) {
-            v = 0.5 + 0.5 * rowA[Bi];
-        } else {
-            const double sc = (oi < 0 ? 0.5 : 1.0) * (oj < 0 ? 0.5 : 1.0);
-            const double a = rowA[Aj], b = rowA[Bj], c = rowB[Aj], d = rowB[Bj];
-            const bool i_hi = (oi & kOrdMask) > (oj & kOrdMask);
-            const double x = i_hi ? b : c, y = i_hi ? c : b;
-            v = ((a + x) + (y + d)) * sc;
-        }
-    }
-    (void)n_prev; (void)n;
-    out[orow * ld + j] = v;
-}
-
-// Float64 storage, cuts whose two source rows fit in LDS (2 x 8 bytes x (n_prev + 1) <= 160 KB): the FULL
-// kernel's shape -- both source rows of an output row staged whole with 16-byte coalesced loads, four 8-byte LDS
-// gathers per entry, coalesced row stores -- with the reference's grouping (src/compute.jl:66-95 climbs the
-// higher-ranked individual first) and no rounding to Float32.  Same arguments as level_naive64_kernel + the number
-// of rows.  PERSISTENT: a workgroup walks rows w = blockIdx.x, + gridDim.x, ... and
-//   - owns the same columns in every row, so their index words (sources, rank word, member) are loaded ONCE into
-//     registers (they were three dependent global loads per entry),
-//   - has the NEXT row pair in flight into registers while the current one is gathered from LDS (rows of 7k+ members
-//     leave room for one workgroup per CU only: nothing else would hide the load latency).
-typedef double d2_t __attribute__((ext_vector_type(2)));   // (HIP's d2_t is a struct of unions: arrays of it stay in scratch)
-constexpr int kF64Cols = 20;      // columns per thread: ceil(10 304 / 512)  (ld of the widest cut whose rows fit)
-constexpr int kF64Pre = 10;       // d2_t pieces per source row and thread: ceil(10 240 / 2 / 512)
-__global__ void __launch_bounds__(512)
-level_full64_kernel(const double *__restrict__ psi, long long ld_prev, int n_prev, double *__restrict__ out, long long ld,
-                    const int *__restrict__ srcA, const int *__restrict__ srcB, const int *__restrict__ ord,
-                    const int *__restrict__ rows, const int *__restrict__ out_rows, const int *__restrict__ colmap, int n_cols,
-                    int lds_row, int n_rows)
-{
-    extern __shared__ double lds64[];
-    double *sA = lds64, *sB = lds64 + lds_row;
-    const int tid = threadIdx.x, nt = blockDim.x;
-    unsigned pkj[kF64Cols];
-    int oj[kF64Cols], jmv[kF64Cols];
-    const int j0 = blockIdx.y * nt * kF64Cols;           // this workgroup's column chunk (outputs wider than 512 x 20 columns take several)
-#pragma unroll
-    for (int k = 0; k < kF64Cols; ++k) {
-        const int j = j0 + tid + k * nt;
-        pkj[k] = 0; oj[k] = 0; jmv[k] = -1;
-        if (j < n_cols) {
-            const int jm = colmap ? colmap[j] : j;
-            jmv[k] = jm; pkj[k] = static_cast<unsigned>(srcA[jm]) | static_cast<unsigned>(srcB[jm]) << 16; oj[k] = ord[jm];
-        }
-    }
-    const int nvec = lds_row >> 1;
-    d2_t ra[kF64Pre], rb[kF64Pre];
-#define GENPHI_F64_FETCH(W)                                                                                                    \
-    {                                                                                                                          \
-        const int fi = rows ? rows[W] : (W);                                                                                   \
-        const d2_t *a2 = reinterpret_cast<const d2_t *>(psi + (long long)srcA[fi] * ld_prev);                            \
-        const d2_t *b2 = reinterpret_cast<const d2_t *>(psi + (long long)srcB[fi] * ld_prev);  /* "none" = the zero row */ \
-        _Pragma("unroll") for (int k = 0; k < kF64Pre; ++k) { const int q = min(tid + k * nt, nvec - 1); ra[k] = a2[q]; rb[k] = b2[q]; } \
-    }
-    int w = blockIdx.x;
-    if (w >= n_rows) return;
-    GENPHI_F64_FETCH(w)
-    for (; w < n_rows; w += gridDim.x) {
-        __syncthreads();                                  // the previous row's gathers are done
-        {
-            d2_t *sA2 = reinterpret_cast<d2_t *>(sA), *sB2 = reinterpret_cast<d2_t *>(sB);
-#pragma unroll
-            for (int k = 0; k < kF64Pre; ++k) { const int q = tid + k * nt; if (q < nvec) { sA2[q] = ra[k]; sB2[q] = rb[k]; } }
-        }
-        const int i = rows ? rows[w] : w;
-        const long long orow = out_rows ? out_rows[w] : i;
-        const int Bi = srcB[i], oi = ord[i];
-        if (w + (int)gridDim.x < n_rows) GENPHI_F64_FETCH(w + (int)gridDim.x)      // in flight behind the gathers
-        __syncthreads();
-        const bool new_i = oi < 0;
-        const int ord_i = oi & kOrdMask;
-        double *orowp = out + orow * ld;
-        unsigned z1 = 0;                                  // opaque zero: the LDS addresses of the 20 columns are row-invariant, and hipcc
-        asm volatile("" : "+s"(z1));                      // would keep all 80 of them in registers across the row loop (spills)
-#pragma unroll
-        for (int k = 0; k < kF64Cols; ++k) {
-            const int j = j0 + tid + k * nt;
-            if (j >= ld) break;
-            double v = 0.0;
-            if (jmv[k] >= 0) {
-                const unsigned pkz = pkj[k] ^ z1;
-                const int ojz = oj[k] ^ static_cast<int>(z1);
-                const unsigned Aj = pkz & 0xffffu, Bj = pkz >> 16;
-                if (jmv[k] == i && new_i) {
-                    v = 0.5 + 0.5 * sA[Bi];
-                } else {
-                    const double sc = (new_i ? 0.5 : 1.0) * (ojz < 0 ? 0.5 : 1.0);
-                    const double a = sA[Aj], b = sA[Bj], c = sB[Aj], d = sB[Bj];
-                    const bool i_hi = ord_i > (ojz & kOrdMask);
-                    const double x = i_hi ? b : c, y = i_hi ? c : b;
-                    v = ((a + x) + (y + d)) * sc;
-                }
-            }
-            orowp[j] = v;
-            if ((k & 1) == 1) __builtin_amdgcn_sched_barrier(0);      // two columns' gathers in flight, not twenty (registers)
-        }
-    }
-    (void)n_prev;
-#undef GENPHI_F64_FETCH
-}
-
-// Float64 storage, cuts whose rows fit in LDS one at a time (8 bytes x (n_prev + 1) <= 160 KB: up to 20,479 members): the SPLIT
-// kernels' shape in its simplest form.  A workgroup walks a contiguous piece of the row list (rows sharing the A source are
-// adjacent in a step's work order) for one chunk of 512 x 14 columns: row A is staged and its terms (a, b) of the chunk's columns
-// kept in registers for as long as the following rows share it; every row with a B source stages that row, gathers (c, d), combines
-// with the reference's grouping and stores.  The next row to stage is in flight into registers behind the gathers.  Same arguments
-// as level_full64_kernel.
-constexpr int kS64Cols = 14;      // columns per thread and chunk (registers: 7 per column + the 80 of the row in flight: 246 VGPRs, no scratch; 16 spills).
-                                  // 14 instead of round 3's 12: genea140's widest cuts (13.7k columns) take 2 chunks instead of 3, i.e. a third fewer stagings
-constexpr int kS64Pre = 20;       // d2_t pieces per source row and thread: 20,480 / 2 / 512
-__global__ void __launch_bounds__(512)
-level_split64_kernel(const double *__restrict__ psi, long long ld_prev, int n_prev, double *__restrict__ out, long long ld,
-                     const int *__restrict__ srcA, const int *__restrict__ srcB, const int *__restrict__ ord,
-                     const int *__restrict__ rows, const int *__restrict__ out_rows, const int *__restrict__ colmap, int n_cols,
-                     int lds_row, int n_rows)
-{
-    extern __shared__ double srow[];
-    const int tid = threadIdx.x;
-    constexpr int nt = 512;
-    unsigned pkj[kS64Cols];
-    int oj[kS64Cols], jmv[kS64Cols];
-    double va[kS64Cols], vb[kS64Cols];
-    const int j0 = blockIdx.y * nt * kS64Cols;
-#pragma unroll
-    for (int k = 0; k < kS64Cols; ++k) {
-        const int j = j0 + tid + k * nt;
-        pkj[k] = 0; oj[k] = 0; jmv[k] = -1; va[k] = vb[k] = 0.0;
-        if (j < n_cols) {
-            const int jm = colmap ? colmap[j] : j;
-            jmv[k] = jm; pkj[k] = static_cast<unsigned>(srcA[jm]) | static_cast<unsigned>(srcB[jm]) << 16; oj[k] = ord[jm];
-        }
-    }
-    const int per = (n_rows + static_cast<int>(gridDim.x) - 1) / static_cast<int>(gridDim.x);
-    const int w0 = blockIdx.x * per, w1 = min(n_rows, w0 + per);
-    if (w0 >= w1) return;
-    const int nvec = lds_row >> 1;
-    d2_t pre[kS64Pre];
-    auto fetch = [&](int r) {
-        const d2_t *g2 = reinterpret_cast<const d2_t *>(psi + (long long)r * ld_prev);
-#pragma unroll
-        for (int k = 0; k < kS64Pre; ++k) pre[k] = g2[min(tid + k * nt, nvec - 1)];
-    };
-    auto to_lds = [&]() {
-        __syncthreads();                                  // the gathers from the previous row are done
-        d2_t *s2 = reinterpret_cast<d2_t *>(srow);
-#pragma unroll
-        for (int k = 0; k < kS64Pre; ++k) { const int q = tid + k * nt; if (q < nvec) s2[q] = pre[k]; }
-        __syncthreads();
-    };
-    // the row staged after (w, A just staged?): B of w, else the first A change / B source of the following rows; -1: none left
-    auto next_stage = [&](int w, bool after_a, int cur_a) -> int {
-        if (after_a) { const int b = srcB[rows ? rows[w] : w]; if (b != n_prev) return b; }
-        for (int v = w + 1; v < w1; ++v) {
-            const int i2 = rows ? rows[v] : v;
-            if (srcA[i2] != cur_a) return srcA[i2];
-            if (srcB[i2] != n_prev) return srcB[i2];
-        }
-        return -1;
-    };
-    int cur_a = -1;
-    {
-        const int i0 = rows ? rows[w0] : w0;
-        fetch(srcA[i0]);                                  // ("none" is the all-zero row: a parentless member's A)
-    }
-    for (int w = w0; w < w1; ++w) {
-        const int i = rows ? rows[w] : w;
-        const long long orow = out_rows ? out_rows[w] : i;
-        const int Ai = srcA[i], Bi = srcB[i], oi = ord[i];
-        const bool new_i = oi < 0;
-        const int ord_i = oi & kOrdMask;
-        unsigned z1 = 0;                                  // opaque zero (see level_full64_kernel)
-        asm volatile("" : "+s"(z1));
-        if (Ai != cur_a) {                                // stage A, keep its terms
-            to_lds();
-            cur_a = Ai;
-            const int nx = next_stage(w, true, cur_a);
-            if (nx >= 0) fetch(nx);
-#pragma unroll
-            for (int k = 0; k < kS64Cols; ++k) {
-                const unsigned pkz = pkj[k] ^ z1;
-                va[k] = srow[pkz & 0xffffu]; vb[k] = srow[pkz >> 16];
-            }
-        }
-        const bool has_b = Bi != n_prev;
-        if (has_b) {
-            to_lds();                                     // row B
-            const int nx = next_stage(w, false, cur_a);
-            if (nx >= 0) fetch(nx);
-        }
-        double *orowp = out + orow * ld;
-#pragma unroll
-        for (int k = 0; k < kS64Cols; ++k) {
-            const int j = j0 + tid + k * nt;
-            if (j >= ld) break;
-            double v = 0.0;
-            if (jmv[k] >= 0) {
-                const unsigned pkz = pkj[k] ^ z1;
-                const int ojz = oj[k] ^ static_cast<int>(z1);
-                if (jmv[k] == i && new_i) {
-                    v = 0.5 + 0.5 * (has_b ? srow[Ai] : 0.0);     // Psi[B][A] = Psi[A][B] (bit-symmetric levels)
-                } else {
-                    const double sc = (new_i ? 0.5 : 1.0) * (ojz < 0 ? 0.5 : 1.0);
-                    const double a = va[k], b = vb[k];
-                    const double c = has_b ? srow[pkz & 0xffffu] : 0.0, d = has_b ? srow[pkz >> 16] : 0.0;
-                    const bool i_hi = ord_i > (ojz & kOrdMask);
-                    const double x = i_hi ? b : c, y = i_hi ? c : b;
-                    v = ((a + x) + (y + d)) * sc;
-                }
-            }
-            orowp[j] = v;
-            if ((k & 1) == 1) __builtin_amdgcn_sched_barrier(0);
-        }
-    }
-}
-
-__global__ void half_identity64_kernel(double *m, long long ld, int n, const int *out_rows, int n_rows, const int *colmap)
-{
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= n_rows) return;
-    // row k of the output is member (colmap ? colmap[k'] ...): used only for the all-founders case,
-    // where every member is a proband: diagonal of the delivered matrix
-    (void)colmap; (void)out_rows; (void)n;
-    m[(long long)k * ld + k] = 0.5;
-}
-
 // ---- SMALL: a run of consecutive level steps whose cuts have <= kSmallMax members, fused -----
 // Deep small pedigrees (hundreds of generations of a few dozen individuals: breeding lines,
 // cfg5) are launch-bound: a level is a few microseconds of work.  One workgroup keeps BOTH
@@ -1766,10 +1508,6 @@ __global__ void half_identity64_kernel(double *m, long long ld, int n, const int
 // (src/compute.jl:105-158 on Float32 storage, one rounding per entry per level).
 constexpr int kSmallMax = 128;                // members per cut
 constexpr int kSmallPitch = kSmallMax + 4;    // row pitch in LDS; column / row n ("none") stay zero
-struct SmallStep {
-    const int *srcA, *srcB, *ord;
-    int n_prev, n;
-};
 
 __global__ void __launch_bounds__(1024)
 levels_small_kernel(const SmallStep *__restrict__ steps, int n_run, const float *__restrict__ in, long long ld_in,
@@ -2015,62 +1753,13 @@ colperm_pipe_kernel(const float *__restrict__ in, float *__restrict__ out, long 
 // ---------------------------------------------------------------------------------------------
 static thread_local std::string g_last_error;
 
-static int fail(int code, const std::string &msg) { g_last_error = msg; return code; }
-
-using genphi::PhaseTrace;      // GENPHI_TRACE=1: wall-clock marks of the phases of a call on stderr (planner.h)
-int genphi_set_error(int code, const std::string &msg) { return fail(code, msg); }   // for loader.cpp
-
-#define HIP_TRY(expr)                                                                           \
-    do {                                                                                        \
-        hipError_t e_ = (expr);                                                                 \
-        if (e_ != hipSuccess)                                                                   \
-            return fail(GENPHI_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_));  \
-    } while (0)
-
-// As HIP_TRY, for an allocation that went through DevBuf::reserve: `what` is the text the message had when the call was spelled out on
-// the plan's raw pointer (tests/golden/sweep_host_contract.json pins it) -- frozen message text, not code, as in resident.h.
-#define HIP_TRY_AS(what, expr)                                                                  \
-    do {                                                                                        \
-        hipError_t e_ = (expr);                                                                 \
-        if (e_ != hipSuccess)                                                                   \
-            return fail(GENPHI_ERR_DEVICE, std::string(what ": ") + hipGetErrorString(e_));     \
-    } while (0)
+int genphi_set_error(int code, const std::string &msg) { g_last_error = msg; return code; }      // (error.h; `fail` in this unit, plan_device.h)
 
 // pk / ord are padded so that the unrolled per-thread column loops need no clamp
 constexpr size_t kIdxPad = 32 * 1024;
 // ... which only the SPLIT kernels do (a chunk of up to 24 x 1024 columns whatever the cut's width); the FULL kernel reads whole quads
 // (a deep pedigree of 200 tiny levels carried 52 MB of padding: 11 of the 14 ms of its first call)
 static size_t idx_pad(const LevelStep &s) { return s.mode == genphi::kModeSplit ? kIdxPad : 1024; }
-
-// Work lists of a SPLIT launch: the hub walk of planner.h (WalkLists) as device arrays.
-//   desc : per work row (storage row, output row, B source, rank word)
-//   seg  : per segment (first work row, hub row, leading rows without B source, type) + terminators
-//   run  : first segment of every run + terminator
-// level_split_fast_kernel takes runs as its items, level_split_kernel (grouping-exact: it keeps one 32-bit rank
-// mask per child in 4 VGPRs, hence segments of at most 4 children) single segments.
-struct DeviceGroups {
-    int4 *desc = nullptr, *seg = nullptr;
-    int4 *run = nullptr;       // (first segment, hub row | n0 << 16, its rows [z, w)) per run + terminator
-    int n_segs = 0, n_runs = 0;
-};
-
-struct DeviceStep {
-    int *srcA = nullptr, *srcB = nullptr, *ord = nullptr, *work = nullptr;
-    unsigned *pk = nullptr;
-    DeviceGroups groups;       // SPLIT
-    // WIDE: row descriptors of rows_compact_kernel for the cut's own rows (A, B, row, scale exponent)
-    // and for the parent rows of Psi_P; the parents' positions; the new rows as a work list
-    int4 *rowdesc = nullptr, *pardesc = nullptr;
-    int *parents = nullptr, *newrows = nullptr;
-    int *pstart = nullptr;     // drag_rows_kernel: first parent of each chunk of 8192 dragged columns
-    int *idx = nullptr;        // source column of every dragged member (= srcA; the sources' SLOTS when the source cut is stored by slot:
-                               // then rowdesc / pardesc / parents hold slots too, see LevelStep::src_slots)
-    int *blk_slot = nullptr;   // (in-place steps) first slot of every granule of 64 new members
-    int2 *tiles = nullptr;     // (in-place steps) the kFT-column tiles of the slot ranges that hold dragged members: (first column, end of the range)
-    int n_tiles = 0;
-    int tile_cols = 256;       // ... their width: 128 for small launches (more, smaller workgroups: cfg3s -2.4 %), 256 otherwise (GENPHI_STAY_TILE forces one)
-    int nn = -1;               // index of the new x new sub-step in genphi_plan::nn_steps / nn_dsteps
-};
 
 // Lays arrays out in ONE device allocation, each on a 256-byte boundary.  The same layout code runs twice: first against a packer
 // without memory -- put() only adds up the size (blob_size) --, then, after the allocation, against the host image and the device
@@ -2118,95 +1807,6 @@ static void put_groups(const genphi::WalkLists &w, DeviceGroups &d, BlobPacker &
     d.n_segs = static_cast<int>(w.seg4.size() / 4) - 2;
     d.n_runs = static_cast<int>(w.run.size() / 4) - 1;
 }
-
-constexpr int kGuardWord = 3;      // d_gcnt[kGuardWord]: the encode guard of a sweep's narrow cuts (group counts use words 0 and 1 of a step's four)
-
-// What exists only while the plan is uploaded.  free_device assigns a default-constructed one: every block goes back to the cache
-// (devbuf.h) and every pointer, size, flag and cache key is what it is before the first upload -- a member added here is reset with the rest.
-// genphi_plan_device_bytes counts idx_blob, lazy_blobs, d_shard_blob, scratch, buf[], result, final_tmp, psi_p, nn_tmp, d_queues,
-// buf64[], result64 and the sparse levels' own figure.  It does NOT count d_glist, d_small, d_cert_p, d_shard_rows / d_shard_out_rows,
-// sh_blob and d_perm_rows (small next to the rest; tests/golden/sweep_host_contract.json pins the figure as it is).
-struct PlanDevice {
-    bool on_device = false;
-    int device = -1;
-    int n_cus = 256;
-    hipStream_t stream = nullptr;
-    // The owned blocks, declared in the order in which a release hands them back to the cache (the assignment in free_device goes member
-    // by member): the cache evicts its oldest idle blocks first and breaks ties between equal sizes by age, so the order decides which
-    // blocks the next plan finds.  Everything else in this struct owns no device memory.
-    DevBuf<char> idx_blob;                       // every index array of the upload (BlobPacker); dsteps / nn_dsteps point into it
-    std::vector<DevBuf<char>> lazy_blobs;        // walk lists uploaded after the index blob (ensure_groups)
-    DevBuf<int> d_shard_rows, d_shard_out_rows;
-    DevBuf<char> d_shard_blob;
-    DevBuf<int> d_glist;
-    DevBuf<int> d_queues;           // 16 work-queue counters per slot (a level step or a new x new sub-step), then d_gcnt and d_cert
-    DevBuf<SmallStep> d_small;      // one entry per level step (levels_small_kernel)
-    DevBuf<char> sh_blob;
-    DevBuf<char> scratch;                        // the queries' staging block (resident_scratch: grown on demand)
-    DevBuf<float> buf[2];                        // the two level buffers (sz.buf_of[][c]: which one holds cut c)
-    DevBuf<float> result, final_tmp;
-    DevBuf<float> psi_p;                         // WIDE: compacted parent matrix Psi[parents][parents]
-    DevBuf<int> d_cert_p;                        // certificates of the rows of psi_p ...
-    DevBuf<float> nn_tmp;                        // in-place WIDE steps: the new x new block before it is scattered to the new members' slots
-    // Float64-storage sweeps (gen.f, pairwise phi): own level matrices and result
-    DevBuf<double> buf64[2], result64;
-    DevBuf<int> d_perm_rows;                     // storage member of each resident proband row (f64 sweeps)
-
-    std::vector<DeviceStep> dsteps;
-    std::vector<const LevelStep *> nn_steps;     // new x new sub-steps of the WIDE steps (owned by the plan's steps)
-    std::vector<DeviceStep> nn_dsteps;
-    genphi::DeviceSizes sz;                      // buf_of[], cert_cut[], cert_off[] and the buffer sizes of this plan (device_sizes.h)
-    int *d_cert_t = nullptr;                     // (inside d_cert_p's block) certificates of the rows of nn_tmp
-    size_t cert_p_words = 0;
-    int *d_final_perm = nullptr;                 // (inside idx_blob)
-    int *d_final_slots = nullptr;                // (the proband cut stayed in place) slot of every proband, result order (inside idx_blob)
-    size_t sweep_words = 0;         // ints of d_queues' block (cleared by ONE memset per sweep)
-    hipGraphExec_t graph_exec = nullptr;   // captured sweep (see genphi_compute_device)
-    // key = (kernel, r0, r1, need_perm, alloc_gen).  A captured graph bakes raw device pointers into
-    // its kernel nodes, so every (re)allocation of a buffer the sweep touches bumps alloc_gen:
-    // the stale graph can then never be replayed, and a fresh eager run precedes the next capture.
-    long long graph_key[5] = {0, 0, 0, 0, 0}, eager_key[5] = {0, 0, 0, 0, 0};
-    bool level_bufs_ready = false;         // buf[] / psi_p exist (ensure_level_buffers)
-    int level_bufs_from = 0;               // ... buf[] sized for the dense matrices of cuts >= this one (the cuts before it live as row lists)
-    bool eager_valid = false;
-    DeviceGroups shard_groups;      // SPLIT lists of the last step restricted to the shard (arrays inside d_shard_blob)
-    // exactness certificates: one word per row of every level matrix (sz.cert_off[c] = first word of
-    // cut c), the per-launch group flags (d_glist) and [certified, other] group counts per step
-    int *d_cert = nullptr, *d_gcnt = nullptr;    // (inside d_queues' block)
-    // narrow cuts (cut_format.h): the format of every cut in the sweep being enqueued (empty: all Float32), and the host copy of the
-    // encode guard -- word kGuardWord of d_gcnt, a spare word of step 0's group counts, cleared with the rest at the start of a sweep
-    std::vector<int> cut_fmt;
-    unsigned *guard_host = nullptr;              // (pinned; cached_pinned)
-    bool guard_pending = false;
-    // Row shards: an upper level only needs the rows its shard's last-level rows descend from
-    // (~80 % of a cut at 8 shards of cfg4, 55-72 % in the two levels below the last).  Per
-    // intermediate step: restricted work list (+ SPLIT descriptors) of the current shard (arrays inside sh_blob).
-    struct ShardStep { int *rows = nullptr; DeviceGroups groups; int n_rows = 0; };
-    std::vector<ShardStep> sh_steps;
-    bool sh_valid = false;
-    int64_t shard_r0 = -1, shard_r1 = -1;
-    bool stay_active = false;                    // this sweep keeps WIDE levels in place (set per compute call)
-    bool res_f64 = false;                        // the resident result is the Float64 one
-    int64_t res_ld = 0, res_row_begin = 0, res_n_rows = 0;
-    bool res_known = false;                      // a genphi_compute_device call has set the resident row range (it may be empty)
-    genphi::OverCache over;                      // genphi_result_over's offsets of the resident result: dropped with it (set_resident_rows)
-    // zero-aware leading levels (sparse_levels.h): created and calibrated by the first product sweep of the plan
-    genphi::SparseLevels *sparse = nullptr;      // (sparse_levels_destroy; its index arrays live inside idx_blob)
-    bool sparse_tried = false;
-    std::vector<hipEvent_t> events;
-};
-
-// The plan: what the planner made of the pedigree and what survives a release of the device, then the device state (created lazily
-// by the first compute)
-struct genphi_plan : PlanDevice {
-    Plan plan;
-    genphi::PlanOptions popt;
-    Tuning tun;                                  // environment hooks, read once in genphi_plan_create
-    genphi_step_fn step_hook = nullptr;          // genphi_plan_set_step_hook: called before every level step of a Float32 sweep
-    void *step_hook_user = nullptr;
-    long long alloc_gen = 1;                     // (graph_key; only ever grows: a graph captured before a release is never replayed after it)
-    int alloc_count = 0;                         // device allocations of uploads so far (GENPHI_TEST_FAIL_ALLOC)
-};
 
 // The resident row range changes -- a compute call begins, the device is released -- and what was derived from the previous result goes.
 static void set_resident_rows(genphi_plan *p, int64_t row_begin, int64_t n_rows, bool known)
@@ -2688,7 +2288,7 @@ int genphi::resident_scratch(genphi_plan *p, size_t bytes, char **scratch)
 }
 genphi::OverCache &genphi::resident_over_cache(genphi_plan *p) { return p->over; }
 
-static hipError_t set_max_lds(const void *fn, size_t bytes)
+hipError_t set_max_lds(const void *fn, size_t bytes)
 {
     // dynamic LDS above 64 KB has to be opted into per kernel AND per device; remember the largest
     // request of each (device, kernel).  Plans on distinct devices may run on distinct host threads.
@@ -3156,7 +2756,7 @@ static int launch_wide_level(genphi_plan *p, int step, const float *psi, float *
 // steps and runs them once to count the non-zero entries of every cut; that fixes k, the last cut kept as row lists, for the life of the
 // plan (values do not depend on k; GENPHI_FLAG_NO_SPARSE runs the same plan densely).  The Float32 product sweep and the Float64-storage
 // sweep share the lists (integer values: exact for both).
-static int ensure_sparse_levels(genphi_plan *p, int kernel, PhaseTrace &trace)
+int ensure_sparse_levels(genphi_plan *p, int kernel, PhaseTrace &trace)
 {
     if (kernel != 0 || p->sparse_tried) return GENPHI_OK;
     p->sparse_tried = true;
@@ -3180,155 +2780,9 @@ static int ensure_sparse_levels(genphi_plan *p, int kernel, PhaseTrace &trace)
     return GENPHI_OK;
 }
 
-// The whole sweep with Float64 level matrices (see level_naive64_kernel): rows [r0, r1) of the
-// proband matrix end up in p->result64 (row pitch = pitch of the last cut).
-static int compute_f64(genphi_plan *p, int64_t r0, int64_t r1, int kernel, genphi_stats *stats, bool timing, bool no_sparse)
-{
-    const Plan &pl = p->plan;
-    const int L = pl.n_levels, n_steps = L - 1;
-    const int64_t N = pl.n_pro, ldN = pl.ld[L - 1], n_rows = r1 - r0;
-    HIP_TRY_AS("genphi::cached_malloc(reinterpret_cast<void **>(ptr), std::max<size_t>(need, 1) * sizeof(double))", p->result64.reserve(static_cast<size_t>(n_rows * ldN)));
-    int rc;
-    // storage member of each resident row (the last cut may be stored in [dragged, new] order)
-    std::vector<int> srow(n_rows), orow(n_rows);
-    for (int64_t k = 0; k < n_rows; ++k) { srow[k] = pl.final_perm.empty() ? static_cast<int>(r0 + k) : pl.final_perm[r0 + k]; orow[k] = static_cast<int>(k); }
-    HIP_TRY_AS("genphi::cached_malloc(reinterpret_cast<void **>(&p->d_perm_rows), 2 * n_rows * sizeof(int))", p->d_perm_rows.reserve(static_cast<size_t>(2 * n_rows)));
-    HIP_TRY(hipMemcpyAsync(p->d_perm_rows, srow.data(), n_rows * sizeof(int), hipMemcpyHostToDevice, p->stream));
-    HIP_TRY(hipMemcpyAsync(p->d_perm_rows + n_rows, orow.data(), n_rows * sizeof(int), hipMemcpyHostToDevice, p->stream));
-    HIP_TRY(hipStreamSynchronize(p->stream));           // host vectors go out of scope
-    if (n_steps == 0) {
-        // all probands parentless: 1/2 I (src/compute.jl:271-274, loop skipped); members = probands in order
-        HIP_TRY(hipMemsetAsync(p->result64, 0, static_cast<size_t>(n_rows * ldN) * sizeof(double), p->stream));
-        std::vector<double> half(1, 0.5);
-        for (int64_t k = 0; k < n_rows; ++k)
-            HIP_TRY(hipMemcpyAsync(p->result64 + k * ldN + (r0 + k), half.data(), sizeof(double), hipMemcpyHostToDevice, p->stream));
-        HIP_TRY(hipStreamSynchronize(p->stream));
-        return GENPHI_OK;
-    }
-    if (timing && n_steps + 2 > GENPHI_MAX_STAT_LEVELS) return fail(GENPHI_ERR_ARG, "too many levels for timing stats");
-    if (timing)
-        while (static_cast<int>(p->events.size()) < n_steps + 3) {
-            hipEvent_t e; HIP_TRY(hipEventCreate(&e)); p->events.push_back(e);
-        }
-    // the leading cuts as lists of their non-zero entries here too (integer values are exact for Float64 as for Float32, sparse_levels.h):
-    // the first dense matrix is written in Float64, compactly
-    {
-        PhaseTrace trace;
-        rc = ensure_sparse_levels(p, kernel, trace);
-        if (rc) return rc;
-    }
-    const int sparse_k = (kernel == 0 && p->sparse && !no_sparse) ? genphi::sparse_levels_k(p->sparse) : -1;
-    {   // Float64 level matrices of the cuts that exist as matrices (cuts 0..sparse_k live as row lists): genea140 2 x 1.5 GB -> 2 x 0.2
-        size_t need[2] = {0, 0};
-        for (int c = sparse_k + 1; c + 1 < L; ++c) need[c & 1] = std::max(need[c & 1], static_cast<size_t>((pl.cut_sizes[c] + 1) * pl.ld[c]));
-        for (int b = 0; b < 2; ++b)
-            if (need[b]) HIP_TRY_AS("genphi::cached_malloc(reinterpret_cast<void **>(ptr), std::max<size_t>(need, 1) * sizeof(double))", p->buf64[b].reserve(need[b]));
-    }
-    const int64_t n0 = pl.cut_sizes[0], ld0 = pl.ld[0];
-    // LDS a workgroup may fill with staged Float64 source rows: 160 KB, or the GENPHI_LDS_CAP_FLOATS test budget (4 bytes a
-    // float), which sends small cuts through level_split64_kernel / level_naive64_kernel too
-    const size_t lds_budget = p->tun.lds_cap_floats >= 16 ? std::min<size_t>(160 * 1024, 4 * static_cast<size_t>(p->tun.lds_cap_floats))
-                                                           : 160 * 1024;
-    if (timing) HIP_TRY(hipEventRecord(p->events[0], p->stream));
-    if (sparse_k < 0) {
-        HIP_TRY(hipMemsetAsync(p->buf64[0], 0, static_cast<size_t>((n0 + 1) * ld0) * sizeof(double), p->stream));
-        hipLaunchKernelGGL(half_identity64_kernel, dim3(static_cast<unsigned>((n0 + 255) / 256)), dim3(256), 0, p->stream, p->buf64[0],
-                           static_cast<long long>(ld0), static_cast<int>(n0), static_cast<const int *>(nullptr), static_cast<int>(n0),
-                           static_cast<const int *>(nullptr));
-        HIP_TRY(hipGetLastError());
-    }
-    for (int s = 0; s < n_steps; ++s) {
-        const LevelStep &st = pl.steps[s];
-        const DeviceStep &d = p->dsteps[s];
-        if (s <= sparse_k) {
-            std::string serr;
-            rc = s < sparse_k ? genphi::sparse_levels_enqueue_step(p->sparse, s, p->stream, serr)
-                              : genphi::sparse_levels_enqueue_dense(p->sparse, p->buf64[(s + 1) & 1], true, true, st.ld, st.ld, p->stream, serr);
-            if (rc == GENPHI_OK && s == sparse_k) rc = genphi::sparse_levels_enqueue_flags(p->sparse, p->stream, serr);
-            if (rc) return fail(rc, "sparse levels: " + serr);
-            if (timing) HIP_TRY(hipEventRecord(p->events[s + 1], p->stream));
-            if (stats && s < GENPHI_MAX_STAT_LEVELS) stats->level_rows[s] = st.n;
-            continue;
-        }
-        const double *psi = p->buf64[s & 1];
-        const bool last = s == n_steps - 1;
-        double *out = last ? p->result64 : p->buf64[(s + 1) & 1];
-        const int rows_n = last ? static_cast<int>(n_rows) : static_cast<int>(st.n);
-        const int *k_rows = last ? p->d_perm_rows : static_cast<const int *>(nullptr);
-        const int *k_orows = last ? p->d_perm_rows + n_rows : static_cast<const int *>(nullptr);
-        const int *k_colmap = (last && !pl.final_perm.empty()) ? p->d_final_perm : static_cast<const int *>(nullptr);
-        const int lds_row64 = static_cast<int>((st.n_prev + 1 + 1) / 2 * 2);
-        const size_t lds64 = 2 * static_cast<size_t>(lds_row64) * sizeof(double);
-        if (kernel != 1 && lds64 <= lds_budget && rows_n > 0) {
-            // both Float64 source rows fit in LDS (cuts up to 10,239 members): the row-staged kernel
-            HIP_TRY(set_max_lds(reinterpret_cast<const void *>(level_full64_kernel), lds64));
-            // (columns per thread <= kF64Cols, row pieces per thread <= kF64Pre for each of these block sizes)
-            const int bs = st.ld <= 64 * kF64Cols && lds_row64 <= 2 * 64 * kF64Pre ? 64 : (st.ld <= 256 * kF64Cols && lds_row64 <= 2 * 256 * kF64Pre ? 256 : 512);
-            const int chunks = static_cast<int>((st.ld + bs * kF64Cols - 1) / (bs * kF64Cols));
-            // resident workgroups per CU: LDS, and the kernel's ~240 VGPRs (two waves per SIMD)
-            const int per_cu = static_cast<int>(std::min<size_t>(512 / bs, std::max<size_t>(1, (160 * 1024) / std::max<size_t>(lds64, 1))));
-            const int grid = std::min(rows_n, std::max(1, p->n_cus * per_cu / chunks));
-            hipLaunchKernelGGL(level_full64_kernel, dim3(static_cast<unsigned>(grid), static_cast<unsigned>(chunks)), dim3(bs), lds64, p->stream, psi,
-                               static_cast<long long>(st.ld_prev), static_cast<int>(st.n_prev), out, static_cast<long long>(st.ld), d.srcA, d.srcB,
-                               d.ord, k_rows, k_orows, k_colmap, static_cast<int>(st.n), lds_row64, rows_n);
-        } else if (kernel != 1 && static_cast<size_t>(lds_row64) * sizeof(double) <= lds_budget && rows_n > 0 && st.n_prev < 65535) {
-            // one Float64 source row fits (cuts up to 20,479 members): the one-row-at-a-time kernel, rows in the step's work order
-            // (same A source adjacent) where the step has one
-            const size_t lds1 = static_cast<size_t>(lds_row64) * sizeof(double);
-            HIP_TRY(set_max_lds(reinterpret_cast<const void *>(level_split64_kernel), lds1));
-            const int chunks = static_cast<int>((st.ld + 512 * kS64Cols - 1) / (512 * kS64Cols));
-            const int *w_rows = last ? k_rows : ((st.mode != genphi::kModeWide && static_cast<int64_t>(st.work.size()) == st.n) ? d.work : static_cast<const int *>(nullptr));
-            const int grid_x = std::min(rows_n, std::max(1, p->n_cus / chunks) * 2);     // (two pieces per CU and chunk: the tail)
-            hipLaunchKernelGGL(level_split64_kernel, dim3(static_cast<unsigned>(grid_x), static_cast<unsigned>(chunks)), dim3(512), lds1, p->stream, psi,
-                               static_cast<long long>(st.ld_prev), static_cast<int>(st.n_prev), out, static_cast<long long>(st.ld), d.srcA, d.srcB,
-                               d.ord, w_rows, k_orows, k_colmap, static_cast<int>(st.n), lds_row64, rows_n);
-        } else {
-            dim3 grid(static_cast<unsigned>(rows_n), static_cast<unsigned>((st.ld + 255) / 256));
-            hipLaunchKernelGGL(level_naive64_kernel, grid, dim3(256), 0, p->stream, psi, static_cast<long long>(st.ld_prev),
-                               static_cast<int>(st.n_prev), out, static_cast<long long>(st.ld), static_cast<int>(st.n), d.srcA, d.srcB, d.ord,
-                               k_rows, k_orows, k_colmap, static_cast<int>(st.n));
-        }
-        HIP_TRY(hipGetLastError());
-        if (!last)           // the all-zero "none" row of this level
-            HIP_TRY(hipMemsetAsync(out + st.n * st.ld, 0, static_cast<size_t>(st.ld) * sizeof(double), p->stream));
-        if (timing) HIP_TRY(hipEventRecord(p->events[s + 1], p->stream));
-        if (stats && s < GENPHI_MAX_STAT_LEVELS) stats->level_rows[s] = rows_n;
-    }
-    (void)N;
-    HIP_TRY(hipStreamSynchronize(p->stream));
-    if (sparse_k >= 0 && !genphi::sparse_levels_flags_ok(p->sparse))
-        return fail(GENPHI_ERR_DEVICE, "sparse levels: a row list did not have the length the plan recorded (internal error)");
-    if (timing) {
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, p->events[0], p->events[n_steps]));
-        stats->total_ms = ms;
-        for (int s = 0; s < n_steps; ++s) {
-            HIP_TRY(hipEventElapsedTime(&ms, p->events[s], p->events[s + 1]));
-            stats->level_ms[s] = ms;
-        }
-        stats->final_ms = stats->level_ms[n_steps - 1];
-        stats->timed = 1;
-    }
-    return GENPHI_OK;
-}
-
-// ---- one Float32 sweep (genphi_compute_device), phase by phase ------------------------------
-
-// The constants of one call
-struct SweepCall {
-    int kernel = 0;
-    int64_t r0 = 0, n_rows = 0;      // the shard: rows [r0, r0 + n_rows) of the proband matrix
-    int sparse_k = -1;               // cuts 0..sparse_k are row lists (sparse_levels.h); -1: every level is a dense matrix
-    // last step WIDE: the whole level (every row, [dragged, new] storage order) goes to final_tmp, then the shard's rows are delivered in
-    // proband order (deliver_proband_order) ...
-    bool need_perm = false;
-    // ... unless the proband cut STAYED IN PLACE at the end of a run (Plan::final_slots): the last step then writes only the new probands'
-    // rows and columns into the run's matrix and the delivery reads from there, by slot -- one pass instead of a compaction + a
-    // permutation (genea140 with every individual a proband: the last step 7.7 -> ... ms).  The per-entry sweep (kernel = 1) knows no slots.
-    bool last_by_slot = false;
-    bool timing = false;
-    std::vector<int> ev_after;       // event recorded after step k (timing)
-};
+// ---- one sweep (genphi_compute_device), phase by phase --------------------------------------
+// Both storage types walk the same phases; a Float64-storage sweep (c.f64) takes prepare_buffers64 / enqueue_sweep64 of sweep_f64.hip
+// where a Float32 one takes prepare_buffers, ensure_shard_lists and run_sweep.
 
 // Argument check, the stats header and the rows the result will hold; *empty: no row to compute (nothing else to do)
 static int begin_call(genphi_plan *p, const genphi_opts *opts, genphi_stats *stats, SweepCall &c, bool *empty)
@@ -3337,7 +2791,10 @@ static int begin_call(genphi_plan *p, const genphi_opts *opts, genphi_stats *sta
     int64_t r0 = 0, r1 = pl.n_pro;
     if (opts && opts->row_end > 0) { r0 = opts->row_begin; r1 = opts->row_end; }
     if (r0 < 0 || r1 > pl.n_pro || r0 > r1) return fail(GENPHI_ERR_ARG, "row shard out of range");
+    c.f64 = opts && (opts->flags & GENPHI_FLAG_STORAGE_F64);
     c.kernel = opts ? opts->kernel : 0; c.r0 = r0; c.n_rows = r1 - r0; c.timing = opts && opts->timing && stats;
+    c.ev_after.resize(std::max(pl.n_levels - 1, 1));
+    for (int k = 0; k < static_cast<int>(c.ev_after.size()); ++k) c.ev_after[k] = k + 1;
     if (stats) {
         std::memset(stats, 0, sizeof(*stats));
         stats->n_steps = std::max(pl.n_levels - 1, 0);
@@ -3354,6 +2811,16 @@ static int begin_call(genphi_plan *p, const genphi_opts *opts, genphi_stats *sta
     return GENPHI_OK;
 }
 
+// The events of a timed sweep: n of them, for n - 3 level steps (event s + 1 after step s, one more after the last step's own launches)
+int ensure_events(genphi_plan *p, int n)
+{
+    if (n - 1 > GENPHI_MAX_STAT_LEVELS) return fail(GENPHI_ERR_ARG, "too many levels for timing stats");
+    while (static_cast<int>(p->events.size()) < n) {
+        hipEvent_t e; HIP_TRY(hipEventCreate(&e)); p->events.push_back(e);
+    }
+    return GENPHI_OK;
+}
+
 // Everything a Float32 sweep writes to: sparse levels, level buffers, timing events, the result, final_tmp, the shard's row arrays
 static int prepare_buffers(genphi_plan *p, SweepCall &c, bool no_sparse, PhaseTrace &trace)
 {
@@ -3366,11 +2833,9 @@ static int prepare_buffers(genphi_plan *p, SweepCall &c, bool no_sparse, PhaseTr
     rc = ensure_level_buffers(p, c.sparse_k + 1);       // (cuts 0..sparse_k never exist as matrices)
     if (rc) return rc;
     trace.mark("ensure_level_buffers");
-    if (c.timing && n_steps + 2 > GENPHI_MAX_STAT_LEVELS) return fail(GENPHI_ERR_ARG, "too many levels for timing stats");
     if (c.timing) {
-        while (static_cast<int>(p->events.size()) < n_steps + 3) {
-            hipEvent_t e; HIP_TRY(hipEventCreate(&e)); p->events.push_back(e);
-        }
+        rc = ensure_events(p, n_steps + 3);
+        if (rc) return rc;
     }
     const int64_t ldN = pl.ld[L - 1], n_rows = c.n_rows;
     rc = ensure_floats(p, p->result, genphi::result_floats(pl, n_rows));
@@ -3390,8 +2855,6 @@ static int prepare_buffers(genphi_plan *p, SweepCall &c, bool no_sparse, PhaseTr
         HIP_TRY_AS("genphi::cached_malloc(reinterpret_cast<void **>(&p->d_shard_rows), n_rows * sizeof(int))", p->d_shard_rows.reserve(n_rows));
         HIP_TRY_AS("genphi::cached_malloc(reinterpret_cast<void **>(&p->d_shard_out_rows), n_rows * sizeof(int))", p->d_shard_out_rows.reserve(n_rows));
     }
-    c.ev_after.resize(std::max(n_steps, 1));
-    for (int k = 0; k < static_cast<int>(c.ev_after.size()); ++k) c.ev_after[k] = k + 1;
     return GENPHI_OK;
 }
 
@@ -3499,7 +2962,22 @@ static int deliver_proband_order(genphi_plan *p, const SweepCall &c, const float
     return fail(GENPHI_ERR_ARG, "internal: colperm geometry");
 }
 
-// The sweep: every launch of one gen.phi, in stream order
+// (plan_device.h) cuts 0..sparse_k are row lists: a list step, or (s == sparse_k) the step that writes cut s+1 as a dense matrix
+int enqueue_list_step(genphi_plan *p, const SweepCall &c, int s, void *dst, bool f64_compact, int fmt, unsigned *guard)
+{
+    const LevelStep &st = p->plan.steps[s];
+    std::string serr;
+    // (f64 and compact of sparse_levels_enqueue_dense always travel together: only the Float64 sweep writes compactly, over the whole pitch)
+    int rc = s < c.sparse_k ? genphi::sparse_levels_enqueue_step(p->sparse, s, p->stream, serr)
+                            : genphi::sparse_levels_enqueue_dense(p->sparse, dst, f64_compact, f64_compact, st.ld, f64_compact ? st.ld : st.width,
+                                                                  p->stream, serr, fmt, guard);
+    if (rc == GENPHI_OK && s == c.sparse_k) rc = genphi::sparse_levels_enqueue_flags(p->sparse, p->stream, serr);
+    if (rc) return fail(rc, "sparse levels: " + serr);
+    if (c.timing) HIP_TRY(hipEventRecord(p->events[s + 1], p->stream));
+    return GENPHI_OK;
+}
+
+// The Float32 sweep: every launch of one gen.phi, in stream order
 static int enqueue_sweep(genphi_plan *p, SweepCall &c)
 {
     const Plan &pl = p->plan;
@@ -3538,14 +3016,8 @@ static int enqueue_sweep(genphi_plan *p, SweepCall &c)
         const float *psi = p->buf[bid[s]];
         if (p->step_hook) p->step_hook(s, n_steps, p->step_hook_user);
         if (s <= sparse_k) {
-            // cuts 0..sparse_k are row lists: a list step, or (s == sparse_k) the step that writes cut s+1 as a dense matrix
-            std::string serr;
-            rc = s < sparse_k ? genphi::sparse_levels_enqueue_step(p->sparse, s, p->stream, serr)
-                              : genphi::sparse_levels_enqueue_dense(p->sparse, p->buf[bid[s + 1]], false, false, st.ld, st.width, p->stream, serr,
-                                                                    p->cut_fmt[s + 1], reinterpret_cast<unsigned *>(p->d_gcnt + kGuardWord));
-            if (rc == GENPHI_OK && s == sparse_k) rc = genphi::sparse_levels_enqueue_flags(p->sparse, p->stream, serr);
-            if (rc) return fail(rc, "sparse levels: " + serr);
-            if (timing) HIP_TRY(hipEventRecord(p->events[s + 1], p->stream));
+            rc = enqueue_list_step(p, c, s, p->buf[bid[s + 1]], false, p->cut_fmt[s + 1], reinterpret_cast<unsigned *>(p->d_gcnt + kGuardWord));
+            if (rc) return rc;
             continue;
         }
         // a run of >= 2 small intermediate steps goes through ONE launch (levels_small_kernel; GENPHI_NO_SMALL: per-level launches only)
@@ -3623,7 +3095,6 @@ static int run_sweep(genphi_plan *p, SweepCall &c, bool graph_allowed)
                               (c.need_perm ? 1 : 0) | (c.sparse_k >= 0 ? 2 : 0), p->alloc_gen};
     const bool same_as_eager = p->eager_valid && std::memcmp(key, p->eager_key, sizeof(key)) == 0;
     const bool use_graph = !c.timing && !p->tun.no_graph && graph_allowed && same_as_eager && n_steps >= 8 && !p->step_hook;
-    if (c.timing) HIP_TRY(hipEventRecord(p->events[0], p->stream));
     if (!use_graph) {
         const int rc = enqueue_sweep(p, c);
         if (rc) return rc;
@@ -3662,11 +3133,22 @@ static int read_timing(genphi_plan *p, const SweepCall &c, genphi_stats *stats)
         stats->level_ms[s] = ms;
     }
     stats->final_ms = stats->level_ms[ne - 1];
-    if (n_steps > 0) {
+    if (n_steps > 0 && !c.f64) {      // (a Float64 sweep delivers in its last step: no event n_steps + 1 was recorded, perm_ms stays 0)
         HIP_TRY(hipEventElapsedTime(&ms, p->events[n_steps + 1], p->events[n_steps]));
         stats->perm_ms = ms;
     }
     stats->timed = 1;
+    return GENPHI_OK;
+}
+
+// What a finished sweep left for the host to look at: the row lists' error flags, and the encode guard of a Float32 sweep's narrow cuts
+// (a Float64 sweep has none and never sets guard_pending; one left over from the Float32 sweep before it is not its business)
+static int check_sweep(const genphi_plan *p, const SweepCall &c)
+{
+    if (c.sparse_k >= 0 && !genphi::sparse_levels_flags_ok(p->sparse))
+        return fail(GENPHI_ERR_DEVICE, "sparse levels: a row list did not have the length the plan recorded (internal error)");
+    if (!c.f64 && p->guard_pending && *p->guard_host != 0u)
+        return fail(GENPHI_ERR_DEVICE, "narrow cuts: an entry was not an integer of its cut's unit or did not fit its format (internal error)");
     return GENPHI_OK;
 }
 
@@ -3686,29 +3168,28 @@ int genphi_compute_device(genphi_plan *p, const genphi_opts *opts, genphi_stats 
     rc = upload_plan(p, opts ? opts->device : -1);
     if (rc) return rc;
     trace.mark("upload_plan");
-    p->res_f64 = flags & GENPHI_FLAG_STORAGE_F64;
-    if (p->res_f64) {
-        p->res_ld = pl.ld[pl.n_levels - 1];
-        return compute_f64(p, c.r0, c.r0 + c.n_rows, c.kernel, stats, c.timing, flags & GENPHI_FLAG_NO_SPARSE);
+    p->res_f64 = c.f64;
+    if (!c.f64 && p->popt.indices_only) return fail(GENPHI_ERR_ARG, "internal: an indices-only plan serves Float64-storage sweeps only");
+    rc = c.f64 ? prepare_buffers64(p, c, flags & GENPHI_FLAG_NO_SPARSE, trace) : prepare_buffers(p, c, flags & GENPHI_FLAG_NO_SPARSE, trace);
+    if (rc) return rc;
+    if (!c.f64) {
+        rc = ensure_shard_lists(p, c);
+        if (rc) return rc;
+        trace.mark("shard lists");
     }
-    if (p->popt.indices_only) return fail(GENPHI_ERR_ARG, "internal: an indices-only plan serves Float64-storage sweeps only");
-    rc = prepare_buffers(p, c, flags & GENPHI_FLAG_NO_SPARSE, trace);
-    if (rc) return rc;
-    rc = ensure_shard_lists(p, c);
-    if (rc) return rc;
-    trace.mark("shard lists");
-    rc = run_sweep(p, c, !(flags & GENPHI_FLAG_NO_GRAPH));
+    // (a Float64 sweep is always enqueued afresh: never captured, and the keys of the Float32 sweep's graph are not its to touch)
+    if (c.timing) HIP_TRY(hipEventRecord(p->events[0], p->stream));
+    rc = c.f64 ? enqueue_sweep64(p, c) : run_sweep(p, c, !(flags & GENPHI_FLAG_NO_GRAPH));
     if (rc) return rc;
     for (int s = 0, n_steps = pl.n_levels - 1; stats && s < n_steps && s < GENPHI_MAX_STAT_LEVELS; ++s)      // the rows every step computed
-        stats->level_rows[s] = s == n_steps - 1 ? (c.need_perm ? pl.steps[s].n : c.n_rows) : runs_shard_list(p, s) ? p->sh_steps[s].n_rows : pl.steps[s].n;
+        stats->level_rows[s] = s == n_steps - 1 ? (c.need_perm ? pl.steps[s].n : c.n_rows)
+                                                : (!c.f64 && runs_shard_list(p, s)) ? p->sh_steps[s].n_rows : pl.steps[s].n;
     if (c.timing && pl.n_levels == 1) HIP_TRY(hipEventRecord(p->events[1], p->stream));
     trace.mark("sweep enqueued");
     HIP_TRY(hipStreamSynchronize(p->stream));
     trace.mark("sweep done");
-    if (c.sparse_k >= 0 && !genphi::sparse_levels_flags_ok(p->sparse))
-        return fail(GENPHI_ERR_DEVICE, "sparse levels: a row list did not have the length the plan recorded (internal error)");
-    if (p->guard_pending && *p->guard_host != 0u)
-        return fail(GENPHI_ERR_DEVICE, "narrow cuts: an entry was not an integer of its cut's unit or did not fit its format (internal error)");
+    rc = check_sweep(p, c);
+    if (rc) return rc;
     return c.timing ? read_timing(p, c, stats) : GENPHI_OK;
 }
 

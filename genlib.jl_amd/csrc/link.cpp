@@ -8,8 +8,7 @@
 #include "link_segments.h"
 
 #include "../../include/genphi.h"
-
-int genphi_set_error(int code, const std::string &msg);      // genphi_hip.hip
+#include "error.h"
 
 namespace genphi {
 

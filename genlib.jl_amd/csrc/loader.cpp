@@ -18,8 +18,7 @@
 #include <vector>
 
 #include "../../include/genphi.h"
-
-extern int genphi_set_error(int code, const std::string &msg);   // genphi_hip.hip
+#include "error.h"
 
 namespace {
 

@@ -39,13 +39,12 @@
 #include "../../include/genphi.h"
 #include "panel_launch.h"
 #include "planner.h"
-
-int genphi_set_error(int code, const std::string &msg);      // genphi_hip.hip
+#include "error.h"
 extern "C" const char *genphi_last_error(void);
 
 namespace {
 
-constexpr int kOrdMask = 0x7fffffff;
+using genphi::kOrdMask;      // (planner.h)
 
 __device__ __forceinline__ float combine4(float a, float b, float c, float d, bool i_hi, double scale)
 {

@@ -33,6 +33,7 @@
 namespace genphi {
 
 constexpr int32_t kNewFlag = INT32_MIN;     // bit 31 of `ord`: member is new (weight 1/2)
+constexpr int kOrdMask = 0x7fffffff;        // ... the rank below it, as every level kernel reads it
 
 // Kernel family of a level step, by the width of the previous cut:
 //   FULL   both source rows of an output row fit in LDS

@@ -1,5 +1,5 @@
 // resident.h -- what a query of the finished resident result may see of a plan (result_queries.hip, result_to_host.cpp), and nothing
-// else of it: genphi_hip.hip keeps genphi_plan private and defines the three accessors below.
+// else of it: genphi_plan (plan_device.h) stays with the sweep's two units, and genphi_hip.hip defines the three accessors below.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -10,8 +10,7 @@
 
 #include "../../include/genphi.h"
 #include "tuning.h"      // ResultTuning, nearest_buf_entries
-
-int genphi_set_error(int code, const std::string &msg);      // genphi_hip.hip
+#include "error.h"
 
 namespace genphi {
 

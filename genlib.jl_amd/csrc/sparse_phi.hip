@@ -59,8 +59,7 @@
 #include "devcache.h"
 #include "planner.h"
 #include "../../include/genphi.h"
-
-int genphi_set_error(int code, const std::string &msg);      // genphi_hip.hip
+#include "error.h"
 
 namespace {
 

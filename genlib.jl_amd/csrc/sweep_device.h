@@ -19,8 +19,7 @@
 #include "devcache.h"
 #include "planner.h"
 #include "sweep_panels.h"
-
-int genphi_set_error(int code, const std::string &msg);      // genphi_hip.hip
+#include "error.h"
 
 #define GENPHI_HIP_TRY(expr)                                                                                    \
     do {                                                                                                        \
