@@ -26,6 +26,7 @@ meaning, printed lines and error behaviour as the reference:
     gen.simuSample(ped); gen.simuProb(..)  # GENLIB's gene dropping: marked alleles of ancestors in the probands (csrc/simu.hip)
     gen.simuIdentity(ped)                  # Jacquard's nine identity coefficients of every pair by gene dropping (csrc/ident.hip)
     gen.simuRetention(ped)                 # founder allele survival, founder genome equivalents by gene dropping (csrc/retain.hip)
+    gen.simuCarriers(ped, pro, controls)   # per founder allele: how many of the cases carry it, by gene dropping (csrc/carry.hip)
     gen.simuSharing(ped, loci=1024)        # linked loci: realised IBD sharing, its variance and the segments (csrc/link.hip)
     gen.simuSegments(ped, loci=1024)       # the lengths of those segments: histogram, within and between groups, per pair
     gen.descendant(ped, 1); gen.children(ped, 1)   # src/identify.jl:203-215, :77-80 (csrc/loader.cpp)
@@ -41,7 +42,7 @@ from collections import OrderedDict
 import numpy as np
 
 from . import _capi
-from ._capi import PhiPlan, KinshipMatrix, GCPlan, OccPlan, RecPlan, DistPlan, DepthPlan, CompletenessPlan, ImplexPlan, SimuPlan, IdentityPlan, RetentionPlan, SharingPlan, GenphiDeviceError, GenphiLibraryMissing  # noqa: F401
+from ._capi import PhiPlan, KinshipMatrix, GCPlan, OccPlan, RecPlan, DistPlan, DepthPlan, CompletenessPlan, ImplexPlan, SimuPlan, IdentityPlan, RetentionPlan, CarriersPlan, SharingPlan, GenphiDeviceError, GenphiLibraryMissing  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
@@ -846,6 +847,106 @@ def simuRetention(pedigree, pro=None, simulNo=5000, seed=None, contributions=Tru
             c = gc(pedigree, pro=listed, ancestors=ids, device=device).astype(np.float64).sum(axis=0)
             p = c[inverse] / (2.0 * len(listed))
         return SimuRetention(probands, alleles, h.survived_to_host(), h.both_to_host(), h.distinct_to_host(), h.simul_no, h.seed, p)
+    finally:
+        h.close()
+
+
+class SimuCarriers:
+    """What gen.simuCarriers returns.  pro: the distinct cases, ascending; controls: the distinct controls, ascending; alleles: int64
+    (n_labels, 2), the ID and the side (0 = from the father) of every founder allele, in label order; carriers, homozygotes: int32
+    (n_labels, W); excluded: int32 (n_labels,) (the definition is the text of genphi_carry_* in include/genphi.h; column 0 of both
+    tables is filled here: the simulations in which no control and no case carries the allele); simulNo and the seed used.  With
+    n = len(pro), W = n + 1 unless maxCount < n cut the tables: then the last column lumps every count >= maxCount, and what needs the
+    exact count n is None.  Every share below is formed once from the integers, in Float64."""
+
+    def __init__(self, pro, controls, alleles, carriers, homozygotes, excluded, simulNo, seed):
+        self.pro, self.controls, self.alleles = pro, controls, alleles
+        self.carriers, self.homozygotes, self.excluded = carriers, homozygotes, excluded
+        self.simulNo, self.seed = simulNo, seed
+        self.lumped = carriers.shape[1] - 1 < len(pro)
+
+    def __repr__(self):
+        return "SimuCarriers(%d cases, %d controls, %d founder alleles, simulNo=%d, seed=%d)" % (len(self.pro), len(self.controls), len(self.alleles),
+                                                                                                self.simulNo, self.seed)
+
+    @property
+    def founders(self):
+        """The IDs of the allele table, ascending: the founders and half-founders of the live set."""
+        return np.unique(self.alleles[:, 0])
+
+    def at_least(self, k, homozygous=False):
+        """(n_labels,): the share of the simulations in which no control and at least k cases carry the allele (homozygous: on both
+        sides).  ValueError for k < 0, or for k beyond the last column of lumped tables."""
+        table = self.homozygotes if homozygous else self.carriers
+        k = int(k)
+        if k < 0 or (self.lumped and k >= table.shape[1]):
+            raise ValueError("gen.simuCarriers: at_least(%d) with columns 0 .. %d%s" % (k, table.shape[1] - 1, " (the last one lumped)" if self.lumped else ""))
+        return table[:, k:].sum(axis=1, dtype=np.int64) / float(self.simulNo)
+
+    @property
+    def mean_carriers(self):
+        """(n_labels,): the mean number of cases that carry the allele, simulations with a carrying control counted as 0; None when
+        the last column lumps."""
+        if self.lumped:
+            return None
+        return (self.carriers.astype(np.int64) @ np.arange(self.carriers.shape[1], dtype=np.int64)) / float(self.simulNo)
+
+    @property
+    def prob_all(self):
+        """(n_labels,): the share of the simulations in which every case and no control carries the allele; None when the last
+        column lumps."""
+        return None if self.lumped else self.carriers[:, -1] / float(self.simulNo)
+
+    @property
+    def prob_all_hom(self):
+        """(n_labels,): the same with every case carrying it on both sides."""
+        return None if self.lumped else self.homozygotes[:, -1] / float(self.simulNo)
+
+    @property
+    def posterior(self):
+        """(n_labels,): prob_all / prob_all.sum(), the posterior of which founder allele introduced a variant that every case and
+        no control carries, under a uniform prior over the founder alleles; zeros when no simulation had such an allele."""
+        if self.lumped:
+            return None
+        last = self.carriers[:, -1].astype(np.int64)
+        total = int(last.sum())
+        return last / float(total) if total else np.zeros(len(last))
+
+    @property
+    def ranking(self):
+        """The labels by prob_all descending, ties by label; None when the last column lumps."""
+        return None if self.lumped else np.lexsort((np.arange(len(self.alleles)), -self.carriers[:, -1].astype(np.int64)))
+
+
+def simuCarriers(pedigree, pro=None, controls=None, simulNo=5000, seed=None, maxCount=None, device=None):
+    """gen.simuCarriers(pedigree, pro = pro(pedigree), controls = None, simulNo = 5000): a set of affected probands (the cases, pro)
+    carries a rare variant -- which founder allele most probably introduced it, and how many of the cases does one founder allele
+    reach?  Every founder allele is dropped down the pedigree under its own label simulNo times (the labels of gen.simuIdentity under
+    the same seed), and per simulation and founder allele the distinct cases that carry it are counted, and those that carry it on
+    both sides; a simulation in which any of the controls (individuals known not to carry the variant) carries the allele is set
+    aside in excluded.  One sweep answers for every founder allele what GENLIB's gen.simuProb answers for one ancestor per call.
+    Returns a SimuCarriers: carriers, homozygotes, excluded, at_least(k), mean_carriers, prob_all, prob_all_hom, posterior, ranking.
+
+    The result is a pure function of the pedigree's relations, the SETS of cases and of controls (order and repeats change nothing),
+    the seed, simulNo and maxCount (include/genphi.h); gen.branching(pedigree, pro=..) first changes nothing.  maxCount=k keeps the
+    columns 0 .. k, the last one holding every count >= k (for many cases: the tables are n_labels x (len(cases) + 1) otherwise).
+    seed=None draws 64 fresh bits; pass a seed to repeat a run.  The sweep and the counts run on the GPU (csrc/carry.hip); only
+    (2 W + 1) n_labels integers come back.
+
+    KeyError for an unknown ID; ValueError for an individual in both lists, an empty pro, more than 32,767 distinct cases, tables of
+    more than 2^31 - 1 cells, simulNo outside 1 .. 2^24 or a negative maxCount.  Each call plans, sweeps and frees its own handle."""
+    cases = globals()["pro"](pedigree) if pro is None else np.ascontiguousarray(pro, dtype=np.int64)
+    others = np.zeros(0, dtype=np.int64) if controls is None else np.ascontiguousarray(controls, dtype=np.int64)
+    h = CarriersPlan(pedigree.ind, pedigree.father, pedigree.mother, cases, others, simul_no=simulNo, seed=seed,
+                     max_count=0 if maxCount is None else maxCount)
+    try:
+        h.compute(device=device)
+        excluded = h.excluded_to_host()
+        tables = []
+        for t in (h.carriers_to_host(), h.homozygotes_to_host()):
+            t[:, 0] = h.simul_no - excluded - t[:, 1:].sum(axis=1, dtype=np.int64)
+            tables.append(t)
+        return SimuCarriers(np.unique(cases), np.unique(others), h.alleles(), tables[0], tables[1], excluded, h.simul_no, h.seed)
     finally:
         h.close()
 

@@ -83,6 +83,8 @@ EXPORTED_SYMBOLS = [
     "genphi_ident_labels_to_host", "genphi_ident_stats", "genphi_ident_destroy",
     "genphi_retain_create", "genphi_retain_levels", "genphi_retain_alleles", "genphi_retain_compute", "genphi_retain_survived_to_host",
     "genphi_retain_both_to_host", "genphi_retain_distinct_to_host", "genphi_retain_stats", "genphi_retain_destroy",
+    "genphi_carry_create", "genphi_carry_levels", "genphi_carry_alleles", "genphi_carry_compute", "genphi_carry_carriers_to_host",
+    "genphi_carry_homozygotes_to_host", "genphi_carry_excluded_to_host", "genphi_carry_stats", "genphi_carry_destroy",
     "genphi_link_create", "genphi_link_levels", "genphi_link_alleles", "genphi_link_compute", "genphi_link_sums_to_host",
     "genphi_link_labels_to_host", "genphi_link_stats", "genphi_link_destroy", "genphi_link_words",
     "genphi_seg_request", "genphi_seg_to_host", "genphi_seg_stats", "genphi_seg_host",
@@ -386,6 +388,23 @@ def lib():
         L.genphi_retain_stats.restype = C.c_int
         L.genphi_retain_destroy.argtypes = [C.c_void_p]
         L.genphi_retain_destroy.restype = None
+        L.genphi_carry_create.argtypes = [C.c_int64, _I64P, _I64P, _I64P, C.c_int64, _I64P, C.c_int64, _I64P, C.c_int64, C.c_uint64, C.c_int32, C.c_int32,
+                                          C.c_int32, C.POINTER(C.c_void_p)]
+        L.genphi_carry_create.restype = C.c_int
+        L.genphi_carry_levels.argtypes = [C.c_void_p, _I64P, _I32P, _I64P]
+        L.genphi_carry_levels.restype = C.c_int
+        L.genphi_carry_alleles.argtypes = [C.c_void_p, _I64P, _I32P, _I64P, _I32P]
+        L.genphi_carry_alleles.restype = C.c_int
+        L.genphi_carry_compute.argtypes = [C.c_void_p, C.c_int32]
+        L.genphi_carry_compute.restype = C.c_int
+        for name in ("carriers", "homozygotes", "excluded"):
+            fn = getattr(L, "genphi_carry_%s_to_host" % name)
+            fn.argtypes = [C.c_void_p, _I32P]
+            fn.restype = C.c_int
+        L.genphi_carry_stats.argtypes = [C.c_void_p, _F64P, _F64P, _F64P, _F64P, _I32P, _I32P, _I64P, _I32P, _I32P, _I64P, _I32P, _I32P, _I32P, _I32P]
+        L.genphi_carry_stats.restype = C.c_int
+        L.genphi_carry_destroy.argtypes = [C.c_void_p]
+        L.genphi_carry_destroy.restype = None
         L.genphi_link_create.argtypes = [C.c_int64, _I64P, _I64P, _I64P, C.c_int64, _I64P, C.c_int32, C.c_int32, C.c_int64, C.c_uint64, C.c_int32,
                                          C.c_int32, C.POINTER(C.c_void_p)]
         L.genphi_link_create.restype = C.c_int
@@ -1759,6 +1778,57 @@ class RetentionPlan(_LabelPlan):
         return self._stats(sweep_ms=C.c_double, mark_ms=C.c_double, algorithmic_bytes=C.c_double, mark_bytes=C.c_double, levels=C.c_int32,
                            panel_cols=C.c_int32, panels=C.c_int64, planes=C.c_int32, chunk_labels=C.c_int32, chunks=C.c_int64,
                            lds_bytes=C.c_int32, lanes_per_row=C.c_int32)
+
+
+class CarriersPlan(_LabelPlan):
+    """The handle of gen.simuCarriers (include/genphi.h, genphi_carry_*): per founder allele, the simulations in which 1, 2, .. of the
+    listed cases carry it and no listed control does, by gene dropping.  Planned on the host at construction (KeyError on an unknown
+    ID; ValueError for an individual in both lists, no cases, more than 32,767 distinct cases, more than 2^31 - 1 cells, simul_no
+    outside 1 .. 2^24, a negative panel_cols, chunk_labels or max_count; no GPU needed), swept on the GPU by compute().  The plan and
+    the labels are gen.IdentityPlan's for the cases followed by the controls.  seed=None draws 64 fresh bits; .seed reports the seed
+    used.  panel_cols: the simulations of a panel (0 = the default).  chunk_labels: the founder alleles of a chunk of the count
+    kernel (0 = the default).  max_count: 0 = a column for every count 0 .. n_cases, else the last column min(n_cases, max_count)
+    holds every count at or above it.  n_cases, n_controls: the distinct individuals of each list; columns: W."""
+
+    _prefix = "carry"
+
+    def __init__(self, ind, father, mother, case_ids, control_ids=None, simul_no=5000, seed=None, panel_cols=0, chunk_labels=0, max_count=0):
+        case_ids = _i64(case_ids).ravel()
+        control_ids = _i64([] if control_ids is None else control_ids).ravel()
+        self._set_seed(seed)
+        self.simul_no = int(simul_no)
+        ind, father, mother = _i64(ind), _i64(father), _i64(mother)
+        h = C.c_void_p()
+        rc = lib().genphi_carry_create(len(ind), ind.ctypes.data_as(_I64P), father.ctypes.data_as(_I64P), mother.ctypes.data_as(_I64P),
+                                       len(case_ids), case_ids.ctypes.data_as(_I64P), len(control_ids), control_ids.ctypes.data_as(_I64P),
+                                       self.simul_no, self.seed, int(panel_cols), int(chunk_labels), int(max_count), C.byref(h))
+        if rc:
+            _raise(rc)
+        self._h = h
+        self.n_pro = len(case_ids) + len(control_ids)
+        self._read_plan()
+        st = self.stats()
+        self.n_cases, self.n_controls, self.columns = st["n_cases"], st["n_controls"], st["columns"]
+
+    def carriers_to_host(self):
+        """int32 (n_labels, columns): at [l, min(c, columns - 1)] the simulations in which c >= 1 distinct cases carry label l on at
+        least one side and no control carries it.  Column 0 is zero (gen.simuCarriers fills it)."""
+        return self._out("carriers_to_host", (self.n_labels, self.columns), np.int32, C.c_int32)
+
+    def homozygotes_to_host(self):
+        """int32 (n_labels, columns): the same for the cases that carry label l on both sides."""
+        return self._out("homozygotes_to_host", (self.n_labels, self.columns), np.int32, C.c_int32)
+
+    def excluded_to_host(self):
+        """int32 (n_labels,): the simulations in which some control carries the label."""
+        return self._out("excluded_to_host", self.n_labels, np.int32, C.c_int32)
+
+    def stats(self):
+        """dict(sweep_ms, count_ms, algorithmic_bytes, count_bytes, levels, panel_cols, panels, planes, chunk_labels, chunks, lds_bytes,
+        columns, n_cases, n_controls) of the last compute()."""
+        return self._stats(sweep_ms=C.c_double, count_ms=C.c_double, algorithmic_bytes=C.c_double, count_bytes=C.c_double, levels=C.c_int32,
+                           panel_cols=C.c_int32, panels=C.c_int64, planes=C.c_int32, chunk_labels=C.c_int32, chunks=C.c_int64,
+                           lds_bytes=C.c_int32, columns=C.c_int32, n_cases=C.c_int32, n_controls=C.c_int32)
 
 
 GENPHI_LINK_FLAG_LABELS = 1

@@ -873,6 +873,61 @@ function simuRetention(pedigree::GenLib.Pedigree, pro::Vector{Int} = GenLib.pro(
 end
 
 """
+    simuCarriers(pedigree::GenLib.Pedigree, pro = GenLib.pro(pedigree); controls = Int[], simulNo = 5000, seed = nothing,
+                 maxCount = 0, device = -1)
+
+How many of the cases `pro` carry every founder allele, by gene dropping (GenLib.jl answers for one ancestor per `simuProb` call; the
+definition is the text of `genphi_carry_*` in include/genphi.h): every founder allele is dropped down the pedigree under its own label
+`simulNo` times, and per simulation and allele the distinct cases that carry it are counted on the GPU (csrc/carry.hip); a
+simulation in which one of `controls` carries the allele goes to `excluded`.  Returns a named tuple: `alleles` (the founder alleles as
+`(ID, side)`, in label order), the Int32 matrices `carriers` and `homozygotes` (`W x length(alleles)`: the library's row-major
+`n_labels x W` is the memory of that array; row `c + 1` holds the count `c`, the last row every count `>= maxCount` when `maxCount`
+is positive and below the number of distinct cases; row 1, the count 0, is filled here), the Int32 vector `excluded`, `prob_all`
+(the last row `./ simulNo`, or `nothing` when it lumps), `simulNo` and the `seed` used (`nothing` draws 64 fresh bits).
+NOT run anywhere yet, like the rest of this file (no Julia in the build container).
+"""
+function simuCarriers(pedigree::GenLib.Pedigree, pro::Vector{Int} = GenLib.pro(pedigree); controls::Vector{Int} = Int[],
+                      simulNo::Integer = 5000, seed::Union{Nothing, UInt64} = nothing, maxCount::Integer = 0, device::Integer = -1)
+    isempty(pro) && throw(ArgumentError("gen.simuCarriers: no cases"))
+    seed64 = isnothing(seed) ? rand(Random.RandomDevice(), UInt64) : seed
+    ind, father, mother, _ = flatten(pedigree)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve ind father mother pro controls check(ccall((:genphi_carry_create, libgenphi), Cint,
+        (Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Int64, Ptr{Int64}, Int64, Ptr{Int64}, Int64, UInt64, Int32, Int32, Int32, Ptr{Ptr{Cvoid}}),
+        length(ind), ind, father, mother, length(pro), pro, length(controls), controls, Int64(simulNo), seed64, Int32(0), Int32(0),
+        Int32(maxCount), h))
+    try
+        n_labels = Ref{Int64}(0)
+        planes = Ref{Int32}(0)
+        check(ccall((:genphi_carry_alleles, libgenphi), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int32}, Ptr{Int64}, Ptr{Int32}),
+                    h[], n_labels, planes, C_NULL, C_NULL))
+        n = Int(n_labels[])
+        ids = Vector{Int64}(undef, n); sides = Vector{Int32}(undef, n)
+        GC.@preserve ids sides check(ccall((:genphi_carry_alleles, libgenphi), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int32}, Ptr{Int64}, Ptr{Int32}),
+                                           h[], C_NULL, C_NULL, ids, sides))
+        columns = Ref{Int32}(0); n_cases = Ref{Int32}(0)
+        check(ccall((:genphi_carry_stats, libgenphi), Cint,
+                    (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}, Ptr{Int64}, Ptr{Int32}, Ptr{Int32},
+                     Ptr{Int64}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}),
+                    h[], C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, columns, n_cases, C_NULL))
+        W = Int(columns[])
+        check(ccall((:genphi_carry_compute, libgenphi), Cint, (Ptr{Cvoid}, Int32), h[], Int32(device)))
+        carriers = Matrix{Int32}(undef, W, n); homozygotes = Matrix{Int32}(undef, W, n); excluded = Vector{Int32}(undef, n)
+        GC.@preserve carriers check(ccall((:genphi_carry_carriers_to_host, libgenphi), Cint, (Ptr{Cvoid}, Ptr{Int32}), h[], carriers))
+        GC.@preserve homozygotes check(ccall((:genphi_carry_homozygotes_to_host, libgenphi), Cint, (Ptr{Cvoid}, Ptr{Int32}), h[], homozygotes))
+        GC.@preserve excluded check(ccall((:genphi_carry_excluded_to_host, libgenphi), Cint, (Ptr{Cvoid}, Ptr{Int32}), h[], excluded))
+        for t in (carriers, homozygotes)
+            t[1, :] .= Int32.(Int(simulNo) .- Int.(excluded) .- vec(sum(Int.(t[2:end, :]), dims = 1)))
+        end
+        lumped = W - 1 < Int(n_cases[])
+        return (alleles = collect(zip(Int.(ids), Int.(sides))), carriers = carriers, homozygotes = homozygotes, excluded = excluded,
+                prob_all = lumped ? nothing : carriers[end, :] ./ Float64(simulNo), simulNo = Int(simulNo), seed = seed64)
+    finally
+        ccall((:genphi_carry_destroy, libgenphi), Cvoid, (Ptr{Cvoid},), h[])
+    end
+end
+
+"""
     simuSegments(pedigree::GenLib.Pedigree, pro = GenLib.pro(pedigree); loci = 1024, length = 1.0, probRecomb = nothing,
                  simulNo = 1000, seed = nothing, bins = nothing, minLoci = 1, groups = nothing, device = -1)
 

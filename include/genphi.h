@@ -1173,6 +1173,74 @@ int genphi_retain_stats(const genphi_retain *h, double *sweep_ms, double *mark_m
                         int64_t *chunks, int32_t *lds_bytes, int32_t *lanes_per_row);
 void genphi_retain_destroy(genphi_retain *h);
 
+/* ---- gen.simuCarriers: the carriers of every founder allele among listed cases (csrc/carry.hip, csrc/carry.h, csrc/label_sweep.h) --
+ * A set of affected probands carries a rare variant: which founder allele most probably introduced it, and how many of the listed
+ * probands does one founder allele reach?  GENLIB's gen.simuProb answers for one ancestor per call; here every founder allele is
+ * answered by one sweep.  The reference has no form of it, so this text is the definition, and it is this package's own.
+ * Inputs.  A pedigree; the cases, at least one individual; the controls, an optional second list of individuals that must not carry
+ * the allele; S and a 64-bit seed.  Both lists count as SETS: order and repeats change nothing.  An individual in both lists is
+ * GENPHI_ERR_ARG.  The listed probands of the plan are the cases followed by the controls: live set, levels, rows, allele table,
+ * labels LP_x[s] / LM_x[s], the rule and the random word R are those of genphi_ident_* above, word for word.  The same (pedigree
+ * relations, seed) therefore gives the same realisation as gen.simuIdentity, gen.simuRetention and gen.simuSharing.
+ * Let n be the number of distinct cases.  Per simulation s < S and label l:
+ *   c1(l, s) = the distinct cases with at least one side equal to l,
+ *   c2(l, s) = the distinct cases with both sides equal to l,
+ *   x(l, s)  = 1 when some control has a side equal to l, else 0.
+ * With W = min(n, max_count) + 1 columns (max_count = 0: W = n + 1; the last column lumps only when max_count < n) the results:
+ *   excluded[l]                       Int32 x n_labels: the s with x = 1.
+ *   carriers[l, min(c1, W - 1)]       Int32 x n_labels x W, row-major: the s with x = 0 and c1 >= 1.
+ *   homozygotes[l, min(c2, W - 1)]    Int32 x n_labels x W, row-major: the s with x = 0 and c2 >= 1.
+ * The device never writes column 0 of either table: it stays 0 in what carriers_to_host and homozygotes_to_host deliver, and the
+ * Python layer fills both as S - excluded[l] - (the sum of the columns c >= 1).  Bits at positions >= S are never counted.
+ * Invariants, all exact.
+ *   1. With no controls the sum over c >= 1 of carriers[l, c] equals survived[l] of genphi_retain_* for the same pedigree, cases,
+ *      seed and S.
+ *   2. With no controls and W = n + 1 the sum over l and c of c (carriers[l, c] + homozygotes[l, c]) is 2 n S: every side of every
+ *      case carries one label.
+ *   3. The sum over c of c homozygotes[l, c] <= the sum over c of c carriers[l, c] for every l, at any W.
+ *   4. Both alleles of a case that is itself a founder have the sum over c >= 1 of carriers equal to S - excluded.
+ *   5. The bytes do not depend on the panel width, the label chunk, or the order and repeats of either list.
+ *   6. Keyed by (ID, side), excluded equals survived of genphi_retain_* run on the controls alone under the same seed (the two
+ *      allele tables differ: on the common keys).
+ *   7. Keyed by (ID, side), adding controls never raises a cell of carriers or homozygotes with c >= 1.
+ * Errors.  Those of genphi_ident_create without the n_pro^2 >= 2^31 refusal.  GENPHI_ERR_ARG, all in create before any device work:
+ * no cases; an individual in both lists; n > 32,767; n_labels x W > 2^31 - 1; S outside 1 .. 2^24; a negative panel_cols,
+ * chunk_labels or max_count.  GENPHI_ERR_ALLOC from compute before any launch, when the device does not hold the results
+ * (4 n_labels (2 W + 1) bytes), the lists and the rows of even a 128-column panel.
+ * Method.  The label sweep of genphi_ident_* (its init and step kernels, shared), then one count kernel per panel that reads the
+ * rows of the cases and the controls in place.  A workgroup owns the 64 simulations of a word and a chunk of the labels; it keeps
+ * one counter dword per (simulation, label) in LDS (c1 in bits 0-15, c2 in bits 16-30, x in bit 31: n <= 32,767 keeps the fields
+ * apart), decodes both sides of every listed individual once, adds by LDS atomics, and reduces the dwords into integer adds
+ * (csrc/carry.hip).
+ *   create            host only (no GPU): ident's checks and plan on the cases followed by the controls; the lists as sets; the
+ *                     limits.  panel_cols as for genphi_ident_create.  chunk_labels: the labels of a chunk, 0 = the default (608,
+ *                     the most that 160 KiB of LDS hold), else rounded up to a multiple of 32 and cut to 608; either is cut to n_labels
+ *                     (tests, A/B).  max_count: 0 = a column for every count, else the last column W - 1 = min(n, max_count)
+ *                     holds every count at or above it
+ *   levels, alleles   as genphi_ident_levels and genphi_ident_alleles
+ *   compute           the sweep on `device` (-1 = current); the three arrays stay resident
+ *   carriers_to_host, homozygotes_to_host    out: n_labels x W Int32, row-major, column 0 zero
+ *   excluded_to_host  out: n_labels Int32
+ *   stats             of the last compute, by HIP events: the device time of init and level steps, and of the count kernel, summed
+ *                     over the panels; the algorithmic bytes of the steps (as genphi_ident_stats); the bytes of the listed rows'
+ *                     planes the count kernel reads (2 (n + controls) x B x 16 per pair of words and chunk); levels; the columns
+ *                     of a panel; the panels; B; the labels of a chunk; the chunks; the LDS bytes of a workgroup of the count
+ *                     kernel; W; n; the distinct controls                                                                      */
+typedef struct genphi_carry genphi_carry;
+int genphi_carry_create(int64_t n_ind, const int64_t *ind, const int64_t *father, const int64_t *mother,
+                        int64_t n_cases, const int64_t *case_ids, int64_t n_controls, const int64_t *control_ids, int64_t simul_no,
+                        uint64_t seed, int32_t panel_cols, int32_t chunk_labels, int32_t max_count, genphi_carry **out);
+int genphi_carry_levels(const genphi_carry *h, int64_t *n_live, int32_t *levels, int64_t *rows_per_level);
+int genphi_carry_alleles(const genphi_carry *h, int64_t *n_labels, int32_t *planes, int64_t *ids, int32_t *sides);
+int genphi_carry_compute(genphi_carry *h, int32_t device);
+int genphi_carry_carriers_to_host(genphi_carry *h, int32_t *out);
+int genphi_carry_homozygotes_to_host(genphi_carry *h, int32_t *out);
+int genphi_carry_excluded_to_host(genphi_carry *h, int32_t *out);
+int genphi_carry_stats(const genphi_carry *h, double *sweep_ms, double *count_ms, double *algorithmic_bytes, double *count_bytes,
+                       int32_t *levels, int32_t *panel_cols, int64_t *panels, int32_t *planes, int32_t *chunk_labels,
+                       int64_t *chunks, int32_t *lds_bytes, int32_t *columns, int32_t *n_cases, int32_t *n_controls);
+void genphi_carry_destroy(genphi_carry *h);
+
 /* ---- gen.simuSharing: linked-locus gene dropping and IBD segments (csrc/link.hip, csrc/link.cpp, csrc/label_sweep.h) ---------------
  * gen.simuIdentity above drops every founder allele at ONE locus.  Here a simulation is a chromosome of L linked loci: a meiosis
  * copies a mosaic of the parent's two chromosomes, and the sharing of a pair of probands is read off locus by locus: how much of the
