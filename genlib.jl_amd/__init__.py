@@ -32,6 +32,7 @@ meaning, printed lines and error behaviour as the reference:
     gen.descendant(ped, 1); gen.children(ped, 1)   # src/identify.jl:203-215, :77-80 (csrc/loader.cpp)
     gen.phiHist(ped); gen.phiQuantile(ped, 0.5)    # the distribution of the pairwise kinships, on the device (csrc/hist.hip)
     gen.phiClusters(ped, 1/16); gen.phiUnrelated(ped, 1/16)   # families and a maximal unrelated set at a kinship cutoff (csrc/clusters.hip)
+    gen.phiTree(ped)                       # the single-linkage tree of the kinships: every cutoff at once (csrc/tree.hip)
 
 All kinship arithmetic runs in hand-written HIP kernels behind the C-ABI in
 include/genphi.h (csrc/genphi_hip.hip); there is no CPU fallback.
@@ -1472,10 +1473,11 @@ class PhiClusters:
     """What gen.phiClusters returns: the connected components of the graph whose edges are the pairs of probands with kinship >=
     `threshold`.  `pro` (int64, the N IDs in the order of the rows, None when no IDs were given with a host matrix), `label` (int32
     (N,), the smallest 0-based position in each proband's cluster), `cluster` (int32 (N,), dense numbers 0 .. K - 1 in the order of
-    each cluster's first member), `sizes` (int64 (K,)) and `n_pairs` (the number of edges)."""
+    each cluster's first member), `sizes` (int64 (K,)) and `n_pairs` (the number of edges; None when the clusters were cut from a gen.phiTree, which never counts
+    them)."""
 
     def __init__(self, threshold, pro, label, n_pairs):
-        self.threshold, self.pro, self.label, self.n_pairs = threshold, pro, label, int(n_pairs)
+        self.threshold, self.pro, self.label, self.n_pairs = threshold, pro, label, None if n_pairs is None else int(n_pairs)
         first = np.flatnonzero(label == np.arange(len(label), dtype=np.int64))      # the first member of every cluster, ascending
         number = np.zeros(len(label), dtype=np.int32)
         number[first] = np.arange(len(first), dtype=np.int32)
@@ -1493,8 +1495,9 @@ class PhiClusters:
         return pos if self.pro is None else self.pro[pos]
 
     def __repr__(self):
-        return "PhiClusters: %d probands in %d clusters at kinship >= %g (%d pairs), the largest of %d" % (
-            len(self.label), len(self.sizes), self.threshold, self.n_pairs, int(self.sizes.max()) if len(self.sizes) else 0)
+        pairs = "pairs not counted" if self.n_pairs is None else "%d pairs" % self.n_pairs       # (None: cut from a gen.phiTree)
+        return "PhiClusters: %d probands in %d clusters at kinship >= %g (%s), the largest of %d" % (
+            len(self.label), len(self.sizes), self.threshold, pairs, int(self.sizes.max()) if len(self.sizes) else 0)
 
 
 class PhiUnrelated:
@@ -1598,6 +1601,144 @@ def phiUnrelated(x, threshold, priority=None, probandIDs=None, device=None):
             keep[i] = True
             barred |= a[i]
     return PhiUnrelated(threshold, ids, keep, degree, 0)
+
+
+class PhiTree:
+    """What gen.phiTree returns: the single-linkage tree of the kinships, as the M = N - n_trees edges of the maximum spanning forest
+    of the graph whose edges are the pairs with kinship >= `floor`, ordered by larger kinship first, then smaller row, then smaller
+    column.  `pro` (int64, the N IDs in the order of the rows, None when no IDs were given with a host matrix), `row`, `col` (int32
+    (M,), 0-based positions, row < col), `pro1`, `pro2` (the IDs at those positions, None without `pro`), `kinship` (float32 (M,),
+    the matrix entries bit for bit), `floor`, `n_trees` (the clusters at `floor`) and `rounds` (the rounds the device took; 0 for a
+    host matrix).  len() is the number of edges."""
+
+    def __init__(self, floor, pro, n, row, col, kinship, n_trees, rounds):
+        self.floor, self.pro, self.n, self.row, self.col, self.kinship = floor, pro, int(n), row, col, kinship
+        self.n_trees, self.rounds = int(n_trees), int(rounds)
+        self.pro1 = None if pro is None else pro[row]
+        self.pro2 = None if pro is None else pro[col]
+
+    def __len__(self):
+        return len(self.row)
+
+    def __repr__(self):
+        top = " from %g" % float(self.kinship[0]) if len(self.row) else ""
+        return "PhiTree: %d probands, %d edges%s down to kinship >= %g, %d tree%s (%d rounds)" % (
+            self.n, len(self.row), top, self.floor, self.n_trees, "" if self.n_trees == 1 else "s", self.rounds)
+
+    def _passing(self, t):
+        """The edges with float64(kinship) >= t are the first k of the list: k."""
+        t = _threshold(t)
+        if t < self.floor:
+            raise ValueError("PhiTree: the tree was built down to kinship %g and says nothing about %g" % (self.floor, t))
+        return int(np.count_nonzero(self.kinship.astype(np.float64) >= t)), t
+
+    def cut(self, t):
+        """int32 (N,): the clusters at kinship >= t, each proband labelled with the smallest position in its cluster (the `label` of
+        gen.phiClusters at threshold t).  ValueError for t < floor or NaN."""
+        k, _ = self._passing(t)
+        parent = list(range(self.n))
+
+        def find(x):
+            while parent[x] != x:
+                parent[x] = parent[parent[x]]
+                x = parent[x]
+            return x
+
+        for a, b in zip(self.row[:k].tolist(), self.col[:k].tolist()):
+            a, b = find(a), find(b)
+            parent[max(a, b)] = min(a, b)                       # the root of a cluster is its smallest position
+        return np.array([find(i) for i in range(self.n)], dtype=np.int32)
+
+    def clusters(self, t):
+        """The PhiClusters of gen.phiClusters at threshold t (its `n_pairs` is None: the tree never counts the pairs)."""
+        label = self.cut(t)
+        return PhiClusters(_threshold(t), self.pro, label, None)
+
+    def heights(self):
+        """(kinship float32 (H,), n_clusters int64 (H,)): the distinct kinships at which something merges, descending, and the
+        number of clusters left once every merge at or above each has happened."""
+        if not len(self.kinship):
+            return np.empty(0, dtype=np.float32), np.empty(0, dtype=np.int64)
+        last = np.flatnonzero(np.append(self.kinship[1:] != self.kinship[:-1], True))       # the last edge of every run of equals
+        return self.kinship[last].copy(), (self.n - (last + 1)).astype(np.int64)
+
+    def linkage(self):
+        """float64 (N - 1, 4): the merge table in SciPy's convention (scipy.cluster.hierarchy; SciPy itself is not needed): row k
+        holds the two clusters that edge k joins, the smaller id first, the distance 1 - kinship, and the size of the new cluster,
+        which gets the id N + k; the ids 0 .. N - 1 are the probands.  ValueError unless the tree is one piece (n_trees == 1)."""
+        if self.n_trees != 1:
+            raise ValueError("PhiTree.linkage: %d trees at kinship >= %g: a merge table needs one (build the tree with a lower floor)" % (
+                self.n_trees, self.floor))
+        n = self.n
+        parent, ident, size = list(range(n)), list(range(n)), [1] * n
+        out = np.empty((len(self.row), 4), dtype=np.float64)
+
+        def find(x):
+            while parent[x] != x:
+                parent[x] = parent[parent[x]]
+                x = parent[x]
+            return x
+
+        for k, (a, b, phi) in enumerate(zip(self.row.tolist(), self.col.tolist(), self.kinship.astype(np.float64).tolist())):
+            a, b = find(a), find(b)
+            out[k] = (min(ident[a], ident[b]), max(ident[a], ident[b]), 1.0 - phi, size[a] + size[b])
+            parent[b] = a
+            ident[a], size[a] = n + k, size[a] + size[b]
+        return out
+
+
+def phiTree(x, floor=None, probandIDs=None, device=None):
+    """The single-linkage tree of the kinships: which probands merge at which kinship, from the closest pairs down to `floor` -- the
+    families of gen.phiClusters at every cutoff at once.  Returns a PhiTree.  Neither GENLIB nor the reference has this function.
+
+    The edges are the pairs i < j with float64(Phi[i, j]) >= floor (gen.phiOver's rule); floor None is the smallest positive
+    Float32, "any positive kinship"; floor <= 0 makes every pair an edge.  Edge (i, j) precedes (i', j') when its kinship is larger,
+    then when i is smaller, then when j is smaller; an edge belongs to the tree iff no path of preceding edges joins its ends
+    (Kruskal's rule), so the answer is unique.  PhiTree.cut(t) gives gen.phiClusters' labels at any t >= floor.
+
+    x a Pedigree: gen.phi's sweep for probandIDs (default gen.pro; duplicates collapse, as gen.phi does), then Boruvka's rounds on the
+    device over the rows of the resident matrix, which is never copied and whose pairs are never listed or sorted
+    (genphi_result_tree).  x a square host matrix: Kruskal's loop over the sorted upper triangle in numpy, rounds = 0.
+    ValueError for a NaN floor, KeyError for an unknown proband ID."""
+    floor = _capi.tree_floor(floor)
+    if floor != floor:
+        raise ValueError("the floor is NaN")
+    if isinstance(x, Pedigree):
+        ids, (row, col, kinship, n_trees, rounds) = _resident_query(x, probandIDs, device, lambda pl: pl.tree(floor))
+        return PhiTree(floor, ids, len(ids), row, col, kinship, n_trees, rounds)
+    m = np.asarray(x, dtype=np.float32)
+    _, ids = _host_matrix(m, probandIDs, "gen.phiTree")
+    n = len(m)
+    i, j = np.triu_indices(n, 1)
+    phi = m[i, j]
+    keep = phi.astype(np.float64) >= floor
+    i, j, phi = i[keep], j[keep], phi[keep]
+    order = np.lexsort((j, i, -phi.astype(np.float64)))         # larger kinship, then smaller row, then smaller column
+    i, j = i[order], j[order]
+    parent = np.arange(n)
+    taken = []
+    for lo in range(0, len(order), 1 << 15):                    # in slices: the edges inside a cluster drop out in numpy
+        if len(taken) == n - 1:
+            break
+        while True:                                             # parent -> the root of every position
+            up = parent[parent]
+            if np.array_equal(up, parent):
+                break
+            parent = up
+        a, b = i[lo:lo + (1 << 15)], j[lo:lo + (1 << 15)]
+        live = np.flatnonzero(parent[a] != parent[b])
+        for e in live.tolist():
+            ra, rb = int(a[e]), int(b[e])
+            while parent[ra] != ra:
+                ra = int(parent[ra])
+            while parent[rb] != rb:
+                rb = int(parent[rb])
+            if ra != rb:
+                parent[max(ra, rb)] = min(ra, rb)
+                taken.append(lo + e)
+    taken = np.asarray(taken, dtype=np.int64)
+    row, col = i[taken].astype(np.int32), j[taken].astype(np.int32)
+    return PhiTree(floor, ids, n, row, col, m[row, col], n - len(taken), 0)
 
 
 class PhiNearest:

@@ -57,7 +57,7 @@ class GenphiStats(C.Structure):
 EXPORTED_SYMBOLS = [
     "genphi_plan_create", "genphi_plan_create_tuned", "genphi_tuning_create", "genphi_tuning_set", "genphi_tuning_destroy", "genphi_plan_levels", "genphi_plan_n_probands", "genphi_plan_step_mode", "genphi_plan_step_info", "genphi_plan_step_slots",
     "genphi_plan_algorithmic_bytes", "genphi_plan_device_bytes", "genphi_plan_device_bytes_needed", "genphi_plan_sparse_levels", "genphi_plan_cut_formats", "genphi_plan_step_walk", "genphi_plan_set_step_hook", "genphi_compute_device", "genphi_result_device",
-    "genphi_result_to_host", "genphi_result_to_host_f64", "genphi_phi_pairs", "genphi_result_sums", "genphi_result_group_sums", "genphi_result_over", "genphi_result_nearest", "genphi_result_matmul", "genphi_result_solve", "genphi_result_eigen", "genphi_result_hist", "genphi_result_select", "genphi_result_clusters", "genphi_result_unrelated", "genphi_result_bootstrap", "genphi_bootstrap_counts", "genphi_result_entries",
+    "genphi_result_to_host", "genphi_result_to_host_f64", "genphi_phi_pairs", "genphi_result_sums", "genphi_result_group_sums", "genphi_result_over", "genphi_result_nearest", "genphi_result_matmul", "genphi_result_solve", "genphi_result_eigen", "genphi_result_hist", "genphi_result_select", "genphi_result_clusters", "genphi_result_unrelated", "genphi_result_tree", "genphi_tree_host", "genphi_result_bootstrap", "genphi_bootstrap_counts", "genphi_result_entries",
     "genphi_compute_f32",
     "genphi_genealogy_read", "genphi_branching", "genphi_free", "genphi_release_cached", "genphi_cached_bytes", "genphi_plan_release_device", "genphi_plan_destroy",
     "genphi_last_error",
@@ -171,6 +171,11 @@ def lib():
         L.genphi_result_unrelated.argtypes = [C.c_void_p, C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.POINTER(C.c_int32), _I64P,
                                               C.POINTER(C.c_int32)]
         L.genphi_result_unrelated.restype = C.c_int
+        L.genphi_result_tree.argtypes = [C.c_void_p, C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _F32P, _I64P, _I64P, C.POINTER(C.c_int32)]
+        L.genphi_result_tree.restype = C.c_int
+        L.genphi_tree_host.argtypes = [_F32P, C.c_int64, C.c_int64, C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _F32P, _I64P, _I64P,
+                                       C.POINTER(C.c_int32)]
+        L.genphi_tree_host.restype = C.c_int
         L.genphi_result_bootstrap.argtypes = [C.c_void_p, C.c_uint64, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), _I64P]
         L.genphi_result_bootstrap.restype = C.c_int
         L.genphi_bootstrap_counts.argtypes = [C.c_int64, C.c_uint64, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]
@@ -861,6 +866,27 @@ class PhiPlan:
             _raise(rc)
         return member.astype(bool), degree, int(rounds.value)
 
+    def tree(self, floor=None):
+        """(row int32 (M,), col int32 (M,), kinship float32 (M,), n_trees, rounds): the single-linkage tree of the kinships, that is
+        the maximum spanning forest of the graph whose edges are the pairs with Phi[i, j] >= floor (genphi_result_over's rule), found
+        on the device by Boruvka's rounds over the FULL resident result (genphi_result_tree).  The M = N - n_trees
+        edges come by larger kinship first, then smaller row, then smaller column; row < col; kinship holds the matrix entries bit
+        for bit.  floor None: the smallest positive Float32, "any positive kinship".  ValueError for a NaN floor, a row shard or a
+        Float64 result, GenphiDeviceError without a resident result."""
+        floor = tree_floor(floor)
+        if floor != floor:
+            raise ValueError("tree: the floor is NaN")
+        n = self.n_probands
+        row, col, kin = np.empty(max(n - 1, 0), dtype=np.int32), np.empty(max(n - 1, 0), dtype=np.int32), np.empty(max(n - 1, 0), dtype=np.float32)
+        m, trees, rounds = C.c_int64(), C.c_int64(), C.c_int32()
+        i32 = C.POINTER(C.c_int32)
+        rc = lib().genphi_result_tree(self._h, floor, row.ctypes.data_as(i32), col.ctypes.data_as(i32), kin.ctypes.data_as(_F32P), C.byref(m),
+                                      C.byref(trees), C.byref(rounds))
+        if rc:
+            _raise(rc)
+        k = int(m.value)
+        return row[:k].copy(), col[:k].copy(), kin[:k].copy(), int(trees.value), int(rounds.value)
+
     def nearest(self, k, cols=True, values=True):
         """(cols int32 (rows, k), values float32 (rows, k)): the k closest relatives of every RESIDENT row, selected on the device
         in one pass over the rows (genphi_result_nearest); the matrix is not copied.  The candidates of row i are
@@ -1044,6 +1070,35 @@ def as_priority(priority, n):
     if n and (int(a.min()) < -2 ** 31 or int(a.max()) > 2 ** 31 - 1):
         raise ValueError("priority outside the int32 range")
     return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def tree_floor(floor):
+    """The floor of gen.phiTree as a float: None is the smallest positive Float32, "any positive kinship"."""
+    return float(np.nextafter(np.float32(0), np.float32(1))) if floor is None else float(floor)
+
+
+def tree_host(m, floor=None):
+    """(row, col, kinship, n_trees, rounds) of genphi_tree_host (host only): gen.phiTree's rounds, with the key arithmetic of the
+    kernels, on a host matrix.  m: Float32 of shape (n, ld), ld >= n: n rows of pitch ld whose first n columns are the matrix; the
+    other columns are never read."""
+    m = np.ascontiguousarray(m, dtype=np.float32)
+    if m.ndim != 2:
+        raise ValueError("tree_host takes a matrix of n rows, got shape %s" % (m.shape,))
+    n, pitch = m.shape
+    floor = tree_floor(floor)
+    if floor != floor:
+        raise ValueError("tree_host: the floor is NaN")
+    if pitch < n:
+        raise ValueError("tree_host: %d rows of %d entries: the pitch is below n" % (n, pitch))
+    row, col, kin = np.empty(max(n - 1, 0), dtype=np.int32), np.empty(max(n - 1, 0), dtype=np.int32), np.empty(max(n - 1, 0), dtype=np.float32)
+    k, trees, rounds = C.c_int64(), C.c_int64(), C.c_int32()
+    i32 = C.POINTER(C.c_int32)
+    rc = lib().genphi_tree_host(m.ctypes.data_as(_F32P), n, pitch, floor, row.ctypes.data_as(i32), col.ctypes.data_as(i32), kin.ctypes.data_as(_F32P),
+                                C.byref(k), C.byref(trees), C.byref(rounds))
+    if rc:
+        _raise(rc)
+    k = int(k.value)
+    return row[:k].copy(), col[:k].copy(), kin[:k].copy(), int(trees.value), int(rounds.value)
 
 
 def as_panel(a, n, what):

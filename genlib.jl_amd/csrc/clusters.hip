@@ -2,7 +2,7 @@
 // resident result without listing an edge: its connected components (genphi_result_clusters: a lock-free union-find over one read of
 // the upper triangle) and a maximal unrelated set (genphi_result_unrelated: the sequential greedy rule, found in rounds over the
 // rows).  include/genphi.h states the contract, DESIGN.md 26 the design and the two correctness arguments.  The plan is seen through
-// resident.h only; the edge test is over_device.h's, the one genphi_result_over lists by.
+// resident.h only; the edge test is over_device.h's, the one genphi_result_over lists by; the union-find is union_find.h's.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -16,51 +16,22 @@
 #include "../../include/genphi.h"
 #include "over_device.h"
 #include "resident.h"
+#include "resident_graph.h"
+#include "union_find.h"
 
 using genphi::al256;
+using genphi::device_error;
+using genphi::find_root;
 using genphi::kOverTile;
+using genphi::need_full_f32;
 using genphi::over_hits;
 using genphi::over_row_hits;
+using genphi::parent_of;
 using genphi::ResidentView;
+using genphi::scratch_for;
+using genphi::unite;
 
 namespace {
-
-// ---------------------------------------------------------------------------------------------
-// union-find.  parent[x] <= x always; x is a root while parent[x] == x.  Every read of parent is an agent-scope atomic load, every
-// write a compare-and-swap of a root (the hook) or an atomicMin with an ancestor (path halving): a word only ever decreases, a
-// root that was hooked never becomes a root again, and a stale read -- the XCDs do not see each other's L2 -- costs a retry.
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ int parent_of(const int *parent, int x)
-{
-    return __hip_atomic_load(parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// a node that was the root of x's tree when it was read; halves the path on the way
-__device__ __forceinline__ int find_root(int *parent, int x)
-{
-    for (;;) {
-        const int p = parent_of(parent, x);
-        if (p == x) return x;
-        const int g = parent_of(parent, p);
-        if (g == p) return p;
-        atomicMin(parent + x, g);                       // g < p: an ancestor of x, nearer the root
-        x = g;
-    }
-}
-
-// joins the trees of a and b; returns a node that was the root of both afterwards.  The larger root goes under the smaller.
-__device__ __forceinline__ int unite(int *parent, int a, int b)
-{
-    for (;;) {
-        a = find_root(parent, a);
-        b = find_root(parent, b);
-        if (a == b) return a;
-        if (a < b) { const int s = a; a = b; b = s; }
-        const int seen = atomicCAS(parent + a, a, b);
-        if (seen == a) return b;                        // a was still a root
-        a = seen;                                       // somebody hooked it first, under `seen`: go on from there (no read can stall this)
-    }
-}
 
 __global__ __launch_bounds__(256) void cluster_init_kernel(int *parent, int *row_count, int n)
 {
@@ -219,37 +190,6 @@ __global__ __launch_bounds__(256) void unrelated_round_kernel(const float *__res
         else if (!any_blocked) __hip_atomic_store(state + i, static_cast<unsigned char>(kIn), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         else atomicAdd(undecided, 1ull);
     }
-}
-
-// ---------------------------------------------------------------------------------------------
-// host side
-// ---------------------------------------------------------------------------------------------
-// Both queries need the full Float32 result: not the Float64 one, not a row shard (an empty one too), a resident result.
-int need_full_f32(const ResidentView &v, const char *name)
-{
-    if (v.res_f64) return genphi_set_error(GENPHI_ERR_ARG, std::string(name) + " works on the Float32 result (gen.phi's matrix)");
-    const bool empty = v.res_known && v.n_rows == 0;
-    if (!empty && (!v.on_device || !v.result || v.n_rows == 0))
-        return genphi_set_error(GENPHI_ERR_DEVICE, "no resident result: call genphi_compute_device first");
-    if (empty || v.row_begin != 0 || v.n_rows != v.n_pro)
-        return genphi_set_error(GENPHI_ERR_ARG, std::string(name) + ": " + std::to_string(v.n_rows) + " of " + std::to_string(v.n_pro) +
-                                                    " rows are resident: the graph needs every row");
-    if (v.ld < v.n_pro || v.ld % 64 != 0 || v.n_pro > INT32_MAX)
-        return genphi_set_error(GENPHI_ERR_DEVICE, std::string(name) + ": unexpected row pitch " + std::to_string(v.ld));
-    return GENPHI_OK;
-}
-
-int scratch_for(genphi_plan *p, size_t bytes, const char *name, const char *what, char **scratch)
-{
-    if (genphi::resident_scratch(p, bytes, scratch) == GENPHI_OK) return GENPHI_OK;
-    return genphi_set_error(GENPHI_ERR_ALLOC, std::string(name) + ": " + std::to_string(bytes) + " bytes of device memory for " + what + ": " + genphi_last_error());
-}
-
-// after an error: the stream is drained (host arrays outlive what was enqueued), the error goes out under the query's name
-int device_error(const ResidentView &v, hipError_t e, const char *name)
-{
-    (void)hipStreamSynchronize(v.stream);
-    return genphi_set_error(GENPHI_ERR_DEVICE, std::string(name) + ": " + hipGetErrorString(e));
 }
 
 }  // namespace

@@ -306,6 +306,43 @@ function phiClusters(pedigree::GenLib.Pedigree, threshold::Real, probandIDs::Vec
 end
 
 """
+    phiTree(pedigree::GenLib.Pedigree, probandIDs::Vector{Int} = GenLib.pro(pedigree); floor::Real = nextfloat(0.0f0),
+            device::Integer = -1)
+
+The single-linkage tree of the kinships -- the families of `phiClusters` at every cutoff at once -- as
+`(pro, row, col, pro1, pro2, kinship, floor, n_trees, rounds)`: the edges of the maximum spanning forest of the graph whose edges are the
+pairs of probands with kinship at or above `floor` (`phiOver`'s rule; the default is the smallest positive `Float32`, "any positive
+kinship"), ordered by larger kinship first, then smaller `row`, then smaller `col` (positions 1-based here, in the order of
+`unique(probandIDs)`; `row < col`).  An edge belongs to the forest iff no path of preceding edges joins its ends, so the answer is unique;
+the connected components of the listed edges with kinship `>= t` are `phiClusters`' at `t` for every `t >= floor`.  The matrix stays on
+the GPU and the pairs are never listed or sorted: `genphi_result_tree` runs Boruvka's rounds there over the rows of the resident matrix.
+The reference has no such function; the definition is this package's own (`include/genphi.h`).  Not run: there is no Julia where this
+package is built and tested.
+"""
+function phiTree(pedigree::GenLib.Pedigree, probandIDs::Vector{Int} = GenLib.pro(pedigree); floor::Real = nextfloat(0.0f0),
+                 device::Integer = -1)
+    isnan(floor) && throw(ArgumentError("the floor is NaN"))
+    ordered = unique(probandIDs)
+    foreach(ID -> pedigree[ID], ordered)                                    # KeyError on unknown ID
+    plan = create_plan(pedigree, ordered, nothing)
+    try
+        opts = Ref(GenphiOpts(Int32(device), 0, 0, 0, 0, 0))
+        check(ccall((:genphi_compute_device, libgenphi), Cint, (Ptr{Cvoid}, Ptr{GenphiOpts}, Ptr{Cvoid}), plan, opts, C_NULL))
+        slots = max(length(ordered) - 1, 0)
+        rows = Vector{Int32}(undef, slots); cols = Vector{Int32}(undef, slots); kinship = Vector{Float32}(undef, slots)
+        m = Ref{Int64}(0); trees = Ref{Int64}(0); rounds = Ref{Int32}(0)
+        GC.@preserve rows cols kinship check(ccall((:genphi_result_tree, libgenphi), Cint,
+            (Ptr{Cvoid}, Float64, Ptr{Int32}, Ptr{Int32}, Ptr{Float32}, Ptr{Int64}, Ptr{Int64}, Ptr{Int32}),
+            plan, Float64(floor), rows, cols, kinship, m, trees, rounds))
+        row = Int.(rows[1:m[]]) .+ 1; col = Int.(cols[1:m[]]) .+ 1
+        return (pro = ordered, row = row, col = col, pro1 = ordered[row], pro2 = ordered[col], kinship = kinship[1:m[]], floor = Float64(floor),
+                n_trees = trees[], rounds = Int(rounds[]))
+    finally
+        destroy_plan(plan)
+    end
+end
+
+"""
     phiUnrelated(pedigree::GenLib.Pedigree, threshold::Real, probandIDs::Vector{Int} = GenLib.pro(pedigree);
                  priority = :degree, device::Integer = -1)
 

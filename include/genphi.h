@@ -498,6 +498,52 @@ int genphi_result_clusters(genphi_plan *plan, double threshold, int32_t *label, 
 int genphi_result_unrelated(genphi_plan *plan, double threshold, const int32_t *priority, uint8_t *member, int32_t *degree,
                             int64_t *n_members, int32_t *rounds);
 
+/* The single-linkage tree of the kinships: which probands merge at which kinship, from the closest pairs down to `floor`.
+ * It is the maximum spanning forest of the graph of genphi_result_clusters taken at every threshold at once, found on the resident
+ * result by Boruvka's rounds.  Neither GENLIB nor the reference has such a function, so this text is the definition.  N is the number
+ * of probands after duplicates collapse (genphi_plan_create); positions are 0-based in that order.
+ *   edges             the pairs i < j with (double)Phi[i][j] >= floor: the rule and the comparison of genphi_result_over.  floor <= 0
+ *                     makes every pair an edge, +infinity gives no edge, NaN is an error.  The padding columns j >= N of the row pitch
+ *                     never take part, and neither does the diagonal.
+ *   the order         edge (i, j) precedes (i', j') when its kinship is larger, then when i is smaller, then when j is smaller.
+ *                     Entries are finite and >= +0, so the Float32 bit pattern orders like the value: a strict total order.
+ *   the forest        an edge belongs to the forest iff no path of preceding edges joins its ends (Kruskal's rule).  Under a strict
+ *                     order the forest is unique: a function of the matrix and floor alone.
+ *   row, col, kinship the M = N - *n_trees edges of the forest in that order: row[k] < col[k], kinship[k] the entry Phi[row[k]][col[k]]
+ *                     bit for bit.  The caller gives arrays of N - 1 entries; entries from M on are not written.
+ *   *n_edges          M
+ *   *n_trees          the connected components of the graph at `floor`: the n_clusters of genphi_result_clusters(floor)
+ *   *rounds           the rounds it took; the number genphi_tree_host takes on the same matrix
+ * Any output pointer may be NULL.  Invariants:
+ *   1. for every t >= floor the connected components of the listed edges with kinship >= t are exactly the labels of
+ *      genphi_result_clusters(t);
+ *   2. the number of listed edges with kinship >= t is N - n_clusters(t);
+ *   3. a larger floor gives the prefix of the list that passes it;
+ *   4. the same call gives the same bytes;
+ *   5. *rounds <= ceil(log2 N) + 1, and it equals the host restatement's.
+ * A round: every row of a component that still grows is read whole (4 N bytes; the best edge out of a component may lead to a column
+ * left of the row) for the row's best edge out of its component; every component picks the best of its rows' edges under the order
+ * above, by integer atomic maxima and minima only; the picked edges, each once, go to the forest and join their ends (the lock-free
+ * union-find of genphi_result_clusters); the labels are flattened, and the host reads 8 bytes: the edges of the round.  A component
+ * that finds no edge out is a finished tree and its rows are not read again.  It ends after a round without an edge or when N - 1
+ * edges are there; a round with an edge at least halves the components that still grow.  The list is sorted on the host.
+ * The full Float32 result must be resident, as for genphi_result_clusters: a row shard (an empty one too) is GENPHI_ERR_ARG, a Float64
+ * result is GENPHI_ERR_ARG, a plan without a resident result GENPHI_ERR_DEVICE; N = 0 or N = 1 is GENPHI_OK with no edge, N trees and
+ * 0 rounds (checked before the result is).  Device memory, in the plan's scratch block: 41 N bytes (per proband two labels, an 8-byte
+ * row key, a 4-byte and an 8-byte component key, a flag, and a 12-byte slot of the edge buffer).  The phiOver counts the library keeps
+ * are not touched.  GENPHI_ERR_ARG: NULL plan, NaN floor, a Float64 result, a row shard; GENPHI_ERR_DEVICE: no resident result;
+ * GENPHI_ERR_ALLOC: the scratch does not fit (found before the first launch).  After an error the plan stays usable, the resident
+ * result is untouched, and no output is written.
+ *
+ * genphi_tree_host: host only (no GPU), in the role of genphi_link_words: the same rounds with the same key arithmetic (csrc/tree_keys.h)
+ * on a host matrix m of n rows with row pitch ld >= n (the columns from n on are never read).  m must be symmetric with finite entries
+ * >= +0, as a result is; both halves are read, as on the device.  The same outputs; GENPHI_ERR_ARG: n outside [0, 2^31), NaN floor,
+ * NULL m with n >= 2, ld < n.                                                                                                       */
+int genphi_result_tree(genphi_plan *plan, double floor, int32_t *row, int32_t *col, float *kinship, int64_t *n_edges, int64_t *n_trees,
+                       int32_t *rounds);
+int genphi_tree_host(const float *m, int64_t n, int64_t ld, double floor, int32_t *row, int32_t *col, float *kinship, int64_t *n_edges,
+                     int64_t *n_trees, int32_t *rounds);
+
 /* GENLIB's gen.phiCI(phiMatrix, prob, b) and gen.fCI(vectF, prob, b): bootstrap confidence intervals of the mean kinship and of the
  * mean inbreeding.  The reference has neither, so this text is the definition.  N is the number of probands after
  * duplicates collapse (genphi_plan_create), N >= 2.
