@@ -27,6 +27,7 @@ meaning, printed lines and error behaviour as the reference:
     gen.simuIdentity(ped)                  # Jacquard's nine identity coefficients of every pair by gene dropping (csrc/ident.hip)
     gen.simuRetention(ped)                 # founder allele survival, founder genome equivalents by gene dropping (csrc/retain.hip)
     gen.simuCarriers(ped, pro, controls)   # per founder allele: how many of the cases carry it, by gene dropping (csrc/carry.hip)
+    gen.simuOrigins(ped, pro, groups)      # which founders the kinship and inbreeding of groups come from (csrc/origin.hip)
     gen.simuSharing(ped, loci=1024)        # linked loci: realised IBD sharing, its variance and the segments (csrc/link.hip)
     gen.simuSegments(ped, loci=1024)       # the lengths of those segments: histogram, within and between groups, per pair
     gen.descendant(ped, 1); gen.children(ped, 1)   # src/identify.jl:203-215, :77-80 (csrc/loader.cpp)
@@ -43,7 +44,7 @@ from collections import OrderedDict
 import numpy as np
 
 from . import _capi
-from ._capi import PhiPlan, KinshipMatrix, GCPlan, OccPlan, RecPlan, DistPlan, DepthPlan, CompletenessPlan, ImplexPlan, SimuPlan, IdentityPlan, RetentionPlan, CarriersPlan, SharingPlan, GenphiDeviceError, GenphiLibraryMissing  # noqa: F401
+from ._capi import PhiPlan, KinshipMatrix, GCPlan, OccPlan, RecPlan, DistPlan, DepthPlan, CompletenessPlan, ImplexPlan, SimuPlan, IdentityPlan, RetentionPlan, CarriersPlan, OriginsPlan, SharingPlan, GenphiDeviceError, GenphiLibraryMissing  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
@@ -948,6 +949,157 @@ def simuCarriers(pedigree, pro=None, controls=None, simulNo=5000, seed=None, max
             t[:, 0] = h.simul_no - excluded - t[:, 1:].sum(axis=1, dtype=np.int64)
             tables.append(t)
         return SimuCarriers(np.unique(cases), np.unique(others), h.alleles(), tables[0], tables[1], excluded, h.simul_no, h.seed)
+    finally:
+        h.close()
+
+
+class SimuOrigins:
+    """What gen.simuOrigins returns.  pro: the distinct probands that are in a group, in order of first appearance; alleles: int64
+    (n_labels, 2), the ID and the side (0 = from the father) of every founder allele, in label order; names: the groups, sorted
+    (["all"] without groups); sizes: int64 (G,), the distinct probands of every group; simulNo and the seed used.  The integer
+    tables (the definition is the text of genphi_origin_* in include/genphi.h): copies, autozygous: int64 (G, n_labels); matches:
+    int64 (G, G, n_labels), symmetric, [a, a] counting the pairs of DIFFERENT probands of a; autozygous_pro: int32 (len(pro),
+    n_labels) with byProband, else None.  Every share below is formed once from the integers, in Float64; a mean over no proband or
+    no pair is NaN."""
+
+    def __init__(self, pro, alleles, names, sizes, copies, autozygous, matches, autozygous_pro, simulNo, seed):
+        self.pro, self.alleles, self.names, self.sizes = pro, alleles, list(names), np.asarray(sizes, dtype=np.int64)
+        self.copies, self.autozygous, self.matches, self.autozygous_pro = copies, autozygous, matches, autozygous_pro
+        self.simulNo, self.seed = simulNo, seed
+
+    def __repr__(self):
+        return "SimuOrigins(%d probands in %d groups, %d founder alleles, simulNo=%d, seed=%d)" % (len(self.pro), len(self.names), len(self.alleles),
+                                                                                                  self.simulNo, self.seed)
+
+    @property
+    def founders(self):
+        """The IDs of the allele table, ascending: the founders and half-founders of the live set."""
+        return np.unique(self.alleles[:, 0])
+
+    def _by_founder(self, table):
+        """table (.., n_labels) with the alleles of one founder summed: (.., len(founders))."""
+        founders, at = np.unique(self.alleles[:, 0], return_inverse=True)
+        out = np.zeros(table.shape[:-1] + (len(founders),), dtype=table.dtype)
+        np.add.at(out, (Ellipsis, at), table)
+        return out
+
+    @property
+    def _pairs(self):
+        """int64 (G, G): the pairs of different probands within a group, n_a n_b between two."""
+        n = self.sizes
+        pairs = np.outer(n, n)
+        pairs[np.diag_indices(len(n))] = n * (n - 1) // 2
+        return pairs
+
+    @staticmethod
+    def _over(num, den):
+        """num / den in Float64, NaN where den is 0."""
+        den = np.asarray(den, dtype=np.float64)
+        return np.divide(num, den, out=np.full(np.broadcast(num, den).shape, np.nan), where=den != 0)
+
+    @property
+    def frequency(self):
+        """(G, n_labels): the expected frequency of every founder allele among the gene copies of a group, copies / (2 n_a S); a row
+        sums to 1."""
+        return self._over(self.copies, (2 * self.sizes * self.simulNo)[:, None])
+
+    @property
+    def kinship(self):
+        """(G, G): the mean kinship within (pairs of different probands) and between groups, the sum over the alleles of matches /
+        (4 S pairs): gen.phiMeanGroups' table by gene dropping."""
+        return self._over(self.matches.sum(axis=2), 4 * self.simulNo * self._pairs)
+
+    @property
+    def kinship_by_allele(self):
+        """(G, G, n_labels): the part of kinship that descends from every founder allele; sums to kinship over the last axis."""
+        return self._over(self.matches, (4 * self.simulNo * self._pairs)[:, :, None])
+
+    def kinship_by_founder(self):
+        """(G, G, len(founders)): kinship_by_allele with the two alleles of a founder summed (from the integers)."""
+        return self._over(self._by_founder(self.matches), (4 * self.simulNo * self._pairs)[:, :, None])
+
+    @property
+    def share(self):
+        """(G, G, n_labels): the share of every founder allele in the kinship of a pair of groups, matches / its sum over the alleles;
+        zeros where the pair of groups has no kinship at all."""
+        total = self.matches.sum(axis=2)
+        return np.divide(self.matches, total[:, :, None], out=np.zeros(self.matches.shape), where=total[:, :, None] != 0)
+
+    @property
+    def inbreeding(self):
+        """(G,): the mean inbreeding of the probands of every group, the sum over the alleles of autozygous / (n_a S)."""
+        return self._over(self.autozygous.sum(axis=1), self.sizes * self.simulNo)
+
+    def inbreeding_by_founder(self):
+        """(G, len(founders)): the part of inbreeding that descends from every founder; sums to inbreeding over the last axis."""
+        return self._over(self._by_founder(self.autozygous), (self.sizes * self.simulNo)[:, None])
+
+    def partial_inbreeding(self):
+        """(len(pro), len(founders)): the partial inbreeding coefficients of every proband (Lacy, Alaks & Walsh 1996): the share of
+        the simulations in which both its alleles descend from the founder.  ValueError without byProband."""
+        if self.autozygous_pro is None:
+            raise ValueError("gen.simuOrigins: partial_inbreeding() needs byProband=True")
+        return self._by_founder(self.autozygous_pro.astype(np.int64)) / float(self.simulNo)
+
+    def ranking(self, a, b, k=10):
+        """The labels of the k founder alleles with the largest share in the kinship of the groups named a and b (a == b: within
+        the group), by larger share and then smaller allele index.  KeyError for an unknown name."""
+        for name in (a, b):
+            if name not in self.names:
+                raise KeyError(name)
+        m = self.matches[self.names.index(a), self.names.index(b)]
+        return np.lexsort((np.arange(len(m)), -m))[:max(int(k), 0)]
+
+
+def simuOrigins(pedigree, pro=None, groups=None, simulNo=5000, seed=None, byProband=False, device=None):
+    """gen.simuOrigins(pedigree, pro = pro(pedigree), groups = None, simulNo = 5000): which founders does the kinship of the probands
+    come from -- within a group, between two groups, and in the inbreeding of the probands themselves (Lacy's partition of kinship and
+    inbreeding by founder; the inbreeding half is the partial inbreeding coefficients of Lacy, Alaks & Walsh 1996)?  Every founder
+    allele is dropped down the pedigree under its own label simulNo times (the labels of gen.simuIdentity under the same seed), and per
+    simulation, founder allele and group the gene copies are counted: k_a copies in group a and k_b in group b are k_a k_b matching
+    copy pairs, so no pair of probands is ever looked at.  Returns a SimuOrigins: copies, autozygous, matches, autozygous_pro,
+    frequency, kinship, kinship_by_allele, kinship_by_founder(), share, inbreeding, inbreeding_by_founder(), partial_inbreeding(),
+    ranking(a, b, k).  Neither GENLIB nor the reference has this function.
+
+    groups: a mapping ID -> group name, as gen._pop returns and gen.simuSegments takes; at most 32 names; probands that are not in it
+    are swept (the realisation is that of the whole list) but counted nowhere.  None: one group named "all".  byProband: keep the
+    (probands x founder alleles) table that partial_inbreeding() needs.  The result is integers added by integer additions: a pure
+    function of the pedigree's relations, the SET of probands with their groups (order and repeats change nothing), the seed and
+    simulNo (include/genphi.h); gen.branching(pedigree, pro=..) first changes nothing.  seed=None draws 64 fresh bits; pass a seed to
+    repeat a run.  The sweep and the counts run on the GPU (csrc/origin.hip); only the tables come back.  Not offered: origins per pair
+    of probands, the exact partial kinship (one kinship sweep per founder), linked loci, more than one device.
+
+    KeyError for an unknown ID; ValueError for an empty pro or groups, no proband in a group, more than 32 groups, more than 32,767
+    distinct probands in a group, more than 2^31 - 1 cells with byProband, or simulNo outside 1 .. 2^24.  Each call plans, sweeps and
+    frees its own handle."""
+    probands = globals()["pro"](pedigree) if pro is None else np.ascontiguousarray(pro, dtype=np.int64)
+    if groups is None:
+        names, labels = ["all"], None
+        grouped = probands
+        of = np.zeros(len(probands), dtype=np.int32)
+    else:
+        if len(groups) == 0:
+            raise ValueError("groups is empty")
+        names = sorted(set(groups.values()))
+        if len(names) > 32:
+            raise ValueError("gen.simuOrigins: %d groups: at most 32" % len(names))
+        index = {name: k for k, name in enumerate(names)}
+        labels = np.array([index[groups[i]] if i in groups else -1 for i in probands.tolist()], dtype=np.int32)
+        grouped, of = probands[labels >= 0], labels[labels >= 0]
+    h = OriginsPlan(pedigree.ind, pedigree.father, pedigree.mother, probands, labels, n_groups=len(names), simul_no=simulNo, seed=seed,
+                    by_proband=byProband)
+    try:
+        h.compute(device=device)
+        first = np.sort(np.unique(grouped, return_index=True)[1])                           # the distinct grouped probands, by first appearance
+        sizes = np.bincount(of[first], minlength=len(names)).astype(np.int64)
+        G = len(names)
+        upper = h.matches_to_host()
+        matches = np.zeros((G, G, h.n_labels), dtype=np.int64)
+        rows, cols = np.triu_indices(G)                                                     # row-major over the upper triangle
+        matches[rows, cols] = upper
+        matches[cols, rows] = upper
+        return SimuOrigins(grouped[first], h.alleles(), names, sizes, h.copies_to_host(), h.autozygous_to_host(), matches,
+                           h.by_proband_to_host() if byProband else None, h.simul_no, h.seed)
     finally:
         h.close()
 

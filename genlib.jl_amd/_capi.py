@@ -85,6 +85,9 @@ EXPORTED_SYMBOLS = [
     "genphi_retain_both_to_host", "genphi_retain_distinct_to_host", "genphi_retain_stats", "genphi_retain_destroy",
     "genphi_carry_create", "genphi_carry_levels", "genphi_carry_alleles", "genphi_carry_compute", "genphi_carry_carriers_to_host",
     "genphi_carry_homozygotes_to_host", "genphi_carry_excluded_to_host", "genphi_carry_stats", "genphi_carry_destroy",
+    "genphi_origin_create", "genphi_origin_levels", "genphi_origin_alleles", "genphi_origin_compute", "genphi_origin_copies_to_host",
+    "genphi_origin_autozygous_to_host", "genphi_origin_matches_to_host", "genphi_origin_by_proband_to_host", "genphi_origin_stats",
+    "genphi_origin_destroy",
     "genphi_link_create", "genphi_link_levels", "genphi_link_alleles", "genphi_link_compute", "genphi_link_sums_to_host",
     "genphi_link_labels_to_host", "genphi_link_stats", "genphi_link_destroy", "genphi_link_words",
     "genphi_seg_request", "genphi_seg_to_host", "genphi_seg_stats", "genphi_seg_host",
@@ -410,6 +413,25 @@ def lib():
         L.genphi_carry_stats.restype = C.c_int
         L.genphi_carry_destroy.argtypes = [C.c_void_p]
         L.genphi_carry_destroy.restype = None
+        L.genphi_origin_create.argtypes = [C.c_int64, _I64P, _I64P, _I64P, C.c_int64, _I64P, _I32P, C.c_int32, C.c_int64, C.c_uint64, C.c_int32, C.c_int32,
+                                           C.c_int32, C.POINTER(C.c_void_p)]
+        L.genphi_origin_create.restype = C.c_int
+        L.genphi_origin_levels.argtypes = [C.c_void_p, _I64P, _I32P, _I64P]
+        L.genphi_origin_levels.restype = C.c_int
+        L.genphi_origin_alleles.argtypes = [C.c_void_p, _I64P, _I32P, _I64P, _I32P]
+        L.genphi_origin_alleles.restype = C.c_int
+        L.genphi_origin_compute.argtypes = [C.c_void_p, C.c_int32]
+        L.genphi_origin_compute.restype = C.c_int
+        for name in ("copies", "autozygous", "matches"):
+            fn = getattr(L, "genphi_origin_%s_to_host" % name)
+            fn.argtypes = [C.c_void_p, _I64P]
+            fn.restype = C.c_int
+        L.genphi_origin_by_proband_to_host.argtypes = [C.c_void_p, _I32P]
+        L.genphi_origin_by_proband_to_host.restype = C.c_int
+        L.genphi_origin_stats.argtypes = [C.c_void_p, _F64P, _F64P, _F64P, _F64P, _I32P, _I32P, _I64P, _I32P, _I32P, _I64P, _I32P, _I32P, _I32P]
+        L.genphi_origin_stats.restype = C.c_int
+        L.genphi_origin_destroy.argtypes = [C.c_void_p]
+        L.genphi_origin_destroy.restype = None
         L.genphi_link_create.argtypes = [C.c_int64, _I64P, _I64P, _I64P, C.c_int64, _I64P, C.c_int32, C.c_int32, C.c_int64, C.c_uint64, C.c_int32,
                                          C.c_int32, C.POINTER(C.c_void_p)]
         L.genphi_link_create.restype = C.c_int
@@ -1884,6 +1906,71 @@ class CarriersPlan(_LabelPlan):
         return self._stats(sweep_ms=C.c_double, count_ms=C.c_double, algorithmic_bytes=C.c_double, count_bytes=C.c_double, levels=C.c_int32,
                            panel_cols=C.c_int32, panels=C.c_int64, planes=C.c_int32, chunk_labels=C.c_int32, chunks=C.c_int64,
                            lds_bytes=C.c_int32, columns=C.c_int32, n_cases=C.c_int32, n_controls=C.c_int32)
+
+
+class OriginsPlan(_LabelPlan):
+    """The handle of gen.simuOrigins (include/genphi.h, genphi_origin_*): per founder allele, the gene copies, the autozygous probands
+    and the matching copy pairs within and between groups of probands, by gene dropping.  Planned on the host at construction (KeyError
+    on an unknown ID; ValueError for no probands or none in a group, n_groups outside 1 .. 32, a group outside -1 .. n_groups - 1, an
+    ID listed with two groups, more than 32,767 distinct probands in a group, more than 2^31 - 1 cells by proband, simul_no outside
+    1 .. 2^24, a negative panel_cols or chunk_labels; no GPU needed), swept on the GPU by compute().  The plan and the labels are
+    gen.IdentityPlan's for the same list.  groups: per listed ID an integer in -1 .. n_groups - 1 (-1: swept, counted nowhere), or None
+    = everyone in group 0 (n_groups = 1).  seed=None draws 64 fresh bits; .seed reports the seed used.  panel_cols: the simulations
+    of a panel (0 = the default).  chunk_labels: the founder alleles of a chunk of the count kernel (0 = the default, the widest).
+    by_proband: keep autozygous_pro.  n_grouped: the distinct probands in any group; n_pairs = n_groups (n_groups + 1) / 2."""
+
+    _prefix = "origin"
+
+    def __init__(self, ind, father, mother, pro_ids, groups=None, n_groups=1, simul_no=5000, seed=None, panel_cols=0, chunk_labels=0, by_proband=False):
+        pro_ids = _i64(pro_ids).ravel()
+        if groups is not None:
+            g = np.asarray(groups).ravel()
+            if len(g) != len(pro_ids):
+                raise ValueError("gen.simuOrigins: %d probands but %d groups" % (len(pro_ids), len(g)))
+            if len(g) and not np.array_equal(g, g.astype(np.int32)):
+                raise ValueError("gen.simuOrigins: the groups must be 32-bit integers")
+            groups = np.ascontiguousarray(g, dtype=np.int32)
+        self._set_seed(seed)
+        self.simul_no = int(simul_no)
+        self.n_groups = int(n_groups)
+        self.by_proband = bool(by_proband)
+        ind, father, mother = _i64(ind), _i64(father), _i64(mother)
+        h = C.c_void_p()
+        rc = lib().genphi_origin_create(len(ind), ind.ctypes.data_as(_I64P), father.ctypes.data_as(_I64P), mother.ctypes.data_as(_I64P),
+                                        len(pro_ids), pro_ids.ctypes.data_as(_I64P), None if groups is None else groups.ctypes.data_as(C.POINTER(C.c_int32)),
+                                        self.n_groups, self.simul_no, self.seed, int(panel_cols), int(chunk_labels), int(self.by_proband), C.byref(h))
+        if rc:
+            _raise(rc)
+        self._h = h
+        self.n_pro = len(pro_ids)
+        self._read_plan()
+        self.n_grouped = self.stats()["n"]
+        self.n_pairs = self.n_groups * (self.n_groups + 1) // 2
+
+    def copies_to_host(self):
+        """int64 (n_groups, n_labels): the gene copies of label l among the distinct probands of group a, summed over the simulations."""
+        return self._out("copies_to_host", (self.n_groups, self.n_labels), np.int64, C.c_int64)
+
+    def autozygous_to_host(self):
+        """int64 (n_groups, n_labels): the probands of group a with both sides equal to label l, summed over the simulations."""
+        return self._out("autozygous_to_host", (self.n_groups, self.n_labels), np.int64, C.c_int64)
+
+    def matches_to_host(self):
+        """int64 (n_pairs, n_labels): the matching copy pairs of label l between different probands of a (pair (a, a)) or between the
+        probands of a and of b, summed over the simulations; the pairs a <= b row-major over the upper triangle."""
+        return self._out("matches_to_host", (self.n_pairs, self.n_labels), np.int64, C.c_int64)
+
+    def by_proband_to_host(self):
+        """int32 (n_grouped, n_labels): the simulations in which both sides of distinct grouped proband i (in order of first appearance)
+        equal label l.  ValueError unless created with by_proband=True."""
+        return self._out("by_proband_to_host", (self.n_grouped, self.n_labels), np.int32, C.c_int32)
+
+    def stats(self):
+        """dict(sweep_ms, count_ms, algorithmic_bytes, count_bytes, levels, panel_cols, panels, planes, chunk_labels, chunks, lds_bytes,
+        n_groups, n) of the last compute()."""
+        return self._stats(sweep_ms=C.c_double, count_ms=C.c_double, algorithmic_bytes=C.c_double, count_bytes=C.c_double, levels=C.c_int32,
+                           panel_cols=C.c_int32, panels=C.c_int64, planes=C.c_int32, chunk_labels=C.c_int32, chunks=C.c_int64,
+                           lds_bytes=C.c_int32, n_groups=C.c_int32, n=C.c_int32)
 
 
 GENPHI_LINK_FLAG_LABELS = 1

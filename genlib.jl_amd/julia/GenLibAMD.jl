@@ -965,6 +965,71 @@ function simuCarriers(pedigree::GenLib.Pedigree, pro::Vector{Int} = GenLib.pro(p
 end
 
 """
+    simuOrigins(pedigree::GenLib.Pedigree, pro = GenLib.pro(pedigree); groups = nothing, simulNo = 5000, seed = nothing,
+                byProband = false, device = -1)
+
+Which founder alleles the kinship within and between groups of probands, and their inbreeding, descend from, by gene dropping on the
+GPU (csrc/origin.hip; GenLib.jl has no form of it; the definition is the text of `genphi_origin_*` in include/genphi.h).  `groups`: a
+`Dict` ID => group name (probands that are not in it are swept but counted nowhere; at most 32 names), `nothing` = one group "all".
+Returns a named tuple: `pro` (the distinct grouped probands by first appearance), `alleles` (the founder alleles as `(ID, side)`, in
+label order), `names` (sorted), `sizes`, the Int64 matrices `copies` and `autozygous` (`length(alleles) x G`: the library's row-major
+`G x n_labels` is the memory of that array), `matches` (`length(alleles) x P`, the pairs `a <= b` of groups row-major over the upper
+triangle, `P = G (G + 1) / 2`), `autozygous_pro` (Int32, `length(alleles) x length(pro)`, or `nothing` without `byProband`),
+`frequency` (`copies ./ (2 n_a simulNo)`), `simulNo` and the `seed` used (`nothing` draws 64 fresh bits).
+NOT run anywhere yet, like the rest of this file (no Julia in the build container).
+"""
+function simuOrigins(pedigree::GenLib.Pedigree, pro::Vector{Int} = GenLib.pro(pedigree); groups::Union{Nothing, AbstractDict} = nothing,
+                     simulNo::Integer = 5000, seed::Union{Nothing, UInt64} = nothing, byProband::Bool = false, device::Integer = -1)
+    isempty(pro) && throw(ArgumentError("gen.simuOrigins: no probands"))
+    seed64 = isnothing(seed) ? rand(Random.RandomDevice(), UInt64) : seed
+    names = isnothing(groups) ? Any["all"] : sort(unique(collect(values(groups))))
+    isempty(names) && throw(ArgumentError("groups is empty"))
+    length(names) > 32 && throw(ArgumentError("gen.simuOrigins: $(length(names)) groups: at most 32"))
+    index = Dict(name => Int32(k - 1) for (k, name) in enumerate(names))
+    labels = isnothing(groups) ? zeros(Int32, length(pro)) : Int32[haskey(groups, i) ? index[groups[i]] : Int32(-1) for i in pro]
+    G = length(names)
+    ind, father, mother, _ = flatten(pedigree)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve ind father mother pro labels check(ccall((:genphi_origin_create, libgenphi), Cint,
+        (Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Int64, Ptr{Int64}, Ptr{Int32}, Int32, Int64, UInt64, Int32, Int32, Int32, Ptr{Ptr{Cvoid}}),
+        length(ind), ind, father, mother, length(pro), pro, labels, Int32(G), Int64(simulNo), seed64, Int32(0), Int32(0),
+        Int32(byProband), h))
+    try
+        n_labels = Ref{Int64}(0)
+        planes = Ref{Int32}(0)
+        check(ccall((:genphi_origin_alleles, libgenphi), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int32}, Ptr{Int64}, Ptr{Int32}),
+                    h[], n_labels, planes, C_NULL, C_NULL))
+        n = Int(n_labels[])
+        ids = Vector{Int64}(undef, n); sides = Vector{Int32}(undef, n)
+        GC.@preserve ids sides check(ccall((:genphi_origin_alleles, libgenphi), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int32}, Ptr{Int64}, Ptr{Int32}),
+                                           h[], C_NULL, C_NULL, ids, sides))
+        check(ccall((:genphi_origin_compute, libgenphi), Cint, (Ptr{Cvoid}, Int32), h[], Int32(device)))
+        seen = Set{Int}()
+        grouped = Int[]; of = Int[]
+        for (i, g) in zip(pro, labels)
+            (g >= 0 && !(i in seen)) || continue
+            push!(seen, i); push!(grouped, i); push!(of, Int(g) + 1)
+        end
+        sizes = [count(==(a), of) for a in 1:G]
+        P = G * (G + 1) ÷ 2
+        copies = Matrix{Int64}(undef, n, G); autozygous = Matrix{Int64}(undef, n, G); matches = Matrix{Int64}(undef, n, P)
+        GC.@preserve copies check(ccall((:genphi_origin_copies_to_host, libgenphi), Cint, (Ptr{Cvoid}, Ptr{Int64}), h[], copies))
+        GC.@preserve autozygous check(ccall((:genphi_origin_autozygous_to_host, libgenphi), Cint, (Ptr{Cvoid}, Ptr{Int64}), h[], autozygous))
+        GC.@preserve matches check(ccall((:genphi_origin_matches_to_host, libgenphi), Cint, (Ptr{Cvoid}, Ptr{Int64}), h[], matches))
+        by_pro = nothing
+        if byProband
+            by_pro = Matrix{Int32}(undef, n, length(grouped))
+            GC.@preserve by_pro check(ccall((:genphi_origin_by_proband_to_host, libgenphi), Cint, (Ptr{Cvoid}, Ptr{Int32}), h[], by_pro))
+        end
+        frequency = copies ./ reshape(2.0 .* sizes .* Float64(simulNo), 1, G)
+        return (pro = grouped, alleles = collect(zip(Int.(ids), Int.(sides))), names = names, sizes = sizes, copies = copies,
+                autozygous = autozygous, matches = matches, autozygous_pro = by_pro, frequency = frequency, simulNo = Int(simulNo), seed = seed64)
+    finally
+        ccall((:genphi_origin_destroy, libgenphi), Cvoid, (Ptr{Cvoid},), h[])
+    end
+end
+
+"""
     simuSegments(pedigree::GenLib.Pedigree, pro = GenLib.pro(pedigree); loci = 1024, length = 1.0, probRecomb = nothing,
                  simulNo = 1000, seed = nothing, bins = nothing, minLoci = 1, groups = nothing, device = -1)
 

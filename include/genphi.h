@@ -1287,6 +1287,87 @@ int genphi_carry_stats(const genphi_carry *h, double *sweep_ms, double *count_ms
                        int64_t *chunks, int32_t *lds_bytes, int32_t *columns, int32_t *n_cases, int32_t *n_controls);
 void genphi_carry_destroy(genphi_carry *h);
 
+/* ---- gen.simuOrigins: which founders the kinship and the inbreeding come from (csrc/origin.hip, csrc/origin.h, csrc/label_sweep.h) --
+ * Which founder alleles do the identical-by-descent alleles of two probands descend from: within a group of probands, between two
+ * groups, and in the inbreeding of the probands themselves?  This is Lacy's partition of kinship and inbreeding by founder; its
+ * inbreeding half is the partial inbreeding coefficients of Lacy, Alaks & Walsh (1996).  The exact recursion is one kinship sweep per
+ * founder; the field computes it by gene dropping.  The reference has no form of it, so this text is the definition, and it is this
+ * package's own.
+ * Inputs.  A pedigree; a list of probands, at least one, which counts as a SET; group[k], per listed entry an Int32 in -1 .. G - 1
+ * (NULL: everyone is in group 0 and G = 1); G in 1 .. 32; S in 1 .. 2^24 and a 64-bit seed.  A proband with group -1 stays in the
+ * plan, so the realisation does not change; it is counted nowhere.  An ID listed twice with two different groups (-1 counts as one)
+ * is GENPHI_ERR_ARG.  On the list as given the live set, levels, rows, allele table, labels LP_x[s] / LM_x[s], the rule and the random
+ * word R are those of genphi_ident_* above, word for word.  The same (pedigree relations, seed) therefore gives the same realisation
+ * as gen.simuIdentity, gen.simuRetention, gen.simuCarriers and gen.simuSharing.
+ * Let n_a be the number of distinct probands of group a, and n the number of distinct probands in any group, ordered by first
+ * appearance in the list.  Per simulation s < S, label l and group a:
+ *   c1_a(l, s) = the distinct probands of a with at least one side equal to l,
+ *   c2_a(l, s) = those with both sides equal to l,
+ *   k_a  = c1_a + c2_a, the gene copies of l in a,
+ *   m_aa = (k_a^2 - c1_a - 3 c2_a) / 2, the matching copy pairs between two DIFFERENT probands of a (the sum over i < j of k_i k_j),
+ *   m_ab = k_a k_b for a < b.
+ * With P = G (G + 1) / 2 and p numbering the pairs a <= b row-major over the upper triangle (p = a G - a (a - 1) / 2 + b - a):
+ *   copies[a, l]           Int64 x G x n_labels, row-major: the sum over s of k_a.
+ *   autozygous[a, l]       Int64 x G x n_labels: the sum over s of c2_a.
+ *   matches[p, l]          Int64 x P x n_labels: the sum over s of m_ab.
+ *   autozygous_pro[i, l]   Int32 x n x n_labels, only when requested: the s in which both sides of distinct proband i equal l.
+ * Bits at positions >= S are never counted.  Word sizes: k <= 65,534, so a term of one simulation is below 2^32; a sum over
+ * simulations is not: every accumulation past a single term is 64-bit.
+ * Invariants, all exact integers.
+ *   1. The sum over l of copies[a, l] is 2 n_a S: every side of every proband carries one label.
+ *   2. With G = 1 and the same list, seed and S, for genphi_carry_* with no controls and W = n + 1: copies[0, l] is the sum over c of
+ *      c (carriers[l, c] + homozygotes[l, c]), and autozygous[0, l] is the sum over c of c homozygotes[l, c].
+ *   3. Against genphi_ident_* on the distinct probands, same seed and S: the sum over l of matches[(a, b), l] equals
+ *      4 n1 + 2 (n3 + n5 + n7) + n8 of its counts, summed over the pairs i < j within a, or over i in a and j in b (the numerator of
+ *      the kinship of gen.simuIdentity); the sum over l of autozygous[a, l] equals the sum over i in a of counts[i, i, 0].
+ *   4. Merging groups adds.  For a union A of groups, copies and autozygous of A are the sums over its parts, and matches[(A, A)] is
+ *      the sum over a in A of m_aa plus the sum over a < b in A of m_ab: every grouping agrees with G = 1.
+ *   5. The sum over i in a of autozygous_pro[i, l] is autozygous[a, l].
+ *   6. A listed founder has autozygous_pro = 0 and, from itself, S copies at each of its own labels; two distinct founders alone in
+ *      their groups have matches = 0 between them.
+ *   7. The bytes do not depend on the panel width, the label chunk, the order or the repeats of the list, or on whether
+ *      autozygous_pro is requested; renumbering the groups permutes the tables.
+ * Errors.  Those of genphi_ident_create without the n_pro^2 >= 2^31 refusal.  GENPHI_ERR_ARG, all in create before any device work:
+ * no probands, or none in a group; G outside 1 .. 32 (NULL group: G must be 1); a group outside -1 .. G - 1; an ID with two groups;
+ * n_a > 32,767 for some a; n x n_labels > 2^31 - 1 when autozygous_pro is requested; S outside 1 .. 2^24; a negative panel_cols or
+ * chunk_labels; by_proband other than 0 or 1.  GENPHI_ERR_ALLOC from compute before any launch, when the device does not hold the
+ * tables (8 n_labels (2 G + P) bytes, and 4 n n_labels), the lists and the rows of even a 128-column panel.
+ * Method.  The label sweep of genphi_ident_* (its init and step kernels, shared), then one count kernel per panel that reads the rows
+ * of the grouped probands in place and never looks at a pair.  A workgroup owns the 64 simulations of a word and a chunk of the
+ * labels; it keeps one counter dword per (simulation, label, group) in LDS (c1 in bits 0-15, c2 in bits 16-30: n_a <= 32,767 keeps
+ * the fields apart), decodes both sides of every grouped proband once, adds by LDS atomics, and after a barrier forms k, c2, m_aa and
+ * m_ab per simulation in 64 bits, sums them over the wave and adds them into the tables with 64-bit integer atomics
+ * (csrc/origin.hip).  Not offered: origins per pair of probands, the exact partial kinship (one sweep per founder), linked loci,
+ * more than one device.
+ *   create            host only (no GPU): ident's checks and plan on the list as given; the list as a set with its groups; the
+ *                     limits.  panel_cols as for genphi_ident_create.  chunk_labels: the labels of a chunk, 0 = the default (the
+ *                     widest: the largest LC with 256 ((LC G) | 1) <= 163,840 bytes of LDS, 639 / G), else as given; either is cut
+ *                     to the widest and to n_labels (tests, A/B).  by_proband: 1 = keep autozygous_pro
+ *   levels, alleles   as genphi_ident_levels and genphi_ident_alleles
+ *   compute           the sweep on `device` (-1 = current); the tables stay resident
+ *   copies_to_host, autozygous_to_host    out: G x n_labels Int64, row-major
+ *   matches_to_host   out: P x n_labels Int64, row-major
+ *   by_proband_to_host    out: n x n_labels Int32, row-major; GENPHI_ERR_ARG unless created with by_proband
+ *   stats             of the last compute, by HIP events: the device time of init and level steps, and of the count kernel, summed
+ *                     over the panels; the algorithmic bytes of the steps (as genphi_ident_stats); the bytes of the grouped rows'
+ *                     planes the count kernel reads (2 n x B x 16 per pair of words and chunk); levels; the columns of a panel; the
+ *                     panels; B; the labels of a chunk; the chunks; the LDS bytes of a workgroup of the count kernel; G; n          */
+typedef struct genphi_origin genphi_origin;
+int genphi_origin_create(int64_t n_ind, const int64_t *ind, const int64_t *father, const int64_t *mother,
+                         int64_t n_pro, const int64_t *pro_ids, const int32_t *group, int32_t n_groups, int64_t simul_no,
+                         uint64_t seed, int32_t panel_cols, int32_t chunk_labels, int32_t by_proband, genphi_origin **out);
+int genphi_origin_levels(const genphi_origin *h, int64_t *n_live, int32_t *levels, int64_t *rows_per_level);
+int genphi_origin_alleles(const genphi_origin *h, int64_t *n_labels, int32_t *planes, int64_t *ids, int32_t *sides);
+int genphi_origin_compute(genphi_origin *h, int32_t device);
+int genphi_origin_copies_to_host(genphi_origin *h, int64_t *out);
+int genphi_origin_autozygous_to_host(genphi_origin *h, int64_t *out);
+int genphi_origin_matches_to_host(genphi_origin *h, int64_t *out);
+int genphi_origin_by_proband_to_host(genphi_origin *h, int32_t *out);
+int genphi_origin_stats(const genphi_origin *h, double *sweep_ms, double *count_ms, double *algorithmic_bytes, double *count_bytes,
+                        int32_t *levels, int32_t *panel_cols, int64_t *panels, int32_t *planes, int32_t *chunk_labels,
+                        int64_t *chunks, int32_t *lds_bytes, int32_t *n_groups, int32_t *n_grouped);
+void genphi_origin_destroy(genphi_origin *h);
+
 /* ---- gen.simuSharing: linked-locus gene dropping and IBD segments (csrc/link.hip, csrc/link.cpp, csrc/label_sweep.h) ---------------
  * gen.simuIdentity above drops every founder allele at ONE locus.  Here a simulation is a chromosome of L linked loci: a meiosis
  * copies a mosaic of the parent's two chromosomes, and the sharing of a pair of probands is read off locus by locus: how much of the
