@@ -28,6 +28,7 @@ meaning, printed lines and error behaviour as the reference:
     gen.simuRetention(ped)                 # founder allele survival, founder genome equivalents by gene dropping (csrc/retain.hip)
     gen.simuCarriers(ped, pro, controls)   # per founder allele: how many of the cases carry it, by gene dropping (csrc/carry.hip)
     gen.simuOrigins(ped, pro, groups)      # which founders the kinship and inbreeding of groups come from (csrc/origin.hip)
+    gen.simuUniqueness(ped, pro, others)   # genome uniqueness of every proband: what only it carries, by gene dropping (csrc/unique.hip)
     gen.simuSharing(ped, loci=1024)        # linked loci: realised IBD sharing, its variance and the segments (csrc/link.hip)
     gen.simuSegments(ped, loci=1024)       # the lengths of those segments: histogram, within and between groups, per pair
     gen.descendant(ped, 1); gen.children(ped, 1)   # src/identify.jl:203-215, :77-80 (csrc/loader.cpp)
@@ -44,7 +45,7 @@ from collections import OrderedDict
 import numpy as np
 
 from . import _capi
-from ._capi import PhiPlan, KinshipMatrix, GCPlan, OccPlan, RecPlan, DistPlan, DepthPlan, CompletenessPlan, ImplexPlan, SimuPlan, IdentityPlan, RetentionPlan, CarriersPlan, OriginsPlan, SharingPlan, GenphiDeviceError, GenphiLibraryMissing  # noqa: F401
+from ._capi import PhiPlan, KinshipMatrix, GCPlan, OccPlan, RecPlan, DistPlan, DepthPlan, CompletenessPlan, ImplexPlan, SimuPlan, IdentityPlan, RetentionPlan, CarriersPlan, OriginsPlan, UniquenessPlan, SharingPlan, GenphiDeviceError, GenphiLibraryMissing  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
@@ -1100,6 +1101,82 @@ def simuOrigins(pedigree, pro=None, groups=None, simulNo=5000, seed=None, byProb
         matches[cols, rows] = upper
         return SimuOrigins(grouped[first], h.alleles(), names, sizes, h.copies_to_host(), h.autozygous_to_host(), matches,
                            h.by_proband_to_host() if byProband else None, h.simul_no, h.seed)
+    finally:
+        h.close()
+
+
+class SimuUniqueness:
+    """What gen.simuUniqueness returns.  pro: the distinct probands, in the order of the rows of the tables (ascending row of the
+    plan); n_pop: the distinct probands and others, the population; simulNo and the seed used.  The integer tables (the definition is
+    the text of genphi_unique_* in include/genphi.h): alleles, autozygous: int32 (len(pro), K); column min(m, K) - 1 holds the founder
+    alleles of the proband that m members of the population carry, K = min(n_pop, maxShare); copies = alleles + autozygous, int64: the
+    gene copies, 2 simulNo per proband.  Every share below is formed once from the integers, in Float64."""
+
+    def __init__(self, pro, n_pop, alleles, autozygous, simulNo, seed):
+        self.pro, self.n_pop, self.alleles, self.autozygous = pro, int(n_pop), alleles, autozygous
+        self.simulNo, self.seed = simulNo, seed
+        self.copies = alleles.astype(np.int64) + autozygous.astype(np.int64)
+        self.lumped = alleles.shape[1] < self.n_pop
+
+    def __repr__(self):
+        return "SimuUniqueness(%d probands in a population of %d, %d columns, simulNo=%d, seed=%d)" % (len(self.pro), self.n_pop, self.alleles.shape[1],
+                                                                                                     self.simulNo, self.seed)
+
+    @property
+    def uniqueness(self):
+        """(len(pro),): MacCluer's genome uniqueness, the probability that a gene copy of the proband is the population's only one
+        (with a single column, which lumps every share, it is 1)."""
+        return self.copies[:, 0] / (2.0 * self.simulNo)
+
+    @property
+    def at_risk(self):
+        """(len(pro),): the expected number of founder alleles lost with the proband."""
+        return self.alleles[:, 0] / float(self.simulNo)
+
+    @property
+    def share_hist(self):
+        """(len(pro), K): the share of the proband's gene copies whose allele min(m, K) members of the population carry; a row sums
+        to 1."""
+        return self.copies / (2.0 * self.simulNo)
+
+    @property
+    def mean_share(self):
+        """(len(pro),): the mean number of members of the population that carry a gene copy of the proband; None when the last column
+        lumps."""
+        if self.lumped:
+            return None
+        return (self.copies @ np.arange(1, self.copies.shape[1] + 1, dtype=np.int64)) / (2.0 * self.simulNo)
+
+    def ranking(self, k=10):
+        """The positions in pro of the k probands with the largest uniqueness, by larger uniqueness and then smaller position."""
+        return np.lexsort((np.arange(len(self.pro)), -self.copies[:, 0]))[:max(int(k), 0)]
+
+
+def simuUniqueness(pedigree, pro=None, others=None, simulNo=5000, seed=None, maxShare=8, device=None):
+    """gen.simuUniqueness(pedigree, pro = pro(pedigree), others = None, simulNo = 5000): for each proband, how much of what it
+    carries is carried by nobody else, and what is lost when it goes -- the genome uniqueness of MacCluer et al. (1986), the statistic
+    by which individuals are ranked for breeding, sampling or sequencing.  Every founder allele is dropped down the pedigree under its
+    own label simulNo times (the labels of gen.simuIdentity under the same seed); per simulation the members of the population (the
+    probands and the others: individuals that count as carriers but are not evaluated) that carry each label are counted, and each
+    side of each proband is entered at the share of its label.  Returns a SimuUniqueness: alleles, autozygous, copies, uniqueness,
+    at_risk, share_hist, mean_share, ranking(k).  Neither GENLIB nor the reference has this function.
+
+    The result is integers added by integer additions: a pure function of the pedigree's relations, the SETS of probands and of
+    others (order and repeats change nothing; an individual in both is a proband), the seed, simulNo and maxShare
+    (include/genphi.h); gen.branching(pedigree, pro=..) first changes nothing.  maxShare=k keeps the columns of the shares 1 .. k, the
+    last one holding every share >= k; maxShare=0 keeps one column per member of the population.  seed=None draws 64 fresh bits; pass
+    a seed to repeat a run.  The sweep and the counts run on the GPU (csrc/unique.hip); only the two tables come back.  Not offered:
+    uniqueness within groups, the simulations in which a proband is the sole carrier of at least one allele, linked loci, more than
+    one device.
+
+    KeyError for an unknown ID; ValueError for an empty pro, more than 65,535 distinct probands and others, tables of more than
+    2^31 - 1 cells, simulNo outside 1 .. 2^24 or a negative maxShare.  Each call plans, sweeps and frees its own handle."""
+    probands = globals()["pro"](pedigree) if pro is None else np.ascontiguousarray(pro, dtype=np.int64)
+    rest = np.zeros(0, dtype=np.int64) if others is None else np.ascontiguousarray(others, dtype=np.int64)
+    h = UniquenessPlan(pedigree.ind, pedigree.father, pedigree.mother, probands, rest, simul_no=simulNo, seed=seed, max_share=maxShare)
+    try:
+        h.compute(device=device)
+        return SimuUniqueness(h.probands(), h.n_pop, h.alleles_to_host(), h.autozygous_to_host(), h.simul_no, h.seed)
     finally:
         h.close()
 

@@ -88,6 +88,8 @@ EXPORTED_SYMBOLS = [
     "genphi_origin_create", "genphi_origin_levels", "genphi_origin_alleles", "genphi_origin_compute", "genphi_origin_copies_to_host",
     "genphi_origin_autozygous_to_host", "genphi_origin_matches_to_host", "genphi_origin_by_proband_to_host", "genphi_origin_stats",
     "genphi_origin_destroy",
+    "genphi_unique_create", "genphi_unique_levels", "genphi_unique_alleles", "genphi_unique_probands", "genphi_unique_compute",
+    "genphi_unique_alleles_to_host", "genphi_unique_autozygous_to_host", "genphi_unique_stats", "genphi_unique_destroy",
     "genphi_link_create", "genphi_link_levels", "genphi_link_alleles", "genphi_link_compute", "genphi_link_sums_to_host",
     "genphi_link_labels_to_host", "genphi_link_stats", "genphi_link_destroy", "genphi_link_words",
     "genphi_seg_request", "genphi_seg_to_host", "genphi_seg_stats", "genphi_seg_host",
@@ -432,6 +434,25 @@ def lib():
         L.genphi_origin_stats.restype = C.c_int
         L.genphi_origin_destroy.argtypes = [C.c_void_p]
         L.genphi_origin_destroy.restype = None
+        L.genphi_unique_create.argtypes = [C.c_int64, _I64P, _I64P, _I64P, C.c_int64, _I64P, C.c_int64, _I64P, C.c_int64, C.c_uint64, C.c_int32, C.c_int32,
+                                           C.c_int32, C.POINTER(C.c_void_p)]
+        L.genphi_unique_create.restype = C.c_int
+        L.genphi_unique_levels.argtypes = [C.c_void_p, _I64P, _I32P, _I64P]
+        L.genphi_unique_levels.restype = C.c_int
+        L.genphi_unique_alleles.argtypes = [C.c_void_p, _I64P, _I32P, _I64P, _I32P]
+        L.genphi_unique_alleles.restype = C.c_int
+        L.genphi_unique_probands.argtypes = [C.c_void_p, _I64P, _I64P]
+        L.genphi_unique_probands.restype = C.c_int
+        L.genphi_unique_compute.argtypes = [C.c_void_p, C.c_int32]
+        L.genphi_unique_compute.restype = C.c_int
+        for name in ("alleles", "autozygous"):
+            fn = getattr(L, "genphi_unique_%s_to_host" % name)
+            fn.argtypes = [C.c_void_p, _I32P]
+            fn.restype = C.c_int
+        L.genphi_unique_stats.argtypes = [C.c_void_p, _F64P, _F64P, _F64P, _F64P, _I32P, _I32P, _I64P, _I32P, _I32P, _I64P, _I32P, _I32P, _I32P, _I32P]
+        L.genphi_unique_stats.restype = C.c_int
+        L.genphi_unique_destroy.argtypes = [C.c_void_p]
+        L.genphi_unique_destroy.restype = None
         L.genphi_link_create.argtypes = [C.c_int64, _I64P, _I64P, _I64P, C.c_int64, _I64P, C.c_int32, C.c_int32, C.c_int64, C.c_uint64, C.c_int32,
                                          C.c_int32, C.POINTER(C.c_void_p)]
         L.genphi_link_create.restype = C.c_int
@@ -1971,6 +1992,60 @@ class OriginsPlan(_LabelPlan):
         return self._stats(sweep_ms=C.c_double, count_ms=C.c_double, algorithmic_bytes=C.c_double, count_bytes=C.c_double, levels=C.c_int32,
                            panel_cols=C.c_int32, panels=C.c_int64, planes=C.c_int32, chunk_labels=C.c_int32, chunks=C.c_int64,
                            lds_bytes=C.c_int32, n_groups=C.c_int32, n=C.c_int32)
+
+
+class UniquenessPlan(_LabelPlan):
+    """The handle of gen.simuUniqueness (include/genphi.h, genphi_unique_*): per proband, the simulations in which a founder allele
+    it carries is carried by 1, 2, .. members of the population (the probands and the others), by gene dropping.  Planned on the host
+    at construction (KeyError on an unknown ID; ValueError for no probands, more than 65,535 distinct probands and others, more than
+    2^31 - 1 cells, simul_no outside 1 .. 2^24, a negative panel_cols, chunk_labels or max_share; no GPU needed), swept on the GPU by
+    compute().  The plan and the labels are gen.IdentityPlan's for the probands followed by the others; an individual in both lists is
+    a proband.  seed=None draws 64 fresh bits; .seed reports the seed used.  panel_cols: the simulations of a panel (0 = the
+    default).  chunk_labels: the founder alleles of a chunk of the count kernel (0 = the default).  max_share: 0 = a column for every
+    share 1 .. n_pop, else the last column holds every share at or above max_share.  n: the distinct probands (the rows of the
+    tables, probands() their IDs); n_pop: the distinct probands and others; columns: K."""
+
+    _prefix = "unique"
+
+    def __init__(self, ind, father, mother, pro_ids, other_ids=None, simul_no=5000, seed=None, panel_cols=0, chunk_labels=0, max_share=0):
+        pro_ids = _i64(pro_ids).ravel()
+        other_ids = _i64([] if other_ids is None else other_ids).ravel()
+        self._set_seed(seed)
+        self.simul_no = int(simul_no)
+        ind, father, mother = _i64(ind), _i64(father), _i64(mother)
+        h = C.c_void_p()
+        rc = lib().genphi_unique_create(len(ind), ind.ctypes.data_as(_I64P), father.ctypes.data_as(_I64P), mother.ctypes.data_as(_I64P),
+                                        len(pro_ids), pro_ids.ctypes.data_as(_I64P), len(other_ids), other_ids.ctypes.data_as(_I64P),
+                                        self.simul_no, self.seed, int(panel_cols), int(chunk_labels), int(max_share), C.byref(h))
+        if rc:
+            _raise(rc)
+        self._h = h
+        self.n_pro = len(pro_ids) + len(other_ids)
+        self._read_plan()
+        st = self.stats()
+        self.n, self.n_pop, self.columns = st["n"], st["n_pop"], st["columns"]
+
+    def probands(self):
+        """int64 (n,): the IDs of the rows of the two tables, the distinct probands in ascending row order (host only)."""
+        ids = np.empty(self.n, np.int64)
+        self._call("probands", None, ids.ctypes.data_as(_I64P))
+        return ids
+
+    def alleles_to_host(self):
+        """int32 (n, columns): at [i, min(m, columns) - 1] the founder alleles that proband i carries, over the simulations, whose
+        carriers in the population number m (a proband with both sides alike counts its allele once)."""
+        return self._out("alleles_to_host", (self.n, self.columns), np.int32, C.c_int32)
+
+    def autozygous_to_host(self):
+        """int32 (n, columns): the same for the simulations in which both sides of proband i carry one allele."""
+        return self._out("autozygous_to_host", (self.n, self.columns), np.int32, C.c_int32)
+
+    def stats(self):
+        """dict(sweep_ms, count_ms, algorithmic_bytes, count_bytes, levels, panel_cols, panels, planes, chunk_labels, chunks, lds_bytes,
+        columns, n, n_pop) of the last compute()."""
+        return self._stats(sweep_ms=C.c_double, count_ms=C.c_double, algorithmic_bytes=C.c_double, count_bytes=C.c_double, levels=C.c_int32,
+                           panel_cols=C.c_int32, panels=C.c_int64, planes=C.c_int32, chunk_labels=C.c_int32, chunks=C.c_int64,
+                           lds_bytes=C.c_int32, columns=C.c_int32, n=C.c_int32, n_pop=C.c_int32)
 
 
 GENPHI_LINK_FLAG_LABELS = 1

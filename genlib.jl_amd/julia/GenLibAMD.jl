@@ -1030,6 +1030,50 @@ function simuOrigins(pedigree::GenLib.Pedigree, pro::Vector{Int} = GenLib.pro(pe
 end
 
 """
+    simuUniqueness(pedigree::GenLib.Pedigree, pro = GenLib.pro(pedigree); others = Int[], simulNo = 5000, seed = nothing,
+                   maxShare = 8, device = -1)
+
+The genome uniqueness of every proband (MacCluer et al. 1986), by gene dropping on the GPU (csrc/unique.hip; GenLib.jl has no form of
+it; the definition is the text of `genphi_unique_*` in include/genphi.h): with how many members of the population (`pro` and `others`,
+individuals that count as carriers but are not evaluated; an individual in both is a proband) a proband shares each founder allele it
+carries.  Returns a named tuple: `pro` (the distinct probands, in the order of the tables), `n_pop`, the Int32 matrices `alleles` and
+`autozygous` (`K x length(pro)`: the library's row-major `n x K` is the memory of that array; row `m` holds the share `m`, the last
+row every share `>= maxShare` when `maxShare` is positive and below `n_pop`), `copies` (their Int64 sum), `uniqueness`
+(`copies[1, :] ./ (2 simulNo)`), `at_risk` (`alleles[1, :] ./ simulNo`), `simulNo` and the `seed` used (`nothing` draws 64 fresh bits).
+NOT run anywhere yet, like the rest of this file (no Julia in the build container).
+"""
+function simuUniqueness(pedigree::GenLib.Pedigree, pro::Vector{Int} = GenLib.pro(pedigree); others::Vector{Int} = Int[],
+                        simulNo::Integer = 5000, seed::Union{Nothing, UInt64} = nothing, maxShare::Integer = 8, device::Integer = -1)
+    isempty(pro) && throw(ArgumentError("gen.simuUniqueness: no probands"))
+    seed64 = isnothing(seed) ? rand(Random.RandomDevice(), UInt64) : seed
+    ind, father, mother, _ = flatten(pedigree)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve ind father mother pro others check(ccall((:genphi_unique_create, libgenphi), Cint,
+        (Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Int64, Ptr{Int64}, Int64, Ptr{Int64}, Int64, UInt64, Int32, Int32, Int32, Ptr{Ptr{Cvoid}}),
+        length(ind), ind, father, mother, length(pro), pro, length(others), others, Int64(simulNo), seed64, Int32(0), Int32(0),
+        Int32(maxShare), h))
+    try
+        columns = Ref{Int32}(0); n_pro = Ref{Int32}(0); n_pop = Ref{Int32}(0)
+        check(ccall((:genphi_unique_stats, libgenphi), Cint,
+                    (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}, Ptr{Int64}, Ptr{Int32}, Ptr{Int32},
+                     Ptr{Int64}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}),
+                    h[], C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, columns, n_pro, n_pop))
+        K = Int(columns[]); n = Int(n_pro[])
+        ids = Vector{Int64}(undef, n)
+        GC.@preserve ids check(ccall((:genphi_unique_probands, libgenphi), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}), h[], C_NULL, ids))
+        check(ccall((:genphi_unique_compute, libgenphi), Cint, (Ptr{Cvoid}, Int32), h[], Int32(device)))
+        alleles = Matrix{Int32}(undef, K, n); autozygous = Matrix{Int32}(undef, K, n)
+        GC.@preserve alleles check(ccall((:genphi_unique_alleles_to_host, libgenphi), Cint, (Ptr{Cvoid}, Ptr{Int32}), h[], alleles))
+        GC.@preserve autozygous check(ccall((:genphi_unique_autozygous_to_host, libgenphi), Cint, (Ptr{Cvoid}, Ptr{Int32}), h[], autozygous))
+        copies = Int64.(alleles) .+ Int64.(autozygous)
+        return (pro = Int.(ids), n_pop = Int(n_pop[]), alleles = alleles, autozygous = autozygous, copies = copies,
+                uniqueness = copies[1, :] ./ (2.0 * simulNo), at_risk = alleles[1, :] ./ Float64(simulNo), simulNo = Int(simulNo), seed = seed64)
+    finally
+        ccall((:genphi_unique_destroy, libgenphi), Cvoid, (Ptr{Cvoid},), h[])
+    end
+end
+
+"""
     simuSegments(pedigree::GenLib.Pedigree, pro = GenLib.pro(pedigree); loci = 1024, length = 1.0, probRecomb = nothing,
                  simulNo = 1000, seed = nothing, bins = nothing, minLoci = 1, groups = nothing, device = -1)
 

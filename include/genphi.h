@@ -1368,6 +1368,84 @@ int genphi_origin_stats(const genphi_origin *h, double *sweep_ms, double *count_
                         int64_t *chunks, int32_t *lds_bytes, int32_t *n_groups, int32_t *n_grouped);
 void genphi_origin_destroy(genphi_origin *h);
 
+/* ---- gen.simuUniqueness: the genome uniqueness of every proband (csrc/unique.hip, csrc/unique.h, csrc/label_sweep.h) ---------------
+ * For each proband, how much of what it carries is carried by nobody else, and what is lost when it goes?  That is the genome
+ * uniqueness of MacCluer et al. (1986), the statistic by which individuals are ranked for breeding, sampling or sequencing.  It has no
+ * closed form on a general pedigree and follows neither from the kinship matrix nor from the tables of genphi_carry_* (which know that
+ * an allele has one carrier, not who) or genphi_origin_* (which know who is autozygous, not who else carries the allele).  The
+ * reference has no form of it, so this text is the definition, and it is this package's own.
+ * Inputs.  A pedigree; pro, the evaluated probands, at least one; others, an optional second list of individuals that count as
+ * carriers but are not evaluated (the rest of the living population); S and a 64-bit seed.  Both lists count as SETS: order and
+ * repeats change nothing.  An individual in both lists is a proband, not an error.  The POPULATION is the distinct probands in
+ * ascending row order, followed by the distinct others that are not probands; n is the number of distinct probands, n_pop the size of
+ * the population.  The listed probands of the plan are pro followed by others: live set, levels, rows, allele table, labels
+ * LP_x[s] / LM_x[s], the rule and the random word R are those of genphi_ident_* above, word for word.  The same (pedigree relations,
+ * seed) therefore gives the same realisation as gen.simuIdentity, gen.simuRetention, gen.simuCarriers and gen.simuOrigins.
+ * Per simulation s < S and label l:
+ *   c1(l, s) = the distinct members of the population with at least one side equal to l (genphi_carry_*'s c1 with the population as
+ *              the cases).
+ * With K = min(n_pop, max_share) columns (max_share = 0: K = n_pop), column min(m, K) - 1 holds share m, so the last column lumps
+ * every m >= K when K < n_pop.  With a and b the two sides of proband i in simulation s, the results:
+ *   alleles[i, .]      Int32 x n x K, row-major.  a != b: one count at the column of c1(a, s) and one at the column of c1(b, s);
+ *                      a = b: one count at the column of c1(a, s).
+ *   autozygous[i, .]   Int32 x n x K, row-major.  a = b: one count at the column of c1(a, s).
+ * Row i is the i-th distinct proband in ascending row order; genphi_unique_probands reports the IDs in that order.  Bits at
+ * positions >= S are never counted.
+ * Invariants, all exact.
+ *   1. For every i the sum of alleles[i, :] plus the sum of autozygous[i, :] is 2 S: every side carries one label.
+ *   2. With no others and K = n, for genphi_carry_* on the same probands as cases, no controls, the same seed and S, and W = n + 1:
+ *      the sum over i of alleles[i, m - 1] is m times the sum over l of carriers[l, m], for every m; and the sum over i and m of
+ *      autozygous[i, m] is the sum over l and c of c homozygotes[l, c].
+ *   3. With no others and K = n: every sum over i of alleles[i, m - 1] is divisible by m, and the sum over m of the quotients is
+ *      the sum over s of distinct[s] of genphi_retain_*: every surviving allele is shared out among its carriers exactly once.
+ *   4. The sum over m of autozygous[i, m] is the sum over l of autozygous_pro[i, l] of genphi_origin_* with by_proband, and the
+ *      inbreeding count counts[i, i, 0] of genphi_ident_* of that proband.
+ *   5. The bytes do not depend on the panel width, the label chunk, or the order and repeats of either list.
+ *   6. Keyed by proband ID, adding others never lowers a share: for every i and m the sum over m' <= m of alleles[i, m'] does not
+ *      rise, and the same holds for autozygous.
+ *   7. A proband that is a founder, has no descendant in the population and is listed alone with any others has alleles[i, 0] = 2 S
+ *      when K > 1 (K = 1: everything is in the one column).  A proband whose two parents are both in the population has
+ *      alleles[i, 0] = 0 when K > 1.
+ *   8. A smaller max_share gives the same leading K - 1 columns; its last column is the sum of the dropped ones.
+ * Errors.  Those of genphi_ident_create without the n_pro^2 >= 2^31 refusal.  GENPHI_ERR_ARG, all in create before any device work:
+ * no probands; n_pop > 65,535 (the counters are 16 bits); n x K > 2^31 - 1 cells ("pass a smaller maxShare"); S outside 1 .. 2^24; a
+ * negative panel_cols, chunk_labels or max_share.  GENPHI_ERR_ALLOC from compute before any launch, when the device does not hold
+ * the results (8 n K bytes), the lists and the rows of even a 128-column panel.
+ * Method.  The label sweep of genphi_ident_* (its init and step kernels, shared), then one count kernel per panel that reads the
+ * rows of the population in place.  A workgroup owns the 64 simulations of a word and a chunk of the labels; it keeps one 16-bit
+ * counter per (simulation, label) in LDS, two to a dword (n_pop <= 65,535 keeps the halves apart), decodes both sides of every
+ * member of the population once and adds by LDS atomics; after a barrier it decodes the probands again, reads the counter of each
+ * side whose label lies in the chunk and adds 1 at the cell of that share by integer atomics, the lanes of a wave that meet in one
+ * of the first columns counted by a ballot first (csrc/unique.hip).  Not offered: uniqueness within groups; the simulations in which
+ * a proband is the sole carrier of at least one allele (that does not add over label chunks); linked loci; more than one device.
+ *   create            host only (no GPU): ident's checks and plan on pro followed by others; the lists as sets; the limits.
+ *                     panel_cols as for genphi_ident_create.  chunk_labels: the labels of a chunk, 0 = the default, else rounded up
+ *                     to a multiple of 64 and cut to 1,216 (the most that 160 KiB of LDS hold); either is cut to n_labels (tests,
+ *                     A/B).  max_share: 0 = a column for every share, else the last column K - 1 = min(n_pop, max_share) - 1 holds
+ *                     every share at or above max_share
+ *   levels, alleles   as genphi_ident_levels and genphi_ident_alleles
+ *   probands          n and, when ids is not NULL, the IDs of the rows of the two tables (n of them)
+ *   compute           the sweep on `device` (-1 = current); the two tables stay resident
+ *   alleles_to_host, autozygous_to_host    out: n x K Int32, row-major
+ *   stats             of the last compute, by HIP events: the device time of init and level steps, and of the count kernel, summed
+ *                     over the panels; the algorithmic bytes of the steps (as genphi_ident_stats); the bytes of the rows' planes the
+ *                     count kernel reads (2 (n_pop + n) x B x 16 per pair of words and chunk); levels; the columns of a panel; the
+ *                     panels; B; the labels of a chunk; the chunks; the LDS bytes of a workgroup of the count kernel; K; n; n_pop */
+typedef struct genphi_unique genphi_unique;
+int genphi_unique_create(int64_t n_ind, const int64_t *ind, const int64_t *father, const int64_t *mother,
+                         int64_t n_pro, const int64_t *pro_ids, int64_t n_others, const int64_t *other_ids, int64_t simul_no,
+                         uint64_t seed, int32_t panel_cols, int32_t chunk_labels, int32_t max_share, genphi_unique **out);
+int genphi_unique_levels(const genphi_unique *h, int64_t *n_live, int32_t *levels, int64_t *rows_per_level);
+int genphi_unique_alleles(const genphi_unique *h, int64_t *n_labels, int32_t *planes, int64_t *ids, int32_t *sides);
+int genphi_unique_probands(const genphi_unique *h, int64_t *n, int64_t *ids);
+int genphi_unique_compute(genphi_unique *h, int32_t device);
+int genphi_unique_alleles_to_host(genphi_unique *h, int32_t *out);
+int genphi_unique_autozygous_to_host(genphi_unique *h, int32_t *out);
+int genphi_unique_stats(const genphi_unique *h, double *sweep_ms, double *count_ms, double *algorithmic_bytes, double *count_bytes,
+                        int32_t *levels, int32_t *panel_cols, int64_t *panels, int32_t *planes, int32_t *chunk_labels,
+                        int64_t *chunks, int32_t *lds_bytes, int32_t *columns, int32_t *n, int32_t *n_pop);
+void genphi_unique_destroy(genphi_unique *h);
+
 /* ---- gen.simuSharing: linked-locus gene dropping and IBD segments (csrc/link.hip, csrc/link.cpp, csrc/label_sweep.h) ---------------
  * gen.simuIdentity above drops every founder allele at ONE locus.  Here a simulation is a chromosome of L linked loci: a meiosis
  * copies a mosaic of the parent's two chromosomes, and the sharing of a pair of probands is read off locus by locus: how much of the
